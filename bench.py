@@ -11,8 +11,13 @@ collective inside the loop; frozen weights are generated on rank 0 and broadcast
 0's JSON line and exits with the children's status.  Under an external torchrun the environment decides.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = the
-implicit-GEMM family, timed with HIP events on the launch stream inside the timed region) and
-`cpu_baseline` (the CPU oracle on a bounded sample of the same workload, rank 0, N=1 only).
+implicit-GEMM family, timed with HIP events on the launch stream inside the timed region).  A plain run sets up, warms
+up, times --steps samplings and prints that line; `--full` adds the measurements the headline does not need, each after
+the timed region: `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, rank 0) and
+`first_stage_decode` (the VAE decode of the sampled latents).
+
+`--dump-outputs DIR` writes what the last timed sampling returned (the latents and the sampler's intermediates, all
+ranks gathered) as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -35,6 +40,7 @@ LATENT = 64
 TFLOP_PER_IMAGE = 107.20  # BASELINE.md section 3, config C3 (hint block once per image)
 PEAK_TFLOPS = 2500.0      # dense fp16 MFMA, MI355X_MICROARCH.md
 PROFILE_TAG = 'r04'       # profiles/<tag>_pmc_traffic.json / _trace_summary.json: offline measurements quoted (and labelled) in the line
+DUMP_BUDGET = 60 * 10**6  # bytes of arrays written by --dump-outputs at most (64 MB with room for the .npy headers)
 
 
 def log(msg):
@@ -139,6 +145,30 @@ def cpu_baseline():
             'sec_per_cfg_pair_eval': sec}
 
 
+def dump_outputs(d, out, inter, rank, world, use_dist):
+    """np.save the last timed sampling's result as d/<name>.npy (float32): `samples` and the sampler's intermediates
+    `x_inter_<i>` / `pred_x0_<i>`, the batches of all ranks gathered in rank order.  Above DUMP_BUDGET bytes in all, the
+    same fixed, seeded subset of batch rows is kept in every array (and listed in `rows.npy`)."""
+    from fgdm_amd import dist as fd
+    arrays = {'samples': out}
+    for k in ('x_inter', 'pred_x0'):
+        arrays.update({f'{k}_{i}': t for i, t in enumerate(inter[k])})
+    arrays = {k: (fd.gather_latents(v, rank, world) if use_dist else v).float().cpu().numpy() for k, v in arrays.items()}
+    if rank != 0:
+        return
+    os.makedirs(d, exist_ok=True)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET:
+        n = arrays['samples'].shape[0]
+        keep = max(1, n * DUMP_BUDGET // total)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays['rows'] = rows.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + '.npy'), v)
+    log(f'outputs of the last timed step written to {d}: {", ".join(sorted(arrays))}')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -146,11 +176,15 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--prompts', type=int, default=PROMPTS_PER_GPU, help='prompts per GPU')
     ap.add_argument('--ddim-steps', type=int, default=DDIM_STEPS)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also measure what the headline does not need: the CPU baseline and the '
+                         'first-stage (VAE) decode')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--controlnets', type=int, default=1,
                     help='control models per UNet (1 = the metric\'s config C3; 2 / 3 = BASELINE configs C4 / C5, use --prompts 8; 0 = the plain UNet, C2)')
     ap.add_argument('--no-first-stage', action='store_true',
-                    help='skip the VAE decode that follows the timed region (PMC passes: counters then cover the path only)')
+                    help='with --full: skip the VAE decode that follows the timed region (PMC passes: counters then cover the '
+                         'path only)')
     ap.add_argument('--profile-stride', type=int, default=31,
                     help='HIP-event bracket every n-th kernel launch of the timed region (coprime with the 830 launches per '
                          'evaluation, so every layer shape is sampled uniformly); 1 = every launch.  Two event packets leave a ~6 us '
@@ -164,9 +198,15 @@ def main():
     ap.add_argument('--dump-latents', default=None,
                     help='after timing, gather the last sampling\'s latents of all ranks (all_gather) and np.save them here (tests: '
                          'N ranks must reproduce the 1-rank result of the same global batch bit for bit)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after timing, write what the last timed sampling returned (latents and intermediates, all ranks) '
+                         'as DIR/<name>.npy, float32')
     ap.add_argument('--dry-run', action='store_true',
                     help='CPU rehearsal of the N-rank plumbing with an analytic stand-in model (tests); measures nothing')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    first_stage = a.full and not a.no_first_stage
 
     if a.twin_streams:
         os.environ['FGDM_TWIN_STREAMS'] = '1'          # read by fgdm_create; inherited by the ranks of --gpus N
@@ -212,7 +252,7 @@ def main():
         engine = None
         sampler = samplers.DDIMSampler(model)
     else:
-        model, n_params, wt = build_model(rank, world, dev, first_stage=not a.no_first_stage, n_controlnets=a.controlnets,
+        model, n_params, wt = build_model(rank, world, dev, first_stage=first_stage, n_controlnets=a.controlnets,
                                           force_bcast=use_dist)
         engine = model.engine
         sampler = samplers.ControlDDIMSampler(model)       # drop-in for controlnet/cldm/ddim_hacked.py:DDIMSampler
@@ -235,14 +275,13 @@ def main():
         cond, uncond = cond0.clone(), uncond0.clone()
         if a.dry_run:
             return sampler.sample(a.ddim_steps, npg, (4, lat, lat), conditioning=cond, verbose=False, eta=0.0, x_T=x_T,
-                                  unconditional_guidance_scale=CFG_SCALE, unconditional_conditioning=uncond)[0]
+                                  unconditional_guidance_scale=CFG_SCALE, unconditional_conditioning=uncond)
         # the call the reference makes at controlnet/initialize_cn.py:86-96 (guess_mode=False: control on both branches)
         # --controlnets 0 (the plain UNet, BASELINE configs[1]): c_concat = None as in cldm.py:840-842
         c_cond = {'c_crossattn': [cond], 'c_concat': hints if hints else None}
         c_uncond = {'c_crossattn': [uncond], 'c_concat': hints if hints else None}
-        out, _ = sampler.sample(a.ddim_steps, npg, (4, LATENT, LATENT), c_cond, verbose=False, eta=0.0, x_T=x_T,
-                                unconditional_guidance_scale=CFG_SCALE, unconditional_conditioning=c_uncond)
-        return out
+        return sampler.sample(a.ddim_steps, npg, (4, LATENT, LATENT), c_cond, verbose=False, eta=0.0, x_T=x_T,
+                              unconditional_guidance_scale=CFG_SCALE, unconditional_conditioning=c_uncond)
 
     def barrier():
         if use_dist:
@@ -253,7 +292,7 @@ def main():
     if rank == 0:
         log(f'weights ready ({n_params / 1e9:.2f} G params, {load_s:.1f} s); warm-up x{a.warmup} ...')
     for _ in range(a.warmup):
-        out = one_step()
+        one_step()
     barrier()
     if rank == 0:
         log(f'timing {a.steps} step(s) of {a.ddim_steps} DDIM steps x {npg} prompts per GPU ...')
@@ -261,7 +300,7 @@ def main():
         engine.profile_begin(a.profile_stride)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        out = one_step()
+        out, inter = one_step()
     if not a.dry_run:
         torch.cuda.synchronize()
     dt_own = time.perf_counter() - t0        # this rank's own time (before it waits for the others)
@@ -282,6 +321,8 @@ def main():
         allx = fd.gather_latents(out, rank, world) if use_dist else out
         if rank == 0:
             np.save(a.dump_latents, allx.float().cpu().numpy())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, inter, rank, world, use_dist)
     if a.dry_run:
         if rank == 0:
             emit({'metric': '512x512 images/sec @ 50 DDIM steps, seg-ControlNet+CFG', 'dry_run': True, 'value': None,
@@ -297,7 +338,7 @@ def main():
     # outside the timed region (VAE decode excluded from the metric, reported separately):
     # decode_first_stage of this rank's latents to 512x512 images
     dec_s = None
-    if not a.no_first_stage:
+    if first_stage:
         img = model.decode_first_stage(out)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -389,6 +430,7 @@ def main():
                         '1.27 TFLOP/image'},
             'per_rank_images_per_s': per_rank,
             'twin_streams': os.environ.get('FGDM_TWIN_STREAMS') == '1',
+            'full': a.full,
             'weights': {'params': n_params, 'load_s': round(load_s, 2), 'bcast_s': wt.get('bcast_s'),
                         'bcast_bytes': wt.get('bcast_bytes'),
                         'note': 'one broadcast of a flat buffer from rank 0 (RCCL over xGMI): fp16 for the tensors the engine '
@@ -401,7 +443,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline()       # rank 0's host cores, after the timed region, at every N
         emit(res)
 

@@ -5,7 +5,7 @@ algorithm for the hot path named by BASELINE.json's north_star (DDIM / PLMS /
 ancestral loop over the SD-v1.x UNet + FG-DM adapter + ControlNet + CFG).
 It exists so that the HIP engine in ``fgdm_amd/`` can be checked; it is NOT a
 product path and nothing in ``fgdm_amd/`` imports it.  Only ``tests/``,
-``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may use it.
+``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of ``bench.py --full`` may use it.
 
 Parity status: PINNED.  Every function here is checked (tests/test_oracle_*.py,
 ``-m "not gpu"``) against golden vectors in ``tests/golden/*.npz`` that were

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -55,3 +57,29 @@ def test_failing_rank_fails_the_launcher():
     r = _run(['--gpus', '2', '--backend', 'gloo', '--dry-run', '--steps', '1', '--warmup', '0', '--prompts', '2', '--ddim-steps', '2'],
              {'FGDM_BENCH_FAIL_RANK': '1'})
     assert r.returncode != 0
+
+
+def test_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs writes the last timed sampling's result (latents + intermediates, both ranks gathered) as float .npy;
+    the inputs are seeded, so a second run with the same arguments writes the same arrays."""
+    runs = []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        r = _run(['--gpus', '2', '--backend', 'gloo', '--dry-run', '--steps', '2', '--warmup', '0', '--prompts', '2',
+                  '--ddim-steps', '4', '--dump-outputs', str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append({f.stem: np.load(f) for f in sorted(d.glob('*.npy'))})
+    a, b = runs
+    assert a['samples'].shape == (4, 4, 8, 8) and 'x_inter_0' in a and 'pred_x0_0' in a
+    assert sorted(a) == sorted(b)
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), k
+
+
+def test_steps_sets_the_timed_steps():
+    r = _run(['--gpus', '1', '--backend', 'gloo', '--dry-run', '--steps', '3', '--warmup', '0', '--prompts', '2', '--ddim-steps', '2'])
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
+    assert j['steps'] == 3 and j['ms_per_step'] > 0 and 'timing 3 step(s)' in r.stderr
+    assert _run(['--gpus', '1', '--backend', 'gloo', '--dry-run', '--steps', '0']).returncode != 0

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(gpus, prompts, dump, cpu_baseline=False):
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--steps', '1', '--warmup', '0', '--ddim-steps', '2',
-           '--prompts', str(prompts), '--no-first-stage', '--dump-latents', dump] + ([] if cpu_baseline else ['--no-cpu-baseline'])
+           '--prompts', str(prompts), '--no-first-stage', '--dump-latents', dump] + (['--full'] if cpu_baseline else [])
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('WORLD_SIZE', None)
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)      # fresh processes only

@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 VAR=$1; A=$2; B=$3; R=${4:-2}
 for i in $(seq 1 $R); do
   for v in $A $B; do
-    env $VAR=$v timeout -k 10 300 python bench.py --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+    env $VAR=$v timeout -k 10 300 python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 fs = d.get('first_stage_decode') or {}
