@@ -2,7 +2,13 @@
 (torch fp32 functional on the SAME fp16-rounded inputs and weights).
 
 Tolerance: normwise relative error <= 1e-3 (the north_star's "1e-3 relative fp16 tolerance"); outputs are
-stored in fp16 (unit roundoff 4.9e-4), accumulation is fp32."""
+stored in fp16 (unit roundoff 4.9e-4), accumulation is fp32.  Next to it, the blockwise error (tests/guarded.py tile_err) stays
+under LOCAL_TOL = 2e-3 over 32 x 32 (row, column) blocks: a ragged last tile or one wrong block that the normwise error averages
+away fails there.
+
+Every output is written into a guarded buffer (tests/guarded.py): payload poisoned with a NaN bit pattern no kernel produces,
+between seeded guard bytes -- an element never written, a store past either end, or a non-finite value fails the case.  Every
+activation input sits between NaN guards, so a read past its end that reaches a result shows up as well."""
 import ctypes as C
 
 import numpy as np
@@ -10,7 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from common import relerr
+from common import relerr, report
+from guarded import LOCAL_TOL, guarded_in, guarded_out, tile_err
 
 pytestmark = pytest.mark.gpu
 
@@ -37,8 +44,27 @@ def rnd(shape, seed, scale=1.0):
     return torch.randn(shape, generator=g) * scale
 
 
-def nhwc16(x):   # NCHW fp32 cpu -> NHWC fp16 cuda
-    return x.permute(0, 2, 3, 1).contiguous().half().cuda()
+def din(t):      # cpu tensor -> device copy between NaN guards
+    return guarded_in(t.contiguous())
+
+
+def nhwc16(x):   # NCHW fp32 cpu -> NHWC fp16 cuda (between NaN guards)
+    return din(x.permute(0, 2, 3, 1).half())
+
+
+def to_rows(x):  # NCHW -> [B H W, C]: the kernels' (row, column) layout, the one tile_err's blocks follow
+    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])
+
+
+def close(what, got, ref, tol=TOL, local=LOCAL_TOL, block=(32, 32)):
+    """normwise error < tol and blockwise error < local; both recorded"""
+    ref = torch.as_tensor(ref).to(got.device)           # both errors in fp64 on the device
+    e = relerr(got, ref)
+    te = tile_err(got, ref, block)
+    report(f'{what} [tile_err {te:.3e}]', e, tol)
+    assert e < tol, (what, e)
+    assert te < local, (what, 'tile_err', te)
+    return e, te
 
 
 def from_nhwc(y, B, H, W, Cc):
@@ -67,6 +93,12 @@ CONV_CASES = [
     (2, 16, 16, 1280, 640, 1280, 3, 1, 0, 0, 'split-K x2 (16x16, K=17280) thin tiles rowvec + resid'),
     (25, 16, 16, 1280, 1280, 1280, 3, 1, 0, 1, 'split-K x2 on 256x320 tiles (16x16, K=23040, B=25) silu'),
     (9, 16, 16, 1280, 0, 1280, 3, 1, 0, 0, 'split-K x2 (16x16, K=11520, a layer without a twin) rowvec + resid'),
+    # split K with M = 1 or 255 mod 256 (ragged images: rows_per_sample <= 64 splits four / eight ways, 64 < rps <= 256 two ways):
+    # the last row tile of every K slice and the reduction pass's tail
+    (9, 3, 19, 640, 0, 320, 3, 1, 0, 1, 'split-K x4, M=513 (rps 57) silu + rowvec + resid'),
+    (5, 3, 17, 1280, 0, 320, 3, 1, 0, 0, 'split-K x8, M=255 (rps 51)'),
+    (3, 9, 19, 1280, 0, 320, 3, 1, 0, 0, 'split-K x2, M=513 (rps 171) rowvec + resid'),
+    (1, 15, 17, 1280, 640, 320, 3, 1, 0, 0, 'split-K x2 concat, M=255 (rps 255)'),
 ]
 
 
@@ -95,17 +127,18 @@ def test_conv(lib, case):
         ref = ref + resid
     x0 = nhwc16(x[:, :C0])
     x1 = nhwc16(x[:, C0:]) if C1 else None
-    out = torch.empty(B * Ho * Wo * Cout, dtype=torch.half, device='cuda')
+    out = guarded_out((B * Ho * Wo, Cout), torch.half)
     # keep every device tensor referenced until the call returns (a temporary's block would be recycled)
     wd, bd = w.cuda(), bias.cuda()
-    rvd = rowvec.cuda() if rowvec is not None else None
+    rvd = din(rowvec) if rowvec is not None else None
     rsd = nhwc16(resid) if resid is not None else None
     rc = lib.fgdm_op_conv2d(_p(x0), C0, _p(x1), C1, _p(wd), _p(bd), _p(rvd), _p(rsd),
-                            B, H, W, Cout, ks, stride, up, act, scale, _p(out), _st())
+                            B, H, W, Cout, ks, stride, up, act, scale, _p(out.t), _st())
     assert rc == 0
     torch.cuda.synchronize()
-    got = from_nhwc(out, B, Ho, Wo, Cout)
-    assert relerr(got, ref) < TOL, tag
+    got = out.check()
+    assert relerr(from_nhwc(got, B, Ho, Wo, Cout), ref) < TOL, tag
+    close(f'conv {tag}', got, to_rows(ref))
 
 
 def test_linear_variants(lib):
@@ -117,31 +150,45 @@ def test_linear_variants(lib):
     y = F.linear(x, w, b)
     a, g = y.chunk(2, dim=-1)
     ref = a * F.gelu(g)
-    out = torch.empty(M, N // 2, dtype=torch.half, device='cuda')
-    xd, wd, bd = x.half().cuda(), w.cuda(), b.cuda()
-    assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, M, K, N, 3, 0, 0, 0, _p(out), _st()) == 0
-    assert relerr(out.float().cpu(), ref) < TOL
+    out = guarded_out((M, N // 2), torch.half)
+    xd, wd, bd = din(x.half()), w.cuda(), b.cuda()
+    assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, M, K, N, 3, 0, 0, 0, _p(out.t), _st()) == 0
+    assert relerr(out.check().float().cpu(), ref) < TOL
+    close('linear GEGLU', out.t, ref)
     # plain + residual, fp32 output, transposed fp16 output (V^T for attention), ragged rows-per-sample (77)
     N2 = 320
     w2, b2 = w[:N2].contiguous(), b[:N2].contiguous()
     ref = F.linear(x, w2, b2)
     res = h16(rnd((M, N2), 14))
-    out = torch.empty(M, N2, dtype=torch.half, device='cuda')
-    w2d, b2d, resd = w2.cuda(), b2.cuda(), res.half().cuda()
-    assert lib.fgdm_op_linear(_p(xd), _p(w2d), _p(b2d), _p(resd), M, K, N2, 0, 0, 0, 0, _p(out), _st()) == 0
-    assert relerr(out.float().cpu(), ref + res) < TOL
-    out32 = torch.empty(M, N2, dtype=torch.float32, device='cuda')
-    assert lib.fgdm_op_linear(_p(xd), _p(w2d), _p(b2d), None, M, K, N2, 0, 1, 0, 0, _p(out32), _st()) == 0
-    assert relerr(out32.cpu(), ref) < 2e-5 + 0 * TOL     # fp32 store: only accumulation-order error
+    out = guarded_out((M, N2), torch.half)
+    w2d, b2d, resd = w2.cuda(), b2.cuda(), din(res.half())
+    assert lib.fgdm_op_linear(_p(xd), _p(w2d), _p(b2d), _p(resd), M, K, N2, 0, 0, 0, 0, _p(out.t), _st()) == 0
+    assert relerr(out.check().float().cpu(), ref + res) < TOL
+    close('linear + resid', out.t, ref + res)
+    out32 = guarded_out((M, N2), torch.float32)
+    assert lib.fgdm_op_linear(_p(xd), _p(w2d), _p(b2d), None, M, K, N2, 0, 1, 0, 0, _p(out32.t), _st()) == 0
+    assert relerr(out32.check().cpu(), ref) < 2e-5 + 0 * TOL     # fp32 store: only accumulation-order error
+    close('linear fp32', out32.t, ref, 2e-5, 2 * 2e-5)      # fp32 store: blockwise 2 x the normwise bar (no fp16 rounding to average)
     for rps, Bt in ((100, 2), (77, 2), (4, 50)):
         Mt = rps * Bt
         ld = (rps + 63) // 64 * 64
-        outT = torch.zeros(Bt, N2, ld, dtype=torch.half, device='cuda')
-        xt = x[:Mt].half().cuda()
-        assert lib.fgdm_op_linear(_p(xt), _p(w2d), _p(b2d), None, Mt, K, N2, 0, 3, rps, ld, _p(outT), _st()) == 0
+        outT = guarded_out((Bt, N2, ld), torch.half)
+        xt = din(x[:Mt].half())
+        assert lib.fgdm_op_linear(_p(xt), _p(w2d), _p(b2d), None, Mt, K, N2, 0, 3, rps, ld, _p(outT.t), _st()) == 0
         want = ref[:Mt].view(Bt, rps, N2).permute(0, 2, 1)
-        assert relerr(outT[:, :, :rps].float().cpu(), want) < TOL
-        assert float(outT[:, :, rps:].abs().max()) == 0.0 if ld > rps else True
+        check_transposed(outT, rps, ld)
+        assert relerr(outT.t[:, :, :rps].float().cpu(), want) < TOL
+        close(f'linear V^T rps {rps}', outT.t[:, :, :rps].reshape(-1, rps), want.reshape(-1, rps))
+
+
+def check_transposed(outT, rps, ld):
+    """OUT_F16_T / OUT_F32_NCHW: every (sample, channel, t < rps) written, the pad columns t >= rps NOT: the engine zeroes the
+    padded part of V^T once (engine.hip, the attention workspace) and the projections write around it.  Neither kernel's
+    transposed epilogue stores to t >= rps (igemm.hip: t = row - b rps with row < M; igemm2.hip's direct path the same, and
+    its 16-byte V^T runs only serve the LayerNorm-consumer path with rows_per_sample % 32 == 0, never a pad column)."""
+    outT.check((slice(None), slice(None), slice(0, rps)))
+    if ld > rps:
+        outT.assert_untouched((slice(None), slice(None), slice(rps, None)))
 
 
 @pytest.mark.parametrize('M,K,N', [(66000, 320, 2560), (16500, 640, 5120)], ids=['L0-like ragged M', 'L1-like ragged M'])
@@ -156,17 +203,18 @@ def test_geglu_persistent_kernel(lib, M, K, N):
     b = rnd((N,), 23, 0.1)
     a, g = F.linear(x, w, b).chunk(2, dim=-1)
     ref = a * F.gelu(g)
-    xd, wd, bd = x.half().cuda(), w.cuda(), b.cuda()
-    out = torch.empty(M, N // 2, dtype=torch.half, device='cuda')
-    assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, M, K, N, 3, 0, 0, 0, _p(out), _st()) == 0
-    assert relerr(out.float().cpu(), ref) < TOL
-    out2 = torch.empty_like(out)
+    xd, wd, bd = din(x.half()), w.cuda(), b.cuda()
+    out = guarded_out((M, N // 2), torch.half)
+    assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, M, K, N, 3, 0, 0, 0, _p(out.t), _st()) == 0
+    assert relerr(out.check().float().cpu(), ref) < TOL
+    close(f'GEGLU persistent M {M}', out.t, ref)     # the ragged last row tile (M % 256 rows) is its own set of blocks
+    out2 = guarded_out((M, N // 2), torch.half)
     try:
         lib.fgdm_debug_force_igemm_cfg(5 + 16)          # 256 x 256 tiles, phase-locked K loop: never the persistent kernel
-        assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, M, K, N, 3, 0, 0, 0, _p(out2), _st()) == 0
+        assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, M, K, N, 3, 0, 0, 0, _p(out2.t), _st()) == 0
     finally:
         lib.fgdm_debug_force_igemm_cfg(0)
-    assert torch.equal(out, out2)
+    assert torch.equal(out.t, out2.check())
 
 
 GN_CASES = [(2, 64, 320, 0, 1e-5, 1), (2, 64, 1280, 640, 1e-5, 1), (1, 16, 1280, 1280, 1e-5, 1),
@@ -190,12 +238,45 @@ def test_groupnorm(lib, case):
     ref = F.group_norm(x, 32, gamma, beta, eps)
     if silu:
         ref = F.silu(ref)
+    out = run_groupnorm(lib, x, C0, gamma, beta, eps, silu)
+    assert relerr(from_nhwc(out, B, HW, 1, Cc), ref) < TOL
+    close(f'GroupNorm B{B} HW{HW} C{C0}+{C1}', out, to_rows(ref))
+
+
+def run_groupnorm(lib, x, C0, gamma, beta, eps, silu):
+    """x: NCHW [B, C, HW, 1] fp32 (fp16-representable), split at C0 into the two sources of the virtual concat -> guarded,
+    checked NHWC output [B HW, C]"""
+    B, Cc, HW = x.shape[0], x.shape[1], x.shape[2]
+    C1 = Cc - C0
     x0 = nhwc16(x[:, :C0])
     x1 = nhwc16(x[:, C0:]) if C1 else None
-    out = torch.empty(B * HW * Cc, dtype=torch.half, device='cuda')
+    out = guarded_out((B * HW, Cc), torch.half)
     gd, bd = gamma.cuda(), beta.cuda()
-    assert lib.fgdm_op_groupnorm(_p(x0), C0, _p(x1), C1, B, HW, _p(gd), _p(bd), eps, silu, _p(out), _st()) == 0
-    assert relerr(from_nhwc(out, B, HW, 1, Cc), ref) < TOL
+    assert lib.fgdm_op_groupnorm(_p(x0), C0, _p(x1), C1, B, HW, _p(gd), _p(bd), eps, silu, _p(out.t), _st()) == 0
+    return out.check()
+
+
+@pytest.mark.parametrize('offset', [8.0, 32.0], ids=lambda o: f'mean{int(o)}std')
+@pytest.mark.parametrize('case', GN_CASES, ids=[f'B{c[0]}_HW{c[1]}_C{c[2]}+{c[3]}' for c in GN_CASES])
+def test_groupnorm_groups_with_large_mean(lib, case, offset):
+    """Every GroupNorm body forms var = E[x^2] - mean^2 from fp32 per-thread sums, which cancels when |mean| >> std.  Each
+    (sample, group) shifted by +-`offset` standard deviations (0.5 ... 1.5 x), per-channel jitter of 0.3 std and a few
+    outlier channels with six times the spread; every path of GN_CASES (register-resident, single kernel, two kernels, concat
+    inside and across slices, ragged HW).  Reference: group_norm in fp64 on the fp16-rounded input."""
+    B, HW, C0, C1, eps, silu = case
+    Cc = C0 + C1
+    x = rnd((B, Cc, HW, 1), 25)
+    x[:, ::97] *= 6.0                                                           # outlier channels
+    goff = offset * (0.5 + rnd((B, 32), 26).abs()) * torch.sign(rnd((B, 32), 27))
+    x = x + goff.repeat_interleave(Cc // 32, dim=1)[:, :, None, None] + 0.3 * rnd((1, Cc, 1, 1), 28)
+    x = h16(x)
+    gamma, beta = 1 + 0.2 * rnd((Cc,), 22), 0.1 * rnd((Cc,), 23)
+    ref = F.group_norm(x.double(), 32, gamma.double(), beta.double(), eps)
+    if silu:
+        ref = F.silu(ref)
+    out = run_groupnorm(lib, x, C0, gamma, beta, eps, silu)
+    e, te = close(f'GroupNorm large mean {offset:g} std B{B} HW{HW} C{C0}+{C1}', out, to_rows(ref))
+    print(f'GroupNorm, group mean ~{offset:g} x std, B{B} HW{HW} C{C0}+{C1}: rel_err={e:.3e} tile_err={te:.3e}')
 
 
 def test_groupnorm_is_bitwise_reproducible(lib):
@@ -204,9 +285,9 @@ def test_groupnorm_is_bitwise_reproducible(lib):
     gamma, beta = torch.ones(Cc).cuda(), torch.zeros(Cc).cuda()
     outs = []
     for _ in range(3):
-        out = torch.empty(B * HW * Cc, dtype=torch.half, device='cuda')
-        assert lib.fgdm_op_groupnorm(_p(x), Cc, None, 0, B, HW, _p(gamma), _p(beta), 1e-5, 1, _p(out), _st()) == 0
-        outs.append(out.clone())
+        out = guarded_out((B * HW * Cc,), torch.half)
+        assert lib.fgdm_op_groupnorm(_p(x), Cc, None, 0, B, HW, _p(gamma), _p(beta), 1e-5, 1, _p(out.t), _st()) == 0
+        outs.append(out.check())
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
 
 
@@ -216,10 +297,12 @@ def test_layernorm(lib, C_):
     x = h16(rnd((rows, C_), 31) * 1.5 + 0.3)
     gamma, beta = 1 + 0.2 * rnd((C_,), 32), 0.1 * rnd((C_,), 33)
     ref = F.layer_norm(x, (C_,), gamma, beta, 1e-5)
-    out = torch.empty(rows, C_, dtype=torch.half, device='cuda')
-    xd, gd, bd = x.half().cuda(), gamma.cuda(), beta.cuda()
-    assert lib.fgdm_op_layernorm(_p(xd), rows, C_, _p(gd), _p(bd), 1e-5, _p(out), _st()) == 0
-    assert relerr(out.float().cpu(), ref) < TOL
+    out = guarded_out((rows, C_), torch.half)
+    xd, gd, bd = din(x.half()), gamma.cuda(), beta.cuda()
+    assert lib.fgdm_op_layernorm(_p(xd), rows, C_, _p(gd), _p(bd), 1e-5, _p(out.t), _st()) == 0
+    torch.cuda.synchronize()
+    assert relerr(out.check().float().cpu(), ref) < TOL
+    close(f'LayerNorm C{C_}', out.t, ref)
 
 
 ATT_CASES = [(2, 8, 64, 64, 40), (1, 8, 4096, 4096, 40), (2, 8, 1024, 1024, 80), (2, 8, 256, 256, 160),
@@ -248,13 +331,17 @@ def test_attention(lib, case):
     sim = torch.matmul(split(q), split(k).transpose(-1, -2)) * d ** -0.5
     ref = torch.matmul(sim.softmax(-1), split(v)).permute(0, 2, 1, 3).reshape(B, T, Cc)
     Tkp = (Tk + 63) // 64 * 64
-    vt = torch.zeros(B, Cc, Tkp, dtype=torch.half)
+    vt = torch.zeros(B, Cc, Tkp, dtype=torch.half)      # pad columns Tk <= t < Tkp zero: the engine's contract for V^T
     vt[:, :, :Tk] = v.permute(0, 2, 1).half()
-    out = torch.empty(B, T, Cc, dtype=torch.half, device='cuda')
-    qd, kd, vtd = q.half().cuda(), k.half().cuda(), vt.cuda()
-    rc = lib.fgdm_op_attention(_p(qd), Cc, _p(kd), Cc, _p(vtd), Tkp, _p(out), Cc, B, Hh, T, Tk, d, _st())
+    out = guarded_out((B, T, Cc), torch.half)
+    # Q rows past T and K rows past Tk (of the last sample) sit in NaN guards: the kernels clamp those reads to the last valid row
+    qd, kd, vtd = din(q.half()), din(k.half()), din(vt)
+    rc = lib.fgdm_op_attention(_p(qd), Cc, _p(kd), Cc, _p(vtd), Tkp, _p(out.t), Cc, B, Hh, T, Tk, d, _st())
     assert rc == 0
-    assert relerr(out.float().cpu(), ref) < TOL
+    torch.cuda.synchronize()
+    assert relerr(out.check().float().cpu(), ref) < TOL
+    # P is rounded to fp16 before the PV product: blockwise 2 x the normwise bar (= LOCAL_TOL)
+    close(f'attention B{B} H{Hh} T{T} Tk{Tk} d{d}', out.t.reshape(B * T, Cc), ref.reshape(B * T, Cc), local=2 * TOL)
 
 
 def test_sampler_kernels(lib):
@@ -277,6 +364,68 @@ def test_sampler_kernels(lib):
     got = E.ancestral_step(x, ec, 1.7, 1.3, 0.2, 0.8, 0.4, nz)
     x0 = 1.7 * x - 1.3 * ec
     assert relerr(got.cpu(), (0.2 * x0 + 0.8 * x + 0.4 * nz).cpu()) < 1e-6
+
+
+SAMPLER_TOL = 1e-6        # fp32 in, fp32 out: only the fp32 rounding of the coefficients and of each operation
+
+
+def _f32_close(what, g, want):
+    got = g.check().cpu()
+    e = relerr(got, want)
+    te = tile_err(got, want, (256,))
+    report(f'{what} [tile_err {te:.3e}]', e, SAMPLER_TOL)
+    assert e < SAMPLER_TOL, (what, e)
+    assert te < 2 * SAMPLER_TOL, (what, 'tile_err', te)
+
+
+@pytest.mark.parametrize('n', [12345, 2 * 4 * 64 * 64])
+def test_sampler_kernels_abi_guarded(lib, n):
+    """The fused sampler updates called through the C ABI (not the engine.py wrappers) on guarded fp32 buffers: an odd element
+    count, every NULL-argument form of fgdm_ddim_step, float64 references."""
+    x, ec, eu, nz = (rnd((n,), s).double() for s in (51, 52, 53, 54))
+    m = torch.rand(n, generator=torch.Generator().manual_seed(55)).double()
+    olds = [rnd((n,), 60 + i).double() for i in range(3)]
+    dx, dec, deu, dnz, dm = (din(t.float()) for t in (x, ec, eu, nz, m))
+    dolds = [din(t.float()) for t in olds]
+    f32 = lambda: guarded_out((n,), torch.float32)
+    a_t, a_prev, sig, cfg = 0.31, 0.42, 0.05, 7.5
+    s1m = float(np.sqrt(1 - a_t))
+    for use_eu in (True, False):
+        for use_nz in (True, False):
+            e = eu + cfg * (ec - eu) if use_eu else ec
+            p0 = (x - s1m * e) / np.sqrt(a_t)
+            xp = np.sqrt(a_prev) * p0 + np.sqrt(1 - a_prev - sig ** 2) * e + (sig * nz if use_nz else 0)
+            # all three outputs, then each one alone (the others NULL)
+            for want_outs in ((1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1)):
+                gs = [f32() if w else None for w in want_outs]
+                rc = lib.fgdm_ddim_step(_p(dx), _p(dec), _p(deu if use_eu else None), cfg, a_t, a_prev, sig, s1m,
+                                        _p(dnz if use_nz else None), *(_p(None if g is None else g.t) for g in gs), n, _st())
+                assert rc == 0
+                torch.cuda.synchronize()
+                for g, want, name in zip(gs, (xp, p0, e), ('x_prev', 'pred_x0', 'e_out')):
+                    if g is not None:
+                        _f32_close(f'ddim_step n{n} eu{int(use_eu)} noise{int(use_nz)} {name}', g, want)
+    for order in (1, 2, 3):
+        o = olds[-order:]
+        want = {1: lambda: (3 * ec - o[-1]) / 2, 2: lambda: (23 * ec - 16 * o[-1] + 5 * o[-2]) / 12,
+                3: lambda: (55 * ec - 59 * o[-1] + 37 * o[-2] - 9 * o[-3]) / 24}[order]()
+        dd = dolds[-order:]
+        e1, e2, e3 = dd[-1], dd[-2] if order >= 2 else None, dd[-3] if order >= 3 else None
+        g = f32()
+        assert lib.fgdm_plms_combine(_p(dec), _p(e1), _p(e2), _p(e3), order, _p(g.t), n, _st()) == 0
+        _f32_close(f'plms_combine n{n} order {order}', g, want)
+    for with_b in (True, False):
+        g = f32()
+        assert lib.fgdm_axpby(_p(dx), 0.5, _p(dec if with_b else None), -1.25, _p(g.t), n, _st()) == 0
+        _f32_close(f'axpby n{n} b{int(with_b)}', g, 0.5 * x + (-1.25 * ec if with_b else 0))
+    g = f32()
+    assert lib.fgdm_mask_blend(_p(dx), _p(dec), _p(dm), _p(g.t), n, _st()) == 0
+    _f32_close(f'mask_blend n{n}', g, x * m + (1 - m) * ec)
+    for use_nz in (True, False):
+        g = f32()
+        assert lib.fgdm_ancestral_step(_p(dx), _p(dec), 1.7, 1.3, 0.2, 0.8, 0.4, _p(dnz if use_nz else None), _p(g.t), n, _st()) == 0
+        x0 = 1.7 * x - 1.3 * ec
+        _f32_close(f'ancestral_step n{n} noise{int(use_nz)}', g, 0.2 * x0 + 0.8 * x + (0.4 * nz if use_nz else 0))
 
 
 # ----------------------------------------------------------------------------- pipelined big-tile kernel (igemm2.hip)
@@ -340,6 +489,117 @@ def test_conv_pipelined_kernel(lib, case):
         lib.fgdm_debug_force_igemm_cfg(0)
 
 
+# the 2-stage kernel's three tiles forced (cfg 1 / 2 / 3: 128x128, 128x64, 64x64; the dispatcher picks 2 and 3 by itself) with
+# M one row short of and one row past a tile, and widths that are not a multiple of the tile width
+TWO_STAGE_CONV_CASES = [
+    (1, 1, 127, 1, 64, 0, 96, 3, 1, 0, 0, 'cfg1 M=127 N=96'),
+    (1, 3, 43, 1, 64, 0, 4, 3, 1, 0, 1, 'cfg1 M=129 N=4 silu'),
+    (2, 1, 127, 1, 64, 64, 192, 3, 1, 0, 0, 'cfg2 M=127 N=192 concat'),
+    (2, 3, 43, 1, 128, 0, 96, 3, 1, 0, 0, 'cfg2 M=129 N=96 rowvec + resid'),
+    (3, 1, 7, 9, 64, 0, 4, 3, 1, 0, 0, 'cfg3 M=63 N=4'),
+    (3, 1, 5, 13, 128, 0, 192, 3, 1, 0, 2, 'cfg3 M=65 N=192 relu rowvec + resid'),
+]
+
+
+@pytest.mark.parametrize('case', TWO_STAGE_CONV_CASES, ids=[c[-1] for c in TWO_STAGE_CONV_CASES])
+def test_conv_two_stage_tiles(lib, case):
+    test_conv_pipelined_kernel(lib, case)
+
+
+TWO_STAGE_BM = {1: 128, 2: 128, 3: 64}
+
+
+@pytest.mark.parametrize('cfg', [1, 2, 3])
+def test_linear_two_stage_tile_edges(lib, cfg):
+    BM, K = TWO_STAGE_BM[cfg], 320
+    x = h16(rnd((BM + 1, K), 81))
+    xd = din(x.half())
+    try:
+        lib.fgdm_debug_force_igemm_cfg(cfg)
+        for N in (4, 96, 192):
+            w, b = h16(rnd((N, K), 82, 1 / np.sqrt(K))), rnd((N,), 83, 0.1)
+            wd, bd = w.cuda(), b.cuda()
+            for M in (BM - 1, BM + 1):
+                res = h16(rnd((M, N), 84))
+                resd = din(res.half())
+                out = guarded_out((M, N), torch.half)
+                assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), _p(resd), M, K, N, 0, 0, 0, 0, _p(out.t), _st()) == 0
+                ref = h16(h16(F.linear(x[:M], w, b)) + res)
+                assert relerr(out.check().float().cpu(), ref) < TOL, (M, N)
+                close(f'2-stage linear cfg {cfg} M{M} N{N}', out.t, ref)
+    finally:
+        lib.fgdm_debug_force_igemm_cfg(0)
+
+
+# pipelined tiles (cfg & 15 -> tile height x width) and their phase-locked K loop (+16)
+PIPE_TILES = {4: (256, 320), 5: (256, 256), 6: (128, 320), 10: (256, 128), 11: (64, 160)}
+
+
+@pytest.mark.parametrize('cfg', [c + p for p in (0, 16) for c in PIPE_TILES])
+def test_linear_pipelined_tile_edges(lib, cfg):
+    """M one row short of a tile, one row past it, and three tiles plus 17 rows, with a residual, on two column tiles: the ragged
+    last row tile of every pipelined tile shape"""
+    BM, BN = PIPE_TILES[cfg & 15]
+    K, N = 320, 2 * BN
+    w, b = h16(rnd((N, K), 85, 1 / np.sqrt(K))), rnd((N,), 86, 0.1)
+    wd, bd = w.cuda(), b.cuda()
+    try:
+        lib.fgdm_debug_force_igemm_cfg(cfg)
+        for M in (BM - 1, BM + 1, 3 * BM + 17):
+            x, res = h16(rnd((M, K), 87)), h16(rnd((M, N), 88))
+            xd, resd = din(x.half()), din(res.half())
+            out = guarded_out((M, N), torch.half)
+            assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), _p(resd), M, K, N, 0, 0, 0, 0, _p(out.t), _st()) == 0
+            ref = h16(h16(F.linear(x, w, b)) + res)
+            assert relerr(out.check().float().cpu(), ref) < TOL, M
+            close(f'pipelined linear cfg {cfg} M{M}', out.t, ref)
+    finally:
+        lib.fgdm_debug_force_igemm_cfg(0)
+
+
+@pytest.mark.parametrize('N', [4, 320, 1280])
+def test_linear_f32_nchw_output(lib, N):
+    """out_kind 2 (OUT_F32_NCHW): the UNet's eps, the ControlNet residuals of the inspection entry and the VAE output leave the
+    GEMM epilogue as fp32 [B][N][rows_per_sample] (ld_out = HW).  N = 4 runs on the 2-stage kernel (the UNet's out conv); the
+    vector path (rows_per_sample % 4 == 0) and a ragged sample length whose boundaries fall inside row tiles; automatic tile,
+    forced cfg 1 and a pipelined tile."""
+    K = 320
+    w, b = h16(rnd((N, K), 75, 1 / np.sqrt(K))), rnd((N,), 76, 0.1)
+    wd, bd = w.cuda(), b.cuda()
+    cfgs = (0, 1, 6) if N % 320 == 0 else (0, 1)
+    try:
+        for rps, Bt in ((100, 3), (77, 3)):
+            Mt = rps * Bt
+            x = h16(rnd((Mt, K), 77))
+            xd = din(x.half())
+            want = F.linear(x, w, b).view(Bt, rps, N).permute(0, 2, 1)
+            for cfg in cfgs:
+                lib.fgdm_debug_force_igemm_cfg(cfg)
+                out = guarded_out((Bt, N, rps), torch.float32)
+                assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, Mt, K, N, 0, 2, rps, rps, _p(out.t), _st()) == 0
+                assert relerr(out.check().cpu(), want) < 2e-5, (cfg, rps)
+                # fp32 store: blockwise 2 x the normwise bar
+                close(f'linear fp32 NCHW N{N} rps {rps} cfg {cfg}', out.t.reshape(-1, rps), want.reshape(-1, rps), 2e-5, 2 * 2e-5)
+    finally:
+        lib.fgdm_debug_force_igemm_cfg(0)
+
+
+@pytest.mark.parametrize('M', [154, 201])
+def test_linear_quick_gelu(lib, M):
+    """act 4, x sigmoid(1.702 x): the CLIP MLP's first projection (768 -> 3072, M = 2 x 77 tokens, and a ragged M); only the
+    2-stage kernel carries it"""
+    K, N = 768, 3072
+    x = h16(rnd((M, K), 78))
+    w, b = h16(rnd((N, K), 79, 1 / np.sqrt(K))), rnd((N,), 80, 0.1)
+    y = F.linear(x, w, b)
+    ref = y * torch.sigmoid(1.702 * y)
+    xd, wd, bd = din(x.half()), w.cuda(), b.cuda()
+    out = guarded_out((M, N), torch.half)
+    assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, M, K, N, 4, 0, 0, 0, _p(out.t), _st()) == 0
+    assert relerr(out.check().float().cpu(), ref) < TOL
+    close(f'linear quick-GELU M{M}', out.t, ref)
+
+
 def test_long_k_linear_at_8_prompts_same_bits_on_every_tile(lib):
     """The 16x16 level's feed-forward output at 8 prompts per GPU (M = 4096, K = 5120 -> 1280, + residual; attention.py:53-64): the
     automatic choice (256x128 tiles, round 4) against torch, and bit for bit against 128x320, 64x160 and the 2-stage kernel --
@@ -348,16 +608,17 @@ def test_long_k_linear_at_8_prompts_same_bits_on_every_tile(lib):
     x = h16(rnd((M, K), 91))
     w, b = h16(rnd((N, K), 92, 1 / np.sqrt(K))), rnd((N,), 93, 0.1)
     res = h16(rnd((M, N), 94))
-    xd, wd, bd, rd = x.half().cuda(), w.cuda(), b.cuda(), res.half().cuda()
+    xd, wd, bd, rd = din(x.half()), w.cuda(), b.cuda(), din(res.half())
     ref = h16(h16(F.linear(x, w, b)) + res)
     outs = {}
     try:
         for cfg in (0, 6, 10, 11, 1):
             lib.fgdm_debug_force_igemm_cfg(cfg)
-            out = torch.empty(M, N, dtype=torch.half, device='cuda')
-            assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), _p(rd), M, K, N, 0, 0, 0, 0, _p(out), _st()) == 0
-            assert relerr(out.float().cpu(), ref) < TOL, cfg
-            outs[cfg] = out
+            out = guarded_out((M, N), torch.half)
+            assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), _p(rd), M, K, N, 0, 0, 0, 0, _p(out.t), _st()) == 0
+            assert relerr(out.check().float().cpu(), ref) < TOL, cfg
+            close(f'long-K linear cfg {cfg}', out.t, ref)
+            outs[cfg] = out.t
     finally:
         lib.fgdm_debug_force_igemm_cfg(0)
     for cfg in (6, 10, 11, 1):
@@ -368,42 +629,46 @@ def test_linear_pipelined_kernel(lib):
     try:
         M, K = 300, 320
         x = h16(rnd((M, K), 71))
-        xd = x.half().cuda()
+        xd = din(x.half())
         # GEGLU through the 256x256 configuration
         N = 2560
         w, b = h16(rnd((N, K), 72, 1 / np.sqrt(K))), rnd((N,), 73, 0.1)
         y = F.linear(x, w, b)
         a, g = y.chunk(2, dim=-1)
-        out = torch.empty(M, N // 2, dtype=torch.half, device='cuda')
         wd, bd = w.cuda(), b.cuda()
         for cfg in (5, 8):
             lib.fgdm_debug_force_igemm_cfg(cfg)
-            out.zero_()
-            assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, M, K, N, 3, 0, 0, 0, _p(out), _st()) == 0
-            assert relerr(out.float().cpu(), a * F.gelu(g)) < TOL, cfg
+            out = guarded_out((M, N // 2), torch.half)
+            assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, M, K, N, 3, 0, 0, 0, _p(out.t), _st()) == 0
+            assert relerr(out.check().float().cpu(), a * F.gelu(g)) < TOL, cfg
+            close(f'pipelined GEGLU cfg {cfg}', out.t, a * F.gelu(g))
         # plain / fp32 / transposed outputs through 256x320 and 128x320
         N2 = 640
         w2, b2 = w[:N2].contiguous(), b[:N2].contiguous()
         w2d, b2d = w2.cuda(), b2.cuda()
         ref = F.linear(x, w2, b2)
         res = h16(rnd((M, N2), 74))
-        resd = res.half().cuda()
+        resd = din(res.half())
         for cfg in (4, 6, 7, 9, 11, 27):      # 11 / 27: the four-wave 64x160 tile, pipelined / phase-locked K loop
             lib.fgdm_debug_force_igemm_cfg(cfg)
-            out = torch.empty(M, N2, dtype=torch.half, device='cuda')
-            assert lib.fgdm_op_linear(_p(xd), _p(w2d), _p(b2d), _p(resd), M, K, N2, 0, 0, 0, 0, _p(out), _st()) == 0
-            assert relerr(out.float().cpu(), ref + res) < TOL, cfg
-            out32 = torch.empty(M, N2, dtype=torch.float32, device='cuda')
-            assert lib.fgdm_op_linear(_p(xd), _p(w2d), _p(b2d), None, M, K, N2, 0, 1, 0, 0, _p(out32), _st()) == 0
-            assert relerr(out32.cpu(), ref) < 2e-5, cfg
+            out = guarded_out((M, N2), torch.half)
+            assert lib.fgdm_op_linear(_p(xd), _p(w2d), _p(b2d), _p(resd), M, K, N2, 0, 0, 0, 0, _p(out.t), _st()) == 0
+            assert relerr(out.check().float().cpu(), ref + res) < TOL, cfg
+            close(f'pipelined linear + resid cfg {cfg}', out.t, ref + res)
+            out32 = guarded_out((M, N2), torch.float32)
+            assert lib.fgdm_op_linear(_p(xd), _p(w2d), _p(b2d), None, M, K, N2, 0, 1, 0, 0, _p(out32.t), _st()) == 0
+            assert relerr(out32.check().cpu(), ref) < 2e-5, cfg
+            close(f'pipelined linear fp32 cfg {cfg}', out32.t, ref, 2e-5, 2 * 2e-5)     # fp32 store: 2 x the normwise bar
             for rps, Bt in ((100, 3), (77, 2)):
                 Mt = rps * Bt
                 ld = (rps + 63) // 64 * 64
-                outT = torch.zeros(Bt, N2, ld, dtype=torch.half, device='cuda')
-                xt = x[:Mt].half().cuda()
-                assert lib.fgdm_op_linear(_p(xt), _p(w2d), _p(b2d), None, Mt, K, N2, 0, 3, rps, ld, _p(outT), _st()) == 0
+                outT = guarded_out((Bt, N2, ld), torch.half)
+                xt = din(x[:Mt].half())
+                assert lib.fgdm_op_linear(_p(xt), _p(w2d), _p(b2d), None, Mt, K, N2, 0, 3, rps, ld, _p(outT.t), _st()) == 0
                 want = ref[:Mt].view(Bt, rps, N2).permute(0, 2, 1)
-                assert relerr(outT[:, :, :rps].float().cpu(), want) < TOL, (cfg, rps)
+                check_transposed(outT, rps, ld)
+                assert relerr(outT.t[:, :, :rps].float().cpu(), want) < TOL, (cfg, rps)
+                close(f'pipelined V^T cfg {cfg} rps {rps}', outT.t[:, :, :rps].reshape(-1, rps), want.reshape(-1, rps))
     finally:
         lib.fgdm_debug_force_igemm_cfg(0)
 
@@ -440,11 +705,14 @@ def test_attention_logit_ranges_d40(lib, gain, shift):
     sim = torch.matmul(split(q).double(), split(k).double().transpose(-1, -2)) * d ** -0.5
     ref = torch.matmul(sim.softmax(-1), split(v).double()).permute(0, 2, 1, 3).reshape(B, T, Cc)
     vt = v.permute(0, 2, 1).half().contiguous()
-    out = torch.empty(B, T, Cc, dtype=torch.half, device='cuda')
-    qd, kd, vtd = q.half().cuda(), k.half().cuda(), vt.cuda()
-    assert lib.fgdm_op_attention(_p(qd), Cc, _p(kd), Cc, _p(vtd), Tk, _p(out), Cc, B, Hh, T, Tk, d, _st()) == 0
-    assert torch.isfinite(out).all()
-    assert relerr(out.float().cpu(), ref) < 2 * TOL, float(sim.abs().max())
+    out = guarded_out((B, T, Cc), torch.half)
+    qd, kd, vtd = din(q.half()), din(k.half()), din(vt)
+    assert lib.fgdm_op_attention(_p(qd), Cc, _p(kd), Cc, _p(vtd), Tk, _p(out.t), Cc, B, Hh, T, Tk, d, _st()) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(out.check()).all()
+    assert relerr(out.t.float().cpu(), ref) < 2 * TOL, float(sim.abs().max())
+    # fp16 P over logits spanning hundreds of log2 units: blockwise 2 x this family's normwise bar
+    close(f'attention logit range gain {gain:g} shift {shift:g}', out.t.reshape(B * T, Cc), ref.reshape(B * T, Cc), 2 * TOL, 4 * TOL)
 
 
 # M, K1, C, N2, act2 (0 / 3 = GEGLU), resid, forced tile cfg (0 = automatic), expected partial-sum slots per row (< 0: from
@@ -481,11 +749,12 @@ def test_layernorm_folded_into_consumer_gemm(lib, case):
     gamma, beta = 1.0 + 0.2 * rnd((Cc,), 5), 0.1 * rnd((Cc,), 6) + 0.05
     w2, b2 = rnd((N2, Cc), 7, Cc ** -0.5), rnd((N2,), 8, 0.1)
     nout = N2 // 2 if act2 == 3 else N2
-    h = torch.empty(M, Cc, dtype=torch.float16, device='cuda')
-    y = torch.empty(M, nout, dtype=torch.float16, device='cuda')
+    gh = guarded_out((M, Cc), torch.float16)
+    gy = guarded_out((M, nout), torch.float16)
+    h, y = gh.t, gy.t
     slots = C.c_int(0)
     dev = lambda t: None if t is None else t.cuda()
-    xs, rs, ws = dev(x), dev(res), [dev(t) for t in (w1, b1, gamma, beta, w2, b2)]
+    xs, rs, ws = din(x), (None if res is None else din(res)), [dev(t) for t in (w1, b1, gamma, beta, w2, b2)]
     try:
         lib.fgdm_debug_force_igemm_cfg(cfg)
         rc = lib.fgdm_op_linear_ln_linear(_p(xs), _p(ws[0]), _p(ws[1]), _p(rs), _p(ws[2]), _p(ws[3]), _p(ws[4]), _p(ws[5]), M, K1, Cc,
@@ -494,11 +763,14 @@ def test_layernorm_folded_into_consumer_gemm(lib, case):
         lib.fgdm_debug_force_igemm_cfg(0)
     assert rc == 0
     assert slots.value == want_slots
+    gh.check()
+    gy.check()
     # producer: fp16 GEMM result, then the fp16 residual added and rounded (the engine's policy)
     h_ref = h16(F.linear(x.float(), h16(w1), b1))
     if use_res:
         h_ref = h16(h_ref + res.float())
     assert relerr(h.float().cpu(), h_ref) < TOL
+    close(f'LayerNorm fold producer M{M} C{Cc} cfg {cfg}', h, h_ref)
     # consumer on the engine's OWN h (so that only the folded LayerNorm + GEMM is judged)
     hh = h.float().cpu()
     wf = h16(w2 * gamma[None, :])
@@ -508,9 +780,11 @@ def test_layernorm_folded_into_consumer_gemm(lib, case):
         a, g = z.chunk(2, dim=-1)
         z = a * F.gelu(g)
     assert relerr(y.float().cpu(), h16(z)) < TOL
+    close(f'LayerNorm fold consumer M{M} C{Cc} N{N2} act{act2} cfg {cfg}', y, h16(z))
     if cfg == 0:      # the same problem forced onto the 2-stage kernels (+ the separate statistics pass): not a bit may differ --
-        h2 = torch.empty_like(h)           # which kernel evaluates a layer depends on the batch size, a sample's result must not
-        y2 = torch.empty_like(y)
+        gh2 = guarded_out((M, Cc), torch.float16)      # which kernel evaluates a layer depends on the batch size, a sample's
+        gy2 = guarded_out((M, nout), torch.float16)    # result must not
+        h2, y2 = gh2.t, gy2.t
         try:
             lib.fgdm_debug_force_igemm_cfg(1)
             assert lib.fgdm_op_linear_ln_linear(_p(xs), _p(ws[0]), _p(ws[1]), _p(rs), _p(ws[2]), _p(ws[3]), _p(ws[4]), _p(ws[5]), M,
@@ -518,6 +792,8 @@ def test_layernorm_folded_into_consumer_gemm(lib, case):
         finally:
             lib.fgdm_debug_force_igemm_cfg(0)
         assert slots.value == -abs(want_slots)
+        gh2.check()
+        gy2.check()
         assert torch.equal(h2, h), 'producer output differs between kernels'
         assert torch.equal(y2, y), 'LayerNorm-folded consumer output differs between kernels'
     # ... which is the reference's LayerNorm -> Linear up to the fp16 rounding of the weights
@@ -542,16 +818,20 @@ def test_layernorm_fold_rows_with_large_mean(lib, offset):
     res = res.half()
     gamma, beta = 1.0 + 0.2 * rnd((Cc,), 5), 0.1 * rnd((Cc,), 6) + 0.05
     w2, b2 = rnd((N2, Cc), 7, Cc ** -0.5), rnd((N2,), 8, 0.1)
-    h = torch.empty(M, Cc, dtype=torch.float16, device='cuda')
-    y = torch.empty(M, N2, dtype=torch.float16, device='cuda')
+    gh = guarded_out((M, Cc), torch.float16)
+    gy = guarded_out((M, N2), torch.float16)
     slots = C.c_int(0)
     ws = [t.cuda() for t in (w1, b1, gamma, beta, w2, b2)]
-    rc = lib.fgdm_op_linear_ln_linear(_p(x.cuda()), _p(ws[0]), _p(ws[1]), _p(res.cuda()), _p(ws[2]), _p(ws[3]), _p(ws[4]), _p(ws[5]), M,
-                                      K1, Cc, N2, 0, _p(h), _p(y), C.byref(slots), _st())
+    xd, rd = din(x), din(res)
+    rc = lib.fgdm_op_linear_ln_linear(_p(xd), _p(ws[0]), _p(ws[1]), _p(rd), _p(ws[2]), _p(ws[3]), _p(ws[4]), _p(ws[5]), M,
+                                      K1, Cc, N2, 0, _p(gh.t), _p(gy.t), C.byref(slots), _st())
     assert rc == 0
-    hh = h.double().cpu()
+    gh.check()
+    y = gy.check()
+    hh = gh.t.double().cpu()
     wf = h16(w2 * gamma[None, :]).double()
     z = F.linear(F.layer_norm(hh, (Cc,), None, None, 1e-5), wf, (w2.double() @ beta.double() + b2.double()))
     err = relerr(y.double().cpu(), z)
     print(f'LayerNorm fold, row mean ~{offset:g} x std: rel_err={err:.3e}')
     assert err < TOL
+    close(f'LayerNorm fold, row mean ~{offset:g} x std', y, z)
