@@ -18,6 +18,7 @@ FLAG_CFG_PAIRS = 8
 
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_GEGLU, ACT_QGELU = 0, 1, 2, 3, 4
 OUT_F16, OUT_F32, OUT_F32_NCHW, OUT_F16_T = 0, 1, 2, 3
+STRIDE2_PAD_BR = -2     # fgdm_op_conv2d `stride`: stride 2, zero padding bottom / right only (the first-stage encoder's Downsample)
 
 
 class FgdmConfig(C.Structure):
@@ -32,6 +33,7 @@ class FgdmConfig(C.Structure):
         ('clip_layers', C.c_int32), ('clip_width', C.c_int32), ('clip_heads', C.c_int32), ('clip_mlp', C.c_int32),
         ('clip_vocab', C.c_int32), ('clip_max_len', C.c_int32),
         ('n_extra_adapters', C.c_int32),
+        ('vae_encoder', C.c_int32),
     ]
 
 
@@ -56,6 +58,8 @@ SIGNATURES = {
     'fgdm_clip_encode': (_i, [_p, _p, _i, _i, _p, _p]),
     'fgdm_run_block': (_i, [_p, C.c_char_p, _p, _i, _p, _i, _p, _p, _i, _i, _i, _p, _i64, C.POINTER(_i64), _p]),
     'fgdm_vae_decode': (_i, [_p, _p, _i, _i, _i, _f, _p, _p]),
+    'fgdm_vae_encode': (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    'fgdm_posterior_sample': (_i, [_p, _p, _f, _p, _i, _i, _i, _p]),
     'fgdm_image_to_uint8': (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     'fgdm_resize_linear_uint8': (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p]),
     'fgdm_uint8_to_hint': (_i, [_p, _i, _i, _i, _i, _p, _p]),

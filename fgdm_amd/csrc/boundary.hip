@@ -104,3 +104,25 @@ int u8_to_hint(const uint8_t* src, float* dst, int B, int HW, int C, hipStream_t
     FGDM_LAUNCH(k_u8_to_hint, dim3(ew_grid((size_t)B * C * HW)), dim3(EW_BLOCK), 0, s, src, dst, B, HW, C);
     return LAUNCH_OK();
 }
+
+// ---------------------------------------------------------------- first-stage posterior (image -> latent boundary)
+// DiagonalGaussianDistribution.sample() / mode() (ldm/modules/distributions/distributions.py:24-37,61-62) times the scale_factor
+// of get_first_stage_encoding (ldm/models/diffusion/ddpm.py:660).  moments [B, 2 zc, HW]: mean | log-variance; noise, z [B, zc, HW]
+// Here because of -ffp-contract=off: under `fast` the compiler also contracts INSIDE its expansion of expf (the split of
+// x log2(e) into a rounded part and its residual) and then counts the residual twice -- measured 6 ulp at x = 10 instead of 1.
+// Uncontracted, the update is also the reference's own sequence of roundings (multiply, add, multiply).
+__global__ void k_posterior_sample(const float* __restrict__ moments, const float* __restrict__ noise, float scale,
+                                   float* __restrict__ z, size_t per /* zc * HW */, size_t n) {
+    EW_LOOP(i, n) {
+        const size_t b = i / per, r = i - b * per;
+        const float mean = moments[b * 2 * per + r];
+        if (!noise) { z[i] = scale * mean; continue; }
+        const float logvar = fminf(fmaxf(moments[(b * 2 + 1) * per + r], -30.0f), 20.0f);
+        z[i] = scale * (mean + expf(0.5f * logvar) * noise[i]);      // expf, not __expf: held to fp32 rounding
+    }
+}
+int posterior_sample(const float* moments, const float* noise, float scale, float* z, int B, int zc, int HW, hipStream_t s) {
+    const size_t per = (size_t)zc * HW, n = (size_t)B * per;
+    FGDM_LAUNCH(k_posterior_sample, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, s, moments, noise, scale, z, per, n);
+    return LAUNCH_OK();
+}

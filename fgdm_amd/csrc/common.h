@@ -58,7 +58,9 @@ __device__ __forceinline__ float silu_f(float x, float k = 1.0f) {
 
 // ---------------------------------------------------------------- implicit GEMM
 // out[m, n] = epilogue( sum_k A[m, k] * W[n, k] ),  m = (b, oy, ox) output pixel, k = (tap, cin)
-enum IgemmMode { IG_LINEAR = 0, IG_CONV3 = 1, IG_CONV3_S2 = 2, IG_CONV3_UP2 = 3 };
+// IG_CONV3_S2_BR: stride 2 with the zero padding on the bottom / right only (the first-stage encoder's Downsample, ldm/modules/
+// diffusionmodules/model.py:72-76: F.pad(x, (0,1,0,1)) then conv3x3 stride 2 padding 0): taps at iy = 2 oy + ky, ix = 2 ox + kx
+enum IgemmMode { IG_LINEAR = 0, IG_CONV3 = 1, IG_CONV3_S2 = 2, IG_CONV3_UP2 = 3, IG_CONV3_S2_BR = 4 };
 enum IgemmAct { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4 /* x * sigmoid(1.702 x), CLIP MLP */ };
 enum IgemmOut { OUT_F16 = 0, OUT_F32 = 1, OUT_F32_NCHW = 2, OUT_F16_T = 3 };
 
@@ -146,6 +148,8 @@ int add_f16(const half_t* a, const half_t* b, half_t* y, size_t n, hipStream_t s
 int add_f16_to_f32(const float* a, const half_t* b, float* y, size_t n, hipStream_t s);   // y = a + float(b): fp32 residual stream
 int timestep_embed(const int64_t* t, const float* t_float, half_t* y, int B, int dim, int rows_pad, hipStream_t s);
 int vae_prequant(const float* z, const float* wb, float scale, half_t* y, int B, int HW, hipStream_t s);
+int vae_moments(const float* h, const float* wb, float* moments, int B, int HW, hipStream_t s);
+int posterior_sample(const float* moments, const float* noise, float scale, float* z, int B, int zc, int HW, hipStream_t s);
 int softmax_rows(const float* S, half_t* P, int rows, int cols, hipStream_t s);
 int image_to_u8(const float* x, uint8_t* y, int B, int C, int HW, int mode, hipStream_t s);
 int resize_linear_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int Ho, int Wo, hipStream_t s);

@@ -292,6 +292,30 @@ int vae_prequant(const float* z, const float* wb, float scale, half_t* y, int B,
     return LAUNCH_OK();
 }
 
+// ---------------------------------------------------------------- first-stage encoder helpers
+// quant_conv (1x1, 8 -> 8; ldm/models/autoencoder.py:326) applied to the encoder's conv_out, fused with the layout change:
+// h [B, HW, 8] fp32 (the GEMM's OUT_F32 rows)  ->  moments [B, 8, HW] fp32.   wb = 64 weights [co][ci] then 8 biases (device, fp32)
+__global__ void k_vae_moments(const float* __restrict__ h, const float* __restrict__ wb, float* __restrict__ moments, int B, int HW) {
+    const size_t n = (size_t)B * HW;
+    EW_LOOP(i, n) {
+        const size_t b = i / HW, p = i - b * HW;
+        const f32x4 lo = *(const f32x4*)(h + i * 8), hi = *(const f32x4*)(h + i * 8 + 4);
+        const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+        for (int co = 0; co < 8; ++co) {
+            float acc = wb[64 + co];
+#pragma unroll
+            for (int ci = 0; ci < 8; ++ci) acc += wb[co * 8 + ci] * v[ci];
+            moments[(b * 8 + co) * HW + p] = acc;
+        }
+    }
+}
+int vae_moments(const float* h, const float* wb, float* moments, int B, int HW, hipStream_t s) {
+    FGDM_LAUNCH(k_vae_moments, dim3(ew_grid((size_t)B * HW)), dim3(EW_BLOCK), 0, s, h, wb, moments, B, HW);
+    return LAUNCH_OK();
+}
+// (k_posterior_sample, the other first-stage encoder helper, lives in boundary.hip: it must be compiled without contraction)
+
 // P[r][:] = softmax(S[r][:]) over `cols` fp32 logits -> fp16 probabilities; one 256-thread block per row
 // (AttnBlock, ldm/modules/diffusionmodules/model.py:190-192: single head, the T x T score matrix of one image)
 __global__ __launch_bounds__(256) void k_softmax_rows(const float* __restrict__ S, half_t* __restrict__ P, int cols) {

@@ -151,17 +151,29 @@ struct Net {
 // First-stage decoder (AutoencoderKL.decode; ldm/modules/diffusionmodules/model.py:462-560)
 struct VRes { int cin = 0, cout = 0; std::string pre; NormW n1, n2; GemmW c1, c2, nin; };
 struct VLevel { std::vector<VRes> blocks; bool up = false; std::string up_pre; GemmW upconv; };
+struct VAttn { std::string pre; NormW norm; GemmW q, k, v, o; };      // AttnBlock (model.py:146-203)
+// First-stage encoder (AutoencoderKL.encode; model.py:368-460), present when fgdm_config::vae_encoder is set
+struct VDown { std::vector<VRes> blocks; bool down = false; std::string down_pre; GemmW downconv; };
+struct VEnc {
+    bool on = false;
+    GemmW conv_in, conv_out;
+    std::vector<VDown> levels;             // execution order: full resolution first
+    VRes mid1, mid2;
+    VAttn attn;
+    NormW norm_out;
+    float* qc = nullptr;                   // quant_conv: 64 weights [co][ci] + 8 biases
+};
 struct Vae {
     bool on = false, packed = false;
     std::string prefix;
     int top = 0, factor = 1;
     GemmW conv_in, conv_out;
     VRes mid1, mid2;
-    std::string attn_pre;
-    NormW attn_norm; GemmW aq, ak, av, ao;
+    VAttn attn;
     std::vector<VLevel> levels;            // execution order: deepest level first
     NormW norm_out;
     float* pq = nullptr;                   // post_quant_conv: 16 weights [co][ci] + 4 biases
+    VEnc enc;
 };
 
 // CLIP text encoder (transformers.CLIPTextModel behind FrozenCLIPEmbedder; ldm/modules/encoders/modules.py:137-162)
@@ -499,7 +511,37 @@ struct fgdm_engine {
         reg_wb(pre + "conv2", {cout, cout, 3, 3});
         if (cin != cout) reg_wb(pre + "nin_shortcut", {cout, cin, 1, 1});
     }
-    // Decoder.__init__ (model.py:486-530) + post_quant_conv (autoencoder.py:303); keys in module-registration order
+    void reg_vattn(VAttn& at, const std::string& pre, int c) {
+        at.pre = pre;
+        reg_wb(pre + "norm", {c});
+        for (const char* n : {"q", "k", "v", "proj_out"}) reg_wb(pre + n, {c, c, 1, 1});
+    }
+    // Encoder.__init__ (model.py:368-435) with double_z = True and in_channels = 3; keys in module-registration order
+    void build_vae_encoder() {
+        const int L = cfg.vae_n_levels, ch = cfg.vae_ch, nrb = cfg.vae_num_res_blocks;
+        VEnc& en = vae.enc;
+        en.on = true;
+        const std::string d = vae.prefix + "encoder.";
+        reg_wb(d + "conv_in", {ch, 3, 3, 3});
+        int block_in = ch;
+        en.levels.resize(L);
+        for (int lvl = 0; lvl < L; ++lvl) {
+            const std::string lp = d + "down." + std::to_string(lvl) + ".";
+            const int block_out = ch * cfg.vae_ch_mult[lvl];
+            VDown& lv = en.levels[lvl];
+            lv.blocks.resize(nrb);
+            for (int i = 0; i < nrb; ++i) { reg_vres(lv.blocks[i], lp + "block." + std::to_string(i) + ".", block_in, block_out); block_in = block_out; }
+            lv.down = lvl != L - 1;
+            if (lv.down) { lv.down_pre = lp + "downsample.conv"; reg_wb(lv.down_pre, {block_in, block_in, 3, 3}); }
+        }
+        reg_vres(en.mid1, d + "mid.block_1.", block_in, block_in);
+        reg_vattn(en.attn, d + "mid.attn_1.", block_in);
+        reg_vres(en.mid2, d + "mid.block_2.", block_in, block_in);
+        reg_wb(d + "norm_out", {block_in});
+        reg_wb(d + "conv_out", {2 * cfg.vae_z_channels, block_in, 3, 3});
+    }
+    // Decoder.__init__ (model.py:486-530) + post_quant_conv (autoencoder.py:303); keys in module-registration order.  With
+    // vae_encoder the whole AutoencoderKL (autoencoder.py:298-303): encoder.*, decoder.*, quant_conv.*, post_quant_conv.*
     int build_vae() {
         const int L = cfg.vae_n_levels, ch = cfg.vae_ch, nrb = cfg.vae_num_res_blocks;
         if (L < 1 || L > FGDM_MAX_LEVELS || (ch & 63) || nrb < 0 || cfg.vae_z_channels != 4 || cfg.vae_out_ch < 1 || cfg.vae_out_ch > 8)
@@ -508,13 +550,12 @@ struct fgdm_engine {
         v.on = true;
         v.prefix = "first_stage_model.";
         v.factor = 1 << (L - 1);
+        if (cfg.vae_encoder) build_vae_encoder();
         const std::string d = v.prefix + "decoder.";
         v.top = ch * cfg.vae_ch_mult[L - 1];
         reg_wb(d + "conv_in", {v.top, 4, 3, 3});
         reg_vres(v.mid1, d + "mid.block_1.", v.top, v.top);
-        v.attn_pre = d + "mid.attn_1.";
-        reg_wb(v.attn_pre + "norm", {v.top});
-        for (const char* n : {"q", "k", "v", "proj_out"}) reg_wb(v.attn_pre + n, {v.top, v.top, 1, 1});
+        reg_vattn(v.attn, d + "mid.attn_1.", v.top);
         reg_vres(v.mid2, d + "mid.block_2.", v.top, v.top);
         std::vector<VLevel> asc(L);
         int block_in = v.top;
@@ -539,6 +580,7 @@ struct fgdm_engine {
         const int c0 = ch * cfg.vae_ch_mult[0];
         reg_wb(d + "norm_out", {c0});
         reg_wb(d + "conv_out", {cfg.vae_out_ch, c0, 3, 3});
+        if (v.enc.on) reg_wb(v.prefix + "quant_conv", {2 * cfg.vae_z_channels, 2 * cfg.vae_z_channels, 1, 1});
         reg_wb(v.prefix + "post_quant_conv", {4, 4, 1, 1});
         return FGDM_OK;
     }
@@ -584,6 +626,8 @@ struct fgdm_engine {
         cns.resize(cfg.n_controlnets);
         for (int k = 0; k < cfg.n_controlnets; ++k)
             build_net(cns[k], k == 0 ? std::string("control_model.") : "control_model_" + std::to_string(k) + ".", true, 0);
+        if (cfg.vae_encoder < 0 || cfg.vae_encoder > 1 || (cfg.vae_encoder && cfg.vae_ch <= 0))
+            return fail(FGDM_ERR_ARG, "vae_encoder: 0 none, 1 first-stage encoder (needs the first-stage config: vae_ch > 0)");
         if (cfg.vae_ch > 0) CHK0(build_vae());
         if (cfg.clip_layers > 0) CHK0(build_clip());
         return FGDM_OK;
@@ -845,16 +889,46 @@ struct fgdm_engine {
         if (r.cin != r.cout) CHK(pack_linear(r.nin, r.pre + "nin_shortcut", true));
         return FGDM_OK;
     }
+    int pack_vattn(VAttn& at) {
+        CHK(pack_norm(at.norm, at.pre + "norm"));
+        CHK(pack_linear(at.q, at.pre + "q", true));
+        CHK(pack_linear(at.k, at.pre + "k", true));
+        CHK(pack_linear(at.v, at.pre + "v", true));
+        CHK(pack_linear(at.o, at.pre + "proj_out", true));
+        return FGDM_OK;
+    }
+    // fp32 [co][ci] weights of a 1x1 convolution followed by its biases, for the per-pixel kernels (vae_prequant, vae_moments)
+    int pack_pointwise(float** dst, const std::string& pre) {
+        const ParamSlot* w = slot(pre + ".weight");
+        const ParamSlot* b = slot(pre + ".bias");
+        if (!w || !b) return FGDM_ERR_STATE;
+        std::vector<float> wb(w->host);
+        wb.insert(wb.end(), b->host.begin(), b->host.end());
+        *dst = upload(wb);
+        return *dst ? FGDM_OK : fail(FGDM_ERR_NOMEM, "hipMalloc failed");
+    }
+    int pack_vae_encoder() {
+        VEnc& en = vae.enc;
+        const std::string d = vae.prefix + "encoder.";
+        CHK(pack_conv3(en.conv_in, d + "conv_in"));          // Cin = 3: the im2col layout, cin_pad 4
+        for (auto& lv : en.levels) {
+            for (auto& r : lv.blocks) CHK(pack_vres(r));
+            if (lv.down) CHK(pack_conv3(lv.downconv, lv.down_pre));
+        }
+        CHK(pack_vres(en.mid1));
+        CHK(pack_vattn(en.attn));
+        CHK(pack_vres(en.mid2));
+        CHK(pack_norm(en.norm_out, d + "norm_out"));
+        CHK(pack_conv3(en.conv_out, d + "conv_out"));
+        return pack_pointwise(&en.qc, vae.prefix + "quant_conv");
+    }
     int pack_vae() {
         Vae& v = vae;
+        if (v.enc.on) CHK(pack_vae_encoder());
         const std::string d = v.prefix + "decoder.";
         CHK(pack_conv3(v.conv_in, d + "conv_in"));
         CHK(pack_vres(v.mid1));
-        CHK(pack_norm(v.attn_norm, v.attn_pre + "norm"));
-        CHK(pack_linear(v.aq, v.attn_pre + "q", true));
-        CHK(pack_linear(v.ak, v.attn_pre + "k", true));
-        CHK(pack_linear(v.av, v.attn_pre + "v", true));
-        CHK(pack_linear(v.ao, v.attn_pre + "proj_out", true));
+        CHK(pack_vattn(v.attn));
         CHK(pack_vres(v.mid2));
         for (auto& lv : v.levels) {
             for (auto& r : lv.blocks) CHK(pack_vres(r));
@@ -862,13 +936,7 @@ struct fgdm_engine {
         }
         CHK(pack_norm(v.norm_out, d + "norm_out"));
         CHK(pack_conv3(v.conv_out, d + "conv_out"));
-        const ParamSlot* w = slot(v.prefix + "post_quant_conv.weight");
-        const ParamSlot* b = slot(v.prefix + "post_quant_conv.bias");
-        if (!w || !b) return FGDM_ERR_STATE;
-        std::vector<float> wb(w->host);
-        wb.insert(wb.end(), b->host.begin(), b->host.end());
-        v.pq = upload(wb);
-        if (!v.pq) return fail(FGDM_ERR_NOMEM, "hipMalloc failed");
+        CHK(pack_pointwise(&v.pq, v.prefix + "post_quant_conv"));
         for (auto& name : order)
             if (name.compare(0, v.prefix.size(), v.prefix) == 0) { auto& ps = params[name]; std::vector<float>().swap(ps.host); }
         v.packed = true;
@@ -1005,15 +1073,16 @@ struct fgdm_engine {
         }
         return rc == FGDM_OK ? rc : fail(rc, "igemm launch failed");
     }
-    // conv3x3 (stride 1/2, or on the nearest-2x upsampled input) -> new tensor
+    // conv3x3 (stride 1/2, FGDM_STRIDE2_PAD_BR, or on the nearest-2x upsampled input) -> new tensor
     int conv3(const GemmW& w, const Tensor& x, const Tensor* x1, int stride, bool up, Epi e, Tensor* out) {
         int Ho = x.H, Wo = x.W, mode = IG_CONV3;
         if (up) { Ho *= 2; Wo *= 2; mode = IG_CONV3_UP2; }
         else if (stride == 2) { Ho = (x.H - 1) / 2 + 1; Wo = (x.W - 1) / 2 + 1; mode = IG_CONV3_S2; }
+        else if (stride == FGDM_STRIDE2_PAD_BR) { Ho = (x.H - 2) / 2 + 1; Wo = (x.W - 2) / 2 + 1; mode = IG_CONV3_S2_BR; }
         const bool own_out = (e.out == nullptr);
         if (own_out) { *out = talloc(x.B, Ho, Wo, w.N); if (!out->p) return fail(FGDM_ERR_NOMEM, "workspace"); }
         if (!w.im2col) return gemm(w, mode, x, x1, Ho, Wo, e, out);
-        if (up || x1 || x.C != w.cin_pad) return fail(FGDM_ERR_ARG, "im2col conv path: unsupported combination");
+        if (up || x1 || x.C != w.cin_pad || stride == FGDM_STRIDE2_PAD_BR) return fail(FGDM_ERR_ARG, "im2col conv path: unsupported combination");
         Tensor A = talloc(1, 1, x.B * Ho * Wo, w.K);
         if (!A.p) return fail(FGDM_ERR_NOMEM, "workspace (im2col)");
         prof.begin(PC_ELEM, s, 2.0 * (double)A.numel() + 2.0 * (double)x.numel());
@@ -1881,13 +1950,12 @@ struct fgdm_engine {
     // AttnBlock.forward (model.py:176-203): ONE head over all C channels.  d = C = 512 does not fit the flash kernel's
     // register budget, so per image: S = C^-1/2 Q K^T (fp32, GEMM with K as the "weight"), row softmax, O = P V
     // (GEMM with V^T, written transposed by the v projection's epilogue, as the weight).
-    int vattn_fwd(const Tensor& x, Tensor* out) {
-        const Vae& v = vae;
+    int vattn_fwd(const VAttn& at, const Tensor& x, Tensor* out) {
         const int B = x.B, T = x.H * x.W, C = x.C;
         if (T & 63) return fail(FGDM_ERR_ARG, "first-stage attention: H*W must be a multiple of 64");
         Tensor g, q, k, vt, a, P;
-        CHK(gnorm(v.attn_norm, x, nullptr, 1e-6f, false, &g));
-        CHK(linear(v.aq, g, Epi{}, &q));
+        CHK(gnorm(at.norm, x, nullptr, 1e-6f, false, &g));
+        CHK(linear(at.q, g, Epi{}, &q));
         k = talloc(1, 1, B * T + 128, C);        // + 128 rows: the GEMM reads whole 128-row weight tiles
         vt = talloc(B, 1, C, T);
         a = talloc(B, x.H, x.W, C);
@@ -1895,8 +1963,8 @@ struct fgdm_engine {
         float* S = (float*)ar->alloc((size_t)T * T * sizeof(float));
         if (!k.p || !vt.p || !a.p || !P.p || !S) return fail(FGDM_ERR_NOMEM, "workspace");
         HIP_TRY(hipMemsetAsync(k.p + (size_t)B * T * C, 0, (size_t)128 * C * sizeof(half_t), s));
-        { Epi e; e.out = k.p; e.ld_out = C; e.rps = T; CHK(linear(v.ak, g, e, nullptr)); }
-        { Epi e; e.out_kind = OUT_F16_T; e.out = vt.p; e.ld_out = T; e.rps = T; CHK(linear(v.av, g, e, nullptr)); }
+        { Epi e; e.out = k.p; e.ld_out = C; e.rps = T; CHK(linear(at.k, g, e, nullptr)); }
+        { Epi e; e.out_kind = OUT_F16_T; e.out = vt.p; e.ld_out = T; e.rps = T; CHK(linear(at.v, g, e, nullptr)); }
         tfree(g);
         for (int b = 0; b < B; ++b) {
             GemmW wk; wk.w = k.p + (size_t)b * T * C; wk.N = T; wk.K = C; wk.k_real = C;
@@ -1910,7 +1978,7 @@ struct fgdm_engine {
         }
         ar->release(S);
         tfree(P); tfree(q); tfree(k); tfree(vt);
-        { Epi e; e.resid = x.p; e.ld_res = C; CHK(linear(v.ao, a, e, out)); }
+        { Epi e; e.resid = x.p; e.ld_res = C; CHK(linear(at.o, a, e, out)); }
         tfree(a);
         return FGDM_OK;
     }
@@ -1934,7 +2002,7 @@ struct fgdm_engine {
             CHK(conv3(v.conv_in, z4, nullptr, 1, false, Epi{}, &h));
             tfree(z4);
             CHK(vres_fwd(v.mid1, h, &t)); tfree(h); h = t;
-            CHK(vattn_fwd(h, &t)); tfree(h); h = t;
+            CHK(vattn_fwd(v.attn, h, &t)); tfree(h); h = t;
             CHK(vres_fwd(v.mid2, h, &t)); tfree(h); h = t;
             for (const VLevel& lv : v.levels) {
                 for (const VRes& r : lv.blocks) { CHK(vres_fwd(r, h, &t)); tfree(h); h = t; }
@@ -1946,6 +2014,47 @@ struct fgdm_engine {
             { Epi e; e.out_kind = OUT_F32_NCHW; e.out = out + (size_t)b0 * out_per_img; e.ld_out = g.H * g.W;
               CHK(conv3(v.conv_out, g, nullptr, 1, false, e, nullptr)); }
             tfree(g);
+        }
+        return FGDM_OK;
+    }
+
+    // LatentDiffusion.encode_first_stage (ddpm.py:952-996, plain branch) -> AutoencoderKL.encode (autoencoder.py:324-328) ->
+    // Encoder.forward (model.py:436-460) + quant_conv.  image fp32 NCHW [B,3,H,W] -> moments fp32 NCHW [B,2*z_channels,H/f,W/f]
+    int vae_encode(const float* image, int B, int H, int W, float* moments) {
+        if (!vae.on || !vae.enc.on) return fail(FGDM_ERR_STATE, "engine was created without a first-stage encoder (vae_encoder = 0)");
+        if (!vae.packed) return fail(FGDM_ERR_STATE, "weights not finalized");
+        const VEnc& en = vae.enc;
+        const int f = vae.factor;
+        if (B <= 0 || H <= 0 || W <= 0 || H % f || W % f || (((H / f) * (W / f)) & 63))
+            return fail(FGDM_ERR_ARG, "first-stage encoder: H and W must be multiples of " + std::to_string(f) + " and (H/" + std::to_string(f) +
+                                      ")*(W/" + std::to_string(f) + ") a multiple of 64 (smallest image 64 x 64)");
+        const int hw = (H / f) * (W / f), zc2 = 2 * cfg.vae_z_channels;
+        // images per pass: ~8 live full-resolution tensors of `ch` channels must fit comfortably in one slab (as vae_decode)
+        const size_t big = (size_t)H * W * cfg.vae_ch * sizeof(half_t) * 8;
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, ((size_t)3 << 30) / std::max<size_t>(big, 1)));
+        for (int b0 = 0; b0 < B; b0 += chunk) {
+            const int nb = std::min(chunk, B - b0);
+            Tensor x4 = talloc(nb, H, W, en.conv_in.cin_pad), h, t;      // 3 -> 4 channels
+            if (!x4.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            if (nchw_f32_to_nhwc_f16(image + (size_t)b0 * 3 * H * W, x4.p, nb, 3, H * W, x4.C, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
+            CHK(conv3(en.conv_in, x4, nullptr, 1, false, Epi{}, &h));
+            tfree(x4);
+            for (const VDown& lv : en.levels) {
+                for (const VRes& r : lv.blocks) { CHK(vres_fwd(r, h, &t)); tfree(h); h = t; }
+                if (lv.down) { CHK(conv3(lv.downconv, h, nullptr, FGDM_STRIDE2_PAD_BR, false, Epi{}, &t)); tfree(h); h = t; }
+            }
+            CHK(vres_fwd(en.mid1, h, &t)); tfree(h); h = t;
+            CHK(vattn_fwd(en.attn, h, &t)); tfree(h); h = t;
+            CHK(vres_fwd(en.mid2, h, &t)); tfree(h); h = t;
+            Tensor g;
+            CHK(gnorm(en.norm_out, h, nullptr, 1e-6f, true, &g));
+            tfree(h);
+            float* h32 = (float*)ar->alloc((size_t)nb * hw * zc2 * sizeof(float));      // conv_out, fp32 [pixel][2 z_channels]
+            if (!h32) return fail(FGDM_ERR_NOMEM, "workspace");
+            { Epi e; e.out_kind = OUT_F32; e.out = h32; e.ld_out = zc2; CHK(conv3(en.conv_out, g, nullptr, 1, false, e, nullptr)); }
+            tfree(g);
+            if (vae_moments(h32, en.qc, moments + (size_t)b0 * zc2 * hw, nb, hw, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "moments kernel");
+            ar->release(h32);
         }
         return FGDM_OK;
     }
@@ -2253,6 +2362,15 @@ int fgdm_vae_decode(fgdm_engine* e, const float* z, int B, int H, int W, float s
     return scoped_call(e, stream, [&] { return e->vae_decode(z, B, H, W, scale, image); });
 }
 
+int fgdm_vae_encode(fgdm_engine* e, const float* image, int B, int H, int W, float* moments, void* stream) {
+    if (!e || !image || !moments) return FGDM_ERR_ARG;
+    return scoped_call(e, stream, [&] { return e->vae_encode(image, B, H, W, moments); });
+}
+int fgdm_posterior_sample(const float* moments, const float* noise, float scale, float* z, int B, int zc, int HW, void* stream) {
+    if (!moments || !z || B <= 0 || zc <= 0 || HW <= 0) return FGDM_ERR_ARG;
+    return posterior_sample(moments, noise, scale, z, B, zc, HW, as_stream(stream));
+}
+
 int fgdm_controlnet(fgdm_engine* e, int cn, const float* x, const int64_t* t, const float* ctx, int B, int H, int W,
                     float* out, int64_t out_capacity_floats, void* stream) {
     if (!e || !x || !t || !ctx || !out) return FGDM_ERR_ARG;
@@ -2361,6 +2479,7 @@ int fgdm_op_conv2d(const void* x0, int C0, const void* x1, int C1, const float* 
                    const void* resid, int B, int H, int W, int Cout, int ksize, int stride, int upsample, int act,
                    float scale, void* out, void* stream) {
     if (!x0 || !w || !out || (ksize != 1 && ksize != 3)) return FGDM_ERR_ARG;
+    if (stride == FGDM_STRIDE2_PAD_BR && (ksize != 3 || upsample)) return FGDM_ERR_ARG;
     hipStream_t s = as_stream(stream);
     const int Cin = C0 + C1, taps = ksize * ksize, K = taps * Cin;
     if (Cin & 63) return FGDM_ERR_ARG;
@@ -2392,6 +2511,10 @@ int fgdm_op_conv2d(const void* x0, int C0, const void* x1, int C1, const float* 
         a.mode = IG_CONV3;
         if (upsample) { a.Ho = 2 * H; a.Wo = 2 * W; a.mode = IG_CONV3_UP2; }
         else if (stride == 2) { a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1; a.mode = IG_CONV3_S2; }
+        else if (stride == FGDM_STRIDE2_PAD_BR) {
+            if (H < 2 || W < 2) return FGDM_ERR_ARG;
+            a.Ho = (H - 2) / 2 + 1; a.Wo = (W - 2) / 2 + 1; a.mode = IG_CONV3_S2_BR;
+        }
     }
     a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = K;
     a.act = act; a.out_kind = OUT_F16; a.out = out; a.ld_out = Cout;

@@ -4,7 +4,8 @@
 //   m = output pixel (b, oy, ox) of an NHWC fp16 activation, k = (tap, cin), W packed [N][K] K-contiguous.
 //
 // Covers every dense contraction of the hot path (SURVEY.md section 2 op inventory): conv3x3 s1 / s2, conv3x3 on a
-// nearest-2x-upsampled input (upsample folded into the address calculation), conv1x1 / nn.Linear, and the
+// nearest-2x-upsampled input (upsample folded into the address calculation), conv3x3 s2 padded bottom / right only
+// (the first-stage encoder's Downsample), conv1x1 / nn.Linear, and the
 // channel concat of the UNet decoder as two base pointers ("virtual concat").  Epilogue fuses bias, the
 // ResBlock timestep-embedding add, SiLU / ReLU / GEGLU, the ControlNet scale and the residual add.
 //
@@ -114,6 +115,9 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_kernel(const IgemmArgs a) 
                     } else if (a.mode == IG_CONV3_S2) {
                         iy = 2 * oy + ky - 1; ix = 2 * ox + kx - 1;
                         ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+                    } else if (a.mode == IG_CONV3_S2_BR) {   // padding on the bottom / right only
+                        iy = 2 * oy + ky; ix = 2 * ox + kx;
+                        ok = iy < a.H && ix < a.W;
                     } else {   // IG_CONV3_UP2: conv over the virtual 2H x 2W nearest-upsampled image
                         const int uy = oy + ky - 1, ux = ox + kx - 1;
                         ok = (unsigned)uy < (unsigned)(2 * a.H) && (unsigned)ux < (unsigned)(2 * a.W);

@@ -132,7 +132,10 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
     // B slot likewise; a surplus B slot repeats the last instruction (same bytes to the same LDS address: harmless)
     int a_pix[LA], a_yx[LA], a_off[LA];      // pixel base, (oy,ox), source chunk offset (halfs); pix = -1: row >= M
     int b_off[LB], b_lds[LB];
-    const int sy = (CONV && a.mode == IG_CONV3_S2) ? 2 : 1;
+    // IG_CONV3_S2_BR (stride 2, zero padding bottom / right only: taps at 2 oy + ky) is the stride-2 walk around the centre
+    // (2 oy + 1, 2 ox + 1): only the origin `br` differs, the taps' displacements and the bounds test are the padded form's
+    const int br = (CONV && a.mode == IG_CONV3_S2_BR) ? 1 : 0;
+    const int sy = (CONV && (a.mode == IG_CONV3_S2 || a.mode == IG_CONV3_S2_BR)) ? 2 : 1;
     const int up = (CONV && a.mode == IG_CONV3_UP2) ? 1 : 0;
 #pragma unroll
     for (int i = 0; i < LA; ++i) {
@@ -148,7 +151,7 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
                 const int b = m / hw, rem = m - b * hw;
                 const int oy = rem / a.Wo, ox = rem - oy * a.Wo;
                 a_pix[i] = b * a.H * a.W;
-                a_yx[i] = ((oy * sy) << 16) | (ox * sy);
+                a_yx[i] = ((oy * sy + br) << 16) | (ox * sy + br);
             }
         }
     }
@@ -181,7 +184,7 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
                 if (CONV) {
                     const int hw = a.Ho * a.Wo;
                     const int b = m / hw, rem = m - b * hw;
-                    const int oy = (rem / a.Wo) * sy, ox = (rem - (rem / a.Wo) * a.Wo) * sy;
+                    const int oy = (rem / a.Wo) * sy + br, ox = (rem - (rem / a.Wo) * a.Wo) * sy + br;
                     // nearest-2x upsampled input (up = 1): (oy, ox) are coordinates of the upsampled image, the centre is the
                     // source pixel (oy >> 1, ox >> 1), and a tap's source displacement depends on the parity of oy / ox:
                     // bits 16 / 17 of the mask say "oy even" / "ox even"

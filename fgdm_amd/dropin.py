@@ -28,7 +28,9 @@ _MAP = {
     'ldm.models.diffusion.plms': {'PLMSSampler': samplers.PLMSSampler},
     'ldm.models.diffusion.dpm_solver': {'DPMSolverSampler': samplers.DPMSolverSampler},
     'ldm.models.diffusion.ddpm': {'LatentDiffusion': models.LatentDiffusion, 'DiffusionWrapper': models.DiffusionWrapper},
+    'ldm.modules.distributions.distributions': {'DiagonalGaussianDistribution': models.DiagonalGaussianDistribution},
     'controlnet.ldm.util': {'instantiate_from_config': config.instantiate_from_config},
+    'controlnet.ldm.modules.distributions.distributions': {'DiagonalGaussianDistribution': models.DiagonalGaussianDistribution},
     'controlnet.cldm.ddim_hacked': {'DDIMSampler': samplers.ControlDDIMSampler},
     'controlnet.cldm.cldm': {'ControlLDM': models.ControlLDM},
     'controlnet.cldm.model': _CLDM_MODEL,

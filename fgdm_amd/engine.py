@@ -23,10 +23,13 @@ SD_CLIP = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hi
 
 
 def make_config(cfg=None, use_adapter=False, n_controlnets=0, hint_channels=3, workspace_bytes=0, vae=None, clip=None,
-                num_prompts=1):
+                num_prompts=1, vae_encoder=False):
     """fgdm_config from the reference's UNetModel kwargs (models/config.yaml:33-48); `vae`: None (no first-stage
     decoder), True (SD_VAE) or the AutoencoderKL `ddconfig` dict; `clip`: None, True (SD_CLIP) or a CLIPTextConfig-style
-    dict (text encoder in the engine)."""
+    dict (text encoder in the engine); `vae_encoder`: also the first-stage ENCODER of that `vae` (AutoencoderKL.encode: the
+    parameter table then lists the whole AutoencoderKL.state_dict(), encoder.* and quant_conv.* included)."""
+    if vae_encoder and not vae:
+        raise ValueError('vae_encoder needs the first-stage config: pass vae=True or a ddconfig dict')
     if cfg is not None and ('target' in cfg or any(k not in SD_V1 for k in cfg)):
         from . import config as _cfgmod          # {target, params} node / OmegaConf / dict with extra UNetModel kwargs
         cfg = _cfgmod.unet_params(cfg)[1]
@@ -62,6 +65,10 @@ def make_config(cfg=None, use_adapter=False, n_controlnets=0, hint_channels=3, w
         c.vae_num_res_blocks = dd['num_res_blocks']
         c.vae_z_channels = dd['z_channels']
         c.vae_out_ch = dd['out_ch']
+        if vae_encoder:
+            if not dd.get('double_z', True) or dd.get('in_channels', 3) != 3:
+                raise ValueError('first-stage encoder: double_z = True and in_channels = 3 are required')
+            c.vae_encoder = 1
     if clip:
         cc = dict(SD_CLIP if clip is True else clip)
         c.clip_layers = cc['num_hidden_layers']
@@ -131,13 +138,14 @@ class Engine:
     """One engine per device: owns packed weights + activation workspace in HBM."""
 
     def __init__(self, cfg=None, use_adapter=False, n_controlnets=0, device=0, workspace_bytes=0, vae=None, clip=None,
-                 num_prompts=1):
+                 num_prompts=1, vae_encoder=False):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError('fgdm_amd.Engine needs a GPU (MI355X); there is no CPU fallback')
         self.config = make_config(cfg, use_adapter, n_controlnets, workspace_bytes=workspace_bytes, vae=vae, clip=clip,
-                                  num_prompts=num_prompts)
+                                  num_prompts=num_prompts, vae_encoder=vae_encoder)
         self.has_vae = bool(vae)
+        self.has_vae_encoder = bool(vae_encoder)
         self.has_clip = bool(clip)
         self.device = torch.device('cuda', device)
         torch.cuda.set_device(self.device)
@@ -306,6 +314,23 @@ class Engine:
         self._check(rc, 'fgdm_vae_decode')
         return img
 
+    def vae_encode(self, image):
+        """AutoencoderKL.encode(image).parameters: fp32 NCHW images [B,3,H,W] in [-1,1] -> fp32 NCHW moments [B,8,H/8,W/8]
+        (channels 0-3 the posterior mean, 4-7 its log-variance).  Needs an engine built with vae_encoder=True."""
+        image = image.to(self.device, torch.float32).contiguous()
+        B, Cc, H, W = image.shape
+        if Cc != 3:
+            raise ValueError(f'vae_encode: image {tuple(image.shape)} must have 3 channels')
+        f = 1 << (self.config.vae_n_levels - 1)
+        moments = torch.empty(B, 2 * self.config.vae_z_channels, H // f, W // f, device=self.device, dtype=torch.float32)
+        rc = self.lib.fgdm_vae_encode(self.h, _ptr(image), B, H, W, _ptr(moments), _stream())
+        self._check(rc, 'fgdm_vae_encode')
+        return moments
+
+    def posterior_sample(self, moments, noise=None, scale=1.0):
+        """scale * DiagonalGaussianDistribution(moments).sample() with the given noise, or scale * mode() without."""
+        return posterior_sample(moments.to(self.device), None if noise is None else noise.to(self.device), scale)
+
     def run_block(self, prefix, x, emb=None, ctx=None, x_skip=None):
         """One block (or one layer of a block, or the FG-DM adapter) of the loaded graph by state-dict prefix, e.g.
         'model.diffusion_model.input_blocks.4.' / '...input_blocks.4.1.' / 'model.diffusion_model.adapter.'.
@@ -414,6 +439,25 @@ def ddim_step(x, e_cond, e_uncond, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_min
     if rc != 0:
         raise RuntimeError(f'fgdm_ddim_step failed: {rc}')
     return x_prev, pred
+
+
+def posterior_sample(moments, noise=None, scale=1.0):
+    """z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) from moments [B, 2*zc, ...] = mean | logvar (device, fp32);
+    noise None: scale * mean (the distribution's mode)."""
+    lib = _lib.load()
+    moments = moments.to(torch.float32).contiguous()
+    B, c2 = moments.shape[:2]
+    if c2 % 2:
+        raise ValueError(f'posterior_sample: moments {tuple(moments.shape)} must hold mean | logvar along dim 1')
+    z = torch.empty((B, c2 // 2, *moments.shape[2:]), device=moments.device, dtype=torch.float32)
+    if noise is not None:
+        noise = noise.to(torch.float32).contiguous()
+        if tuple(noise.shape) != tuple(z.shape):
+            raise ValueError(f'posterior_sample: noise {tuple(noise.shape)} must have the shape of the mean {tuple(z.shape)}')
+    rc = lib.fgdm_posterior_sample(_ptr(moments), _ptr(noise), float(scale), _ptr(z), B, c2 // 2, z[0, 0].numel(), _stream())
+    if rc != 0:
+        raise RuntimeError(f'fgdm_posterior_sample failed: {rc}')
+    return z
 
 
 def cfg_combine(e_cond, e_uncond, cfg_scale):

@@ -9,7 +9,8 @@ They expose what the samplers and the inference scripts require of `model` (SURV
 alphas_cumprod(_prev), device, parameterization, apply_model, q_sample, control_scales, cuda()/to()/eval(),
 ema_scope(), load_state_dict().  All network arithmetic runs in the HIP engine; the per-step latent updates run
 in the sampler kernels.  decode_first_stage (ddpm.py:832-889) runs in the engine too when the
-model is built with a `first_stage_config`, and get_learned_conditioning (FrozenCLIPEmbedder's transformer,
+model is built with a `first_stage_config` -- and encode_first_stage / get_first_stage_encoding (ddpm.py:952-996, 648-661)
+when it is also built with `first_stage_encoder=True` -- and get_learned_conditioning (FrozenCLIPEmbedder's transformer,
 ldm/modules/encoders/modules.py:137-162) when it is built with a `cond_stage_config`; only the BPE
 tokenizer (host code of the third-party `transformers` package) stays outside: `model.tokenizer`.
 """
@@ -37,6 +38,51 @@ class _Buffers:
         self.num_timesteps = int(tabs['betas'].shape[0])
 
 
+class DiagonalGaussianDistribution:
+    """ldm/modules/distributions/distributions.py:24-63: the posterior AutoencoderKL.encode returns.  `parameters` holds
+    mean | log-variance along dim 1.  On the GPU sample() and mode() are one launch of the engine's posterior kernel; the
+    remaining members (std, var, kl, nll: training-side quantities) are plain tensor expressions, as are all of them on CPU tensors."""
+
+    def __init__(self, parameters, deterministic=False):
+        self.parameters = parameters
+        self.mean, logvar = torch.chunk(parameters, 2, dim=1)
+        self.logvar = torch.clamp(logvar, -30.0, 20.0)
+        self.deterministic = deterministic
+        if deterministic:
+            self.var = self.std = torch.zeros_like(self.mean)
+        else:
+            self.std = torch.exp(0.5 * self.logvar)
+            self.var = torch.exp(self.logvar)
+
+    def sample(self, scale=1.0):
+        """mean + std * noise; the noise is drawn on the CPU generator and moved to the device, as the reference draws it
+        (distributions.py:36), so one torch.manual_seed gives both the same noise.  `scale` (not in the reference) folds the
+        scale_factor of get_first_stage_encoding into the same kernel."""
+        noise = torch.randn(self.mean.shape).to(device=self.parameters.device)
+        if self.parameters.is_cuda and not self.deterministic:
+            return _k.posterior_sample(self.parameters, noise, scale)
+        x = self.mean + self.std * noise
+        return x if scale == 1.0 else scale * x
+
+    def mode(self, scale=1.0):
+        if self.parameters.is_cuda:
+            return _k.posterior_sample(self.parameters, None, scale)
+        return self.mean if scale == 1.0 else scale * self.mean
+
+    def kl(self, other=None):
+        if self.deterministic:
+            return torch.Tensor([0.])
+        if other is None:
+            return 0.5 * torch.sum(self.mean ** 2 + self.var - 1.0 - self.logvar, dim=[1, 2, 3])
+        return 0.5 * torch.sum((self.mean - other.mean) ** 2 / other.var + self.var / other.var - 1.0 - self.logvar + other.logvar,
+                               dim=[1, 2, 3])
+
+    def nll(self, sample, dims=(1, 2, 3)):
+        if self.deterministic:
+            return torch.Tensor([0.])
+        return 0.5 * torch.sum(float(np.log(2.0 * np.pi)) + self.logvar + (sample - self.mean) ** 2 / self.var, dim=list(dims))
+
+
 class DiffusionWrapper:
     """ddpm.py:1829-1848: holds `.diffusion_model` (here: the HIP engine) and the conditioning key."""
 
@@ -50,14 +96,14 @@ class LatentDiffusion(_Buffers):
                  beta_schedule='linear', linear_start=0.00085, linear_end=0.012, cosine_s=8e-3, given_betas=None,
                  v_posterior=0.0, parameterization='eps', conditioning_key='crossattn', scale_factor=0.18215,
                  channels=4, image_size=32, log_every_t=200, clip_denoised=False, device=0, first_stage_config=None,
-                 cond_stage_config=None, **ignored):
+                 cond_stage_config=None, first_stage_encoder=False, **ignored):
         if parameterization != 'eps':
             raise NotImplementedError('only eps-parameterization is used by the shipped configs (models/config.yaml)')
         if conditioning_key != 'crossattn':
             raise NotImplementedError("only conditioning_key='crossattn' is on the hot path (models/config.yaml:15)")
         self.engine = engine if engine is not None else _k.Engine(device=device, **self.engine_args(
             unet_config=unet_config, use_adapter=use_adapter, n_controlnets=n_controlnets, num_prompts=num_prompts,
-            first_stage_config=first_stage_config, cond_stage_config=cond_stage_config))
+            first_stage_config=first_stage_config, cond_stage_config=cond_stage_config, first_stage_encoder=first_stage_encoder))
         self.device = self.engine.device
         self.model = DiffusionWrapper(self.engine, conditioning_key)
         self.parameterization = parameterization
@@ -73,6 +119,7 @@ class LatentDiffusion(_Buffers):
         self.clip_version = 'openai/clip-vit-large-patch14'
         self.max_length = 77
         self.first_stage_decode = None      # optional callable(z / scale_factor) -> image overriding the engine's decoder
+        self.first_stage_encode = None      # optional callable(image) -> posterior (or latent tensor) overriding the engine's encoder
         self._register_schedule(self.device, kind=beta_schedule, timesteps=timesteps, linear_start=linear_start,
                                 linear_end=linear_end, cosine_s=cosine_s, v_posterior=v_posterior,
                                 given_betas=given_betas)
@@ -80,7 +127,7 @@ class LatentDiffusion(_Buffers):
 
     @classmethod
     def engine_args(cls, unet_config=None, use_adapter=True, n_controlnets=0, num_prompts=1, first_stage_config=None,
-                    cond_stage_config=None, **ignored):
+                    cond_stage_config=None, first_stage_encoder=False, **ignored):
         """Constructor arguments of the reference model -> keyword arguments of fgdm_amd.engine.Engine / make_config (a pure
         function: works without a GPU).  unet_config as the scripts pass it: {target: ...UNetModel, params: {...}}
         (models/config.yaml:33-48; OmegaConf or dict) or the bare parameter dict; the target and its flags select the
@@ -92,8 +139,11 @@ class LatentDiffusion(_Buffers):
             use_adapter = 'time'
         if kind == 'adapt' or uflags.get('num_prompts', 1) > 1:
             num_prompts = max(num_prompts, int(uflags.get('num_prompts', num_prompts)))
-        return dict(cfg=cfg, use_adapter=use_adapter, n_controlnets=n_controlnets, num_prompts=num_prompts,
+        args = dict(cfg=cfg, use_adapter=use_adapter, n_controlnets=n_controlnets, num_prompts=num_prompts,
                     vae=cls._ddconfig(first_stage_config), clip=cls._clipconfig(cond_stage_config))
+        if first_stage_encoder:       # (absent otherwise: models built as before ask the engine for what they asked before)
+            args['vae_encoder'] = True
+        return args
 
     @staticmethod
     def _ddconfig(first_stage_config):
@@ -184,6 +234,32 @@ class LatentDiffusion(_Buffers):
             raise NotImplementedError('this model was built without first_stage_config; pass one (or set '
                                       'model.first_stage_decode to a callable)')
         return self.engine.vae_decode(z, 1. / self.scale_factor)
+
+    def encode_first_stage(self, x):
+        """ddpm.py:952-996 for an AutoencoderKL first stage (plain branch): first_stage_model.encode(x), the posterior of an
+        image batch fp32 NCHW [B,3,H,W] in [-1,1]."""
+        if hasattr(self, 'split_input_params'):
+            raise NotImplementedError('split_input_params (patch-wise encoding of large images) is not supported')
+        if self.first_stage_encode is not None:
+            return self.first_stage_encode(x)
+        if not getattr(self.engine, 'has_vae_encoder', False):
+            raise NotImplementedError('this model was built without the first-stage encoder; build it with first_stage_config '
+                                      'and first_stage_encoder=True (Engine(..., vae=..., vae_encoder=True)), or set '
+                                      'model.first_stage_encode to a callable')
+        return DiagonalGaussianDistribution(self.engine.vae_encode(x))
+
+    def get_first_stage_encoding(self, encoder_posterior):
+        """ddpm.py:648-661: scale_factor * (a sample of the posterior | the tensor itself | the channel concat of samples)."""
+        if isinstance(encoder_posterior, list):
+            return torch.cat([item.sample(self.scale_factor) if isinstance(item, DiagonalGaussianDistribution)
+                              else self.scale_factor * item.sample() for item in encoder_posterior], 1)
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            return encoder_posterior.sample(self.scale_factor)
+        if isinstance(encoder_posterior, torch.Tensor):
+            if encoder_posterior.is_cuda and encoder_posterior.dtype == torch.float32:
+                return _k.axpby(encoder_posterior.contiguous(), self.scale_factor, None, 0.0)
+            return self.scale_factor * encoder_posterior
+        raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
 
     # ---- apply_model (ddpm.py:1035-1044,1130-1136 non-tiled branch; DiffusionWrapper crossattn mode)
     @staticmethod

@@ -51,6 +51,14 @@ def context(n, seed=43, tokens=77, dim=768):
     return _rng('context', seed).standard_normal((n, tokens, dim), dtype=np.float32)
 
 
+def image(n, res=512, seed=46, grid=8):
+    """RGB image in [-1,1] for the first-stage encoder, [n, 3, res, res]: the hint() palette (flat regions with sharp edges)
+    mapped to [-1,1] plus 0.1 N(0,1) texture, clipped."""
+    base = hint(n, res=res, seed=seed, grid=grid) * 2.0 - 1.0
+    tex = _rng('image', seed).standard_normal(base.shape, dtype=np.float32)
+    return np.clip(base + np.float32(0.1) * tex, -1.0, 1.0).astype(np.float32)
+
+
 def hint(n, res=512, seed=45, grid=8):
     """Segmentation-like RGB hint in [0,1]: grid x grid random palette colours, nearest-upsampled."""
     g = _rng('hint', seed)

@@ -47,6 +47,11 @@ typedef struct fgdm_config {
     int32_t clip_layers, clip_width, clip_heads, clip_mlp, clip_vocab, clip_max_len;
     int32_t n_extra_adapters;  /* AdaptUNetModel num_prompts - 1 (openaimodel.py:993-999): further Adapters whose features are
                                 * summed onto the FG-DM adapter's; needs use_adapter = 1 */
+    int32_t vae_encoder;       /* 0: first-stage DECODER only (the parameter table ends decoder.*, post_quant_conv.*); 1: the whole
+                                * AutoencoderKL in its registration order (ldm/models/autoencoder.py:298-303): encoder.*, decoder.*,
+                                * quant_conv.*, post_quant_conv.*, with double_z = True and in_channels = 3 (models/config.yaml:55-69)
+                                * and the ch / ch_mult / num_res_blocks / z_channels above.  Needs vae_ch > 0.  (Appended last: the
+                                * offsets of the earlier fields are those of engines built before the encoder existed.) */
 } fgdm_config;
 
 #define FGDM_DTYPE_F32 0
@@ -118,6 +123,18 @@ int fgdm_clip_encode(fgdm_engine* e, const int64_t* ids, int B, int T, float* ou
  * image fp32 NCHW [B, vae_out_ch, f*H, f*W], f = 2^(vae_n_levels-1).  Needs an engine created with vae_ch > 0 and the
  * first_stage_model.decoder.* / first_stage_model.post_quant_conv.* tensors loaded. */
 int fgdm_vae_decode(fgdm_engine* e, const float* z, int B, int H, int W, float scale, float* image, void* stream);
+/* First-stage encode: LatentDiffusion.encode_first_stage (ldm/models/diffusion/ddpm.py:952-996, plain branch) =
+ * AutoencoderKL.encode (autoencoder.py:324-328): image fp32 NCHW [B,3,H,W] in [-1,1] (device) ->
+ * moments fp32 NCHW [B, 2*z_channels, H/f, W/f] = DiagonalGaussianDistribution.parameters (channels [0, z_channels) the mean,
+ * the rest the log-variance).  Encoder.forward (ldm/modules/diffusionmodules/model.py:436-460) then quant_conv.  H and W must be
+ * multiples of f = 2^(vae_n_levels-1) and (H/f)*(W/f) a multiple of 64 (smallest image 64 x 64).  Needs an engine created with
+ * vae_encoder = 1 (else FGDM_ERR_STATE) and every first_stage_model.* tensor loaded. */
+int fgdm_vae_encode(fgdm_engine* e, const float* image, int B, int H, int W, float* moments, void* stream);
+/* DiagonalGaussianDistribution.sample()/mode() (ldm/modules/distributions/distributions.py:24-37,61-62) times scale (the
+ * scale_factor of get_first_stage_encoding, ddpm.py:660): z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise), fp32;
+ * moments [B, 2*zc, HW], noise and z [B, zc, HW] (device).  noise NULL: mode(), z = scale * mean.  Stateless. */
+int fgdm_posterior_sample(const float* moments, const float* noise /* NULL: mode */, float scale, float* z,
+                          int B, int zc, int HW, void* stream);
 
 /* Stage boundary of the two-factor chain (device pointers; byte work, bit-exact to the reference's expressions):
  *  fgdm_image_to_uint8: fp32 NCHW image -> uint8 NHWC.  mode 0 = uint8(255 * clamp((x+1)/2, 0, 1))
@@ -191,7 +208,11 @@ int fgdm_workspace_stats(fgdm_engine* e, int64_t* peak_bytes, int64_t* reserved_
 int fgdm_launch_stats(fgdm_engine* e, int64_t* replayed_launches, int64_t* fused_launches, int64_t* fused_problems);
 
 /* Per-kernel entry points used by the parity tests (tests/test_gpu_ops.py); weights given in the reference's
- * native layouts (fp32, [Cout,Cin,kh,kw] / [N,K]) and packed on the fly.  Activations fp16 NHWC. */
+ * native layouts (fp32, [Cout,Cin,kh,kw] / [N,K]) and packed on the fly.  Activations fp16 NHWC.
+ * fgdm_op_conv2d `stride`: 1, 2 (padding 1 on every side), or FGDM_STRIDE2_PAD_BR: stride 2 with the zero padding on the bottom
+ * and right only -- the first-stage encoder's Downsample (ldm/modules/diffusionmodules/model.py:72-76: F.pad(x, (0,1,0,1)) then
+ * conv3x3 stride 2 padding 0), ksize 3 only; out is [B, (H-2)/2+1, (W-2)/2+1, Cout]. */
+#define FGDM_STRIDE2_PAD_BR (-2)
 int fgdm_op_conv2d(const void* x0, int C0, const void* x1, int C1, const float* w, const float* bias,
                    const float* rowvec, const void* resid, int B, int H, int W, int Cout, int ksize, int stride,
                    int upsample, int act, float scale, void* out, void* stream);

@@ -200,6 +200,32 @@ def g_vae():
     save('vae', **out)
 
 
+def g_vae_enc():
+    """First-stage encoder: the reference's AutoencoderKL.encode (moments), get_first_stage_encoding's sample / mode times
+    scale_factor, the first Downsample alone, and the key list of the whole AutoencoderKL.state_dict().  Images: synth.image by seed."""
+    from ldm.models.autoencoder import AutoencoderKL
+    from oracle import vae as ovae
+    m = AutoencoderKL(ddconfig=vae_ddconfig(), lossconfig={'target': 'torch.nn.Identity'}, embed_dim=4).eval()
+    shapes = load_synth(m, 'first_stage_model.')
+    img = lambda n, res: torch.from_numpy(synth.image(n, res=res, seed=res))      # seed = resolution
+    out = {}
+    with torch.no_grad():
+        for n, res in ((2, 64), (1, 128), (1, 512)):
+            out[f'moments_{res}'] = m.encode(img(n, res)).parameters
+        x = img(2, 64)
+        assert not torch.equal(x[0], x[1])
+        torch.manual_seed(7)
+        out['z_sample_64'] = ovae.SCALE_FACTOR * m.encode(x).sample()
+        out['z_mode_64'] = ovae.SCALE_FACTOR * m.encode(x).mode()
+        down0_y = m.encoder.down[0].downsample(m.encoder.conv_in(x))
+    save('vae_enc', **out)
+    if not AC_SUFFIX:      # (one convolution: held to the per-kernel bar, which needs no autocast floor)
+        save('vae_enc_down0', down0_y=down0_y)      # [2,128,32,32] fp32 = 1 MiB raw: a file of its own keeps each under the size limit
+    with open(os.path.join(GOLD, 'vae_encoder_keys.json'), 'w') as f:
+        json.dump({k: list(v) for k, v in shapes.items()}, f)
+    print('wrote vae_encoder_keys.json', len(shapes))
+
+
 def g_clip():
     """CLIP text encoder.  Third-party: FrozenCLIPEmbedder = transformers.CLIPTextModel
     (ldm/modules/encoders/modules.py:137-162); run here from the installed transformers with synthetic weights."""
@@ -757,12 +783,13 @@ def g_full_size():
 ALL = dict(schedule=g_schedule, ddpm_schedule=g_ddpm_schedule, param_keys=g_param_keys, ops=g_ops,
            unet_full=g_unet_full, controlnet_full=g_controlnet_full, small_nets=g_small_nets,
            samplers=g_samplers, samplers2=g_samplers2, samplers3=g_samplers3, sampler_unet=g_sampler_unet, vae=g_vae, clip=g_clip, adapt_unet=g_adapt_unet, full_size=g_full_size,
-           full_size_check=g_full_size_check)
+           full_size_check=g_full_size_check, vae_enc=g_vae_enc)
 
 
 # generators that are ALSO run with the reference's modules under the emulated torch.autocast("cuda") policy
 # (scripts/txt2img_fgdm_inference.py:212-217 wraps the whole sampling loop in it) -> tests/golden/<name>_ac.npz
-AC = ('ops', 'unet_full', 'controlnet_full', 'small_nets', 'sampler_unet', 'adapt_unet', 'vae', 'clip', 'full_size', 'full_size_check')
+AC = ('ops', 'unet_full', 'controlnet_full', 'small_nets', 'sampler_unet', 'adapt_unet', 'vae', 'clip', 'full_size', 'full_size_check',
+      'vae_enc')
 
 
 def main():
