@@ -56,6 +56,9 @@ SIGNATURES = {
     'fgdm_set_context': (_i, [_p, _p, _i, _p]),
     'fgdm_apply_model': (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     'fgdm_clip_encode': (_i, [_p, _p, _i, _i, _p, _p]),
+    'fgdm_clip_encode_skip': (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    'fgdm_set_context_tokens': (_i, [_p, _i]),
+    'fgdm_get_context_tokens': (_i, [_p]),
     'fgdm_run_block': (_i, [_p, C.c_char_p, _p, _i, _p, _i, _p, _p, _i, _i, _i, _p, _i64, C.POINTER(_i64), _p]),
     'fgdm_vae_decode': (_i, [_p, _p, _i, _i, _i, _f, _p, _p]),
     'fgdm_vae_encode': (_i, [_p, _p, _i, _i, _i, _p, _p]),

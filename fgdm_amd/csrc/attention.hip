@@ -593,6 +593,263 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(const half_t* __restric
 }
 
 // =====================================================================================================================
+// Long text contexts (96 < Tk <= 256: two or three 77-token parts joined along the token axis, cldm.py:836-849 / hack.py:23-68).
+// The design of attn_cross_kernel with NS sub-tiles of 32 keys: all keys of a (batch, head) staged once, ONE barrier, the maximum
+// over all NS score tiles before any exp2 (a spike may sit in any of them), every wave walking cpw chunks of 32 queries with the
+// next chunk's Q requested early.  K / V^T for 256 keys need up to 123 KB (d = 80), so the LDS is dynamic; d = 160 fits up to
+// NS = 7 (155 KB) and falls back to attn_kernel beyond.  At NS = 8 the scores alone are 128 fp32 registers per lane: the kernel
+// runs at one workgroup per CU by LDS anyway, so the 512-register budget of one wave per SIMD is its to use.
+constexpr int attn_cross_long_lds(int D, int NS) {
+    const int DP = (D + 15) / 16 * 16, DT = (D + 31) / 32, KEYS = NS * 32;
+    return KEYS * (DP * 2 + 16) + DT * 32 * (KEYS * 2 + 72) + (D <= 80 ? 4 * 32 * (D * 2 + 8) : 0);
+}
+template <int D, int NS>
+__global__ __launch_bounds__(256) void attn_cross_long_kernel(const half_t* __restrict__ Q, int ldq,
+                                                              const half_t* __restrict__ K, int ldk,
+                                                              const half_t* __restrict__ Vt, int ldvt,
+                                                              half_t* __restrict__ O, int ldo,
+                                                              int H, int T, int Tk, float sl2e, int cpw) {
+    constexpr int KEYS = NS * 32;
+    constexpr int DP = (D + 15) / 16 * 16, NKS = DP / 16, DT = (D + 31) / 32;
+    constexpr bool ONES = (DT * 32 > D);
+    constexpr bool FOLD = (DP > D) && (D % 8 == 0);      // same Q scaling rule as attn_kernel (the spare slot itself stays 0 here)
+    constexpr int KS = DP * 2 + 16;            // K row stride (bytes): odd multiple of 16
+    constexpr int VS = KEYS * 2 + 72;          // V^T row stride: 66 dwords = 2 mod 32 -> b64 reads conflict-free like the 34 above
+    constexpr int DC = D / 8;
+    // Q rows enter and O rows leave through a wave-private [32][D] LDS tile, so that global memory sees 16-byte pieces of whole
+    // 2 D-byte row slices (a lane per query row means 64 different lines per instruction, 8 bytes each on the way out)
+    constexpr bool RELAY = D <= 80;
+    constexpr int RS = D * 2 + 8;              // 22 / 42 dwords per row: 8-byte accesses of 16 consecutive rows hit 16 banks
+    constexpr int PCS = 32 * (D / 8), KP = (PCS + 63) / 64;      // 16-byte pieces of a 32-row chunk; per lane
+    static_assert(attn_cross_long_lds(D, NS) == KEYS * KS + DT * 32 * VS + (RELAY ? 4 * 32 * RS : 0), "LDS size formula");
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // attn_cross_long_lds(D, NS) bytes: beyond the static 64 KB
+    char* Ks = smem;
+    char* Vs = smem + KEYS * KS;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lq = lane & 31, lh = lane >> 5;
+    const int qpw = 128 * cpw;                               // queries per workgroup
+    const int ncb = (T + qpw - 1) / qpw;
+    const int nb = gridDim.x;
+    int logical;
+    {
+        const int bid = blockIdx.x, xcd = bid & 7, qd = nb >> 3, r = nb & 7;
+        logical = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (bid >> 3);
+    }
+    const int head = logical % H, rest = logical / H;
+    const int cblk = rest % ncb, b = rest / ncb;
+
+    const half_t* Kb = K + (size_t)b * Tk * ldk + head * D;
+    const half_t* Vb = Vt + ((size_t)b * H + head) * D * ldvt;
+    // ---- stage K (rows past Tk repeat the last valid one: their scores are masked) and V^T (rows are padded to 64-key multiples):
+    // every global load of the workgroup is issued before the first LDS store -- ONE memory round trip (as loops of load / store
+    // pairs the staging was 5-6 dependent round trips, most of a workgroup's life)
+    constexpr int KPC = KEYS * (DP / 8), VPC = DT * 32 * (KEYS / 8);
+    constexpr int KPT = (KPC + 255) / 256, VPT = (VPC + 255) / 256;
+    h8 kst[KPT], vst[VPT];
+#pragma unroll
+    for (int u = 0; u < KPT; ++u) {
+        const int i = tid + 256 * u, key = i / (DP / 8), c = i - key * (DP / 8);
+        kst[u] = (h8)(half_t)0;
+        if (i < KPC && c < DC) kst[u] = *(const h8*)(Kb + (size_t)min(key, Tk - 1) * ldk + c * 8);
+    }
+#pragma unroll
+    for (int u = 0; u < VPT; ++u) {
+        const int i = tid + 256 * u, r = i / (KEYS / 8), c = i - r * (KEYS / 8);
+        vst[u] = (r == D) ? (h8)(half_t)1 : (h8)(half_t)0;
+        if (i < VPC && r < D) vst[u] = *(const h8*)(Vb + (size_t)r * ldvt + c * 8);
+    }
+    char* scr = smem + KEYS * KS + DT * 32 * VS + (threadIdx.x >> 6) * 32 * RS;      // this wave's tile
+    // the chunk's Q rows: per-lane fragments straight from global memory, or (RELAY) 16-byte pieces in row order
+    constexpr int NQ = RELAY ? KP : NKS;
+    auto load_q = [&](int q0, h8 (&qr)[NQ]) {      // q0: first query of the chunk (wave-uniform)
+        if constexpr (RELAY) {
+#pragma unroll
+            for (int u = 0; u < KP; ++u) {
+                const int c = lane + 64 * u, row = c / (D / 8), ck = c - row * (D / 8);
+                qr[u] = (h8)(half_t)0;
+                if (c < PCS && q0 + row < T) qr[u] = *(const h8*)(Q + ((size_t)b * T + q0 + row) * ldq + head * D + ck * 8);
+            }
+        } else {
+#pragma unroll
+            for (int s2 = 0; s2 < NKS; ++s2) {
+                const int c = 16 * s2 + 8 * lh;
+                qr[s2] = (h8)(half_t)0;
+                if (c < D && q0 + lq < T) qr[s2] = *(const h8*)(Q + ((size_t)b * T + q0 + lq) * ldq + head * D + c);
+            }
+        }
+    };
+    const int q_first = cblk * qpw + wave * 32;              // chunk i of this wave: queries q_first + i * 128 + [0, 32)
+    h8 qn[NQ];
+    load_q(q_first, qn);
+#pragma unroll
+    for (int u = 0; u < KPT; ++u) {
+        const int i = tid + 256 * u, key = i / (DP / 8), c = i - key * (DP / 8);
+        if (i < KPC) *(h8*)(Ks + key * KS + c * 16) = kst[u];
+    }
+#pragma unroll
+    for (int u = 0; u < VPT; ++u) {
+        const int i = tid + 256 * u, r = i / (KEYS / 8), c = i - r * (KEYS / 8);
+        if (i < VPC) {
+            const h8 v = vst[u];
+            const h4 lo = {v[0], v[1], v[2], v[3]}, hi = {v[4], v[5], v[6], v[7]};
+            *(h4*)(Vs + r * VS + c * 16) = lo;
+            *(h4*)(Vs + r * VS + c * 16 + 8) = hi;
+        }
+    }
+    __syncthreads();
+
+    const int kfrag = lq * KS + 8 * lh * 2, vfrag = lq * VS + 4 * lh * 2;
+    for (int i = 0; i < cpw; ++i) {
+        const int q0 = __builtin_amdgcn_readfirstlane(q_first + i * 128);
+        if (q0 >= T) break;                                  // wave-uniform: this chunk starts past the end
+        const int q = q0 + lq;
+        h8 qf[NKS];
+        if constexpr (RELAY) {
+#pragma unroll
+            for (int u = 0; u < KP; ++u) {
+                const int c = lane + 64 * u, row = c / (D / 8), ck = c - row * (D / 8);
+                if (c < PCS) {
+                    const h4 lo = {qn[u][0], qn[u][1], qn[u][2], qn[u][3]}, hi = {qn[u][4], qn[u][5], qn[u][6], qn[u][7]};
+                    *(h4*)(scr + row * RS + ck * 16) = lo;
+                    *(h4*)(scr + row * RS + ck * 16 + 8) = hi;
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int s2 = 0; s2 < NKS; ++s2) {
+                const int c = 16 * s2 + 8 * lh;
+                qf[s2] = (h8)(half_t)0;
+                if (c < D) {
+                    const h4 lo = *(const h4*)(scr + lq * RS + c * 2), hi = *(const h4*)(scr + lq * RS + c * 2 + 8);
+                    qf[s2] = h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // fragments read before the tile is reused for O
+        } else {
+#pragma unroll
+            for (int s2 = 0; s2 < NKS; ++s2) qf[s2] = qn[s2];
+        }
+        if (i + 1 < cpw) load_q(q0 + 128, qn);
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int s2 = 0; s2 < NKS; ++s2)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) qf[s2][j] = (half_t)((float)qf[s2][j] * sl2e);
+        }
+        // ---- S^T = K Q^T, all keys
+        f32x16 sacc[NS];
+#pragma unroll
+        for (int sub = 0; sub < NS; ++sub) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sacc[sub][r] = 0.f;
+#pragma unroll
+            for (int s2 = 0; s2 < NKS; ++s2) {
+                const h8 kf = *(const h8*)(Ks + kfrag + sub * 32 * KS + 16 * s2 * 2);
+                sacc[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s2], sacc[sub], 0, 0, 0);
+            }
+        }
+        // every sub-tile that can hold a key >= Tk is masked (the dispatch picks NS = ceil(Tk / 32), where that is the last one only;
+        // the test is wave-uniform, so full sub-tiles cost one scalar compare).  Sub-tile 0 always holds key 0 < Tk.
+#pragma unroll
+        for (int sub = 1; sub < NS; ++sub)
+            if ((sub + 1) * 32 > Tk) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    if (key >= Tk) sacc[sub][r] = -INFINITY;
+                }
+            }
+        float mx = sacc[0][0];
+#pragma unroll
+        for (int sub = 0; sub < NS; ++sub)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[sub][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float sc = FOLD ? 1.0f : sl2e;
+        float psum = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < NS; ++sub)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float pv = __builtin_amdgcn_exp2f((sacc[sub][r] - mx) * sc);
+                sacc[sub][r] = pv;
+                if constexpr (!ONES) psum += pv;
+            }
+        // ---- O^T = V^T P^T (row D of O^T: the sum of the fp16 probabilities)
+        f32x16 oacc[DT];
+#pragma unroll
+        for (int t = 0; t < DT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < NS; ++sub)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                h8 pf;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pf[j] = (half_t)sacc[sub][8 * s2 + j];
+#pragma unroll
+                for (int t = 0; t < DT; ++t) {
+                    const char* vp = Vs + vfrag + t * 32 * VS + (sub * 32 + 16 * s2) * 2;
+                    const h4 v0 = *(const h4*)vp, v1 = *(const h4*)(vp + 16);
+                    const h8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                    oacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[t], 0, 0, 0);
+                }
+            }
+        float l_tot;
+        if constexpr (ONES) {
+            constexpr int rr = D % 32;
+            constexpr int reg = (rr & 3) + 4 * (rr >> 3);
+            constexpr int owner_half = (rr >> 2) & 1;
+            const float mine = oacc[D / 32][reg];
+            const float other = __shfl_xor(mine, 32);
+            l_tot = (lh == owner_half) ? mine : other;
+        } else {
+            l_tot = psum + __shfl_xor(psum, 32);
+        }
+        const float inv = 1.0f / l_tot;
+        if constexpr (RELAY) {
+#pragma unroll
+            for (int t = 0; t < DT; ++t)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int dd = t * 32 + 8 * g + 4 * lh;
+                    if (dd < D) {
+                        h4 pk = {(half_t)(oacc[t][4 * g] * inv), (half_t)(oacc[t][4 * g + 1] * inv),
+                                 (half_t)(oacc[t][4 * g + 2] * inv), (half_t)(oacc[t][4 * g + 3] * inv)};
+                        *(h4*)(scr + lq * RS + dd * 2) = pk;
+                    }
+                }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int u = 0; u < KP; ++u) {
+                const int c = lane + 64 * u, row = c / (D / 8), ck = c - row * (D / 8);
+                if (c < PCS && q0 + row < T) {
+                    const h4 lo = *(const h4*)(scr + row * RS + ck * 16), hi = *(const h4*)(scr + row * RS + ck * 16 + 8);
+                    *(h8*)(O + ((size_t)b * T + q0 + row) * ldo + head * D + ck * 8) = h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the tile is free for the next chunk's Q
+        } else if (q < T) {
+            half_t* op = O + ((size_t)b * T + q) * ldo + head * D;
+#pragma unroll
+            for (int t = 0; t < DT; ++t)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int dd = t * 32 + 8 * g + 4 * lh;
+                    if (dd < D) {
+                        h4 pk = {(half_t)(oacc[t][4 * g] * inv), (half_t)(oacc[t][4 * g + 1] * inv),
+                                 (half_t)(oacc[t][4 * g + 2] * inv), (half_t)(oacc[t][4 * g + 3] * inv)};
+                        *(h4*)(op + dd) = pk;
+                    }
+                }
+        }
+    }
+}
+
+
+// =====================================================================================================================
 // Ping-pong variant for long self-attention (round 2).  PMC on the kernel above (T = Tk = 4096, d = 40): per SIMD the matrix
 // pipe is busy 40 % of the time and the vector ALU 52 % -- and the two hardly ever at the same moment: three free-running
 // waves per SIMD drift into the same phase, all in their softmax, then all in their MFMAs.  Here a workgroup has EIGHT waves,
@@ -1530,6 +1787,25 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
     }
 }
 
+// hipFuncSetAttribute is per device: the "attribute set" flag of an instantiation is kept per device id
+template <int D, int NS>
+static int launch_cross_long(dim3 grid, const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
+                             int ldo, int H, int T, int Tk, float sl2e, int cpw, hipStream_t s) {
+    constexpr int smem = attn_cross_long_lds(D, NS);
+    static_assert(smem <= 160 * 1024, "does not fit the 160 KB of a CU");
+    constexpr int MAXDEV = 64;
+    static bool attr_set[MAXDEV] = {};
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return FGDM_ERR_HIP;
+    auto k = attn_cross_long_kernel<D, NS>;
+    if (!attr_set[dev]) {
+        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return FGDM_ERR_HIP;
+        attr_set[dev] = true;
+    }
+    FGDM_LAUNCH(k, grid, dim3(256), smem, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw);
+    return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+}
+
 int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
                      int ldo, int B, int H, int T, int Tk, int d, int q_prescaled, hipStream_t s) {
     if (B <= 0 || H <= 0 || T <= 0 || Tk <= 0) return FGDM_ERR_ARG;
@@ -1588,6 +1864,26 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
             default: return FGDM_ERR_ARG;
         }
         return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+    }
+    // two or three text parts (96 < Tk <= 256): the key-resident kernel with NS = ceil(Tk / 32) sub-tiles, so that only the last one
+    // can hold a key >= Tk and NS * 32 <= ldvt.  FGDM_ATTN_CROSS_LONG: query chunks per wave, 0 = the general kernel (A/B).  Default 8:
+    // staging 154 - 256 keys costs as much traffic as the Q + O rows of 4 chunks, and at T = 1024 eight chunks make one workgroup
+    // per (batch, head) (measured: profiles/long_context_attention.txt; 4 chunks do not beat attn_kernel at d = 80)
+    static const int cross_long = getenv("FGDM_ATTN_CROSS_LONG") ? atoi(getenv("FGDM_ATTN_CROSS_LONG")) : 8;
+    if (cross_long > 0 && Tk > 96 && Tk <= 256 && T >= 128) {
+        const int ns = (Tk + 31) / 32;
+        if (ldvt >= ns * 32 && (d == 40 || d == 80 || (d == 160 && ns <= 7))) {
+            const int cpw = std::min(cross_long, T / 128);
+            const dim3 gridc(((T + 128 * cpw - 1) / (128 * cpw)) * H * B);
+#define ATT_XL(DD, NN) case NN: return launch_cross_long<DD, NN>(gridc, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw, s);
+            switch (d) {
+                case 40: switch (ns) { ATT_XL(40, 4) ATT_XL(40, 5) ATT_XL(40, 6) ATT_XL(40, 7) ATT_XL(40, 8) } break;
+                case 80: switch (ns) { ATT_XL(80, 4) ATT_XL(80, 5) ATT_XL(80, 6) ATT_XL(80, 7) ATT_XL(80, 8) } break;
+                case 160: switch (ns) { ATT_XL(160, 4) ATT_XL(160, 5) ATT_XL(160, 6) ATT_XL(160, 7) } break;
+            }
+#undef ATT_XL
+            return FGDM_ERR_ARG;
+        }
     }
     const dim3 grid(((T + 127) / 128) * H * B), block(256);
     switch (d) {

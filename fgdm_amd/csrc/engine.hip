@@ -302,6 +302,7 @@ struct fgdm_engine {
     struct CtxKV { Tensor k, vt; };
     std::unordered_map<const Layer*, CtxKV> ctx_cache;
     int ctx_B = 0, ctx_T = 0;
+    int ctx_tokens = 77;                 // tokens behind every ctx / cond / uncond pointer (fgdm_set_context_tokens); 77 = one CLIP chunk
     Arena arena;
     half_t* zero = nullptr;
     // packed weights in HBM, per component (state-dict prefix): re-packing a component frees its previous copy
@@ -1192,7 +1193,7 @@ struct fgdm_engine {
         if (!finalized) return fail(FGDM_ERR_STATE, "weights not finalized");
         if (B <= 0) return fail(FGDM_ERR_ARG, "bad shape");
         drop_context();
-        Tensor ctx16 = talloc(B, 1, 77, cfg.context_dim);
+        Tensor ctx16 = talloc(B, 1, ctx_tokens, cfg.context_dim);
         if (!ctx16.p) return fail(FGDM_ERR_NOMEM, "workspace");
         if (f32_to_f16(ctx, ctx16.p, ctx16.numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "convert kernel");
         auto walk = [&](const Block& blk) -> int {
@@ -1209,7 +1210,7 @@ struct fgdm_engine {
         CHK(walk_net(unet));
         for (auto& n : cns) CHK(walk_net(n));
         tfree(ctx16);
-        ctx_B = B; ctx_T = 77;
+        ctx_B = B; ctx_T = ctx_tokens;
         return FGDM_OK;
     }
 
@@ -1264,7 +1265,7 @@ struct fgdm_engine {
             CHK(dcopy((char*)s2f + sb, s2.p, sb));
             ar->release(s2.p); s2.p = s2f;
         }
-        // --- attn2 (cross, 77-token context), norm2 folded into to_q
+        // --- attn2 (cross, ctx_tokens-token context), norm2 folded into to_q
         if (!ln_fold) CHK(lnorm(l.ln2, h2, &nrm));
         { Epi e; if (ln_fold) e.ln = &s2; CHK(linear(l.q2, ln_fold ? h2 : nrm, e, &q2)); }
         if (s2.p) ar->release(s2.p);
@@ -1524,7 +1525,7 @@ struct fgdm_engine {
         for (const Layer& l : *blk) { needs_ctx |= l.type == L_ATTN; needs_emb |= l.type == L_RES; }
         if ((needs_ctx && !ctx) || (needs_emb && !emb)) return fail(FGDM_ERR_ARG, "fgdm_run_block: this block needs ctx / emb");
         if (needs_ctx) {
-            ctx16 = talloc(B, 1, 77, cfg.context_dim);
+            ctx16 = talloc(B, 1, ctx_tokens, cfg.context_dim);
             if (!ctx16.p) return fail(FGDM_ERR_NOMEM, "workspace");
             if (f32_to_f16(ctx, ctx16.p, ctx16.numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "convert kernel");
         }
@@ -1734,7 +1735,7 @@ struct fgdm_engine {
         Net& n = unet;
         const int HW = H * W;
         Tensor x4 = talloc(B, H, W, 4), ctx16;
-        if (ctx) ctx16 = talloc(B, 1, 77, cfg.context_dim);
+        if (ctx) ctx16 = talloc(B, 1, ctx_tokens, cfg.context_dim);
         else if (ctx_B != B) return fail(FGDM_ERR_STATE, "ctx is NULL but no context of this batch size was registered (fgdm_set_context)");
         if (!x4.p || (ctx && !ctx16.p)) return fail(FGDM_ERR_NOMEM, "workspace");
         if (nchw_f32_to_nhwc_f16(x, x4.p, B, 4, HW, 4, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
@@ -1885,10 +1886,15 @@ struct fgdm_engine {
 
     // ------------------------------------------------------------------------------------ text encoder
     // CLIPTextModel.forward -> last_hidden_state (pre-LN transformer, causal attention, quick-GELU MLP)
-    int clip_encode(const int64_t* ids, int B, int T, float* out) {
+    // clip_skip > 1: final_layer_norm(hidden_states[-clip_skip]) (controlnet/cldm/hack.py:40-45); hidden_states[-k] is the output
+    // of layer L - k + 1 of L, so the last clip_skip - 1 layers are not run
+    int clip_encode(const int64_t* ids, int B, int T, float* out, int clip_skip = 0) {
         if (!clip.on) return fail(FGDM_ERR_STATE, "engine was created without a text encoder (clip_layers = 0)");
         if (!clip.packed) return fail(FGDM_ERR_STATE, "weights not finalized");
         if (B <= 0 || T <= 0 || T > cfg.clip_max_len) return fail(FGDM_ERR_ARG, "bad shape (T must be <= clip_max_len)");
+        if (clip_skip > cfg.clip_layers + 1) return fail(FGDM_ERR_ARG, "clip_skip exceeds the number of hidden states");
+        const int n_run = cfg.clip_layers - (clip_skip > 1 ? clip_skip - 1 : 0);
+        int li = 0;
         const int W = cfg.clip_width, rows = B * T;
         // the hidden states are an fp32 residual stream, as under the reference's autocast: fp32 embeddings, every branch
         // (attention / MLP output, a fp16 GEMM result) is promoted when added to it, LayerNorm reads fp32
@@ -1903,6 +1909,7 @@ struct fgdm_engine {
             return layernorm32_launch(src, rows, W, nw.g, nw.b, 1e-5f, dst->p, nullptr, s) == FGDM_OK ? FGDM_OK : fail(FGDM_ERR_HIP, "layernorm");
         };
         for (const ClipLayer& l : clip.layers) {
+            if (li++ >= n_run) break;
             CHK(ln32(l.ln1, h, &n));
             CHK(linear(l.qkv, n, Epi{}, &qkv));
             tfree(n);
@@ -2357,6 +2364,20 @@ int fgdm_clip_encode(fgdm_engine* e, const int64_t* ids, int B, int T, float* ou
     return scoped_call(e, stream, [&] { return e->clip_encode(ids, B, T, out); });
 }
 
+int fgdm_clip_encode_skip(fgdm_engine* e, const int64_t* ids, int B, int T, int clip_skip, float* out, void* stream) {
+    if (!e || !ids || !out) return FGDM_ERR_ARG;
+    return scoped_call(e, stream, [&] { return e->clip_encode(ids, B, T, out, clip_skip); });
+}
+
+int fgdm_set_context_tokens(fgdm_engine* e, int tokens) {
+    if (!e) return FGDM_ERR_ARG;
+    if (tokens < 1) return e->fail(FGDM_ERR_ARG, "context token count must be >= 1");
+    if (tokens != e->ctx_tokens) { e->drop_context(); e->ctx_tokens = tokens; }      // cached projections have the old length
+    return FGDM_OK;
+}
+
+int fgdm_get_context_tokens(const fgdm_engine* e) { return e ? e->ctx_tokens : FGDM_ERR_ARG; }
+
 int fgdm_vae_decode(fgdm_engine* e, const float* z, int B, int H, int W, float scale, float* image, void* stream) {
     if (!e || !z || !image) return FGDM_ERR_ARG;
     return scoped_call(e, stream, [&] { return e->vae_decode(z, B, H, W, scale, image); });
@@ -2377,7 +2398,7 @@ int fgdm_controlnet(fgdm_engine* e, int cn, const float* x, const int64_t* t, co
     if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
     if (cn < 0 || cn >= (int)e->cns.size()) return e->fail(FGDM_ERR_ARG, "no such ControlNet");
     return scoped_call(e, stream, [&]() -> int {
-        Tensor x4 = e->talloc(B, H, W, 4), ctx16 = e->talloc(B, 1, 77, e->cfg.context_dim);
+        Tensor x4 = e->talloc(B, H, W, 4), ctx16 = e->talloc(B, 1, e->ctx_tokens, e->cfg.context_dim);
         if (!x4.p || !ctx16.p) return e->fail(FGDM_ERR_NOMEM, "workspace");
         if (nchw_f32_to_nhwc_f16(x, x4.p, B, 4, H * W, 4, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "layout kernel");
         if (f32_to_f16(ctx, ctx16.p, ctx16.numel(), e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "convert kernel");
@@ -2443,10 +2464,10 @@ int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* u
     return scoped_call(e, stream, [&]() -> int {
     const bool cfg_on = uncond && cfg_scale != 1.0f;
     const int Bm = cfg_on ? 2 * B : B;
-    const size_t n = (size_t)B * 4 * H * W, nctx = (size_t)B * 77 * e->cfg.context_dim;
+    const size_t n = (size_t)B * 4 * H * W, nctx = (size_t)B * e->ctx_tokens * e->cfg.context_dim;
     float* x2 = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
     float* eps = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
-    float* c2 = (float*)e->arena.alloc(Bm * 77 * (size_t)e->cfg.context_dim * sizeof(float));
+    float* c2 = (float*)e->arena.alloc(Bm * (size_t)e->ctx_tokens * e->cfg.context_dim * sizeof(float));
     int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * Bm * sizeof(int64_t));
     if (!x2 || !eps || !c2 || !tdev) return e->fail(FGDM_ERR_NOMEM, "workspace");
     std::vector<int64_t> th((size_t)S * Bm);

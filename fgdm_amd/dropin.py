@@ -18,10 +18,12 @@ If the real reference packages are already imported, install(replace=True) swaps
 import sys
 import types
 
-from . import config, initialize_cn, models, samplers, seg2image
+from . import config, hack, initialize_cn, models, samplers, seg2image
 
 _CLDM_MODEL = {'load_state_dict': initialize_cn.load_state_dict, 'get_state_dict': initialize_cn.get_state_dict,
                'create_model': config.create_model}
+_HACK = {'hack_everything': hack.hack_everything, 'disable_verbosity': hack.disable_verbosity,
+         'enable_sliced_attention': hack.enable_sliced_attention}      # controlnet/cldm/hack.py:11-28
 _MAP = {
     'ldm.util': {'instantiate_from_config': config.instantiate_from_config},              # scripts/txt2img_fgdm_inference.py:17
     'ldm.models.diffusion.ddim': {'DDIMSampler': samplers.DDIMSampler},
@@ -34,10 +36,12 @@ _MAP = {
     'controlnet.cldm.ddim_hacked': {'DDIMSampler': samplers.ControlDDIMSampler},
     'controlnet.cldm.cldm': {'ControlLDM': models.ControlLDM},
     'controlnet.cldm.model': _CLDM_MODEL,
+    'controlnet.cldm.hack': _HACK,
     'controlnet.initialize_cn': {'initialize_controlnet': initialize_cn.initialize_controlnet,
                                  'process': initialize_cn.process},
     # controlnet/seg2image_inference.py runs from inside controlnet/ and imports the bare package names (:18-19)
     'cldm.model': _CLDM_MODEL,
+    'cldm.hack': _HACK,
     'cldm.ddim_hacked': {'DDIMSampler': samplers.ControlDDIMSampler},
     'cldm.cldm': {'ControlLDM': models.ControlLDM},
     'controlnet.seg2image_inference': {'process': seg2image.process, 'setup': seg2image.setup},

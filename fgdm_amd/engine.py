@@ -159,6 +159,7 @@ class Engine:
         self.use_adapter = bool(use_adapter)
         self._hint_keys = [None] * n_controlnets
         self._ctx_policy = ContextCachePolicy()      # context tensor whose K/V projections the engine holds
+        self._ctx_tokens = self.lib.fgdm_get_context_tokens(self.h)      # tokens per context (77 unless changed)
         self._conds_key, self._conds_keep = None, None
         self.cache_context = os.environ.get('FGDM_CONTEXT_CACHE', '1') != '0'
 
@@ -252,6 +253,16 @@ class Engine:
         self._check(self.lib.fgdm_set_adapter_conds(self.h, ptrs, len(dev), B, H, W, _stream()), 'fgdm_set_adapter_conds')
         self._conds_key, self._conds_keep = key, list(conds)
 
+    def set_context_tokens(self, tokens):
+        """Token count of every context handed over from now on (cat(c_crossattn, 1) may hold several 77-token parts,
+        ddpm.py:1835-1837 / hack.py:23-68).  A changed count drops the engine's registered projections, so the cache policy
+        starts afresh as well: the next tensor is a new context even if it is an object seen before."""
+        tokens = int(tokens)
+        if tokens != self._ctx_tokens:
+            self._check(self.lib.fgdm_set_context_tokens(self.h, tokens), 'fgdm_set_context_tokens')
+            self._ctx_tokens = tokens
+            self._ctx_policy = ContextCachePolicy()
+
     def apply_model(self, x, t, ctx, control_scales=None, flags=0, pcond=None, out=None):
         x = x.to(self.device, torch.float32).contiguous()
         t_int = t_flt = None
@@ -262,9 +273,7 @@ class Engine:
         B, Cc, H, W = x.shape
         if Cc != 4 or ctx.shape[0] != B or t.shape[0] != B:
             raise ValueError(f'apply_model: x {tuple(x.shape)}, t {tuple(t.shape)}, context {tuple(ctx.shape)} do not agree')
-        if ctx.shape[1] != 77:
-            raise NotImplementedError(f'context of {ctx.shape[1]} tokens: the engine takes one 77-token CLIP context per sample '
-                                      '(several c_crossattn entries concatenated along the token axis are not supported)')
+        self.set_context_tokens(ctx.shape[1])
         # The conditioning is the same tensor OBJECT in every denoising step: its to_k / to_v projections are computed
         # once (fgdm_set_context) and reused while that object is unmodified (torch bumps _version on in-place writes;
         # holding the object keeps its storage from being recycled under the same address).
@@ -295,12 +304,14 @@ class Engine:
         self._check(rc, 'fgdm_apply_model')
         return eps
 
-    def clip_encode(self, ids):
-        """CLIPTextModel(input_ids=ids).last_hidden_state: int64 ids [B, T<=77] -> fp32 [B, T, 768] on the device."""
+    def clip_encode(self, ids, clip_skip=0):
+        """CLIPTextModel(input_ids=ids).last_hidden_state: int64 ids [B, T<=77] -> fp32 [B, T, 768] on the device.
+        clip_skip > 1: final_layer_norm(hidden_states[-clip_skip]) instead (controlnet/cldm/hack.py:40-45)."""
         ids = torch.as_tensor(ids).to(self.device, torch.int64).contiguous()
         B, T = ids.shape
         out = torch.empty(B, T, self.config.clip_width, device=self.device, dtype=torch.float32)
-        self._check(self.lib.fgdm_clip_encode(self.h, _ptr(ids), B, T, _ptr(out), _stream()), 'fgdm_clip_encode')
+        self._check(self.lib.fgdm_clip_encode_skip(self.h, _ptr(ids), B, T, int(clip_skip), _ptr(out), _stream()),
+                    'fgdm_clip_encode_skip')
         return out
 
     def vae_decode(self, z, scale=1.0):
@@ -337,6 +348,8 @@ class Engine:
         fp32 NCHW in and out; returns a flat fp32 tensor (the caller knows the block's output shape)."""
         f32 = lambda v: None if v is None else v.to(self.device, torch.float32).contiguous()
         x, emb, ctx, x_skip = f32(x), f32(emb), f32(ctx), f32(x_skip)
+        if ctx is not None:
+            self.set_context_tokens(ctx.shape[1])
         B, Cc, H, W = x.shape
         cap = 4 * B * 1280 * 4 * H * W            # generous: an Upsample quadruples the pixels
         out = torch.empty(cap, device=self.device, dtype=torch.float32)
@@ -351,6 +364,7 @@ class Engine:
         x = x.to(self.device, torch.float32).contiguous()
         t = t.to(self.device, torch.int64).contiguous()
         ctx = ctx.to(self.device, torch.float32).contiguous()
+        self.set_context_tokens(ctx.shape[1])
         B, _, H, W = x.shape
         shapes = self.control_shapes(B, H, W)
         total = sum(int(np.prod(s)) for s in shapes)
@@ -411,6 +425,9 @@ class Engine:
         cond = cond.to(self.device, torch.float32).contiguous()
         if uncond is not None:
             uncond = uncond.to(self.device, torch.float32).contiguous()
+            if tuple(uncond.shape) != tuple(cond.shape):      # the loop runs cat([uncond, cond]) as one batch (ddim.py:222-226)
+                raise ValueError(f'sample_ddim: cond {tuple(cond.shape)} and uncond {tuple(uncond.shape)} must agree')
+        self.set_context_tokens(cond.shape[1])
         B, _, H, W = x.shape
         S = len(timesteps)
         ts = (C.c_int64 * S)(*[int(v) for v in timesteps])

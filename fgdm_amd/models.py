@@ -19,7 +19,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import _lib, config as _cfg, schedule
+from . import _lib, config as _cfg, hack as _hack, schedule
 from . import engine as _k
 
 
@@ -118,6 +118,9 @@ class LatentDiffusion(_Buffers):
         self.tokenizer = None               # callable(list[str]) -> int64 ids [B,77]; default: transformers.CLIPTokenizer
         self.clip_version = 'openai/clip-vit-large-patch14'
         self.max_length = 77
+        self.raw_tokenizer = None           # callable(list[str]) -> list[list[int]] without special tokens (the long-prompt route)
+        self.special_tokens = None          # (BOS, EOS, PAD) of raw_tokenizer; default: the tokenizer's own, else CLIP's
+        self.clip_hack, self.clip_skip = _hack.state()      # controlnet/cldm/hack.py:23-28 (hack_everything)
         self.first_stage_decode = None      # optional callable(z / scale_factor) -> image overriding the engine's decoder
         self.first_stage_encode = None      # optional callable(image) -> posterior (or latent tensor) overriding the engine's encoder
         self._register_schedule(self.device, kind=beta_schedule, timesteps=timesteps, linear_start=linear_start,
@@ -213,15 +216,39 @@ class LatentDiffusion(_Buffers):
                                            return_tensors='pt')['input_ids']
         return self.tokenizer(text)
 
+    def _tokenize_raw(self, text):
+        """_hacked_clip_forward's tokenizer call (controlnet/cldm/hack.py:33-38): raw ids, no special tokens, no truncation."""
+        if self.raw_tokenizer is None:
+            try:
+                from transformers import CLIPTokenizer
+                tok = CLIPTokenizer.from_pretrained(self.clip_version)
+            except Exception as e:      # no vocabulary files on this machine (no network)
+                raise RuntimeError(f'CLIP tokenizer files for {self.clip_version} are not available ({e}); set '
+                                   'model.raw_tokenizer to a callable list[str] -> list[list[int]] (no special tokens)') from e
+            self.raw_tokenizer = lambda t: tok(t, truncation=False, add_special_tokens=False)['input_ids']
+            if self.special_tokens is None:
+                self.special_tokens = (tok.bos_token_id, tok.eos_token_id, tok.pad_token_id)
+        return self.raw_tokenizer(text)
+
     def get_learned_conditioning(self, c):
         """ddpm.py get_learned_conditioning -> cond_stage_model.encode(c): list of prompts (or ready token ids) ->
-        [B, 77, 768]."""
+        [B, 77, 768]; after hack_everything (controlnet/cldm/hack.py:23-68) three 75-token chunks per prompt -> [B, 231, 768],
+        and ready token ids are then read as [B, 3, 77] (or [3B, 77]) chunk arrays."""
         if self.cond_stage_model is not None:
             return self.cond_stage_model(c)
         if not getattr(self.engine, 'has_clip', False):
             raise NotImplementedError('this model was built without cond_stage_config; pass one (or set '
                                       'model.cond_stage_model to a callable returning [B,77,768])')
-        ids = c if torch.is_tensor(c) or isinstance(c, np.ndarray) else self._tokenize(list(c))
+        ready = torch.is_tensor(c) or isinstance(c, np.ndarray)
+        if self.clip_hack:
+            if ready:
+                ids = torch.as_tensor(c).reshape(-1, _hack.MAX_LENGTH)
+                y = self.engine.clip_encode(ids, clip_skip=self.clip_skip)
+                return y.reshape(-1, _hack.CHUNKS * _hack.MAX_LENGTH, y.shape[-1])
+            raw = self._tokenize_raw(list(c))
+            bos, eos, pad = self.special_tokens or (_hack.BOS, _hack.EOS, _hack.PAD)
+            return _hack.encode(self.engine, raw, self.clip_skip, bos, eos, pad)
+        ids = c if ready else self._tokenize(list(c))
         return self.engine.clip_encode(ids)
 
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False, n=None):
@@ -262,15 +289,23 @@ class LatentDiffusion(_Buffers):
         raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
 
     # ---- apply_model (ddpm.py:1035-1044,1130-1136 non-tiled branch; DiffusionWrapper crossattn mode)
-    @staticmethod
-    def _context(cond):
+    def _context(self, cond):
+        """cc = torch.cat(c_crossattn, 1) (ddpm.py:1835-1837; cldm.py:846).  Several parts are joined once per list of tensor
+        objects: the samplers pass the same parts in every step, and handing the engine the SAME joined tensor lets it keep
+        the context's K/V projections.  The memo holds the parts, so their ids cannot be recycled (_version: in-place writes)."""
         if isinstance(cond, dict):
             cc = cond['c_crossattn']
         elif isinstance(cond, (list, tuple)):
             cc = list(cond)
         else:
             cc = [cond]
-        return cc[0] if len(cc) == 1 else torch.cat(cc, 1)
+        if len(cc) == 1:
+            return cc[0]
+        key = tuple((id(t), t._version) for t in cc)
+        memo = getattr(self, '_ctx_cat_memo', None)
+        if memo is None or memo[0] != key:
+            self._ctx_cat_memo = memo = (key, list(cc), torch.cat(cc, 1))
+        return memo[2]
 
     def apply_model(self, x_noisy, t, cond, return_ids=False, **kwargs):
         if return_ids:

@@ -477,6 +477,8 @@ class ControlDDIMSampler(DDIMSampler):
                 return None
         if len(uc['c_crossattn']) != len(c['c_crossattn']):
             return None
+        if any(a.shape[1:] != b.shape[1:] for a, b in zip(uc['c_crossattn'], c['c_crossattn'])):
+            return None      # e.g. a 231-token prompt against a 77-token negative prompt: two calls (ddim_hacked.py:190-191)
         return {'c_concat': hc, 'c_crossattn': [torch.cat([a, b]) for a, b in zip(uc['c_crossattn'], c['c_crossattn'])]}
 
 

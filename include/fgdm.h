@@ -6,7 +6,8 @@
  *     fgdm_last_error() gives a message for the last failing call on that engine;
  *   - all tensor arguments are DEVICE pointers owned by the caller (e.g. torch tensor.data_ptr()), except
  *     fgdm_load_tensor which accepts host or device memory;
- *   - latents / eps are fp32 NCHW [B,4,H,W]; timesteps int64 [B]; context fp32 [B,77,ctx_dim];
+ *   - latents / eps are fp32 NCHW [B,4,H,W]; timesteps int64 [B]; context fp32 [B,77,ctx_dim] ("77" below: the engine's
+ *     context token count, 77 unless fgdm_set_context_tokens changed it);
  *     hints fp32 NCHW [B,3,8H,8W] in [0,1];
  *   - the engine owns weights and workspace; one engine per device; not thread-safe; all work is enqueued on
  *     the stream passed in (a hipStream_t cast to void*; NULL = default stream), no implicit synchronisation.
@@ -108,6 +109,17 @@ int fgdm_set_adapter_conds(fgdm_engine* e, const float* const* conds, int n_cond
  * fgdm_apply_model calls with ctx == NULL and the same B then reuse those projections.  A later fgdm_set_context or
  * fgdm_finalize_weights replaces / drops them. */
 int fgdm_set_context(fgdm_engine* e, const float* ctx, int B, void* stream);
+/* Text contexts of any length.  The reference joins the text conditioning along the token axis before the UNet sees it:
+ * DiffusionWrapper.forward, cc = torch.cat(c_crossattn, 1) (ldm/models/diffusion/ddpm.py:1835-1837); ControlLDM.apply_model,
+ * cond_txt = torch.cat(cond['c_crossattn'], 1) (controlnet/cldm/cldm.py:836-849); and its long-prompt route encodes every prompt
+ * as three 77-token chunks, a [B,231,768] context (controlnet/cldm/hack.py:23-68).  CrossAttention takes any number of keys
+ * (ldm/modules/attention.py:177-199).  fgdm_set_context_tokens states how many tokens every ctx / cond / uncond pointer passed
+ * FROM NOW ON holds per sample (fgdm_set_context, fgdm_apply_model, fgdm_controlnet, fgdm_sample_ddim, fgdm_run_block): fp32
+ * [B,tokens,context_dim].  Default 77.  Any tokens >= 1 is computed correctly; 64 < tokens <= 256 runs on the key-resident
+ * text-attention kernels.  A changed count drops the projections registered by fgdm_set_context.  tokens < 1: FGDM_ERR_ARG.
+ * All samples of a batch share the count.  No launch, no synchronisation beyond freeing the dropped projections. */
+int fgdm_set_context_tokens(fgdm_engine* e, int tokens);
+int fgdm_get_context_tokens(const fgdm_engine* e);
 int fgdm_apply_model(fgdm_engine* e, const float* x, const int64_t* t, const float* t_float, const float* ctx,
                      const float* pcond, const float* control_scales, int B, int H, int W, int flags, float* eps_out,
                      void* stream);
@@ -116,6 +128,11 @@ int fgdm_apply_model(fgdm_engine* e, const float* x, const int64_t* t, const flo
  * ids int64 [B, T] (device; T <= clip_max_len, the tokenizer's padded max_length) -> last_hidden_state fp32 [B, T, W]
  * (device).  Needs clip_layers > 0 and the cond_stage_model.transformer.text_model.* tensors loaded. */
 int fgdm_clip_encode(fgdm_engine* e, const int64_t* ids, int B, int T, float* out, void* stream);
+/* The long-prompt route's transformer_encode (controlnet/cldm/hack.py:40-45): clip_skip > 1 gives
+ * text_model.final_layer_norm(hidden_states[-clip_skip]), i.e. the last clip_skip - 1 layers are not run (clip_skip <=
+ * clip_layers + 1; hidden_states[0] are the embeddings); clip_skip <= 1 is exactly fgdm_clip_encode.  The chunked [B,231,W]
+ * context of hack.py:47-68 is this call on ids [3B,77] read as [B,3*77,W] (rows (b f) -> b (f i): already contiguous). */
+int fgdm_clip_encode_skip(fgdm_engine* e, const int64_t* ids, int B, int T, int clip_skip, float* out, void* stream);
 
 /* First-stage decode: LatentDiffusion.decode_first_stage (ldm/models/diffusion/ddpm.py:832-889, plain branch) =
  * AutoencoderKL.decode(scale * z) (ldm/models/autoencoder.py:330-333; Decoder.forward,

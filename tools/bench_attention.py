@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Time the fused attention kernel on the shapes of the C3 workload (B = 32 rows of a CFG batch, 8 heads); TF/s are
-ALGORITHMIC (4 B T Tk C).  Usage (GPU box): python tools/bench_attention.py [--iters 20]"""
+ALGORITHMIC (4 B T Tk C).  Usage (GPU box): python tools/bench_attention.py [--iters 20] [--long]
+--long: the text-attention shapes at two and three 77-token parts (154 / 231 keys) with the 77-key shape as the control; run it
+once per setting of FGDM_ATTN_CROSS_LONG (0 = the general kernel, the dispatch of before) for a same-box A/B."""
 import argparse
 import ctypes as C
 import os
@@ -11,15 +13,23 @@ from fgdm_amd import _lib
 
 SHAPES = [(32, 8, 4096, 4096, 40), (32, 8, 4096, 77, 40), (32, 8, 1024, 1024, 80), (32, 8, 1024, 77, 80),
           (32, 8, 256, 256, 160), (32, 8, 256, 77, 160), (32, 8, 64, 64, 160), (16, 8, 4096, 4096, 40)]
+# cross-attention at two / three text parts (cat(c_crossattn, 1); controlnet/cldm/hack.py: 231 tokens), 77 keys as the control
+LONG_SHAPES = [(32, 8, 4096, 154, 40), (32, 8, 4096, 231, 40), (32, 8, 1024, 154, 80), (32, 8, 1024, 231, 80),
+               (32, 8, 256, 154, 160), (32, 8, 256, 231, 160), (32, 8, 4096, 77, 40),
+               # the other sub-tile counts of the key-resident kernel (NS = 4, 6, 7)
+               (32, 8, 4096, 120, 40), (32, 8, 4096, 190, 40), (32, 8, 1024, 120, 80), (32, 8, 1024, 190, 80),
+               (32, 8, 256, 120, 160), (32, 8, 256, 190, 160), (32, 8, 256, 220, 160)]
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--only', type=int, default=-1, help='index into SHAPES (profiling runs)')
+    ap.add_argument('--long', action='store_true', help='the long-context text-attention shapes (LONG_SHAPES)')
     a = ap.parse_args()
     lib = _lib.load()
-    for B, H, T, Tk, d in (SHAPES if a.only < 0 else [SHAPES[a.only]]):
+    shapes = LONG_SHAPES if a.long else SHAPES
+    for B, H, T, Tk, d in (shapes if a.only < 0 else [shapes[a.only]]):
         ms = C.c_float()
         rc = lib.fgdm_bench_attention(B, H, T, Tk, d, a.iters, C.byref(ms))
         fl = 4.0 * B * T * Tk * H * d

@@ -780,16 +780,85 @@ def g_full_size():
     save('full_size', **arrs)
 
 
+
+# --------------------------------------------------------------------------- long text contexts
+def g_long_context():
+    """Contexts of two and three 77-token parts (cat(c_crossattn, 1), ddpm.py:1835-1837 / cldm.py:846; hack.py:23-68):
+    full-width UNetModel.forward / forward_original at latent 8 x 8, ControlNet + ControlledUnetModel at 16 x 16."""
+    import long_context_inputs as li
+    from ldm.modules.diffusionmodules.openaimodel import UNetModel
+    from controlnet.cldm.cldm import ControlNet, ControlledUnetModel
+    arrs = {}
+    with torch.no_grad():
+        t = torch.tensor(li.T, dtype=torch.long)
+        arrs['t'] = t
+        m = UNetModel(**ref_cfg(gi.SD_CFG)).eval()
+        load_synth(m, 'model.diffusion_model.')
+        for tok in li.TOKENS:
+            arrs[f'eps_orig_{tok}'] = m(li.x(8), t, context=li.ctx(tok), use_original=True)
+            arrs[f'eps_fgdm_{tok}'] = m(li.x(8), t, context=li.ctx(tok))
+        del m
+        cn = ControlNet(**ref_cfg(gi.SD_CFG, hint_channels=3)).eval()
+        load_synth(cn, 'control_model.')
+        cu = ControlledUnetModel(**ref_cfg(gi.SD_CFG)).eval()
+        load_synth(cu, 'model.diffusion_model.')
+        ctx = li.ctx(231)
+        ctrl = cn(x=li.x(16), hint=li.hint(128), timesteps=t, context=ctx)
+        arrs['eps_ctrl_231'] = cu(x=li.x(16), timesteps=t, context=ctx, control=ctrl, only_mid_control=False)
+    save('long_context', **arrs)
+
+
+def g_clip_hack_tokens():
+    """The [3, 77] id arrays the reference's long-prompt route feeds its transformer (controlnet/cldm/hack.py:32-68), recorded
+    with a stub tokenizer (raw ids in, no vocabulary) and a stub transformer (records its input_ids)."""
+    import long_context_inputs as li
+    for name in ('clip', 'kornia'):       # imported at module level by ldm/modules/encoders/modules.py, unused on this path
+        sys.modules.setdefault(name, types.ModuleType(name))
+    # transformers probes optional packages with importlib.util.find_spec: hide the spec-less stubs while importing it (g_clip)
+    hidden = {k: sys.modules.pop(k) for k in list(sys.modules) if k.split('.')[0] in ('torchvision', 'omegaconf', 'taming',
+                                                                                      'pytorch_lightning')}
+    try:
+        from transformers import CLIPTokenizer, CLIPTextModel, logging  # noqa: F401
+    finally:
+        sys.modules.update(hidden)
+    from controlnet.cldm import hack
+
+    class Tok:
+        bos_token_id, eos_token_id, pad_token_id = 49406, 49407, 49407
+
+        def __call__(self, text, truncation=False, add_special_tokens=False):
+            assert not truncation and not add_special_tokens
+            return {'input_ids': [list(t) for t in text]}      # the "prompts" are raw token lists already
+
+    class Xf:
+        def __call__(self, input_ids, output_hidden_states=False):
+            self.seen = input_ids
+            return types.SimpleNamespace(last_hidden_state=torch.zeros(input_ids.shape[0], input_ids.shape[1], 1))
+
+    me = types.SimpleNamespace(tokenizer=Tok(), transformer=Xf(), clip_skip=0, device='cpu')
+    raws = [li.raw_tokens(n) for n in li.RAW_LENGTHS]
+    z = hack._hacked_clip_forward(me, raws)
+    assert tuple(z.shape) == (len(raws), 231, 1)
+    fed = me.transformer.seen.reshape(len(raws), 3, 77)
+    out = {'bos': 49406, 'eos': 49407, 'pad': 49407,
+           'cases': [{'raw_length': n, 'ids': fed[i].tolist()} for i, n in enumerate(li.RAW_LENGTHS)]}
+    path = os.path.join(GOLD, 'clip_hack_tokens.json')
+    with open(path, 'w') as f:
+        json.dump(out, f)
+    print(f'wrote {path}')
+
+
 ALL = dict(schedule=g_schedule, ddpm_schedule=g_ddpm_schedule, param_keys=g_param_keys, ops=g_ops,
            unet_full=g_unet_full, controlnet_full=g_controlnet_full, small_nets=g_small_nets,
            samplers=g_samplers, samplers2=g_samplers2, samplers3=g_samplers3, sampler_unet=g_sampler_unet, vae=g_vae, clip=g_clip, adapt_unet=g_adapt_unet, full_size=g_full_size,
-           full_size_check=g_full_size_check, vae_enc=g_vae_enc)
+           full_size_check=g_full_size_check, vae_enc=g_vae_enc, long_context=g_long_context,
+           clip_hack_tokens=g_clip_hack_tokens)
 
 
 # generators that are ALSO run with the reference's modules under the emulated torch.autocast("cuda") policy
 # (scripts/txt2img_fgdm_inference.py:212-217 wraps the whole sampling loop in it) -> tests/golden/<name>_ac.npz
 AC = ('ops', 'unet_full', 'controlnet_full', 'small_nets', 'sampler_unet', 'adapt_unet', 'vae', 'clip', 'full_size', 'full_size_check',
-      'vae_enc')
+      'vae_enc', 'long_context')
 
 
 def main():
