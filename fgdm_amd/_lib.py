@@ -89,6 +89,9 @@ SIGNATURES = {
     'fgdm_op_groupnorm': (_i, [_p, _i, _p, _i, _i, _i, _p, _p, _f, _i, _p, _p]),
     'fgdm_op_layernorm': (_i, [_p, _i, _i, _p, _p, _f, _p, _p]),
     'fgdm_op_attention': (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+    'fgdm_op_attention_ex': (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    'fgdm_debug_last_attention_kernel': (_i, []),
+    'fgdm_op_small_attention': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

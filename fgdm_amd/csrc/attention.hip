@@ -1787,6 +1787,18 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
     }
 }
 
+// Which kernel attention_launch chose on its last successful call in this process (fgdm_debug_last_attention_kernel: the parity
+// tests assert that a case reaches the kernel it was written for).  Host side only: one store of a plain int per launch.
+enum AttnKernelId { ATT_KID_NONE = 0, ATT_KID_GENERAL = 1, ATT_KID_CROSS = 2, ATT_KID_CROSS_LONG = 3, ATT_KID_PP = 4, ATT_KID_DQ16 = 5,
+                    ATT_KID_DQ32 = 6 };
+static int g_last_attn_kernel = ATT_KID_NONE;
+int attention_last_kernel() { return g_last_attn_kernel; }
+static int att_launched(int kid) {
+    if (hipGetLastError() != hipSuccess) return FGDM_ERR_HIP;
+    g_last_attn_kernel = kid;
+    return FGDM_OK;
+}
+
 // hipFuncSetAttribute is per device: the "attribute set" flag of an instantiation is kept per device id
 template <int D, int NS>
 static int launch_cross_long(dim3 grid, const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
@@ -1803,7 +1815,7 @@ static int launch_cross_long(dim3 grid, const half_t* Q, int ldq, const half_t* 
         attr_set[dev] = true;
     }
     FGDM_LAUNCH(k, grid, dim3(256), smem, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw);
-    return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+    return att_launched(ATT_KID_CROSS_LONG);
 }
 
 int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
@@ -1832,11 +1844,11 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
 #undef ATT_ABL_CASE
                 default: return FGDM_ERR_ARG;
             }
-            return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+            return att_launched(dq == 3 ? ATT_KID_DQ32 : ATT_KID_DQ16);
         }
         if (dq == 1) FGDM_LAUNCH((attn_dq_kernel<40, 4>), gridq, blockq, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
         else FGDM_LAUNCH((attn_dq32_kernel<40, 4>), gridq, blockq, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
-        return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+        return att_launched(dq == 1 ? ATT_KID_DQ16 : ATT_KID_DQ32);
     }
     // d = 80: the same kernel at one wave per SIMD (its two strands need ~280 registers); FGDM_ATTN_DQ80=0: the ping-pong kernel
     static const int dq80 = getenv("FGDM_ATTN_DQ80") ? atoi(getenv("FGDM_ATTN_DQ80")) : 1;
@@ -1844,13 +1856,13 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
         (size_t)d * ldvt * 2 < (1u << 31)) {
         const dim3 gridq((T / 256) * H * B), blockq(256);
         FGDM_LAUNCH((attn_dq32_kernel<80, 4>), gridq, blockq, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
-        return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+        return att_launched(ATT_KID_DQ32);
     }
     if (pp_on && T >= 256 && Tk >= 256 && (d == 40 || d == 80)) {
         const dim3 grid2(((T + 255) / 256) * H * B), block2(512);
         if (d == 40) FGDM_LAUNCH(attn_pp_kernel<40>, grid2, block2, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
         else FGDM_LAUNCH(attn_pp_kernel<80>, grid2, block2, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
-        return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+        return att_launched(ATT_KID_PP);
     }
     // the text tokens: all keys staged once per workgroup, several query chunks per wave; FGDM_ATTN_CROSS=0 switches it off (A/B)
     static const int cross = getenv("FGDM_ATTN_CROSS") ? atoi(getenv("FGDM_ATTN_CROSS")) : 4;
@@ -1863,7 +1875,7 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
             case 160: FGDM_LAUNCH(attn_cross_kernel<160>, gridc, blockc, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw); break;
             default: return FGDM_ERR_ARG;
         }
-        return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+        return att_launched(ATT_KID_CROSS);
     }
     // two or three text parts (96 < Tk <= 256): the key-resident kernel with NS = ceil(Tk / 32) sub-tiles, so that only the last one
     // can hold a key >= Tk and NS * 32 <= ldvt.  FGDM_ATTN_CROSS_LONG: query chunks per wave, 0 = the general kernel (A/B).  Default 8:
@@ -1892,5 +1904,5 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
         case 160: FGDM_LAUNCH(attn_kernel<160>, grid, block, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e); break;
         default: return FGDM_ERR_ARG;
     }
-    return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+    return att_launched(ATT_KID_GENERAL);
 }

@@ -136,6 +136,7 @@ int layernorm_launch(const half_t* x, int rows, int C, const float* gamma, const
 // O[b, t, h*d + :] = softmax(Q K^T * d^-1/2) V ; Q [B, T, ldq], K [B, Tk, ldk], Vt [B, H*d, ldvt] (keys contiguous)
 int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt,
                      half_t* O, int ldo, int B, int H, int T, int Tk, int d, int q_prescaled, hipStream_t s);
+int attention_last_kernel();      // AttnKernelId (attention.hip) of the last successful attention_launch of this process
 
 // ---------------------------------------------------------------- elementwise
 int nchw_f32_to_nhwc_f16(const float* x, half_t* y, int B, int C, int HW, int Cpad, hipStream_t s);

@@ -2855,5 +2855,19 @@ int fgdm_op_attention(const void* q, int ldq, const void* k, int ldk, const void
     if (!q || !k || !vt || !o) return FGDM_ERR_ARG;
     return attention_launch((const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)vt, ldvt, (half_t*)o, ldo, B, heads, T, Tk, d, 0, as_stream(stream));
 }
+// Diagnostic entries of tests/test_gpu_attention_calls.py: the flag the engine's own calls pass, the kernel the dispatch chose,
+// and the text encoder's attention kernel on its own.
+int fgdm_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo, int B,
+                         int heads, int T, int Tk, int d, int q_prescaled, void* stream) {
+    if (!q || !k || !vt || !o) return FGDM_ERR_ARG;
+    return attention_launch((const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)vt, ldvt, (half_t*)o, ldo, B, heads, T, Tk, d,
+                            q_prescaled ? 1 : 0, as_stream(stream));
+}
+int fgdm_debug_last_attention_kernel(void) { return attention_last_kernel(); }
+int fgdm_op_small_attention(const void* qkv, int ld, int koff, int voff, void* out, int ldo, int B, int heads, int T, int d,
+                            int causal, void* stream) {
+    if (!qkv || !out) return FGDM_ERR_ARG;
+    return small_attention_launch((const half_t*)qkv, ld, koff, voff, (half_t*)out, ldo, B, heads, T, d, causal, as_stream(stream));
+}
 
 }  // extern "C"

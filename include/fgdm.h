@@ -260,8 +260,28 @@ int fgdm_op_groupnorm(const void* x0, int C0, const void* x1, int C1, int B, int
                       const float* beta, float eps, int silu, void* out, void* stream);
 int fgdm_op_layernorm(const void* x, int rows, int C, const float* gamma, const float* beta, float eps,
                       void* out, void* stream);
+/* O[b, t, h d + :] = softmax(Q K^T d^-1/2) V, all fp16: Q [B, T, ldq], K [B, Tk, ldk] (head h at columns [h d, (h+1) d) of a row;
+ * ldq, ldk multiples of 8, ldo of 4; columns of a row beyond heads * d are never read, and never written in O), V transposed:
+ * vt [B, heads * d, ldvt], keys contiguous, ldvt a multiple of 8 and >= roundup(Tk, 64).  Contract for the columns of a V^T row:
+ * [0, Tk) the values; [Tk, roundup(Tk, 64)) must be ZERO (the kernels load whole 32- / 64-key tiles and multiply the pad
+ * columns by probabilities that are exactly 0, so anything finite would do, a NaN or Inf would not); columns >=
+ * roundup(Tk, 64) are read by no kernel and may hold anything.  d is 40, 80 or 160. */
 int fgdm_op_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo,
                       int B, int heads, int T, int Tk, int d, void* stream);
+/* Diagnostic entries (tests/test_gpu_attention_calls.py); the product path does not call them.
+ * fgdm_op_attention_ex: fgdm_op_attention with the engine's q_prescaled flag passed through.  q_prescaled = 1: Q already carries
+ * log2(e) d^-1/2 (the engine folds it into the to_q weights), so O = softmax(ln 2 * Q K^T) V and the kernels scale by exactly 1.
+ * fgdm_debug_last_attention_kernel: which kernel the dispatch chose on the last successful attention call of this process:
+ * 0 none yet, 1 general (attn_kernel), 2 text-token (attn_cross_kernel), 3 long-text (attn_cross_long_kernel), 4 ping-pong
+ * (attn_pp_kernel), 5 two-strand 16-wide (attn_dq_kernel), 6 two-strand 32-wide (attn_dq32_kernel).
+ * fgdm_op_small_attention: the text encoder's attention, softmax(q k^T d^-1/2 (j <= i when causal)) v with q | k | v as column
+ * blocks of one fp16 [B T, ld] matrix (q at column 0, k at koff, v at voff; head h at columns [64 h, 64 h + 64) of its block),
+ * out fp16 [B T, ldo]; d = 64 and 1 <= T <= 128, anything else is FGDM_ERR_ARG before any launch. */
+int fgdm_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo,
+                         int B, int heads, int T, int Tk, int d, int q_prescaled, void* stream);
+int fgdm_debug_last_attention_kernel(void);
+int fgdm_op_small_attention(const void* qkv, int ld, int koff, int voff, void* out, int ldo, int B, int heads, int T, int d,
+                            int causal, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@ import torch
 
 import golden_inputs as gi
 import long_context_inputs as li
+from attention_dispatch import expected_kernel
 from common import check_net, gold, net_tol, params, relerr, report
 from fgdm_amd import synth
 from guarded import guarded_in, guarded_out
@@ -69,6 +70,7 @@ def test_attention_long_text_contexts(lib, Tk, d):
             kd = din(k.half())                               # K rows past Tk (of the last sample) sit in NaN guards
             rc = lib.fgdm_op_attention(_p(qd), Cc, _p(kd), Cc, _p(vtd), Tkp, _p(out.t), Cc, B, Hh, T, Tk, d, _st())
             assert rc == 0
+            assert lib.fgdm_debug_last_attention_kernel() == expected_kernel(T, Tk, d), (T, Tk, d)
             torch.cuda.synchronize()
             what = f'attention long context B{B} H{Hh} T{T} Tk{Tk} d{d} spike@{key}'
             e = relerr(out.check().float().cpu(), ref)

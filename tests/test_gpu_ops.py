@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from attention_dispatch import expected_kernel
 from common import relerr, report
 from guarded import LOCAL_TOL, guarded_in, guarded_out, tile_err
 
@@ -338,6 +339,8 @@ def test_attention(lib, case):
     qd, kd, vtd = din(q.half()), din(k.half()), din(vt)
     rc = lib.fgdm_op_attention(_p(qd), Cc, _p(kd), Cc, _p(vtd), Tkp, _p(out.t), Cc, B, Hh, T, Tk, d, _st())
     assert rc == 0
+    # the kernel the case comments speak of is the kernel that ran (tests/attention_dispatch.py restates the dispatch rules)
+    assert lib.fgdm_debug_last_attention_kernel() == expected_kernel(T, Tk, d), case
     torch.cuda.synchronize()
     assert relerr(out.check().float().cpu(), ref) < TOL
     # P is rounded to fp16 before the PV product: blockwise 2 x the normwise bar (= LOCAL_TOL)
