@@ -92,6 +92,14 @@ SIGNATURES = {
     'fgdm_op_attention_ex': (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     'fgdm_debug_last_attention_kernel': (_i, []),
     'fgdm_op_small_attention': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+    'fgdm_op_vae_attention': (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    'fgdm_op_softmax_rows': (_i, [_p, _p, _i, _i, _p]),
+    'fgdm_op_nchw_to_nhwc': (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    'fgdm_op_nhwc_to_nchw': (_i, [_p, _p, _i, _i, _i, _p]),
+    'fgdm_op_avgpool2': (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    'fgdm_op_transpose_pad': (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    'fgdm_op_timestep_embed': (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    'fgdm_op_add_f16': (_i, [_p, _p, _p, _i64, _p]),
 }
 
 _lib = None

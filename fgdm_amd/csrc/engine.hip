@@ -189,6 +189,60 @@ struct Clip {
 
 static int roundup(int x, int m) { return (x + m - 1) / m * m; }
 
+// Column order of a packed conv3x3 weight row: kmap[k_packed] = index into the source row [Cin][3][3], or -1 for a pad column
+// (left zero).  Cin % 64 == 0, implicit GEMM: k = (c / 64 * 9 + tap) * 64 + c % 64 (64-channel chunk outermost, then tap: the order
+// the kernels walk K, see igemm2.hip), *cin_pad = Cin, K = 9 Cin.  Otherwise the im2col route: channels padded to *cin_pad (a
+// multiple of 8 when Cin is one, else of 4: the granule of k_im2col), k = tap * cin_pad + c, K = roundup64(9 cin_pad).
+// One function for Engine::pack_conv3 and fgdm_op_conv2d.
+static std::vector<int> conv3_kmap(int Cin, int* cin_pad) {
+    const bool implicit = (Cin % 64) == 0;
+    const int cp = implicit ? Cin : roundup(Cin, Cin % 8 == 0 ? 8 : 4);
+    const int K = implicit ? 9 * Cin : roundup(9 * cp, 64);
+    std::vector<int> kmap(K, -1);
+    for (int tap = 0; tap < 9; ++tap)
+        for (int c = 0; c < Cin; ++c) {
+            const int k = implicit ? ((c >> 6) * 9 + tap) * 64 + (c & 63) : tap * cp + c;
+            kmap[k] = c * 9 + tap;
+        }
+    *cin_pad = cp;
+    return kmap;
+}
+
+// The im2col route of a conv3x3 (padding 1, stride 1 or 2): A[m][tap * C + c] into the caller's workspace A [B Ho Wo, K], then
+// `gemm_rows(A, B, Ho, Wo, K, rows_per_sample)`: the caller's LINEAR GEMM over the rows of A viewed as [B, Ho, Wo, K], the rows
+// of one sample being its Ho Wo output pixels.  One sequence for Engine::conv3 (whose GEMM goes through the engine's arena and
+// timer) and fgdm_op_conv2d (caller-owned buffers); `after_im2col()` closes the engine's timer bracket around the first kernel.
+template <class After, class Gemm>
+static int im2col_conv(const half_t* x, half_t* A, int B, int H, int W, int C, int stride, int K, hipStream_t s,
+                       After&& after_im2col, Gemm&& gemm_rows) {
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const int rc = im2col3x3(x, A, B, H, W, C, stride, K, s);
+    after_im2col();
+    if (rc != FGDM_OK) return rc;
+    return gemm_rows(A, B, Ho, Wo, K, Ho * Wo);
+}
+
+// The core of AttnBlock.forward (model.py:188-199) for B images of T tokens, ONE head over all C channels, per image:
+// S = C^-1/2 Q K^T (fp32 [T, T]; a GEMM whose "weight" is the image's K rows), P = row softmax (fp16), O = P V (a GEMM over
+// K = T whose weight is the image's V^T [C, T]).  S and P are reused by every image.  q [B T, C]; k [B T + 128, C] (the GEMM
+// reads whole weight tiles of up to 128 rows: the rows after an image's keys must be readable and finite, they feed only score
+// columns >= T that are never written); vt [B, C, T]; out [B T, C].
+// `gemm_rows(Wt, N, K, A, M, out_kind, out, ld_out, scale)`: the caller's LINEAR GEMM out = scale * A Wt^T without bias.
+// One loop for Engine::vattn_fwd and fgdm_op_vae_attention.  Returns the first failing step's code; *softmax_failed tells which.
+template <class Gemm>
+static int vattn_core(const half_t* q, const half_t* k, const half_t* vt, half_t* out, float* S, half_t* P, int B, int T, int C,
+                      hipStream_t s, bool* softmax_failed, Gemm&& gemm_rows) {
+    *softmax_failed = false;
+    for (int b = 0; b < B; ++b) {
+        int rc = gemm_rows(k + (size_t)b * T * C, T, C, q + (size_t)b * T * C, T, OUT_F32, (void*)S, T, 1.0f / sqrtf((float)C));
+        if (rc != FGDM_OK) return rc;
+        if (softmax_rows(S, P, T, T, s) != FGDM_OK) { *softmax_failed = true; return FGDM_ERR_HIP; }
+        rc = gemm_rows(vt + (size_t)b * C * T, C, T, P, T, OUT_F16, (void*)(out + (size_t)b * T * C), C, 1.0f);
+        if (rc != FGDM_OK) return rc;
+    }
+    return FGDM_OK;
+}
+
 // Built-in kernel timer: when enabled, every launch is bracketed by HIP events recorded on the launch stream
 // (the same stream the kernels run on), so per-kernel-class device time, launch counts and the ALGORITHMIC
 // flops / bytes of exactly those launches can be read back without an external profiler.
@@ -767,20 +821,11 @@ struct fgdm_engine {
         const ParamSlot* b = slot(pre + ".bias");
         if (!w || !b) return FGDM_ERR_STATE;
         const int N = (int)w->shape[0], Cin = (int)w->shape[1];
-        const bool implicit = (Cin % 64) == 0;
-        const int cp = implicit ? Cin : roundup(Cin, Cin % 8 == 0 ? 8 : 4);
-        const int K = implicit ? 9 * Cin : roundup(9 * cp, 64);
-        std::vector<int> kmap(K, -1);
-        for (int tap = 0; tap < 9; ++tap)
-            for (int c = 0; c < Cin; ++c) {
-                // implicit GEMM: k = (c / 64 * 9 + tap) * 64 + c % 64  (64-channel chunk outermost, then tap: the order the
-                // kernels walk K, see igemm2.hip); im2col path: k = tap * cin_pad + c.  Source row layout is [Cin][3][3].
-                const int k = implicit ? ((c >> 6) * 9 + tap) * 64 + (c & 63) : tap * cp + c;
-                kmap[k] = c * 9 + tap;
-            }
-        g.im2col = !implicit;
+        int cp = 0;
+        const std::vector<int> kmap = conv3_kmap(Cin, &cp);      // source row layout is [Cin][3][3]
+        g.im2col = (Cin % 64) != 0;
         g.cin_pad = cp;
-        return pack_rows(g, {{w->host.data(), N}}, Cin * 9, K, kmap, {b->host.data()}, false);
+        return pack_rows(g, {{w->host.data(), N}}, Cin * 9, (int)kmap.size(), kmap, {b->host.data()}, false);
     }
     int pack_norm(NormW& n, const std::string& pre) {
         const ParamSlot* w = slot(pre + ".weight");
@@ -1087,12 +1132,15 @@ struct fgdm_engine {
         Tensor A = talloc(1, 1, x.B * Ho * Wo, w.K);
         if (!A.p) return fail(FGDM_ERR_NOMEM, "workspace (im2col)");
         prof.begin(PC_ELEM, s, 2.0 * (double)A.numel() + 2.0 * (double)x.numel());
-        int rc = im2col3x3(x.p, A.p, x.B, x.H, x.W, x.C, stride, w.K, s);
-        prof.end(s);
-        if (rc != FGDM_OK) return fail(rc, "im2col failed");
-        Tensor Av = A; Av.B = x.B; Av.H = Ho; Av.W = Wo; Av.C = w.K;
-        if (!e.rps) e.rps = Ho * Wo;
-        rc = gemm(w, IG_LINEAR, Av, nullptr, Ho, Wo, e, out);
+        bool in_gemm = false;
+        const int rc = im2col_conv(x.p, A.p, x.B, x.H, x.W, x.C, stride, w.K, s, [&]() { prof.end(s); },
+            [&](half_t* Ap, int Bv, int Hv, int Wv, int Kv, int rps) {
+                in_gemm = true;
+                Tensor Av; Av.p = Ap; Av.B = Bv; Av.H = Hv; Av.W = Wv; Av.C = Kv;
+                if (!e.rps) e.rps = rps;
+                return gemm(w, IG_LINEAR, Av, nullptr, Hv, Wv, e, out);
+            });
+        if (rc != FGDM_OK && !in_gemm) return fail(rc, "im2col failed");
         tfree(A);
         return rc;
     }
@@ -1973,16 +2021,15 @@ struct fgdm_engine {
         { Epi e; e.out = k.p; e.ld_out = C; e.rps = T; CHK(linear(at.k, g, e, nullptr)); }
         { Epi e; e.out_kind = OUT_F16_T; e.out = vt.p; e.ld_out = T; e.rps = T; CHK(linear(at.v, g, e, nullptr)); }
         tfree(g);
-        for (int b = 0; b < B; ++b) {
-            GemmW wk; wk.w = k.p + (size_t)b * T * C; wk.N = T; wk.K = C; wk.k_real = C;
-            Tensor qb; qb.p = q.p + (size_t)b * T * C; qb.B = 1; qb.H = 1; qb.W = T; qb.C = C;
-            { Epi e; e.out_kind = OUT_F32; e.out = S; e.ld_out = T; e.rps = T; e.scale = 1.0f / sqrtf((float)C);
-              CHK(gemm(wk, IG_LINEAR, qb, nullptr, 1, T, e, nullptr)); }
-            if (softmax_rows(S, P.p, T, T, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "softmax kernel");
-            GemmW wv; wv.w = vt.p + (size_t)b * C * T; wv.N = C; wv.K = T; wv.k_real = T;
-            { Epi e; e.out = a.p + (size_t)b * T * C; e.ld_out = C; e.rps = T;
-              CHK(gemm(wv, IG_LINEAR, P, nullptr, 1, T, e, nullptr)); }
-        }
+        bool softmax_failed = false;
+        const int rc = vattn_core(q.p, k.p, vt.p, a.p, S, P.p, B, T, C, s, &softmax_failed,
+            [&](const half_t* Wt, int N, int K, const half_t* A, int M, int out_kind, void* o, int ld_out, float scale) {
+                GemmW w; w.w = const_cast<half_t*>(Wt); w.N = N; w.K = K; w.k_real = K;
+                Tensor xa; xa.p = const_cast<half_t*>(A); xa.B = 1; xa.H = 1; xa.W = M; xa.C = K;
+                Epi e; e.out_kind = out_kind; e.out = o; e.ld_out = ld_out; e.rps = M; e.scale = scale;
+                return gemm(w, IG_LINEAR, xa, nullptr, 1, M, e, nullptr);
+            });
+        if (rc != FGDM_OK) return softmax_failed ? fail(rc, "softmax kernel") : rc;
         ar->release(S);
         tfree(P); tfree(q); tfree(k); tfree(vt);
         { Epi e; e.resid = x.p; e.ld_res = C; CHK(linear(at.o, a, e, out)); }
@@ -2119,6 +2166,56 @@ static half_t* g_zero_page() {
     static half_t* z = nullptr;
     if (!z) { if (hipMalloc(&z, 4096) != hipSuccess) return nullptr; (void)hipMemset(z, 0, 4096); }
     return z;
+}
+
+// Engine::gemm for the op-level test entries that share a launch sequence with the engine (im2col_conv, vattn_core): the same
+// IgemmArgs the engine would build -- its split-K plan included -- with hipMalloc'ed scratch instead of the arena and no timer.
+// The caller has filled the operands and the epilogue; synchronise before `tmp` goes out of scope.
+static int op_gemm_rows(IgemmArgs& a, const half_t* A, int B, int Ho, int Wo, int K, int rps, TmpDev& tmp, hipStream_t s) {
+    a.A0 = A; a.C0 = K; a.A1 = nullptr; a.C1 = 0;
+    a.zero = g_zero_page();
+    if (!a.zero) return FGDM_ERR_NOMEM;
+    a.B = B; a.H = Ho; a.W = Wo; a.Ho = Ho; a.Wo = Wo;
+    a.M = B * Ho * Wo; a.K = K; a.mode = IG_LINEAR; a.rows_per_sample = rps;
+    a.splitk = igemm_splitk_factor(a);
+    if (a.splitk > 1) {
+        if (hipMalloc(&a.ws, (size_t)a.splitk * a.M * a.N * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
+        tmp.ptrs.push_back(a.ws);
+    }
+    return igemm_launch(a, s);
+}
+
+// fgdm_op_conv2d for Cin % 64 != 0: the weight packed by conv3_kmap as Engine::pack_conv3 packs it, then im2col_conv as
+// Engine::conv3 runs it.  x fp16 NHWC with cin_pad channels.
+static int op_conv3_im2col(const half_t* x, int Cin, const float* w, const float* bias, const float* rowvec, const half_t* resid,
+                           int B, int H, int W, int Cout, int stride, int act, float scale, void* out, hipStream_t s) {
+    int cp = 0;
+    const std::vector<int> kmap = conv3_kmap(Cin, &cp);
+    const int K = (int)kmap.size(), Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    std::vector<float> wh((size_t)Cout * Cin * 9), bh(Cout, 0.f);
+    if (hipMemcpy(wh.data(), w, wh.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
+    if (bias && hipMemcpy(bh.data(), bias, Cout * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
+    const size_t npad = igemm_npad(Cout);
+    std::vector<half_t> pk(npad * (size_t)K, (half_t)0);
+    std::vector<float> bp(npad, 0.f);
+    for (int n = 0; n < Cout; ++n) {
+        bp[n] = bh[n];
+        for (int k = 0; k < K; ++k) if (kmap[k] >= 0) pk[(size_t)n * K + k] = (half_t)wh[(size_t)n * Cin * 9 + kmap[k]];
+    }
+    TmpDev tmp;
+    half_t* A = nullptr;
+    if (hipMalloc(&A, (size_t)B * Ho * Wo * K * sizeof(half_t)) != hipSuccess) return FGDM_ERR_NOMEM;
+    tmp.ptrs.push_back(A);
+    IgemmArgs a{};
+    a.Wt = tmp.up(pk); a.bias = tmp.up(bp);
+    if (!a.Wt || !a.bias) return FGDM_ERR_NOMEM;
+    a.rowvec = rowvec; a.rv_stride = Cout;
+    a.resid = resid; a.ld_res = Cout;
+    a.N = Cout; a.act = act; a.out_kind = OUT_F16; a.out = out; a.ld_out = Cout; a.scale = scale;
+    const int rc = im2col_conv(x, A, B, H, W, cp, stride, K, s, []() {},
+        [&](half_t* Ap, int Bv, int Hv, int Wv, int Kv, int rps) { return op_gemm_rows(a, Ap, Bv, Hv, Wv, Kv, rps, tmp, s); });
+    (void)hipStreamSynchronize(s);   // temporaries are freed on return
+    return rc;
 }
 
 
@@ -2503,7 +2600,11 @@ int fgdm_op_conv2d(const void* x0, int C0, const void* x1, int C1, const float* 
     if (stride == FGDM_STRIDE2_PAD_BR && (ksize != 3 || upsample)) return FGDM_ERR_ARG;
     hipStream_t s = as_stream(stream);
     const int Cin = C0 + C1, taps = ksize * ksize, K = taps * Cin;
-    if (Cin & 63) return FGDM_ERR_ARG;
+    if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || C0 <= 0 || C1 < 0) return FGDM_ERR_ARG;
+    if (Cin & 63) {     // the im2col route: exactly the combinations Engine::conv3 accepts on it
+        if (ksize != 3 || C1 || x1 || upsample || (stride != 1 && stride != 2)) return FGDM_ERR_ARG;
+        return op_conv3_im2col((const half_t*)x0, C0, w, bias, rowvec, (const half_t*)resid, B, H, W, Cout, stride, act, scale, out, s);
+    }
     std::vector<float> wh((size_t)Cout * K), bh(Cout, 0.f);
     if (hipMemcpy(wh.data(), w, wh.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
     if (bias && hipMemcpy(bh.data(), bias, Cout * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
@@ -2868,6 +2969,58 @@ int fgdm_op_small_attention(const void* qkv, int ld, int koff, int voff, void* o
                             int causal, void* stream) {
     if (!qkv || !out) return FGDM_ERR_ARG;
     return small_attention_launch((const half_t*)qkv, ld, koff, voff, (half_t*)out, ldo, B, heads, T, d, causal, as_stream(stream));
+}
+
+// Diagnostic entries of tests/test_gpu_narrow_ops.py; the product path does not call them.
+// The per-image loop of Engine::vattn_fwd (vattn_core) on caller-owned q / k / vt / out, with S and P of its own.
+int fgdm_op_vae_attention(const void* q, const void* k, const void* vt, void* out, int B, int T, int C, void* stream) {
+    if (!q || !k || !vt || !out || B <= 0 || T <= 0 || C <= 0 || (T & 63) || (C & 63)) return FGDM_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    TmpDev tmp;
+    float* S = nullptr;
+    half_t* P = nullptr;
+    if (hipMalloc(&S, (size_t)T * T * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
+    tmp.ptrs.push_back(S);
+    if (hipMalloc(&P, (size_t)T * T * sizeof(half_t)) != hipSuccess) return FGDM_ERR_NOMEM;
+    tmp.ptrs.push_back(P);
+    bool softmax_failed = false;
+    const int rc = vattn_core((const half_t*)q, (const half_t*)k, (const half_t*)vt, (half_t*)out, S, P, B, T, C, s, &softmax_failed,
+        [&](const half_t* Wt, int N, int K, const half_t* A, int M, int out_kind, void* o, int ld_out, float scale) {
+            IgemmArgs a{};
+            a.Wt = Wt; a.N = N; a.act = ACT_NONE; a.out_kind = out_kind; a.out = o; a.ld_out = ld_out; a.scale = scale;
+            return op_gemm_rows(a, A, 1, 1, M, K, M, tmp, s);
+        });
+    (void)hipStreamSynchronize(s);   // S and P are freed on return
+    return rc;
+}
+// Pass-throughs to the host launchers of elementwise.hip, pointer / shape checks in front.
+int fgdm_op_softmax_rows(const float* S, void* P, int rows, int cols, void* stream) {
+    if (!S || !P || rows <= 0 || cols <= 0) return FGDM_ERR_ARG;
+    return softmax_rows(S, (half_t*)P, rows, cols, as_stream(stream));
+}
+int fgdm_op_nchw_to_nhwc(const float* x, void* y, int B, int C, int HW, int Cpad, void* stream) {
+    if (!x || !y || B <= 0 || C <= 0 || HW <= 0 || Cpad < C) return FGDM_ERR_ARG;
+    return nchw_f32_to_nhwc_f16(x, (half_t*)y, B, C, HW, Cpad, as_stream(stream));
+}
+int fgdm_op_nhwc_to_nchw(const void* x, float* y, int B, int C, int HW, void* stream) {
+    if (!x || !y || B <= 0 || C <= 0 || HW <= 0) return FGDM_ERR_ARG;
+    return nhwc_f16_to_nchw_f32((const half_t*)x, y, B, C, HW, as_stream(stream));
+}
+int fgdm_op_avgpool2(const void* x, void* y, int B, int H, int W, int C, void* stream) {
+    if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || (H & 1) || (W & 1)) return FGDM_ERR_ARG;
+    return avgpool2((const half_t*)x, (half_t*)y, B, H, W, C, as_stream(stream));
+}
+int fgdm_op_transpose_pad(const void* v, void* vt, int B, int Tk, int C, int Tkpad, void* stream) {
+    if (!v || !vt || B <= 0 || Tk <= 0 || C <= 0 || Tkpad < Tk) return FGDM_ERR_ARG;
+    return transpose_pad_keys((const half_t*)v, (half_t*)vt, B, Tk, C, Tkpad, as_stream(stream));
+}
+int fgdm_op_timestep_embed(const int64_t* t, const float* t_float, void* y, int B, int dim, int rows_pad, void* stream) {
+    if ((!t && !t_float) || !y || B <= 0 || dim < 2 || (dim & 1) || rows_pad < B) return FGDM_ERR_ARG;
+    return timestep_embed(t, t_float, (half_t*)y, B, dim, rows_pad, as_stream(stream));
+}
+int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream) {
+    if (!a || !b || !y || n <= 0 || (n & 7)) return FGDM_ERR_ARG;
+    return add_f16((const half_t*)a, (const half_t*)b, (half_t*)y, (size_t)n, as_stream(stream));
 }
 
 }  // extern "C"

@@ -283,6 +283,45 @@ int fgdm_debug_last_attention_kernel(void);
 int fgdm_op_small_attention(const void* qkv, int ld, int koff, int voff, void* out, int ldo, int B, int heads, int T, int d,
                             int causal, void* stream);
 
+/* Diagnostic entries (tests/test_gpu_narrow_ops.py); the product path does not call them.  Every argument error is FGDM_ERR_ARG
+ * before any launch.
+ *
+ * fgdm_op_conv2d with (C0 + C1) % 64 != 0 -- the first convolution of every network: UNet / ControlNet conv_in, the adapter input,
+ * ControlNet.input_hint_block up to its 256-wide layer (controlnet/cldm/cldm.py:655-671), the first-stage conv_in's (ldm/modules/
+ * diffusionmodules/model.py:390,484).  Accepted for ksize == 3, C1 == 0 (x1 NULL), upsample == 0 and stride 1 or 2, the combinations
+ * the engine's own im2col route takes; anything else stays FGDM_ERR_ARG.  C0 is the logical Cin; x0 is fp16 NHWC with cin_pad
+ * channels, cin_pad = roundup(Cin, 8) when Cin % 8 == 0, else roundup(Cin, 4).  Contract for the pad channels [Cin, cin_pad) of
+ * x0: they must be FINITE (the engine's layout kernel leaves them +0); their columns of the packed weight are exactly zero, so a
+ * finite value there changes no bit of the result.  w is [Cout, Cin, 3, 3] fp32; all epilogue arguments work as for Cin % 64 == 0.
+ *
+ * fgdm_op_vae_attention: the core of the first-stage AttnBlock (ldm/modules/diffusionmodules/model.py:176-203, lines 188-199: ONE
+ * head over all C channels), per image b: out_b = softmax(C^-1/2 q_b k_b^T) v_b, as the engine evaluates it (fp32 scores by a GEMM
+ * with the K rows as weight, row softmax to fp16, a GEMM over T with V^T as weight).  All fp16: q [B T, C]; k [B T + 128, C];
+ * vt [B, C, T] (V transposed, tokens contiguous); out [B T, C].  T and C multiples of 64.  Contract for the 128 rows after the last
+ * key row of k: they must be readable and FINITE (the GEMM loads whole weight tiles of up to 128 rows; the rows beyond an image's
+ * T keys -- the next image's keys, or this pad -- feed only score columns >= T, which are never written); what follows them is
+ * read by no kernel.  vt: when C is a multiple of 128 nothing beyond [B, C, T] is read and anything may follow; otherwise up to 64
+ * further rows of T halves after the last image's V^T must be readable (they feed only output columns >= C, never written). */
+int fgdm_op_vae_attention(const void* q, const void* k, const void* vt, void* out, int B, int T, int C, void* stream);
+/* One entry per kernel of the layout / elementwise group, on caller-owned device buffers; asynchronous on `stream`.
+ *  fgdm_op_softmax_rows: P = fp16(softmax(S)) over the `cols` fp32 logits of each of `rows` rows (AttnBlock, model.py:190-192).
+ *  fgdm_op_nchw_to_nhwc: x fp32 [B, C, HW] -> y fp16 [B, HW, Cpad], channels >= C exactly +0 (Cpad >= C).
+ *  fgdm_op_nhwc_to_nchw: x fp16 [B, HW, C] -> y fp32 [B, C, HW].
+ *  fgdm_op_avgpool2: AvgPool2d(2) on fp16 NHWC [B, H, W, C] -> [B, H/2, W/2, C] (the adapter's Downsample with use_conv = False,
+ *      ldm/modules/encoders/adapter.py:270-273); H, W even, C a multiple of 8.
+ *  fgdm_op_transpose_pad: v fp16 [B, Tk, C] -> vt fp16 [B, C, Tkpad], columns [Tk, Tkpad) exactly zero (Tkpad >= Tk).
+ *  fgdm_op_timestep_embed: timestep_embedding (ldm/modules/diffusionmodules/util.py:160-180): y fp16 [rows_pad, dim], row b < B =
+ *      [cos(t_b f_k) | sin(t_b f_k)], f_k = exp(-ln(1e4) k / (dim / 2)); t int64 [B], or fp32 t_float [B] when non-NULL ("these may be
+ *      fractional", util.py:165); rows [B, rows_pad) exactly zero.  dim even.
+ *  fgdm_op_add_f16: y = a + b on n fp16 elements, summed in fp32 and rounded once; n a multiple of 8; y may alias a. */
+int fgdm_op_softmax_rows(const float* S, void* P, int rows, int cols, void* stream);
+int fgdm_op_nchw_to_nhwc(const float* x, void* y, int B, int C, int HW, int Cpad, void* stream);
+int fgdm_op_nhwc_to_nchw(const void* x, float* y, int B, int C, int HW, void* stream);
+int fgdm_op_avgpool2(const void* x, void* y, int B, int H, int W, int C, void* stream);
+int fgdm_op_transpose_pad(const void* v, void* vt, int B, int Tk, int C, int Tkpad, void* stream);
+int fgdm_op_timestep_embed(const int64_t* t, const float* t_float, void* y, int B, int dim, int rows_pad, void* stream);
+int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

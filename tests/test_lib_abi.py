@@ -97,6 +97,49 @@ def test_unsupported_configs_are_rejected(lib):
         eng.param_shapes(eng.make_config(gi.SMALL_CFG, use_adapter=True))
 
 
+def test_narrow_op_entries_refuse_bad_arguments(lib):
+    """The diagnostic entries of tests/test_gpu_narrow_ops.py return FGDM_ERR_ARG before any launch (so without a GPU too): the
+    pointers below are never dereferenced."""
+    import ctypes as C
+    p, null = C.c_void_p(1 << 20), None
+    # fgdm_op_conv2d with Cin % 64 != 0: ksize 3, C1 == 0, no upsample, stride 1 or 2 only
+    conv = lambda C0, x1, C1, ks, stride, up: lib.fgdm_op_conv2d(p, C0, x1, C1, p, p, null, null, 1, 8, 8, 16, ks, stride, up, 0, 1.0, p, null)
+    assert conv(4, null, 0, 1, 1, 0) < 0                      # ksize 1
+    assert conv(4, p, 4, 3, 1, 0) < 0                         # a concatenated input
+    assert conv(4, null, 0, 3, 1, 1) < 0                      # upsample
+    assert conv(4, null, 0, 3, _lib.STRIDE2_PAD_BR, 0) < 0    # the encoder's bottom / right padding
+    assert conv(4, null, 0, 3, 3, 0) < 0                      # stride 3
+    assert conv(96, null, 0, 1, 1, 0) < 0
+    assert lib.fgdm_op_conv2d(null, 4, null, 0, p, p, null, null, 1, 8, 8, 16, 3, 1, 0, 0, 1.0, p, null) < 0
+    assert lib.fgdm_op_conv2d(p, 4, null, 0, p, p, null, null, 0, 8, 8, 16, 3, 1, 0, 0, 1.0, p, null) < 0
+    # fgdm_op_vae_attention: NULL pointers, T % 64 != 0, C % 64 != 0
+    for args in ((null, p, p, p), (p, null, p, p), (p, p, null, p), (p, p, p, null)):
+        assert lib.fgdm_op_vae_attention(*args, 1, 64, 512, null) < 0
+    assert lib.fgdm_op_vae_attention(p, p, p, p, 1, 100, 512, null) < 0
+    assert lib.fgdm_op_vae_attention(p, p, p, p, 1, 64, 100, null) < 0
+    assert lib.fgdm_op_vae_attention(p, p, p, p, 0, 64, 512, null) < 0
+    # the layout / elementwise entries
+    assert lib.fgdm_op_softmax_rows(null, p, 4, 64, null) < 0 and lib.fgdm_op_softmax_rows(p, null, 4, 64, null) < 0
+    assert lib.fgdm_op_softmax_rows(p, p, 0, 64, null) < 0 and lib.fgdm_op_softmax_rows(p, p, 4, 0, null) < 0
+    assert lib.fgdm_op_nchw_to_nhwc(null, p, 1, 3, 64, 4, null) < 0 and lib.fgdm_op_nchw_to_nhwc(p, null, 1, 3, 64, 4, null) < 0
+    assert lib.fgdm_op_nchw_to_nhwc(p, p, 1, 4, 64, 3, null) < 0         # Cpad < C
+    assert lib.fgdm_op_nhwc_to_nchw(null, p, 1, 4, 64, null) < 0 and lib.fgdm_op_nhwc_to_nchw(p, null, 1, 4, 64, null) < 0
+    assert lib.fgdm_op_nhwc_to_nchw(p, p, 1, 4, 0, null) < 0
+    assert lib.fgdm_op_avgpool2(null, p, 1, 8, 8, 8, null) < 0 and lib.fgdm_op_avgpool2(p, null, 1, 8, 8, 8, null) < 0
+    assert lib.fgdm_op_avgpool2(p, p, 1, 7, 8, 8, null) < 0              # odd H
+    assert lib.fgdm_op_avgpool2(p, p, 1, 8, 7, 8, null) < 0              # odd W
+    assert lib.fgdm_op_avgpool2(p, p, 1, 8, 8, 12, null) < 0             # C % 8
+    assert lib.fgdm_op_transpose_pad(null, p, 1, 77, 320, 128, null) < 0 and lib.fgdm_op_transpose_pad(p, null, 1, 77, 320, 128, null) < 0
+    assert lib.fgdm_op_transpose_pad(p, p, 1, 77, 320, 64, null) < 0     # Tkpad < Tk
+    assert lib.fgdm_op_timestep_embed(null, null, p, 1, 320, 1, null) < 0 and lib.fgdm_op_timestep_embed(p, null, null, 1, 320, 1, null) < 0
+    assert lib.fgdm_op_timestep_embed(p, null, p, 2, 320, 1, null) < 0   # rows_pad < B
+    assert lib.fgdm_op_timestep_embed(p, null, p, 1, 321, 1, null) < 0   # odd dim
+    assert lib.fgdm_op_add_f16(null, p, p, 8, null) < 0 and lib.fgdm_op_add_f16(p, null, p, 8, null) < 0
+    assert lib.fgdm_op_add_f16(p, p, null, 8, null) < 0
+    assert lib.fgdm_op_add_f16(p, p, p, 12, null) < 0                    # n % 8
+    assert lib.fgdm_op_add_f16(p, p, p, 0, null) < 0
+
+
 def test_engine_needs_gpu_no_fallback(lib):
     import torch
     if torch.cuda.is_available():
