@@ -22,9 +22,9 @@
 //
 // (variants that were measured and rejected, and what bounds these kernels: DESIGN.md section 4.2 / 4.3)
 #include "common.h"
+#include "knobs.h"
 #include <type_traits>
 #include <algorithm>
-#include <stdlib.h>
 
 #pragma clang diagnostic ignored "-Winline-asm"     // M0 named as an asm clobber (att_dma16): reserved register, on purpose
 #define ATT_THR 8.0f
@@ -1799,21 +1799,13 @@ static int att_launched(int kid) {
     return FGDM_OK;
 }
 
-// hipFuncSetAttribute is per device: the "attribute set" flag of an instantiation is kept per device id
 template <int D, int NS>
 static int launch_cross_long(dim3 grid, const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
                              int ldo, int H, int T, int Tk, float sl2e, int cpw, hipStream_t s) {
     constexpr int smem = attn_cross_long_lds(D, NS);
     static_assert(smem <= 160 * 1024, "does not fit the 160 KB of a CU");
-    constexpr int MAXDEV = 64;
-    static bool attr_set[MAXDEV] = {};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return FGDM_ERR_HIP;
-    auto k = attn_cross_long_kernel<D, NS>;
-    if (!attr_set[dev]) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return FGDM_ERR_HIP;
-        attr_set[dev] = true;
-    }
+    constexpr auto k = attn_cross_long_kernel<D, NS>;
+    if (fgdm_dyn_lds<k>(smem) != FGDM_OK) return FGDM_ERR_HIP;
     FGDM_LAUNCH(k, grid, dim3(256), smem, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw);
     return att_launched(ATT_KID_CROSS_LONG);
 }
@@ -1826,16 +1818,15 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
     // log2 domain with ONE fp16 rounding; the kernels then multiply by exactly 1
     const float sl2e = q_prescaled ? 1.0f : 1.4426950408889634f / sqrtf((float)d);
     // long self-attention: the eight-wave ping-pong kernel (256 queries per workgroup); FGDM_ATTN_PP=0 switches it off (A/B)
-    static const bool pp_on = !(getenv("FGDM_ATTN_PP") && atoi(getenv("FGDM_ATTN_PP")) == 0);
-    // ... and the two-strand kernel where its shape conditions hold (FGDM_ATTN_DQ: 0 = off, 1 = plain, 2 = rotated tail)
+    const bool pp_on = knob_once(KNOB_ATTN_PP) != 0;
     // ... and the two-strand kernels where their shape conditions hold.  FGDM_ATTN_DQ: 0 = off, 1 = 16-wide V^T P^T (the faster one
     // on random operands: 756 vs 733 TF/s at B32 T4096), 3 = 32-wide V^T P^T (default: the faster one inside the network, where the
     // activations toggle less and the chip holds its clock: attention family 357 vs 362 ms per sampling pass, 421 before)
-    static const int dq = getenv("FGDM_ATTN_DQ") ? atoi(getenv("FGDM_ATTN_DQ")) : 3;
+    const int dq = knob_once(KNOB_ATTN_DQ);
     if (dq > 0 && d == 40 && T % 256 == 0 && Tk % 64 == 0 && Tk >= 128 && (size_t)64 * ldk * 2 < (1u << 31) &&
         (size_t)d * ldvt * 2 < (1u << 31)) {
         const dim3 gridq((T / 256) * H * B), blockq(256);
-        static const int abl = getenv("FGDM_ATTN_ABL") ? atoi(getenv("FGDM_ATTN_ABL")) : 0;     // tools/bench_attention.py only
+        const int abl = knob_once(KNOB_ATTN_ABL);    // tools/bench_attention.py only
         if (abl) {
             switch (abl + (dq == 3 ? 1000 : 0)) {
 #define ATT_ABL_CASE(v) case v: FGDM_LAUNCH((attn_dq_kernel<40, 4, v>), gridq, blockq, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e); break; \
@@ -1851,7 +1842,7 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
         return att_launched(dq == 1 ? ATT_KID_DQ16 : ATT_KID_DQ32);
     }
     // d = 80: the same kernel at one wave per SIMD (its two strands need ~280 registers); FGDM_ATTN_DQ80=0: the ping-pong kernel
-    static const int dq80 = getenv("FGDM_ATTN_DQ80") ? atoi(getenv("FGDM_ATTN_DQ80")) : 1;
+    const int dq80 = knob_once(KNOB_ATTN_DQ80);
     if (dq80 > 0 && d == 80 && T % 256 == 0 && Tk % 64 == 0 && Tk >= 128 && (size_t)64 * ldk * 2 < (1u << 31) &&
         (size_t)d * ldvt * 2 < (1u << 31)) {
         const dim3 gridq((T / 256) * H * B), blockq(256);
@@ -1865,7 +1856,7 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
         return att_launched(ATT_KID_PP);
     }
     // the text tokens: all keys staged once per workgroup, several query chunks per wave; FGDM_ATTN_CROSS=0 switches it off (A/B)
-    static const int cross = getenv("FGDM_ATTN_CROSS") ? atoi(getenv("FGDM_ATTN_CROSS")) : 4;
+    const int cross = knob_once(KNOB_ATTN_CROSS);
     if (cross > 0 && Tk > 64 && Tk <= 96 && ldvt >= 96 && T >= 128) {
         const int cpw = std::min(cross, T / 128);
         const dim3 gridc(((T + 128 * cpw - 1) / (128 * cpw)) * H * B), blockc(256);
@@ -1881,7 +1872,7 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
     // can hold a key >= Tk and NS * 32 <= ldvt.  FGDM_ATTN_CROSS_LONG: query chunks per wave, 0 = the general kernel (A/B).  Default 8:
     // staging 154 - 256 keys costs as much traffic as the Q + O rows of 4 chunks, and at T = 1024 eight chunks make one workgroup
     // per (batch, head) (measured: profiles/long_context_attention.txt; 4 chunks do not beat attn_kernel at d = 80)
-    static const int cross_long = getenv("FGDM_ATTN_CROSS_LONG") ? atoi(getenv("FGDM_ATTN_CROSS_LONG")) : 8;
+    const int cross_long = knob_once(KNOB_ATTN_CROSS_LONG);
     if (cross_long > 0 && Tk > 96 && Tk <= 256 && T >= 128) {
         const int ns = (Tk + 31) / 32;
         if (ldvt >= ns * 32 && (d == 40 || d == 80 || (d == 160 && ns <= 7))) {

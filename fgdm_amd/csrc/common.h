@@ -124,6 +124,9 @@ size_t igemm_npad(int n);   // rows the packed weight must provide
 
 // ---------------------------------------------------------------- norms
 // GroupNorm(32 groups) over NHWC fp16, optionally over the virtual concat of two sources; fp32 statistics.
+// pixels per partial-sum chunk of the two-kernel path (round 4: 64 -> 256, the reduction tail of a stats workgroup was as long as its
+// loads: 64x64 x 320 channels, B = 32: 50.1 -> 45.5 us for both kernels, B = 16: 32.1 -> 29.3; profiles/r04_gn_chunk.txt)
+#define GN_PIX_PER_CHUNK 256
 void groupnorm_set_group(bool on);     // while the engine records: attach the grouped form to single-pass GroupNorm launches (default on)
 int groupnorm_launch(const half_t* x0, int C0, const half_t* x1, int C1, int B, int HW,
                      const float* gamma, const float* beta, float eps, int silu,
@@ -177,6 +180,22 @@ int ancestral_step(const float* x, const float* eps, float sqrt_recip, float sqr
                    float std, const float* noise, float* out, size_t n, hipStream_t s);
 
 #define HIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return FGDM_ERR_HIP; } while (0)
+
+// Opt `Kernel` in to `bytes` of dynamic LDS (a launch may ask for 64 KB without it), once per kernel and device: the attribute
+// belongs to a device's copy of the function, so every instantiation keeps its "set" flags per device id.  Call it ahead of
+// FGDM_LAUNCH (a recorded walk then sets the attribute while it records).
+template <auto Kernel>
+int fgdm_dyn_lds(int bytes) {
+    constexpr int MAXDEV = 64;
+    static bool set[MAXDEV] = {};
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return FGDM_ERR_HIP;
+    if (!set[dev]) {
+        HIP_TRY(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        set[dev] = true;
+    }
+    return FGDM_OK;
+}
 
 // ---------------------------------------------------------------- deferred launches (twin-layer grouped launches)
 // While the engine RECORDS (engine.hip: apply_model with FGDM_PAIR_LAUNCH), nothing is enqueued: every launch site goes through

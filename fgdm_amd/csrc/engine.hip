@@ -8,8 +8,8 @@
 //   SpatialTransformer & friends    ldm/modules/attention.py:152-292
 //   Adapter                         ldm/modules/encoders/adapter.py:280-346
 //   ControlNet / ControlledUnet     controlnet/cldm/cldm.py:27-50, 545-813, 836-849
-#include "common.h"
-#include "../../include/fgdm.h"
+#include "engine_shared.h"
+#include "knobs.h"
 
 #include <algorithm>
 #include <array>
@@ -186,62 +186,6 @@ struct Clip {
     std::vector<ClipLayer> layers;
     NormW final_ln;
 };
-
-static int roundup(int x, int m) { return (x + m - 1) / m * m; }
-
-// Column order of a packed conv3x3 weight row: kmap[k_packed] = index into the source row [Cin][3][3], or -1 for a pad column
-// (left zero).  Cin % 64 == 0, implicit GEMM: k = (c / 64 * 9 + tap) * 64 + c % 64 (64-channel chunk outermost, then tap: the order
-// the kernels walk K, see igemm2.hip), *cin_pad = Cin, K = 9 Cin.  Otherwise the im2col route: channels padded to *cin_pad (a
-// multiple of 8 when Cin is one, else of 4: the granule of k_im2col), k = tap * cin_pad + c, K = roundup64(9 cin_pad).
-// One function for Engine::pack_conv3 and fgdm_op_conv2d.
-static std::vector<int> conv3_kmap(int Cin, int* cin_pad) {
-    const bool implicit = (Cin % 64) == 0;
-    const int cp = implicit ? Cin : roundup(Cin, Cin % 8 == 0 ? 8 : 4);
-    const int K = implicit ? 9 * Cin : roundup(9 * cp, 64);
-    std::vector<int> kmap(K, -1);
-    for (int tap = 0; tap < 9; ++tap)
-        for (int c = 0; c < Cin; ++c) {
-            const int k = implicit ? ((c >> 6) * 9 + tap) * 64 + (c & 63) : tap * cp + c;
-            kmap[k] = c * 9 + tap;
-        }
-    *cin_pad = cp;
-    return kmap;
-}
-
-// The im2col route of a conv3x3 (padding 1, stride 1 or 2): A[m][tap * C + c] into the caller's workspace A [B Ho Wo, K], then
-// `gemm_rows(A, B, Ho, Wo, K, rows_per_sample)`: the caller's LINEAR GEMM over the rows of A viewed as [B, Ho, Wo, K], the rows
-// of one sample being its Ho Wo output pixels.  One sequence for Engine::conv3 (whose GEMM goes through the engine's arena and
-// timer) and fgdm_op_conv2d (caller-owned buffers); `after_im2col()` closes the engine's timer bracket around the first kernel.
-template <class After, class Gemm>
-static int im2col_conv(const half_t* x, half_t* A, int B, int H, int W, int C, int stride, int K, hipStream_t s,
-                       After&& after_im2col, Gemm&& gemm_rows) {
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    const int rc = im2col3x3(x, A, B, H, W, C, stride, K, s);
-    after_im2col();
-    if (rc != FGDM_OK) return rc;
-    return gemm_rows(A, B, Ho, Wo, K, Ho * Wo);
-}
-
-// The core of AttnBlock.forward (model.py:188-199) for B images of T tokens, ONE head over all C channels, per image:
-// S = C^-1/2 Q K^T (fp32 [T, T]; a GEMM whose "weight" is the image's K rows), P = row softmax (fp16), O = P V (a GEMM over
-// K = T whose weight is the image's V^T [C, T]).  S and P are reused by every image.  q [B T, C]; k [B T + 128, C] (the GEMM
-// reads whole weight tiles of up to 128 rows: the rows after an image's keys must be readable and finite, they feed only score
-// columns >= T that are never written); vt [B, C, T]; out [B T, C].
-// `gemm_rows(Wt, N, K, A, M, out_kind, out, ld_out, scale)`: the caller's LINEAR GEMM out = scale * A Wt^T without bias.
-// One loop for Engine::vattn_fwd and fgdm_op_vae_attention.  Returns the first failing step's code; *softmax_failed tells which.
-template <class Gemm>
-static int vattn_core(const half_t* q, const half_t* k, const half_t* vt, half_t* out, float* S, half_t* P, int B, int T, int C,
-                      hipStream_t s, bool* softmax_failed, Gemm&& gemm_rows) {
-    *softmax_failed = false;
-    for (int b = 0; b < B; ++b) {
-        int rc = gemm_rows(k + (size_t)b * T * C, T, C, q + (size_t)b * T * C, T, OUT_F32, (void*)S, T, 1.0f / sqrtf((float)C));
-        if (rc != FGDM_OK) return rc;
-        if (softmax_rows(S, P, T, T, s) != FGDM_OK) { *softmax_failed = true; return FGDM_ERR_HIP; }
-        rc = gemm_rows(vt + (size_t)b * C * T, C, T, P, T, OUT_F16, (void*)(out + (size_t)b * T * C), C, 1.0f);
-        if (rc != FGDM_OK) return rc;
-    }
-    return FGDM_OK;
-}
 
 // Built-in kernel timer: when enabled, every launch is bracketed by HIP events recorded on the launch stream
 // (the same stream the kernels run on), so per-kernel-class device time, launch counts and the ALGORITHMIC
@@ -1822,7 +1766,7 @@ struct fgdm_engine {
         std::vector<RecOp> rec_un;
         struct RecGuard { ~RecGuard() { g_rec = nullptr; igemm_set_pair_hint(1); } } rec_guard;   // whatever path leaves: recording ends
         if (paired) {
-            static const bool fat = !(getenv("FGDM_PAIR_FAT_TILES") && atoi(getenv("FGDM_PAIR_FAT_TILES")) == 0);       // A/B knob
+            const bool fat = knob_once(KNOB_PAIR_FAT_TILES) != 0;      // A/B knob
             if (fat) igemm_set_pair_hint(std::min<int>(group_max, 1 + (int)cns.size()));
             groupnorm_set_group(gn_group);
             int rc = FGDM_OK;
@@ -2149,76 +2093,7 @@ struct fgdm_engine {
 };
 
 // ================================================================================================ C ABI
-static hipStream_t as_stream(void* p) { return (hipStream_t)p; }
-
-struct TmpDev {
-    std::vector<void*> ptrs;
-    ~TmpDev() { for (void* p : ptrs) (void)hipFree(p); }
-    template <typename T> T* up(const std::vector<T>& h) {
-        T* d = nullptr;
-        if (hipMalloc(&d, std::max<size_t>(h.size() * sizeof(T), 256)) != hipSuccess) return nullptr;
-        (void)hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-        ptrs.push_back(d);
-        return d;
-    }
-};
-static half_t* g_zero_page() {
-    static half_t* z = nullptr;
-    if (!z) { if (hipMalloc(&z, 4096) != hipSuccess) return nullptr; (void)hipMemset(z, 0, 4096); }
-    return z;
-}
-
-// Engine::gemm for the op-level test entries that share a launch sequence with the engine (im2col_conv, vattn_core): the same
-// IgemmArgs the engine would build -- its split-K plan included -- with hipMalloc'ed scratch instead of the arena and no timer.
-// The caller has filled the operands and the epilogue; synchronise before `tmp` goes out of scope.
-static int op_gemm_rows(IgemmArgs& a, const half_t* A, int B, int Ho, int Wo, int K, int rps, TmpDev& tmp, hipStream_t s) {
-    a.A0 = A; a.C0 = K; a.A1 = nullptr; a.C1 = 0;
-    a.zero = g_zero_page();
-    if (!a.zero) return FGDM_ERR_NOMEM;
-    a.B = B; a.H = Ho; a.W = Wo; a.Ho = Ho; a.Wo = Wo;
-    a.M = B * Ho * Wo; a.K = K; a.mode = IG_LINEAR; a.rows_per_sample = rps;
-    a.splitk = igemm_splitk_factor(a);
-    if (a.splitk > 1) {
-        if (hipMalloc(&a.ws, (size_t)a.splitk * a.M * a.N * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
-        tmp.ptrs.push_back(a.ws);
-    }
-    return igemm_launch(a, s);
-}
-
-// fgdm_op_conv2d for Cin % 64 != 0: the weight packed by conv3_kmap as Engine::pack_conv3 packs it, then im2col_conv as
-// Engine::conv3 runs it.  x fp16 NHWC with cin_pad channels.
-static int op_conv3_im2col(const half_t* x, int Cin, const float* w, const float* bias, const float* rowvec, const half_t* resid,
-                           int B, int H, int W, int Cout, int stride, int act, float scale, void* out, hipStream_t s) {
-    int cp = 0;
-    const std::vector<int> kmap = conv3_kmap(Cin, &cp);
-    const int K = (int)kmap.size(), Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    std::vector<float> wh((size_t)Cout * Cin * 9), bh(Cout, 0.f);
-    if (hipMemcpy(wh.data(), w, wh.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
-    if (bias && hipMemcpy(bh.data(), bias, Cout * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
-    const size_t npad = igemm_npad(Cout);
-    std::vector<half_t> pk(npad * (size_t)K, (half_t)0);
-    std::vector<float> bp(npad, 0.f);
-    for (int n = 0; n < Cout; ++n) {
-        bp[n] = bh[n];
-        for (int k = 0; k < K; ++k) if (kmap[k] >= 0) pk[(size_t)n * K + k] = (half_t)wh[(size_t)n * Cin * 9 + kmap[k]];
-    }
-    TmpDev tmp;
-    half_t* A = nullptr;
-    if (hipMalloc(&A, (size_t)B * Ho * Wo * K * sizeof(half_t)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(A);
-    IgemmArgs a{};
-    a.Wt = tmp.up(pk); a.bias = tmp.up(bp);
-    if (!a.Wt || !a.bias) return FGDM_ERR_NOMEM;
-    a.rowvec = rowvec; a.rv_stride = Cout;
-    a.resid = resid; a.ld_res = Cout;
-    a.N = Cout; a.act = act; a.out_kind = OUT_F16; a.out = out; a.ld_out = Cout; a.scale = scale;
-    const int rc = im2col_conv(x, A, B, H, W, cp, stride, K, s, []() {},
-        [&](half_t* Ap, int Bv, int Hv, int Wv, int Kv, int rps) { return op_gemm_rows(a, Ap, Bv, Hv, Wv, Kv, rps, tmp, s); });
-    (void)hipStreamSynchronize(s);   // temporaries are freed on return
-    return rc;
-}
-
-
+// (the op-level test entries are in ops_abi.hip, the micro-benchmark entries in bench_abi.hip)
 static int make_desc(const fgdm_config* cfg, fgdm_engine** out) {
     fgdm_engine* e = new fgdm_engine();
     e->cfg = *cfg;
@@ -2253,17 +2128,17 @@ int fgdm_create(const fgdm_config* cfg, int device, fgdm_engine** out) {
     int rc = make_desc(cfg, &e);
     if (rc != FGDM_OK) { g_create_err = "unsupported configuration"; return rc; }
     e->device = device;
-    if (const char* v = getenv("FGDM_LN_FOLD")) e->ln_fold = atoi(v) != 0;
+    e->ln_fold = knob_on(KNOB_LN_FOLD);
     rc = e->ensure_device();
     if (rc != FGDM_OK) {
         g_create_err = e->err + " [" + hipGetErrorString(hipGetLastError()) + "]";
         delete e;
         return rc;
     }
-    if (const char* v = getenv("FGDM_TWIN_STREAMS")) e->twin_streams = atoi(v) != 0;
-    if (const char* v = getenv("FGDM_PAIR_LAUNCH")) e->pair_launch = atoi(v) != 0;
-    if (const char* v = getenv("FGDM_GROUP_MAX")) e->group_max = std::max(2, std::min(FGDM_MAX_GROUP, atoi(v)));
-    if (const char* v = getenv("FGDM_GN_GROUP")) e->gn_group = atoi(v) != 0;
+    e->twin_streams = knob_on(KNOB_TWIN_STREAMS);
+    e->pair_launch = knob_on(KNOB_PAIR_LAUNCH);
+    e->group_max = std::max(2, std::min(FGDM_MAX_GROUP, knob_int(KNOB_GROUP_MAX)));
+    e->gn_group = knob_on(KNOB_GN_GROUP);
     if (e->twin_streams && !e->cns.empty()) {
         if (hipStreamCreateWithFlags(&e->s2, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -2290,7 +2165,7 @@ void fgdm_destroy(fgdm_engine* e) {
     for (auto& n : e->cns) if (n.guided.p) (void)hipFree(n.guided.p);
     e->drop_context();
     e->drop_adapter_conds();
-    if (getenv("FGDM_PAIR_DEBUG") && e->replayed_launches)
+    if (knob_text(KNOB_PAIR_DEBUG) && e->replayed_launches)
         fprintf(stderr, "[fgdm] grouped twin launches: %ld of %ld replayed launches were fused (%ld problems)\n", e->paired_launches, e->replayed_launches, e->paired_problems);
     if (e->s2) { (void)hipStreamSynchronize(e->s2); (void)hipStreamDestroy(e->s2); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -2396,7 +2271,7 @@ int fgdm_profile_end(fgdm_engine* e, double* out) {
     }
     for (int c = 0; c < PC_COUNT; ++c) { out[c * 4 + 2] = e->prof.work[c]; out[c * 4 + 3] = e->prof.bytes[c]; }
     // optional per-shape dump: FGDM_PROF_DUMP=<path>  ->  "tag <tab> launches <tab> total_ms <tab> work"
-    if (const char* path = getenv("FGDM_PROF_DUMP")) {
+    if (const char* path = knob_text(KNOB_PROF_DUMP)) {
         std::map<std::string, std::array<double, 3>> agg;
         for (auto& r : e->prof.recs) {
             if (!r.e1) continue;
@@ -2590,437 +2465,6 @@ int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* u
     e->arena.release(x2); e->arena.release(eps); e->arena.release(c2); e->arena.release(tdev);
     return rc;
     });
-}
-
-// ------------------------------------------------------------------------------------ op-level test entries
-int fgdm_op_conv2d(const void* x0, int C0, const void* x1, int C1, const float* w, const float* bias, const float* rowvec,
-                   const void* resid, int B, int H, int W, int Cout, int ksize, int stride, int upsample, int act,
-                   float scale, void* out, void* stream) {
-    if (!x0 || !w || !out || (ksize != 1 && ksize != 3)) return FGDM_ERR_ARG;
-    if (stride == FGDM_STRIDE2_PAD_BR && (ksize != 3 || upsample)) return FGDM_ERR_ARG;
-    hipStream_t s = as_stream(stream);
-    const int Cin = C0 + C1, taps = ksize * ksize, K = taps * Cin;
-    if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || C0 <= 0 || C1 < 0) return FGDM_ERR_ARG;
-    if (Cin & 63) {     // the im2col route: exactly the combinations Engine::conv3 accepts on it
-        if (ksize != 3 || C1 || x1 || upsample || (stride != 1 && stride != 2)) return FGDM_ERR_ARG;
-        return op_conv3_im2col((const half_t*)x0, C0, w, bias, rowvec, (const half_t*)resid, B, H, W, Cout, stride, act, scale, out, s);
-    }
-    std::vector<float> wh((size_t)Cout * K), bh(Cout, 0.f);
-    if (hipMemcpy(wh.data(), w, wh.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
-    if (bias && hipMemcpy(bh.data(), bias, Cout * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
-    const size_t npad = igemm_npad(Cout);
-    std::vector<half_t> pk(npad * (size_t)K, (half_t)0);
-    std::vector<float> bp(npad, 0.f);
-    for (int n = 0; n < Cout; ++n) {
-        bp[n] = bh[n];
-        for (int tap = 0; tap < taps; ++tap)
-            for (int c = 0; c < Cin; ++c) {
-                const size_t k = taps == 9 ? (size_t)((c >> 6) * 9 + tap) * 64 + (c & 63) : (size_t)c;
-                pk[(size_t)n * K + k] = (half_t)wh[((size_t)n * Cin + c) * taps + tap];
-            }
-    }
-    TmpDev tmp;
-    IgemmArgs a{};
-    a.A0 = (const half_t*)x0; a.C0 = C0; a.A1 = (const half_t*)x1; a.C1 = C1;
-    a.Wt = tmp.up(pk); a.bias = tmp.up(bp);
-    a.zero = g_zero_page();
-    if (!a.Wt || !a.bias || !a.zero) return FGDM_ERR_NOMEM;
-    a.rowvec = rowvec; a.rv_stride = Cout;
-    a.resid = (const half_t*)resid; a.ld_res = Cout;
-    a.B = B; a.H = H; a.W = W;
-    a.Ho = H; a.Wo = W; a.mode = IG_LINEAR;
-    if (ksize == 3) {
-        a.mode = IG_CONV3;
-        if (upsample) { a.Ho = 2 * H; a.Wo = 2 * W; a.mode = IG_CONV3_UP2; }
-        else if (stride == 2) { a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1; a.mode = IG_CONV3_S2; }
-        else if (stride == FGDM_STRIDE2_PAD_BR) {
-            if (H < 2 || W < 2) return FGDM_ERR_ARG;
-            a.Ho = (H - 2) / 2 + 1; a.Wo = (W - 2) / 2 + 1; a.mode = IG_CONV3_S2_BR;
-        }
-    }
-    a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = K;
-    a.act = act; a.out_kind = OUT_F16; a.out = out; a.ld_out = Cout;
-    a.rows_per_sample = a.Ho * a.Wo; a.scale = scale;
-    a.splitk = igemm_splitk_factor(a);
-    if (a.splitk > 1) {
-        if (hipMalloc(&a.ws, (size_t)a.splitk * a.M * a.N * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
-        tmp.ptrs.push_back(a.ws);
-    }
-    const int rc = igemm_launch(a, s);
-    (void)hipStreamSynchronize(s);   // temporaries are freed on return
-    return rc;
-}
-
-int fgdm_op_linear(const void* x, const float* w, const float* bias, const void* resid, int M, int K, int N, int act,
-                   int out_kind, int rows_per_sample, int ld_out, void* out, void* stream) {
-    if (!x || !w || !out || (K & 63)) return FGDM_ERR_ARG;
-    hipStream_t s = as_stream(stream);
-    std::vector<float> wh((size_t)N * K), bh(N, 0.f);
-    if (hipMemcpy(wh.data(), w, wh.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
-    if (bias && hipMemcpy(bh.data(), bias, N * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
-    const size_t npad = igemm_npad(N);
-    std::vector<half_t> pk(npad * (size_t)K, (half_t)0);
-    std::vector<float> bp(npad, 0.f);
-    for (int pr = 0; pr < N; ++pr) {
-        int sr = pr;
-        if (act == ACT_GEGLU) { const int grp = pr >> 6, within = pr & 63; sr = within < 32 ? grp * 32 + within : N / 2 + grp * 32 + (within - 32); }
-        bp[pr] = bh[sr];
-        for (int k = 0; k < K; ++k) pk[(size_t)pr * K + k] = (half_t)wh[(size_t)sr * K + k];
-    }
-    TmpDev tmp;
-    IgemmArgs a{};
-    a.A0 = (const half_t*)x; a.C0 = K;
-    a.Wt = tmp.up(pk); a.bias = tmp.up(bp); a.zero = g_zero_page();
-    if (!a.Wt || !a.bias || !a.zero) return FGDM_ERR_NOMEM;
-    const int nout = act == ACT_GEGLU ? N / 2 : N;
-    a.resid = (const half_t*)resid; a.ld_res = nout;
-    a.B = 1; a.H = 1; a.W = M; a.Ho = 1; a.Wo = M;
-    a.M = M; a.N = N; a.K = K; a.mode = IG_LINEAR; a.act = act; a.out_kind = out_kind;
-    a.out = out; a.ld_out = ld_out ? ld_out : nout;
-    a.rows_per_sample = rows_per_sample ? rows_per_sample : M; a.scale = 1.f;
-    const int rc = igemm_launch(a, s);
-    (void)hipStreamSynchronize(s);
-    return rc;
-}
-
-// h = x W1^T + b1 (+ resid), fp16, with the LayerNorm partial sums of its rows produced on the way (from the GEMM's own
-// epilogue when the chosen kernel can, else by row_stats), then y = act(LayerNorm(h) W2^T + b2) with the LayerNorm folded
-// into the second GEMM: the producer / consumer pair of every transformer-block LayerNorm (attention.py:234-240).
-// *slots_used receives the number of partial-sum slots per row (1 = the separate row_stats pass ran).
-int fgdm_op_linear_ln_linear(const void* x, const float* w1, const float* b1, const void* resid, const float* gamma,
-                             const float* beta, const float* w2, const float* b2, int M, int K1, int C, int N2, int act2,
-                             void* h_out, void* y_out, int* slots_used, void* stream) {
-    if (!x || !w1 || !gamma || !beta || !w2 || !h_out || !y_out || (K1 & 63) || (C & 63)) return FGDM_ERR_ARG;
-    hipStream_t s = as_stream(stream);
-    auto host = [](const float* d, size_t n, std::vector<float>& v) { v.resize(n); return hipMemcpy(v.data(), d, n * sizeof(float), hipMemcpyDefault) == hipSuccess; };
-    std::vector<float> W1, B1(C, 0.f), G, Bt, W2, B2(N2, 0.f);
-    if (!host(w1, (size_t)C * K1, W1) || !host(gamma, C, G) || !host(beta, C, Bt) || !host(w2, (size_t)N2 * C, W2)) return FGDM_ERR_HIP;
-    if (b1 && !host(b1, C, B1)) return FGDM_ERR_HIP;
-    if (b2 && !host(b2, N2, B2)) return FGDM_ERR_HIP;
-    const size_t np1 = igemm_npad(C), np2 = igemm_npad(N2);
-    std::vector<half_t> p1(np1 * (size_t)K1, (half_t)0), p2(np2 * (size_t)C, (half_t)0);
-    std::vector<float> bp1(np1, 0.f), bp2(np2, 0.f), u2(np2, 0.f);
-    for (int n = 0; n < C; ++n) { bp1[n] = B1[n]; for (int k = 0; k < K1; ++k) p1[(size_t)n * K1 + k] = (half_t)W1[(size_t)n * K1 + k]; }
-    for (int pr = 0; pr < N2; ++pr) {
-        int sr = pr;
-        if (act2 == ACT_GEGLU) { const int grp = pr >> 6, within = pr & 63; sr = within < 32 ? grp * 32 + within : N2 / 2 + grp * 32 + (within - 32); }
-        double us = 0.0, cs = 0.0;
-        for (int k = 0; k < C; ++k) {
-            const half_t wq = (half_t)(W2[(size_t)sr * C + k] * G[k]);
-            p2[(size_t)pr * C + k] = wq;
-            us += (double)(float)wq;
-            cs += (double)Bt[k] * (double)W2[(size_t)sr * C + k];
-        }
-        u2[pr] = (float)us;
-        bp2[pr] = (float)((double)B2[sr] + cs);
-    }
-    TmpDev tmp;
-    IgemmArgs a{};
-    a.A0 = (const half_t*)x; a.C0 = K1; a.Wt = tmp.up(p1); a.bias = tmp.up(bp1); a.zero = g_zero_page();
-    a.resid = (const half_t*)resid; a.ld_res = C;
-    a.B = 1; a.H = 1; a.W = M; a.Ho = 1; a.Wo = M; a.M = M; a.N = C; a.K = K1; a.mode = IG_LINEAR; a.act = ACT_NONE;
-    a.out_kind = OUT_F16; a.out = h_out; a.ld_out = C; a.rows_per_sample = M; a.scale = 1.f;
-    if (!a.Wt || !a.bias || !a.zero) return FGDM_ERR_NOMEM;
-    int slots = igemm_stats_slots(a);
-    float* stats = nullptr;
-    if (hipMalloc(&stats, (size_t)M * std::max(slots, row_stats_slots(C)) * 2 * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(stats);
-    if (slots) a.stats_out = stats;
-    int rc = igemm_launch(a, s);
-    if (rc == FGDM_OK && !slots) { slots = row_stats_slots(C); rc = row_stats_launch((const half_t*)h_out, M, C, stats, s); }
-    if (slots_used) *slots_used = a.stats_out ? slots : -slots;      // negative: the separate pass produced them
-    if (rc != FGDM_OK) { (void)hipStreamSynchronize(s); return rc; }
-    IgemmArgs b{};
-    b.A0 = (const half_t*)h_out; b.C0 = C; b.Wt = tmp.up(p2); b.bias = tmp.up(bp2); b.zero = a.zero;
-    b.ln_stats = stats; b.ln_slots = slots; b.ln_u = tmp.up(u2); b.ln_eps = 1e-5f;
-    const int nout = act2 == ACT_GEGLU ? N2 / 2 : N2;
-    b.B = 1; b.H = 1; b.W = M; b.Ho = 1; b.Wo = M; b.M = M; b.N = N2; b.K = C; b.mode = IG_LINEAR; b.act = act2;
-    b.out_kind = OUT_F16; b.out = y_out; b.ld_out = nout; b.rows_per_sample = M; b.scale = 1.f;
-    if (!b.Wt || !b.bias || !b.ln_u) return FGDM_ERR_NOMEM;
-    rc = igemm_launch(b, s);
-    (void)hipStreamSynchronize(s);
-    return rc;
-}
-
-int fgdm_debug_force_igemm_cfg(int cfg) { igemm_set_force_cfg(cfg); return FGDM_OK; }
-
-// Micro-benchmark of one conv / linear shape on random data: average device ms over `iters` launches.
-int fgdm_bench_igemm(int B, int H, int W, int C0, int C1, int Cout, int ksize, int stride, int upsample, int act,
-                     int use_resid, int cfg, int iters, float* avg_ms) {
-    if (!avg_ms || iters <= 0 || (ksize != 1 && ksize != 3)) return FGDM_ERR_ARG;
-    const int Cin = C0 + C1, taps = ksize * ksize, K = taps * Cin;
-    if (Cin & 63) return FGDM_ERR_ARG;
-    int Ho = H, Wo = W, mode = ksize == 3 ? IG_CONV3 : IG_LINEAR;
-    if (ksize == 3 && upsample) { Ho = 2 * H; Wo = 2 * W; mode = IG_CONV3_UP2; }
-    else if (ksize == 3 && stride == 2) { Ho = (H - 1) / 2 + 1; Wo = (W - 1) / 2 + 1; mode = IG_CONV3_S2; }
-    const size_t M = (size_t)B * Ho * Wo, nin = (size_t)B * H * W;
-    const size_t npad = igemm_npad(Cout);
-    const int nout = act == ACT_GEGLU ? Cout / 2 : Cout;
-    unsigned st = 12345u;
-    // FGDM_BENCH_DATA_SCALE=0 benches all-zero operands: the gap to random data is the chip lowering its clock under load
-    const float dscale = getenv("FGDM_BENCH_DATA_SCALE") ? (float)atof(getenv("FGDM_BENCH_DATA_SCALE")) : 1.0f;
-    auto rnd = [&]() { st = st * 1664525u + 1013904223u; return dscale * (((st >> 9) & 0xffff) / 32768.0f - 1.0f); };
-    std::vector<half_t> hx0(nin * C0), hx1(nin * (size_t)std::max(C1, 1)), hw(npad * (size_t)K), hr(M * nout);
-    std::vector<float> hb(npad);
-    for (auto& v : hx0) v = (half_t)rnd();
-    for (auto& v : hx1) v = (half_t)rnd();
-    const float ws = 1.0f / sqrtf((float)K);
-    for (auto& v : hw) v = (half_t)(rnd() * ws);
-    for (auto& v : hr) v = (half_t)rnd();
-    for (auto& v : hb) v = rnd() * 0.1f;
-    TmpDev tmp;
-    half_t* out = nullptr;
-    if (hipMalloc(&out, M * nout * sizeof(half_t)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(out);
-    IgemmArgs a{};
-    a.A0 = tmp.up(hx0); a.C0 = C0; a.A1 = C1 ? tmp.up(hx1) : nullptr; a.C1 = C1;
-    a.Wt = tmp.up(hw); a.bias = tmp.up(hb); a.zero = g_zero_page();
-    a.resid = use_resid ? tmp.up(hr) : nullptr; a.ld_res = nout;
-    if (!a.A0 || !a.Wt || !a.bias || !a.zero) return FGDM_ERR_NOMEM;
-    a.B = B; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.mode = mode;
-    a.M = (int)M; a.N = Cout; a.K = K; a.act = act; a.out_kind = OUT_F16; a.out = out; a.ld_out = nout;
-    a.rows_per_sample = Ho * Wo; a.scale = 1.f; a.force_cfg = cfg & 0xff; a.debug = (cfg >> 8) & 0xff;
-    if ((cfg & 0xff) == 0) {
-        a.splitk = igemm_splitk_factor(a);
-        if (a.splitk > 1) {
-            if (hipMalloc(&a.ws, (size_t)a.splitk * a.M * a.N * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
-            tmp.ptrs.push_back(a.ws);
-        }
-    }
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    int rc = FGDM_OK;
-    for (int i = 0; i < 3 && rc == FGDM_OK; ++i) rc = igemm_launch(a, nullptr);
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters && rc == FGDM_OK; ++i) rc = igemm_launch(a, nullptr);
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return rc;
-}
-
-// Feed-forward pair of a transformer block (GEGLU projection C -> 8C, then 4C -> C with the residual) on M random token rows,
-// evaluated in row chunks of `chunk` rows that reuse ONE intermediate buffer: does the 4C intermediate of a chunk stay on chip
-// (L2 / Infinity Cache) between its producer and its consumer?  chunk = M: the two launches the engine makes today.
-int fgdm_bench_ff(int M, int Cw, int chunk, int iters, float* avg_ms) {
-    if (!avg_ms || iters <= 0 || M <= 0 || chunk <= 0 || (Cw % 320) || (M % chunk)) return FGDM_ERR_ARG;
-    const int N1 = 8 * Cw, K2 = 4 * Cw;
-    unsigned st = 4321u;
-    auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 9) & 0xffff) / 32768.0f - 1.0f; };
-    std::vector<half_t> hx((size_t)M * Cw), hw1(igemm_npad(N1) * (size_t)Cw), hw2(igemm_npad(Cw) * (size_t)K2);
-    std::vector<float> hb1(igemm_npad(N1)), hb2(igemm_npad(Cw));
-    for (auto& v : hx) v = (half_t)rnd();
-    for (auto& v : hw1) v = (half_t)(rnd() / sqrtf((float)Cw));
-    for (auto& v : hw2) v = (half_t)(rnd() / sqrtf((float)K2));
-    for (auto& v : hb1) v = rnd() * 0.1f;
-    for (auto& v : hb2) v = rnd() * 0.1f;
-    TmpDev tmp;
-    half_t *h = nullptr, *out = nullptr;
-    if (hipMalloc(&h, (size_t)chunk * K2 * sizeof(half_t)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(h);
-    if (hipMalloc(&out, (size_t)M * Cw * sizeof(half_t)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(out);
-    const half_t* x = tmp.up(hx);
-    IgemmArgs g{}, f{};
-    g.Wt = tmp.up(hw1); g.bias = tmp.up(hb1); g.zero = g_zero_page();
-    f.Wt = tmp.up(hw2); f.bias = tmp.up(hb2); f.zero = g.zero;
-    if (!x || !g.Wt || !g.bias || !f.Wt || !f.bias || !g.zero) return FGDM_ERR_NOMEM;
-    g.C0 = Cw; g.B = 1; g.H = 1; g.W = chunk; g.Ho = 1; g.Wo = chunk; g.M = chunk; g.N = N1; g.K = Cw; g.mode = IG_LINEAR;
-    g.act = ACT_GEGLU; g.out_kind = OUT_F16; g.out = h; g.ld_out = K2; g.rows_per_sample = chunk; g.scale = 1.f;
-    f.A0 = h; f.C0 = K2; f.B = 1; f.H = 1; f.W = chunk; f.Ho = 1; f.Wo = chunk; f.M = chunk; f.N = Cw; f.K = K2; f.mode = IG_LINEAR;
-    f.act = ACT_NONE; f.out_kind = OUT_F16; f.ld_out = Cw; f.ld_res = Cw; f.rows_per_sample = chunk; f.scale = 1.f;
-    auto pass = [&]() {
-        int rc = FGDM_OK;
-        for (int r0 = 0; r0 < M && rc == FGDM_OK; r0 += chunk) {
-            g.A0 = x + (size_t)r0 * Cw;
-            rc = igemm_launch(g, nullptr);
-            f.resid = x + (size_t)r0 * Cw; f.out = out + (size_t)r0 * Cw;
-            if (rc == FGDM_OK) rc = igemm_launch(f, nullptr);
-        }
-        return rc;
-    };
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    int rc = FGDM_OK;
-    for (int i = 0; i < 2 && rc == FGDM_OK; ++i) rc = pass();
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters && rc == FGDM_OK; ++i) rc = pass();
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return rc;
-}
-
-// Micro-benchmark of the fused attention kernel on random data: average device ms over `iters` launches.
-int fgdm_bench_attention(int B, int heads, int T, int Tk, int d, int iters, float* avg_ms) {
-    if (!avg_ms || iters <= 0 || B <= 0 || heads <= 0 || T <= 0 || Tk <= 0) return FGDM_ERR_ARG;
-    const int C = heads * d, Tkp = (Tk + 63) / 64 * 64;
-    unsigned st = 4242u;
-    auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 9) & 0xffff) / 32768.0f - 1.0f; };
-    std::vector<half_t> hq((size_t)B * T * C), hk((size_t)B * Tk * C), hv((size_t)B * C * Tkp, (half_t)0);
-    // FGDM_BENCH_DATA_SCALE (default 1) scales the operands: 0 gives the all-zero run that separates data-dependent
-    // power draw from instruction issue.
-    const char* dsv = getenv("FGDM_BENCH_DATA_SCALE");
-    const float ds = dsv ? (float)atof(dsv) : 1.0f;
-    for (auto& v : hq) v = (half_t)(rnd() * 1.5f * ds);
-    for (auto& v : hk) v = (half_t)(rnd() * 1.5f * ds);
-    for (size_t r = 0; r < (size_t)B * C; ++r) for (int t = 0; t < Tk; ++t) hv[r * Tkp + t] = (half_t)(rnd() * ds);
-    TmpDev tmp;
-    half_t* o = nullptr;
-    if (hipMalloc(&o, (size_t)B * T * C * sizeof(half_t)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(o);
-    const half_t *dq = tmp.up(hq), *dk = tmp.up(hk), *dv = tmp.up(hv);
-    if (!dq || !dk || !dv) return FGDM_ERR_NOMEM;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    int rc = FGDM_OK;
-    for (int i = 0; i < 3 && rc == FGDM_OK; ++i) rc = attention_launch(dq, C, dk, C, dv, Tkp, o, C, B, heads, T, Tk, d, 0, nullptr);
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters && rc == FGDM_OK; ++i) rc = attention_launch(dq, C, dk, C, dv, Tkp, o, C, B, heads, T, Tk, d, 0, nullptr);
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return rc;
-}
-
-// Micro-benchmark of one GroupNorm / LayerNorm shape on random data: average device ms over `iters` launches.
-// kind 0: GroupNorm32(+SiLU) over [B, HW, C0 (+ C1 virtual concat)]; kind 1: LayerNorm over [B * HW, C0].
-int fgdm_bench_norm(int kind, int B, int HW, int C0, int C1, int silu, int iters, float* avg_ms) {
-    if (!avg_ms || iters <= 0 || B <= 0 || HW <= 0) return FGDM_ERR_ARG;
-    const int C = C0 + C1;
-    const size_t n0 = (size_t)B * HW * C0, n1 = (size_t)B * HW * (size_t)std::max(C1, 1), n = (size_t)B * HW * C;
-    unsigned st = 777u;
-    auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 9) & 0xffff) / 32768.0f - 1.0f; };
-    std::vector<half_t> h0(n0), h1(n1);
-    for (auto& v : h0) v = (half_t)rnd();
-    for (auto& v : h1) v = (half_t)rnd();
-    std::vector<float> g(C), b(C);
-    for (int i = 0; i < C; ++i) { g[i] = 1.f + 0.2f * rnd(); b[i] = 0.1f * rnd(); }
-    TmpDev tmp;
-    half_t* out = nullptr;
-    float* ws = nullptr;
-    if (hipMalloc(&out, n * sizeof(half_t)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(out);
-    if (hipMalloc(&ws, groupnorm_ws_floats(B, HW) * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(ws);
-    const half_t* d0 = tmp.up(h0);
-    const half_t* d1 = C1 ? tmp.up(h1) : nullptr;
-    const float* dg = tmp.up(g);
-    const float* db = tmp.up(b);
-    if (!d0 || !dg || !db) return FGDM_ERR_NOMEM;
-    auto run = [&]() {
-        return kind == 0 ? groupnorm_launch(d0, C0, d1, C1, B, HW, dg, db, 1e-5f, silu, out, ws, nullptr)
-                         : layernorm_launch(d0, B * HW, C0, dg, db, 1e-5f, out, nullptr);
-    };
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    int rc = FGDM_OK;
-    for (int i = 0; i < 3 && rc == FGDM_OK; ++i) rc = run();
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters && rc == FGDM_OK; ++i) rc = run();
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return rc;
-}
-
-int fgdm_op_groupnorm(const void* x0, int C0, const void* x1, int C1, int B, int HW, const float* gamma, const float* beta,
-                      float eps, int silu, void* out, void* stream) {
-    if (!x0 || !gamma || !beta || !out) return FGDM_ERR_ARG;
-    hipStream_t s = as_stream(stream);
-    float* ws = nullptr;
-    if (hipMalloc(&ws, groupnorm_ws_floats(B, HW) * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
-    const int rc = groupnorm_launch((const half_t*)x0, C0, (const half_t*)x1, C1, B, HW, gamma, beta, eps, silu, (half_t*)out, ws, s);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(ws);
-    return rc;
-}
-int fgdm_op_layernorm(const void* x, int rows, int C, const float* gamma, const float* beta, float eps, void* out, void* stream) {
-    if (!x || !gamma || !beta || !out) return FGDM_ERR_ARG;
-    return layernorm_launch((const half_t*)x, rows, C, gamma, beta, eps, (half_t*)out, as_stream(stream));
-}
-int fgdm_op_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo, int B,
-                      int heads, int T, int Tk, int d, void* stream) {
-    if (!q || !k || !vt || !o) return FGDM_ERR_ARG;
-    return attention_launch((const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)vt, ldvt, (half_t*)o, ldo, B, heads, T, Tk, d, 0, as_stream(stream));
-}
-// Diagnostic entries of tests/test_gpu_attention_calls.py: the flag the engine's own calls pass, the kernel the dispatch chose,
-// and the text encoder's attention kernel on its own.
-int fgdm_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo, int B,
-                         int heads, int T, int Tk, int d, int q_prescaled, void* stream) {
-    if (!q || !k || !vt || !o) return FGDM_ERR_ARG;
-    return attention_launch((const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)vt, ldvt, (half_t*)o, ldo, B, heads, T, Tk, d,
-                            q_prescaled ? 1 : 0, as_stream(stream));
-}
-int fgdm_debug_last_attention_kernel(void) { return attention_last_kernel(); }
-int fgdm_op_small_attention(const void* qkv, int ld, int koff, int voff, void* out, int ldo, int B, int heads, int T, int d,
-                            int causal, void* stream) {
-    if (!qkv || !out) return FGDM_ERR_ARG;
-    return small_attention_launch((const half_t*)qkv, ld, koff, voff, (half_t*)out, ldo, B, heads, T, d, causal, as_stream(stream));
-}
-
-// Diagnostic entries of tests/test_gpu_narrow_ops.py; the product path does not call them.
-// The per-image loop of Engine::vattn_fwd (vattn_core) on caller-owned q / k / vt / out, with S and P of its own.
-int fgdm_op_vae_attention(const void* q, const void* k, const void* vt, void* out, int B, int T, int C, void* stream) {
-    if (!q || !k || !vt || !out || B <= 0 || T <= 0 || C <= 0 || (T & 63) || (C & 63)) return FGDM_ERR_ARG;
-    hipStream_t s = as_stream(stream);
-    TmpDev tmp;
-    float* S = nullptr;
-    half_t* P = nullptr;
-    if (hipMalloc(&S, (size_t)T * T * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(S);
-    if (hipMalloc(&P, (size_t)T * T * sizeof(half_t)) != hipSuccess) return FGDM_ERR_NOMEM;
-    tmp.ptrs.push_back(P);
-    bool softmax_failed = false;
-    const int rc = vattn_core((const half_t*)q, (const half_t*)k, (const half_t*)vt, (half_t*)out, S, P, B, T, C, s, &softmax_failed,
-        [&](const half_t* Wt, int N, int K, const half_t* A, int M, int out_kind, void* o, int ld_out, float scale) {
-            IgemmArgs a{};
-            a.Wt = Wt; a.N = N; a.act = ACT_NONE; a.out_kind = out_kind; a.out = o; a.ld_out = ld_out; a.scale = scale;
-            return op_gemm_rows(a, A, 1, 1, M, K, M, tmp, s);
-        });
-    (void)hipStreamSynchronize(s);   // S and P are freed on return
-    return rc;
-}
-// Pass-throughs to the host launchers of elementwise.hip, pointer / shape checks in front.
-int fgdm_op_softmax_rows(const float* S, void* P, int rows, int cols, void* stream) {
-    if (!S || !P || rows <= 0 || cols <= 0) return FGDM_ERR_ARG;
-    return softmax_rows(S, (half_t*)P, rows, cols, as_stream(stream));
-}
-int fgdm_op_nchw_to_nhwc(const float* x, void* y, int B, int C, int HW, int Cpad, void* stream) {
-    if (!x || !y || B <= 0 || C <= 0 || HW <= 0 || Cpad < C) return FGDM_ERR_ARG;
-    return nchw_f32_to_nhwc_f16(x, (half_t*)y, B, C, HW, Cpad, as_stream(stream));
-}
-int fgdm_op_nhwc_to_nchw(const void* x, float* y, int B, int C, int HW, void* stream) {
-    if (!x || !y || B <= 0 || C <= 0 || HW <= 0) return FGDM_ERR_ARG;
-    return nhwc_f16_to_nchw_f32((const half_t*)x, y, B, C, HW, as_stream(stream));
-}
-int fgdm_op_avgpool2(const void* x, void* y, int B, int H, int W, int C, void* stream) {
-    if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || (H & 1) || (W & 1)) return FGDM_ERR_ARG;
-    return avgpool2((const half_t*)x, (half_t*)y, B, H, W, C, as_stream(stream));
-}
-int fgdm_op_transpose_pad(const void* v, void* vt, int B, int Tk, int C, int Tkpad, void* stream) {
-    if (!v || !vt || B <= 0 || Tk <= 0 || C <= 0 || Tkpad < Tk) return FGDM_ERR_ARG;
-    return transpose_pad_keys((const half_t*)v, (half_t*)vt, B, Tk, C, Tkpad, as_stream(stream));
-}
-int fgdm_op_timestep_embed(const int64_t* t, const float* t_float, void* y, int B, int dim, int rows_pad, void* stream) {
-    if ((!t && !t_float) || !y || B <= 0 || dim < 2 || (dim & 1) || rows_pad < B) return FGDM_ERR_ARG;
-    return timestep_embed(t, t_float, (half_t*)y, B, dim, rows_pad, as_stream(stream));
-}
-int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream) {
-    if (!a || !b || !y || n <= 0 || (n & 7)) return FGDM_ERR_ARG;
-    return add_f16((const half_t*)a, (const half_t*)b, (half_t*)y, (size_t)n, as_stream(stream));
 }
 
 }  // extern "C"

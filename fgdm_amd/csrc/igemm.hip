@@ -14,7 +14,7 @@
 // conflict-free for ds_read_b128 fragment reads; 2-stage LDS ring, one barrier per K-step; each wave
 // owns a (BM/WM)x(BN/WN) tile of v_mfma_f32_32x32x16_f16 accumulators; XCD-aware block->tile remap.
 #include "common.h"
-#include <stdlib.h>
+#include "knobs.h"
 #include <algorithm>
 
 #define LDS_AS __attribute__((address_space(3)))
@@ -307,12 +307,8 @@ size_t igemm_npad(int n) { return (size_t)((n + 127) / 128) * 128; }
 template <int BM, int BN, int WM, int WN>
 static int launch_cfg(const IgemmArgs& a, hipStream_t s) {
     constexpr int smem = 2 * (BM + BN) * 128;
-    static bool attr_set = false;
-    auto k = igemm_kernel<BM, BN, WM, WN>;
-    if (!attr_set) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
+    constexpr auto k = igemm_kernel<BM, BN, WM, WN>;
+    if (fgdm_dyn_lds<k>(smem) != FGDM_OK) return FGDM_ERR_HIP;
     const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
     FGDM_LAUNCH(k, dim3(ntm * ntn), dim3(WM * WN * 64), smem, s, a);
     return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
@@ -336,8 +332,8 @@ static int pick_force(const IgemmArgs& a) {
         if (force >= 4) force = 0;
         if (force == 0) return 0;
     }
-    static const bool small_tiles = !(getenv("FGDM_IGEMM_SMALL_TILES") && atoi(getenv("FGDM_IGEMM_SMALL_TILES")) == 0);        // A/B knob
-    static const bool other_widths = !(getenv("FGDM_IGEMM_OTHER_WIDTHS") && atoi(getenv("FGDM_IGEMM_OTHER_WIDTHS")) == 0);   // A/B knob
+    const bool small_tiles = knob_once(KNOB_IGEMM_SMALL_TILES) != 0;        // A/B knob
+    const bool other_widths = knob_once(KNOB_IGEMM_OTHER_WIDTHS) != 0;   // A/B knob
     if (force == 0) {
         const bool geglu = a.act == ACT_GEGLU;
         if (!geglu && a.N % 320 == 0) {
@@ -347,7 +343,7 @@ static int pick_force(const IgemmArgs& a) {
             // level's (M = 64 rows per sample), and (round 4: FGDM_IGEMM_SMALL_M=0 switches it off) those whose 128 x 320 grid --
             // times the number of problems a grouped launch will carry -- stays under three quarters of the CUs while the 64 x 160
             // grid fills every CU twice: the 16x16 level at 8 prompts per GPU (M = 4096: 128 tiles of 128 x 320, 512 of 64 x 160)
-            static const bool small_m = !(getenv("FGDM_IGEMM_SMALL_M") && atoi(getenv("FGDM_IGEMM_SMALL_M")) == 0);              // A/B knob
+            const bool small_m = knob_once(KNOB_IGEMM_SMALL_M) != 0;              // A/B knob
             const bool lin64 = a.mode == IG_LINEAR && !(a.K & 31) && !(a.C0 & 31) && !(a.C1 & 31) && small_tiles;
             const long b64 = (long)((a.M + 63) / 64) * (a.N / 160);
             // ... except the long-K ones among them (the 16x16 level's feed-forward output, K = 5120, at 8 prompts per GPU): 64 x 160 tiles
@@ -379,7 +375,7 @@ int igemm_stats_slots(const IgemmArgs& a) {
     if (f < 4) return 0;
     const int tile = (f - 4) & 15;
     // (tile 7, 64 x 160: its two 80-column waves per row meet in LDS and write the same 160-column slots)
-    static const bool stats64 = !(getenv("FGDM_IGEMM_STATS64") && atoi(getenv("FGDM_IGEMM_STATS64")) == 0);       // A/B knob (same bits either way)
+    const bool stats64 = knob_once(KNOB_IGEMM_STATS64) != 0;       // A/B knob (same bits either way)
     return (tile == 0 || tile == 2 || tile == 3 || tile == 5 || (tile == 7 && stats64)) ? a.N / 160 : 0;
 }
 
@@ -398,7 +394,7 @@ int igemm_launch(const IgemmArgs& a, hipStream_t s) {
     }
     int force = pick_force(a);
     // diagnostic knob for A/B runs (tools/ab_bench.sh): automatic choices take the 32x32x16 instantiations
-    static const bool mfma32 = getenv("FGDM_IGEMM_MFMA32") && atoi(getenv("FGDM_IGEMM_MFMA32")) != 0;
+    const bool mfma32 = knob_once(KNOB_IGEMM_MFMA32) != 0;
     if (mfma32 && force >= 4 && force <= 6 && !a.force_cfg && !g_force_cfg) force += 3;
     if (force >= 4) return igemm2_launch(a, force - 4, s);
     struct Cfg { int bm, bn; float eff; int per_cu; };

@@ -10,6 +10,7 @@
 //     channels per register quad: the tile is bounced through wave-private LDS as fp16 and leaves as 16-byte
 //     row-contiguous stores with a 16-byte residual read (the old 2-byte stores cost ~135 us per 84 MB tensor).
 #include "common.h"
+#include "knobs.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -1167,12 +1168,8 @@ template <bool LN>
 int launch_geglu_persist(const IgemmArgs& a, int ntiles, int contiguous, hipStream_t s) {
     constexpr int smem = 4 * (256 + 256) * ROWB + 2 * (256 + 2 * 256 + 256) * 4;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    static bool attr_set = false;
-    auto k = igemm2_geglu_persist_kernel<LN>;
-    if (!attr_set) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
+    constexpr auto k = igemm2_geglu_persist_kernel<LN>;
+    if (fgdm_dyn_lds<k>(smem) != FGDM_OK) return FGDM_ERR_HIP;
     FGDM_LAUNCH(k, dim3(256), dim3(512), smem, s, a, ntiles, contiguous);
     return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
 }
@@ -1182,12 +1179,8 @@ int launch2p(const IgemmArgs& a, hipStream_t s) {
     constexpr int ring = ring_bytes<BM, BN, STAGES, PIPE>();
     constexpr int smem = ring + (1 + RV_MAX) * BN * 4 + (2 * BM + BN) * 4;      // + staged bias, emb rows, LayerNorm (mean, rstd), u
     static_assert(smem <= 160 * 1024, "LDS budget");
-    static bool attr_set = false;
-    auto k = igemm2_kernel<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>;
-    if (!attr_set) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set = true;
-    }
+    constexpr auto k = igemm2_kernel<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>;
+    if (fgdm_dyn_lds<k>(smem) != FGDM_OK) return FGDM_ERR_HIP;
     const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
     const unsigned gx = (unsigned)(ntm * ntn * (SPLIT ? a.splitk : 1));
     if (fgdm_recording()) {
@@ -1197,12 +1190,8 @@ int launch2p(const IgemmArgs& a, hipStream_t s) {
         };
         // the hot instantiations (pipelined loop, straight-line epilogue) have a twin that takes two argument sets
         if constexpr (PIPE != 0 && PATH != 0 && !SPLIT && !ABL && MS == 16) {
-            static bool pair_attr_set = false;
-            auto kp = igemm2_pair_kernel<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>;
-            if (!pair_attr_set) {
-                HIP_TRY(hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-                pair_attr_set = true;
-            }
+            constexpr auto kp = igemm2_pair_kernel<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>;
+            if (fgdm_dyn_lds<kp>(smem) != FGDM_OK) return FGDM_ERR_HIP;
             IgemmGroupFn pf = [](const IgemmArgs* const* av, int n, unsigned grid_x, hipStream_t rs) -> int {
                 if (n < 2 || n > FGDM_MAX_GROUP) return FGDM_ERR_ARG;
                 IgemmArgsG pg;
@@ -1240,7 +1229,7 @@ int epilogue_path(const IgemmArgs& a) {
 // it) takes the ablation instantiation: PATH 1 of the FAST non-LayerNorm tiles.
 template <int BM, int BN, int WM, int WN, int STAGES, bool CONV, bool GEGLU, bool SPLIT, int MS, bool LN, bool FAST, int PIPE>
 int launch2(const IgemmArgs& a, hipStream_t s) {
-    static const bool fast_on = !(getenv("FGDM_IGEMM_EPI_PATHS") && atoi(getenv("FGDM_IGEMM_EPI_PATHS")) == 0);   // A/B knob
+    const bool fast_on = knob_once(KNOB_IGEMM_EPI_PATHS) != 0;   // A/B knob
     if constexpr (FAST && !SPLIT && !LN) {
         if (a.debug)
             return epilogue_path<BM, GEGLU, LN>(a) == 1 ? launch2p<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, 1, (PIPE == 2 ? 1 : PIPE), true>(a, s)
@@ -1321,7 +1310,7 @@ void igemm_set_twin_layers(bool on) { g_twin_layers = on; }
 int igemm_splitk_factor(const IgemmArgs& a) {
     if (a.force_cfg || a.act == ACT_GEGLU || a.out_kind != OUT_F16 || a.N % 320 || (a.K & 31)) return 1;
     const int nk = a.K >> 5;
-    static const bool fat = !(getenv("FGDM_SPLITK_FAT") && atoi(getenv("FGDM_SPLITK_FAT")) == 0);          // A/B knob
+    const bool fat = knob_once(KNOB_SPLITK_FAT) != 0;          // A/B knob
     // the decoder's convolutions of the 16x16 level (they have no ControlNet twin to share a launch with): two ways, so that at
     // B = 32 they fill the chip with 256 x 320 tiles (2560->1280: 576 -> 479 us with the reduction pass; three or four ways 551 /
     // 509; 1280->1280: 301 -> ~255).  The K = 11520 layers WITH a twin stay whole: as twin launches they are on fat tiles already
@@ -1355,21 +1344,22 @@ static bool halo_geometry(const IgemmArgs& a) {
 // cfg >> 4: K loop: 0 = the process default (FGDM_IGEMM_PIPE, default 1), 1 = the phase-locked loop, 2 = the software-pipelined one
 int igemm2_launch(const IgemmArgs& a, int cfg, hipStream_t s) {
     if ((a.K & 31) || (a.C0 & 31) || (a.C1 & 31)) return FGDM_ERR_ARG;
-    static const int pipe_default = getenv("FGDM_IGEMM_PIPE") ? atoi(getenv("FGDM_IGEMM_PIPE")) : 1;
+    const int pipe_default = knob_once(KNOB_IGEMM_PIPE);
     const int tile = cfg & 15, psel = cfg >> 4;
     // the pipelined loop addresses with 32-bit byte offsets: operands of 4 GB or more stay on the phase-locked loop
     const size_t px = a.mode == IG_LINEAR ? (size_t)a.M : (size_t)a.B * a.H * a.W;
     const bool small = px * (size_t)std::max(a.C0, a.C1) * 2 < (1ull << 32) && (size_t)(a.N + 320) * a.K * 2 < (1ull << 32);
     const bool pipe = (psel == 0 ? pipe_default != 0 : psel == 2) && small;
+    // the halo loop (PIPE = 2) where the geometry allows it (halo_geometry).  FGDM_IGEMM_HALO=0: A/B knob
+    const bool halo = knob_once(KNOB_IGEMM_HALO) != 0 && pipe && halo_geometry(a);
     const int bn = (tile == 1 || tile == 4) ? 256 : tile == 6 ? 128 : tile == 7 ? 160 : 320;
     if (a.N % bn) return FGDM_ERR_ARG;          // weight rows beyond N are not padded to this tile
     if (a.act == ACT_GEGLU && bn != 256) return FGDM_ERR_ARG;
     if (a.splitk > 1) {
         if ((tile != 2 && tile != 0) || a.ln_stats) return FGDM_ERR_ARG;
         // the halo loop for split K too (round 4): every K slice must be whole 32-channel sub-chunks (nine steps each)
-        static const bool halo_sk = !(getenv("FGDM_IGEMM_HALO") && atoi(getenv("FGDM_IGEMM_HALO")) == 0);
         const int nk_all = a.K >> 5;
-        if (halo_sk && pipe && halo_geometry(a) && nk_all % a.splitk == 0 && (nk_all / a.splitk) % 9 == 0)
+        if (halo && nk_all % a.splitk == 0 && (nk_all / a.splitk) % 9 == 0)
             return tile == 0 ? launch2<256, 320, 4, 2, 4, true, false, true, 16, false, false, 2>(a, s)
                              : launch2<128, 320, 4, 2, 4, true, false, true, 16, false, false, 2>(a, s);
         if (tile == 0 && pipe)       // (the phase-locked loop has no 256 x 320 split-K instantiation: 128 x 320 below)
@@ -1384,16 +1374,13 @@ int igemm2_launch(const IgemmArgs& a, int cfg, hipStream_t s) {
     if (a.ln_stats && a.mode != IG_LINEAR) return FGDM_ERR_ARG;
     // the persistent GEGLU projection (igemm2_geglu_persist_kernel): 256 workgroups walk the tiles once there are more tiles than
     // CUs.  FGDM_IGEMM_PERSIST=0: A/B knob (the outputs are bit-identical either way)
-    static const int persist_mode = getenv("FGDM_IGEMM_PERSIST") ? atoi(getenv("FGDM_IGEMM_PERSIST")) : 1;      // 1 = round-robin tiles, 2 = contiguous runs
+    const int persist_mode = knob_once(KNOB_IGEMM_PERSIST);     // 1 = round-robin tiles, 2 = contiguous runs
     const bool persist_on = persist_mode != 0;
     if (persist_on && tile == 1 && pipe && a.act == ACT_GEGLU && a.mode == IG_LINEAR && !a.C1 && a.out_kind == OUT_F16 && !a.rowvec &&
         !a.resid && !a.out2 && !a.stats_out && !a.debug && a.N % 256 == 0) {
         const int ntiles = ((a.M + 255) / 256) * (a.N / 256);
         if (ntiles > 256) return a.ln_stats ? launch_geglu_persist<true>(a, ntiles, persist_mode == 2, s) : launch_geglu_persist<false>(a, ntiles, persist_mode == 2, s);
     }
-    // the halo loop (PIPE = 2) where the geometry allows it (halo_geometry).  FGDM_IGEMM_HALO=0: A/B knob
-    static const bool halo_on = !(getenv("FGDM_IGEMM_HALO") && atoi(getenv("FGDM_IGEMM_HALO")) == 0);
-    const bool halo = halo_on && pipe && halo_geometry(a);
     switch (tile) {
         case 0: return halo ? launch_tile<256, 320, 16, 2>(a, s) : pipe ? launch_tile<256, 320, 16, 1>(a, s) : launch_tile<256, 320, 16, 0>(a, s);
         case 1: return pipe ? launch_tile<256, 256, 16, 1>(a, s) : launch_tile<256, 256, 16, 0>(a, s);

@@ -5,13 +5,9 @@
 // Reference semantics: GroupNorm32 (ldm/modules/diffusionmodules/util.py:223-225, eps 1e-5),
 // Normalize (ldm/modules/attention.py:76-77, eps 1e-6), nn.LayerNorm (attention.py:226-228, eps 1e-5).
 #include "common.h"
+#include "knobs.h"
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
-
-// pixels per partial-sum chunk of the two-kernel path (round 4: 64 -> 256, the reduction tail of a stats workgroup was as long as its
-// loads: 64x64 x 320 channels, B = 32: 50.1 -> 45.5 us for both kernels, B = 16: 32.1 -> 29.3; profiles/r04_gn_chunk.txt)
-#define GN_PIX_PER_CHUNK 256
 
 __device__ __forceinline__ const half_t* src_octet(const half_t* x0, int C0, const half_t* x1, int C1,
                                                    size_t pix, int o) {
@@ -458,10 +454,10 @@ int groupnorm_launch(const half_t* x0, int C0, const half_t* x1, int C1, int B, 
         // 640+640 45.0 -> 34.4 / 31.2 -> 27.8, 1280+640 67.1 -> 55.0.  The 64x64 level stays on two kernels: C = 320 50.7 -> 45.8 at
         // B = 32 but 32.1 -> 34.9 at B = 16, 320+320 (sixteen slices per sample, two rounds of workgroups) 94.4 -> 107.3, and nothing
         // end to end (which kernel runs must not depend on the batch: a sample's bits must not)
-        static const int reg_hw = getenv("FGDM_GN_REG") ? atoi(getenv("FGDM_GN_REG")) : 1024;      // A/B knob: largest HW taken (0 = off)
+        const int reg_hw = knob_once(KNOB_GN_REG);         // A/B knob: largest HW taken (0 = off)
         const bool reg_on = HW <= reg_hw;
         const int cpg = C >> 5;
-        static const int ng_max = getenv("FGDM_GN_REG_NG") ? atoi(getenv("FGDM_GN_REG_NG")) : 4;        // experiment knob: widest slice, in groups
+        const int ng_max = knob_once(KNOB_GN_REG_NG);      // experiment knob: widest slice, in groups
         for (int NG = ng_max; reg_on && NG >= 1; NG >>= 1) {           // the widest slice that fits: longer runs per pixel row
             const int CW = NG * cpg;
             if (CW & 7) continue;
@@ -471,24 +467,11 @@ int groupnorm_launch(const half_t* x0, int C0, const half_t* x1, int C1, int B, 
             if (np > 21) continue;
             const size_t smem = ((size_t)PI * CW * 2 + 8 + 2 * (size_t)CW + 2 * (size_t)CW) * sizeof(float);
             if (smem > 150 * 1024) continue;
-            static bool attr_set = false;
-            if (!attr_set) {
-                if (hipFuncSetAttribute((const void*)gn_reg_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)gn_reg_kernel<11>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)gn_reg_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)gn_reg_kernel<21>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-                    return FGDM_ERR_HIP;
-                attr_set = true;
-            }
-            static bool attr2_set = false;
-            if (!attr2_set) {
-                if (hipFuncSetAttribute((const void*)gn_reg_group_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)gn_reg_group_kernel<11>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)gn_reg_group_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)gn_reg_group_kernel<21>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-                    return FGDM_ERR_HIP;
-                attr2_set = true;
-            }
+            constexpr int lds = 150 * 1024;      // (gn_single_pass_launch picks among these, and a replay may take the grouped form)
+            if (fgdm_dyn_lds<gn_reg_kernel<6>>(lds) || fgdm_dyn_lds<gn_reg_kernel<11>>(lds) || fgdm_dyn_lds<gn_reg_kernel<16>>(lds) ||
+                fgdm_dyn_lds<gn_reg_kernel<21>>(lds) || fgdm_dyn_lds<gn_reg_group_kernel<6>>(lds) || fgdm_dyn_lds<gn_reg_group_kernel<11>>(lds) ||
+                fgdm_dyn_lds<gn_reg_group_kernel<16>>(lds) || fgdm_dyn_lds<gn_reg_group_kernel<21>>(lds))
+                return FGDM_ERR_HIP;
             GnRec r{{x0, x1, gamma, beta, out}, C0, C1, B, HW, NG, silu, eps, np <= 6 ? 6 : np <= 11 ? 11 : np <= 16 ? 16 : 21, (unsigned)smem};
             return gn_single_pass_launch(r, (unsigned)((32 / NG) * 8 * ((B + 7) / 8)), s);
         }
@@ -503,7 +486,7 @@ int groupnorm_launch(const half_t* x0, int C0, const half_t* x1, int C1, int B, 
         // first choice: slices of <= 40 KB (3+ workgroups per CU overlap their load / apply phases), else up to 64 KB (two per
         // CU).  Fatter slices (82 KB at the 32x32 level: one workgroup per CU, its load, reduce and store phases back to back)
         // measured 37.5 us for an 84 MB pass where the two-kernel path below moves 126 MB in about 25
-        static const int max_kb = getenv("FGDM_GN_FUSED_MAXKB") ? atoi(getenv("FGDM_GN_FUSED_MAXKB")) : 64;      // tuning knob
+        const int max_kb = knob_once(KNOB_GN_FUSED_MAXKB);      // tuning knob
         for (int pass = 0; pass < 2; ++pass)
         for (int NG = 4; NG >= 1; NG >>= 1) {
             const int CW = NG * cpg;
@@ -513,20 +496,10 @@ int groupnorm_launch(const half_t* x0, int C0, const half_t* x1, int C1, int B, 
             const int OW = CW >> 3, PI = NT / OW;
             const size_t smem = slice + ((size_t)PI * CW * 2 + 8 + 2 * (size_t)CW) * sizeof(float);
             if (smem > 150 * 1024) continue;
-            static bool attr_set = false;
-            if (!attr_set) {
-                if (hipFuncSetAttribute((const void*)gn_fused_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)gn_fused_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-                    return FGDM_ERR_HIP;
-                attr_set = true;
-            }
-            static bool attr2_set = false;
-            if (!attr2_set) {
-                if (hipFuncSetAttribute((const void*)gn_fused_group_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)gn_fused_group_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-                    return FGDM_ERR_HIP;
-                attr2_set = true;
-            }
+            constexpr int lds = 150 * 1024;
+            if (fgdm_dyn_lds<gn_fused_kernel<256>>(lds) || fgdm_dyn_lds<gn_fused_kernel<512>>(lds) ||
+                fgdm_dyn_lds<gn_fused_group_kernel<256>>(lds) || fgdm_dyn_lds<gn_fused_group_kernel<512>>(lds))
+                return FGDM_ERR_HIP;
             GnRec r{{x0, x1, gamma, beta, out}, C0, C1, B, HW, NG, silu, eps, NT, (unsigned)smem};
             return gn_single_pass_launch(r, (unsigned)((32 / NG) * 8 * ((B + 7) / 8)), s);
         }
@@ -534,7 +507,7 @@ int groupnorm_launch(const half_t* x0, int C0, const half_t* x1, int C1, int B, 
     { const int rc = try_reg(); if (rc != 1) return rc; }
     // pixels per partial-sum chunk of the two-kernel path: a constant of the build (a sample's bits must not depend on it varying);
     // FGDM_GN_CHUNK is a tuning knob for experiments (multiples of 64, so that the workspace bound above holds)
-    static const int ppc_env = getenv("FGDM_GN_CHUNK") ? atoi(getenv("FGDM_GN_CHUNK")) : GN_PIX_PER_CHUNK;
+    const int ppc_env = knob_once(KNOB_GN_CHUNK);
     const int ppc = (ppc_env >= 64 && ppc_env % 64 == 0) ? ppc_env : GN_PIX_PER_CHUNK;
     const int nchunk = (HW + ppc - 1) / ppc;
     float* partial = ws;

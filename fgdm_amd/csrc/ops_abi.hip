@@ -1,0 +1,268 @@
+// Op-level test entries of the C ABI (fgdm_op_*, fgdm_debug_*): single kernels and short launch sequences on caller-owned
+// buffers, for the per-kernel parity tests.  No engine: they restate the weight packing and the IgemmArgs on their own, and
+// share with engine.hip only the launch sequences of engine_shared.h (im2col_conv, vattn_core, conv3_kmap).
+#include "engine_shared.h"
+
+// The host-side packing of every entry below.  w [N][Ks] and bias [N] (or null), fp32 on the host or the device, become what the
+// GEMM kernels read: a.Wt [igemm_npad(N)][K] fp16 and a.bias [npad] fp32 on the device (owned by `tmp`; pad rows and columns zero).
+// Packed row n is source row n, or -- geglu -- the value and the gate rows interleaved in runs of 32 (the 64-column groups whose
+// halves the GEGLU epilogue multiplies); packed column k is source column kmap[k] (no kmap: k itself; -1: a pad column).
+// With gamma / beta [K] the LayerNorm of A's rows is folded in (IgemmArgs::ln_stats): the weight is fp16(gamma_k w_nk), a.ln_u its
+// row sums and the bias gains sum_k beta_k w_nk.
+static int op_pack(IgemmArgs& a, TmpDev& tmp, const float* w, const float* bias, int N, int K, int Ks, bool geglu,
+                   const int* kmap = nullptr, const float* gamma = nullptr, const float* beta = nullptr) {
+    auto host = [](const float* d, size_t n, std::vector<float>& v) { v.resize(n); return hipMemcpy(v.data(), d, n * sizeof(float), hipMemcpyDefault) == hipSuccess; };
+    std::vector<float> wh, bh(N, 0.f), g, bt;
+    if (!host(w, (size_t)N * Ks, wh) || (bias && !host(bias, N, bh))) return FGDM_ERR_HIP;
+    if (gamma && (!host(gamma, K, g) || !host(beta, K, bt))) return FGDM_ERR_HIP;
+    const size_t npad = igemm_npad(N);
+    std::vector<half_t> pk(npad * (size_t)K, (half_t)0);
+    std::vector<float> bp(npad, 0.f), u(gamma ? npad : 0, 0.f);
+    for (int pr = 0; pr < N; ++pr) {
+        int sr = pr;
+        if (geglu) { const int grp = pr >> 6, within = pr & 63; sr = within < 32 ? grp * 32 + within : N / 2 + grp * 32 + (within - 32); }
+        const float* row = &wh[(size_t)sr * Ks];
+        double us = 0.0, cs = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const int ks = kmap ? kmap[k] : k;
+            if (ks < 0) continue;
+            const half_t wq = (half_t)(gamma ? row[ks] * g[k] : row[ks]);
+            pk[(size_t)pr * K + k] = wq;
+            if (gamma) { us += (double)(float)wq; cs += (double)bt[k] * (double)row[ks]; }
+        }
+        bp[pr] = gamma ? (float)((double)bh[sr] + cs) : bh[sr];
+        if (gamma) u[pr] = (float)us;
+    }
+    a.Wt = tmp.up(pk); a.bias = tmp.up(bp);
+    if (gamma) a.ln_u = tmp.up(u);
+    return a.Wt && a.bias && (!gamma || a.ln_u) ? FGDM_OK : FGDM_ERR_NOMEM;
+}
+
+// Engine::gemm for the op-level test entries that share a launch sequence with the engine (im2col_conv, vattn_core): the same
+// IgemmArgs the engine would build -- its split-K plan included -- with hipMalloc'ed scratch instead of the arena and no timer.
+// The caller has filled the operands and the epilogue; synchronise before `tmp` goes out of scope.
+static int op_gemm_rows(IgemmArgs& a, const half_t* A, int B, int Ho, int Wo, int K, int rps, TmpDev& tmp, hipStream_t s) {
+    a.A0 = A; a.C0 = K; a.A1 = nullptr; a.C1 = 0;
+    a.zero = g_zero_page();
+    if (!a.zero) return FGDM_ERR_NOMEM;
+    a.B = B; a.H = Ho; a.W = Wo; a.Ho = Ho; a.Wo = Wo;
+    a.M = B * Ho * Wo; a.K = K; a.mode = IG_LINEAR; a.rows_per_sample = rps;
+    if (plan_splitk(a, tmp) != FGDM_OK) return FGDM_ERR_NOMEM;
+    return igemm_launch(a, s);
+}
+
+// fgdm_op_conv2d for Cin % 64 != 0: the weight in conv3_kmap's column order, as Engine::pack_conv3 packs it, then im2col_conv as
+// Engine::conv3 runs it.  x fp16 NHWC with cin_pad channels.
+static int op_conv3_im2col(const half_t* x, int Cin, const float* w, const float* bias, const float* rowvec, const half_t* resid,
+                           int B, int H, int W, int Cout, int stride, int act, float scale, void* out, hipStream_t s) {
+    int cp = 0;
+    const std::vector<int> kmap = conv3_kmap(Cin, &cp);
+    const int K = (int)kmap.size(), Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    TmpDev tmp;
+    IgemmArgs a{};
+    const int prc = op_pack(a, tmp, w, bias, Cout, K, Cin * 9, false, kmap.data());
+    if (prc != FGDM_OK) return prc;
+    half_t* A = tmp.alloc<half_t>((size_t)B * Ho * Wo * K);
+    if (!A) return FGDM_ERR_NOMEM;
+    a.rowvec = rowvec; a.rv_stride = Cout;
+    a.resid = resid; a.ld_res = Cout;
+    a.N = Cout; a.act = act; a.out_kind = OUT_F16; a.out = out; a.ld_out = Cout; a.scale = scale;
+    const int rc = im2col_conv(x, A, B, H, W, cp, stride, K, s, []() {},
+        [&](half_t* Ap, int Bv, int Hv, int Wv, int Kv, int rps) { return op_gemm_rows(a, Ap, Bv, Hv, Wv, Kv, rps, tmp, s); });
+    (void)hipStreamSynchronize(s);   // temporaries are freed on return
+    return rc;
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------ op-level test entries
+int fgdm_op_conv2d(const void* x0, int C0, const void* x1, int C1, const float* w, const float* bias, const float* rowvec,
+                   const void* resid, int B, int H, int W, int Cout, int ksize, int stride, int upsample, int act,
+                   float scale, void* out, void* stream) {
+    if (!x0 || !w || !out || (ksize != 1 && ksize != 3)) return FGDM_ERR_ARG;
+    if (stride == FGDM_STRIDE2_PAD_BR && (ksize != 3 || upsample)) return FGDM_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    const int Cin = C0 + C1, taps = ksize * ksize, K = taps * Cin;
+    if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || C0 <= 0 || C1 < 0) return FGDM_ERR_ARG;
+    if (Cin & 63) {     // the im2col route: exactly the combinations Engine::conv3 accepts on it
+        if (ksize != 3 || C1 || x1 || upsample || (stride != 1 && stride != 2)) return FGDM_ERR_ARG;
+        return op_conv3_im2col((const half_t*)x0, C0, w, bias, rowvec, (const half_t*)resid, B, H, W, Cout, stride, act, scale, out, s);
+    }
+    std::vector<int> kmap(K);        // source row [Cin][taps] -> the order the kernels walk K: 64-channel chunk, then tap, then channel
+    for (int tap = 0; tap < taps; ++tap)
+        for (int c = 0; c < Cin; ++c) kmap[taps == 9 ? ((c >> 6) * 9 + tap) * 64 + (c & 63) : c] = c * taps + tap;
+    TmpDev tmp;
+    IgemmArgs a{};
+    const int prc = op_pack(a, tmp, w, bias, Cout, K, K, false, kmap.data());
+    if (prc != FGDM_OK) return prc;
+    a.A0 = (const half_t*)x0; a.C0 = C0; a.A1 = (const half_t*)x1; a.C1 = C1;
+    a.zero = g_zero_page();
+    if (!a.zero) return FGDM_ERR_NOMEM;
+    a.rowvec = rowvec; a.rv_stride = Cout;
+    a.resid = (const half_t*)resid; a.ld_res = Cout;
+    a.B = B; a.H = H; a.W = W;
+    a.Ho = H; a.Wo = W; a.mode = IG_LINEAR;
+    if (ksize == 3) {
+        a.mode = IG_CONV3;
+        if (upsample) { a.Ho = 2 * H; a.Wo = 2 * W; a.mode = IG_CONV3_UP2; }
+        else if (stride == 2) { a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1; a.mode = IG_CONV3_S2; }
+        else if (stride == FGDM_STRIDE2_PAD_BR) {
+            if (H < 2 || W < 2) return FGDM_ERR_ARG;
+            a.Ho = (H - 2) / 2 + 1; a.Wo = (W - 2) / 2 + 1; a.mode = IG_CONV3_S2_BR;
+        }
+    }
+    a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = K;
+    a.act = act; a.out_kind = OUT_F16; a.out = out; a.ld_out = Cout;
+    a.rows_per_sample = a.Ho * a.Wo; a.scale = scale;
+    if (plan_splitk(a, tmp) != FGDM_OK) return FGDM_ERR_NOMEM;
+    const int rc = igemm_launch(a, s);
+    (void)hipStreamSynchronize(s);   // temporaries are freed on return
+    return rc;
+}
+
+int fgdm_op_linear(const void* x, const float* w, const float* bias, const void* resid, int M, int K, int N, int act,
+                   int out_kind, int rows_per_sample, int ld_out, void* out, void* stream) {
+    if (!x || !w || !out || (K & 63)) return FGDM_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    TmpDev tmp;
+    IgemmArgs a{};
+    const int prc = op_pack(a, tmp, w, bias, N, K, K, act == ACT_GEGLU);
+    if (prc != FGDM_OK) return prc;
+    a.A0 = (const half_t*)x; a.C0 = K;
+    a.zero = g_zero_page();
+    if (!a.zero) return FGDM_ERR_NOMEM;
+    const int nout = act == ACT_GEGLU ? N / 2 : N;
+    a.resid = (const half_t*)resid; a.ld_res = nout;
+    a.B = 1; a.H = 1; a.W = M; a.Ho = 1; a.Wo = M;
+    a.M = M; a.N = N; a.K = K; a.mode = IG_LINEAR; a.act = act; a.out_kind = out_kind;
+    a.out = out; a.ld_out = ld_out ? ld_out : nout;
+    a.rows_per_sample = rows_per_sample ? rows_per_sample : M; a.scale = 1.f;
+    const int rc = igemm_launch(a, s);
+    (void)hipStreamSynchronize(s);
+    return rc;
+}
+
+// h = x W1^T + b1 (+ resid), fp16, with the LayerNorm partial sums of its rows produced on the way (from the GEMM's own
+// epilogue when the chosen kernel can, else by row_stats), then y = act(LayerNorm(h) W2^T + b2) with the LayerNorm folded
+// into the second GEMM: the producer / consumer pair of every transformer-block LayerNorm (attention.py:234-240).
+// *slots_used receives the number of partial-sum slots per row (1 = the separate row_stats pass ran).
+int fgdm_op_linear_ln_linear(const void* x, const float* w1, const float* b1, const void* resid, const float* gamma,
+                             const float* beta, const float* w2, const float* b2, int M, int K1, int C, int N2, int act2,
+                             void* h_out, void* y_out, int* slots_used, void* stream) {
+    if (!x || !w1 || !gamma || !beta || !w2 || !h_out || !y_out || (K1 & 63) || (C & 63)) return FGDM_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    TmpDev tmp;
+    IgemmArgs a{}, b{};
+    int rc = op_pack(a, tmp, w1, b1, C, K1, K1, false);
+    if (rc == FGDM_OK) rc = op_pack(b, tmp, w2, b2, N2, C, C, act2 == ACT_GEGLU, nullptr, gamma, beta);
+    if (rc != FGDM_OK) return rc;
+    a.A0 = (const half_t*)x; a.C0 = K1; a.zero = g_zero_page();
+    a.resid = (const half_t*)resid; a.ld_res = C;
+    a.B = 1; a.H = 1; a.W = M; a.Ho = 1; a.Wo = M; a.M = M; a.N = C; a.K = K1; a.mode = IG_LINEAR; a.act = ACT_NONE;
+    a.out_kind = OUT_F16; a.out = h_out; a.ld_out = C; a.rows_per_sample = M; a.scale = 1.f;
+    if (!a.zero) return FGDM_ERR_NOMEM;
+    int slots = igemm_stats_slots(a);
+    float* stats = tmp.alloc<float>((size_t)M * std::max(slots, row_stats_slots(C)) * 2);
+    if (!stats) return FGDM_ERR_NOMEM;
+    if (slots) a.stats_out = stats;
+    rc = igemm_launch(a, s);
+    if (rc == FGDM_OK && !slots) { slots = row_stats_slots(C); rc = row_stats_launch((const half_t*)h_out, M, C, stats, s); }
+    if (slots_used) *slots_used = a.stats_out ? slots : -slots;      // negative: the separate pass produced them
+    if (rc != FGDM_OK) { (void)hipStreamSynchronize(s); return rc; }
+    b.A0 = (const half_t*)h_out; b.C0 = C; b.zero = a.zero;
+    b.ln_stats = stats; b.ln_slots = slots; b.ln_eps = 1e-5f;
+    const int nout = act2 == ACT_GEGLU ? N2 / 2 : N2;
+    b.B = 1; b.H = 1; b.W = M; b.Ho = 1; b.Wo = M; b.M = M; b.N = N2; b.K = C; b.mode = IG_LINEAR; b.act = act2;
+    b.out_kind = OUT_F16; b.out = y_out; b.ld_out = nout; b.rows_per_sample = M; b.scale = 1.f;
+    rc = igemm_launch(b, s);
+    (void)hipStreamSynchronize(s);
+    return rc;
+}
+
+int fgdm_debug_force_igemm_cfg(int cfg) { igemm_set_force_cfg(cfg); return FGDM_OK; }
+
+int fgdm_op_groupnorm(const void* x0, int C0, const void* x1, int C1, int B, int HW, const float* gamma, const float* beta,
+                      float eps, int silu, void* out, void* stream) {
+    if (!x0 || !gamma || !beta || !out) return FGDM_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    float* ws = nullptr;
+    if (hipMalloc(&ws, groupnorm_ws_floats(B, HW) * sizeof(float)) != hipSuccess) return FGDM_ERR_NOMEM;
+    const int rc = groupnorm_launch((const half_t*)x0, C0, (const half_t*)x1, C1, B, HW, gamma, beta, eps, silu, (half_t*)out, ws, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(ws);
+    return rc;
+}
+int fgdm_op_layernorm(const void* x, int rows, int C, const float* gamma, const float* beta, float eps, void* out, void* stream) {
+    if (!x || !gamma || !beta || !out) return FGDM_ERR_ARG;
+    return layernorm_launch((const half_t*)x, rows, C, gamma, beta, eps, (half_t*)out, as_stream(stream));
+}
+int fgdm_op_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo, int B,
+                      int heads, int T, int Tk, int d, void* stream) {
+    if (!q || !k || !vt || !o) return FGDM_ERR_ARG;
+    return attention_launch((const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)vt, ldvt, (half_t*)o, ldo, B, heads, T, Tk, d, 0, as_stream(stream));
+}
+// Diagnostic entries of tests/test_gpu_attention_calls.py: the flag the engine's own calls pass, the kernel the dispatch chose,
+// and the text encoder's attention kernel on its own.
+int fgdm_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo, int B,
+                         int heads, int T, int Tk, int d, int q_prescaled, void* stream) {
+    if (!q || !k || !vt || !o) return FGDM_ERR_ARG;
+    return attention_launch((const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)vt, ldvt, (half_t*)o, ldo, B, heads, T, Tk, d,
+                            q_prescaled ? 1 : 0, as_stream(stream));
+}
+int fgdm_debug_last_attention_kernel(void) { return attention_last_kernel(); }
+int fgdm_op_small_attention(const void* qkv, int ld, int koff, int voff, void* out, int ldo, int B, int heads, int T, int d,
+                            int causal, void* stream) {
+    if (!qkv || !out) return FGDM_ERR_ARG;
+    return small_attention_launch((const half_t*)qkv, ld, koff, voff, (half_t*)out, ldo, B, heads, T, d, causal, as_stream(stream));
+}
+
+// Diagnostic entries of tests/test_gpu_narrow_ops.py; the product path does not call them.
+// The per-image loop of Engine::vattn_fwd (vattn_core) on caller-owned q / k / vt / out, with S and P of its own.
+int fgdm_op_vae_attention(const void* q, const void* k, const void* vt, void* out, int B, int T, int C, void* stream) {
+    if (!q || !k || !vt || !out || B <= 0 || T <= 0 || C <= 0 || (T & 63) || (C & 63)) return FGDM_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    TmpDev tmp;
+    float* S = tmp.alloc<float>((size_t)T * T);
+    half_t* P = tmp.alloc<half_t>((size_t)T * T);
+    if (!S || !P) return FGDM_ERR_NOMEM;
+    bool softmax_failed = false;
+    const int rc = vattn_core((const half_t*)q, (const half_t*)k, (const half_t*)vt, (half_t*)out, S, P, B, T, C, s, &softmax_failed,
+        [&](const half_t* Wt, int N, int K, const half_t* A, int M, int out_kind, void* o, int ld_out, float scale) {
+            IgemmArgs a{};
+            a.Wt = Wt; a.N = N; a.act = ACT_NONE; a.out_kind = out_kind; a.out = o; a.ld_out = ld_out; a.scale = scale;
+            return op_gemm_rows(a, A, 1, 1, M, K, M, tmp, s);
+        });
+    (void)hipStreamSynchronize(s);   // S and P are freed on return
+    return rc;
+}
+// Pass-throughs to the host launchers of elementwise.hip, pointer / shape checks in front.
+int fgdm_op_softmax_rows(const float* S, void* P, int rows, int cols, void* stream) {
+    if (!S || !P || rows <= 0 || cols <= 0) return FGDM_ERR_ARG;
+    return softmax_rows(S, (half_t*)P, rows, cols, as_stream(stream));
+}
+int fgdm_op_nchw_to_nhwc(const float* x, void* y, int B, int C, int HW, int Cpad, void* stream) {
+    if (!x || !y || B <= 0 || C <= 0 || HW <= 0 || Cpad < C) return FGDM_ERR_ARG;
+    return nchw_f32_to_nhwc_f16(x, (half_t*)y, B, C, HW, Cpad, as_stream(stream));
+}
+int fgdm_op_nhwc_to_nchw(const void* x, float* y, int B, int C, int HW, void* stream) {
+    if (!x || !y || B <= 0 || C <= 0 || HW <= 0) return FGDM_ERR_ARG;
+    return nhwc_f16_to_nchw_f32((const half_t*)x, y, B, C, HW, as_stream(stream));
+}
+int fgdm_op_avgpool2(const void* x, void* y, int B, int H, int W, int C, void* stream) {
+    if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || (H & 1) || (W & 1)) return FGDM_ERR_ARG;
+    return avgpool2((const half_t*)x, (half_t*)y, B, H, W, C, as_stream(stream));
+}
+int fgdm_op_transpose_pad(const void* v, void* vt, int B, int Tk, int C, int Tkpad, void* stream) {
+    if (!v || !vt || B <= 0 || Tk <= 0 || C <= 0 || Tkpad < Tk) return FGDM_ERR_ARG;
+    return transpose_pad_keys((const half_t*)v, (half_t*)vt, B, Tk, C, Tkpad, as_stream(stream));
+}
+int fgdm_op_timestep_embed(const int64_t* t, const float* t_float, void* y, int B, int dim, int rows_pad, void* stream) {
+    if ((!t && !t_float) || !y || B <= 0 || dim < 2 || (dim & 1) || rows_pad < B) return FGDM_ERR_ARG;
+    return timestep_embed(t, t_float, (half_t*)y, B, dim, rows_pad, as_stream(stream));
+}
+int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream) {
+    if (!a || !b || !y || n <= 0 || (n & 7)) return FGDM_ERR_ARG;
+    return add_f16((const half_t*)a, (const half_t*)b, (half_t*)y, (size_t)n, as_stream(stream));
+}
+
+}  // extern "C"

@@ -101,18 +101,8 @@ int small_attention_launch(const half_t* qkv, int ld, int koff, int voff, half_t
                            int d, int causal, hipStream_t s) {
     if (d != 64 || T <= 0 || T > 128 || B <= 0 || heads <= 0) return FGDM_ERR_ARG;
     const size_t smem = (size_t)T * (64 + 2) * 3 * sizeof(half_t) + (size_t)T * (T + 1) * sizeof(float);
-    auto k = small_attn_kernel<64>;
-    // hipFuncSetAttribute is per device (as launch_cross_long in attention.hip): on a second device T > ~88 would otherwise ask
-    // for more dynamic LDS than that device's default allows
-    constexpr int MAXDEV = 64;
-    static bool attr_set[MAXDEV] = {};
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return FGDM_ERR_HIP;
-    if (!attr_set[dev]) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 66 * 6 + 128 * 129 * 4) != hipSuccess)
-            return FGDM_ERR_HIP;
-        attr_set[dev] = true;
-    }
+    constexpr auto k = small_attn_kernel<64>;
+    if (fgdm_dyn_lds<k>(128 * 66 * 6 + 128 * 129 * 4) != FGDM_OK) return FGDM_ERR_HIP;     // T = 128, the largest this entry takes
     FGDM_LAUNCH(k, dim3(heads, B), dim3(256), smem, s, qkv, ld, koff, voff, out, ldo, T, causal, 1.0f / sqrtf((float)d));
     return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
 }

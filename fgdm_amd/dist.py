@@ -34,7 +34,7 @@ def _ships_as_fp16(key, shape):
     """Tensors the engine stores as fp16 UNCHANGED may travel as fp16: every >= 2-D weight except the ones listed in
     _FP32_SUFFIXES.  1-D tensors (biases, norm affine) stay fp32 in the engine and travel as fp32.  With this rule a rank fed
     from the broadcast holds bit-identical packed weights to one that loaded the fp32 state dict directly
-    (tests/test_gpu_dropin.py::test_broadcast_layout_is_bit_identical_to_fp32_load)."""
+    (tests/test_gpu_nets.py::test_broadcast_layout_is_bit_identical_to_fp32_load)."""
     return len(shape) >= 2 and not key.endswith(_FP32_SUFFIXES)
 
 

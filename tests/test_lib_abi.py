@@ -140,6 +140,34 @@ def test_narrow_op_entries_refuse_bad_arguments(lib):
     assert lib.fgdm_op_add_f16(p, p, p, 0, null) < 0
 
 
+CSRC = os.path.join(ROOT, 'fgdm_amd', 'csrc')
+
+
+def _csrc_files_with(text):
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.h')) and text in open(os.path.join(CSRC, f)).read())
+
+
+def test_environment_is_read_through_the_knob_table_only():
+    assert _csrc_files_with('getenv(') == ['knobs.h']
+
+
+def test_knob_table_matches_readme():
+    """The names in csrc/knobs.h's table and in the README's table of the native library's switches are the same set."""
+    table = re.search(r'#define FGDM_KNOBS\(X\)(.*?)\n\n', open(os.path.join(CSRC, 'knobs.h')).read(), re.S).group(1)
+    knobs = set(re.findall(r'"(FGDM_[A-Z0-9_]+)"', table))
+    assert len(knobs) >= 29, knobs
+    readme = open(os.path.join(ROOT, 'README.md')).read()
+    section = readme[readme.index('### Environment switches'):readme.index('Read by the Python side')]
+    rows = [ln for ln in section.splitlines() if ln.startswith('| `FGDM_')]
+    documented = set(re.findall(r'`(FGDM_[A-Z0-9_]+)', '\n'.join(rows)))
+    assert knobs == documented, knobs ^ documented
+
+
+def test_dynamic_lds_is_opted_in_by_one_helper():
+    sites = [(f, open(os.path.join(CSRC, f)).read().count('hipFuncSetAttribute')) for f in _csrc_files_with('hipFuncSetAttribute')]
+    assert sites == [('common.h', 1)], sites
+
+
 def test_engine_needs_gpu_no_fallback(lib):
     import torch
     if torch.cuda.is_available():
