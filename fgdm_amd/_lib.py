@@ -62,6 +62,10 @@ SIGNATURES = {
     'fgdm_run_block': (_i, [_p, C.c_char_p, _p, _i, _p, _i, _p, _p, _i, _i, _i, _p, _i64, C.POINTER(_i64), _p]),
     'fgdm_vae_decode': (_i, [_p, _p, _i, _i, _i, _f, _p, _p]),
     'fgdm_vae_encode': (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    'fgdm_unfold': (_i, [_p] + [_i] * 10 + [_p, _p]),
+    'fgdm_fold_weighted': (_i, [_p, _p, _p] + [_i] * 9 + [_p, _p]),
+    'fgdm_vae_decode_patches': (_i, [_p, _p, _i, _i, _i, _f] + [_i] * 5 + [_p, _p, _i, _p, _p]),
+    'fgdm_apply_model_patches': (_i, [_p, _p, _p, _p, _p] + [_i] * 7 + [_p, _p, _i, _i, _p, _p]),
     'fgdm_posterior_sample': (_i, [_p, _p, _f, _p, _i, _i, _i, _p]),
     'fgdm_image_to_uint8': (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     'fgdm_resize_linear_uint8': (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p]),

@@ -179,6 +179,20 @@ int mask_blend(const float* a, const float* b, const float* m, float* y, size_t 
 int ancestral_step(const float* x, const float* eps, float sqrt_recip, float sqrt_recipm1, float coef1, float coef2,
                    float std, const float* noise, float* out, size_t n, hipStream_t s);
 
+// ---------------------------------------------------------------- patch-wise routes (patches.hip)
+// An NCHW fp32 tensor [B, C, H, W] cut into Ly x Lx crops of [kh, kw] cells every (sh, sw): crop l = ly * Lx + lx starts at
+// (ly * sh, lx * sw), the column order of torch.nn.Unfold.  patch_plan fills Ly / Lx; must_cover: FGDM_ERR_ARG unless every cell
+// lies in a crop ((size - k) % s == 0 and s <= k per axis: what the weighted fold needs to have a non-zero divisor everywhere).
+struct PatchGeom { int B, C, H, W, kh, kw, sh, sw, Ly, Lx; };
+int patch_plan(int H, int W, int kh, int kw, int sh, int sw, bool must_cover, int* Ly, int* Lx);
+int unfold_crops(const float* x, float* out /* [n, B, C, kh, kw] */, const PatchGeom& g, int l0, int n, hipStream_t s);
+// acc (+)= sum_l (w_pix * w_tie[l]) * o[l - l0] over the crops [l0, l0 + n) (l0 == 0 overwrites acc); passes must come in
+// ascending order.  fold_finish: out = acc / folded weighting; out may be acc.
+int fold_accumulate(const float* o, const float* w_pix, const float* w_tie, float* acc, const PatchGeom& g, int l0, int n,
+                    hipStream_t s);
+int fold_finish(const float* acc, const float* w_pix, const float* w_tie, float* out, const PatchGeom& g, hipStream_t s);
+int repeat_words(const void* src, void* dst /* [reps][words] */, size_t words /* 32-bit */, int reps, hipStream_t s);
+
 #define HIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return FGDM_ERR_HIP; } while (0)
 
 // Opt `Kernel` in to `bytes` of dynamic LDS (a launch may ask for 64 KB without it), once per kernel and device: the attribute

@@ -2364,6 +2364,81 @@ int fgdm_posterior_sample(const float* moments, const float* noise, float scale,
     return posterior_sample(moments, noise, scale, z, B, zc, HW, as_stream(stream));
 }
 
+// ---- patch-wise routes (split_input_params; kernels in patches.hip).  Argument errors come before any launch.
+int fgdm_vae_decode_patches(fgdm_engine* e, const float* z, int B, int H, int W, float scale, int kh, int kw, int sh, int sw,
+                            int f, const float* w_pix, const float* w_tie, int max_crops_per_pass, float* image, void* stream) {
+    if (!e) return FGDM_ERR_ARG;
+    if (!z || !w_pix || !w_tie || !image || B <= 0 || max_crops_per_pass < 0) return e->fail(FGDM_ERR_ARG, "patch decode: null pointer or bad batch / pass size");
+    if (!e->vae.on) return e->fail(FGDM_ERR_STATE, "engine was created without a first-stage decoder (vae_ch = 0)");
+    if (!e->vae.packed) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    if (f != e->vae.factor) return e->fail(FGDM_ERR_ARG, "patch decode: f (vqf) must equal the decoder's upscaling factor " + std::to_string(e->vae.factor));
+    PatchGeom gz{B, 4, H, W, kh, kw, sh, sw, 0, 0};
+    if (patch_plan(H, W, kh, kw, sh, sw, true, &gz.Ly, &gz.Lx) != FGDM_OK)
+        return e->fail(FGDM_ERR_ARG, "patch decode: the crops do not cover the latent grid ((size - ks) % stride != 0, stride > ks or ks > size)");
+    if ((kh * kw) & 63) return e->fail(FGDM_ERR_ARG, "patch decode: kh * kw must be a multiple of 64 (first-stage attention)");
+    const int oc = e->cfg.vae_out_ch, L = gz.Ly * gz.Lx;
+    const PatchGeom gi{B, oc, H * f, W * f, kh * f, kw * f, sh * f, sw * f, gz.Ly, gz.Lx};
+    int step = std::min(max_crops_per_pass, L);
+    if (step == 0) {      // fgdm_vae_decode's images-per-pass rule, applied to the L * B crop images
+        const size_t big = (size_t)gi.kh * gi.kw * e->cfg.vae_ch * sizeof(half_t) * 8;
+        const size_t imgs = std::max<size_t>(1, std::min<size_t>((size_t)L * B, ((size_t)3 << 30) / std::max<size_t>(big, 1)));
+        step = (int)std::max<size_t>(1, std::min<size_t>((size_t)L, imgs / (size_t)B));
+    }
+    return scoped_call(e, stream, [&]() -> int {
+        const size_t zc_n = (size_t)B * 4 * kh * kw, oc_n = (size_t)B * oc * gi.kh * gi.kw;
+        float* zc = (float*)e->arena.alloc((size_t)step * zc_n * sizeof(float));
+        float* ocr = (float*)e->arena.alloc((size_t)step * oc_n * sizeof(float));
+        if (!zc || !ocr) return e->fail(FGDM_ERR_NOMEM, "workspace");
+        for (int l0 = 0; l0 < L; l0 += step) {
+            const int n = std::min(step, L - l0);
+            if (unfold_crops(z, zc, gz, l0, n, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "unfold kernel");
+            CHK(e->vae_decode(zc, n * B, kh, kw, scale, ocr));
+            if (fold_accumulate(ocr, w_pix, w_tie, image, gi, l0, n, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "fold kernel");
+        }
+        if (fold_finish(image, w_pix, w_tie, image, gi, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "fold kernel");
+        e->arena.release(zc); e->arena.release(ocr);
+        return FGDM_OK;
+    });
+}
+
+int fgdm_apply_model_patches(fgdm_engine* e, const float* x, const int64_t* t, const float* t_float, const float* ctx, int B,
+                             int H, int W, int kh, int kw, int sh, int sw, const float* w_pix, const float* w_tie,
+                             int max_crops_per_pass, int flags, float* eps_out, void* stream) {
+    if (!e) return FGDM_ERR_ARG;
+    if (!x || (!t && !t_float) || !w_pix || !w_tie || !eps_out || B <= 0 || max_crops_per_pass < 0)
+        return e->fail(FGDM_ERR_ARG, "patch apply_model: null pointer or bad batch / pass size");
+    if (!ctx) return e->fail(FGDM_ERR_ARG, "patch apply_model: ctx must be given (a registered context covers B rows, a pass has n*B)");
+    if (!e->cns.empty()) return e->fail(FGDM_ERR_ARG, "patch apply_model: ControlLDM.apply_model has no patch branch (engine has ControlNets)");
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    PatchGeom g{B, 4, H, W, kh, kw, sh, sw, 0, 0};
+    if (patch_plan(H, W, kh, kw, sh, sw, true, &g.Ly, &g.Lx) != FGDM_OK)
+        return e->fail(FGDM_ERR_ARG, "patch apply_model: the crops do not cover the latent grid ((size - ks) % stride != 0, stride > ks or ks > size)");
+    const int L = g.Ly * g.Lx, step = max_crops_per_pass > 0 ? std::min(max_crops_per_pass, L) : L;
+    const int fl = (flags & FGDM_FLAG_USE_ORIGINAL) | FGDM_FLAG_NO_CONTROL;      // CFG_PAIRS cleared: rows are (l, b)
+    return scoped_call(e, stream, [&]() -> int {
+        const size_t xc_n = (size_t)B * 4 * kh * kw, ctx_n = (size_t)B * e->ctx_tokens * e->cfg.context_dim;
+        float* xc = (float*)e->arena.alloc((size_t)step * xc_n * sizeof(float));
+        float* ec = (float*)e->arena.alloc((size_t)step * xc_n * sizeof(float));
+        float* cr = (float*)e->arena.alloc((size_t)step * ctx_n * sizeof(float));
+        void* tr = e->arena.alloc((size_t)step * B * sizeof(int64_t));
+        if (!xc || !ec || !cr || !tr) return e->fail(FGDM_ERR_NOMEM, "workspace");
+        // t and the context of every crop (ddpm.py:1116,1119); a shorter last pass reads a prefix of the same buffers
+        if (repeat_words(ctx, cr, ctx_n, step, e->s) != FGDM_OK ||
+            repeat_words(t_float ? (const void*)t_float : (const void*)t, tr, t_float ? (size_t)B : (size_t)2 * B, step, e->s) != FGDM_OK)
+            return e->fail(FGDM_ERR_HIP, "repeat kernel");
+        for (int l0 = 0; l0 < L; l0 += step) {
+            const int n = std::min(step, L - l0);
+            if (unfold_crops(x, xc, g, l0, n, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "unfold kernel");
+            CHK(e->apply_model(xc, t_float ? nullptr : (const int64_t*)tr, t_float ? (const float*)tr : nullptr, cr, nullptr, nullptr,
+                               n * B, kh, kw, fl, ec));
+            if (fold_accumulate(ec, w_pix, w_tie, eps_out, g, l0, n, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "fold kernel");
+        }
+        if (fold_finish(eps_out, w_pix, w_tie, eps_out, g, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "fold kernel");
+        e->arena.release(xc); e->arena.release(ec); e->arena.release(cr); e->arena.release(tr);
+        return FGDM_OK;
+    });
+}
+
 int fgdm_controlnet(fgdm_engine* e, int cn, const float* x, const int64_t* t, const float* ctx, int B, int H, int W,
                     float* out, int64_t out_capacity_floats, void* stream) {
     if (!e || !x || !t || !ctx || !out) return FGDM_ERR_ARG;

@@ -325,6 +325,49 @@ class Engine:
         self._check(rc, 'fgdm_vae_decode')
         return img
 
+    def vae_decode_patches(self, z, scale, ks, stride, f, w_pix, w_tie, max_crops_per_pass=0):
+        """decode_first_stage with split_input_params (ddpm.py:841-878): z [B,4,H,W] in (kh, kw) latent crops every `stride`,
+        each decoded like vae_decode and blended with w_pix [f kh, f kw], w_tie [L] (device fp32, fgdm_amd/patches.py) into
+        fp32 [B,3,f H,f W].  max_crops_per_pass bounds the crops decoded together (0: the decoder's own rule)."""
+        z = z.to(self.device, torch.float32).contiguous()
+        B, Cc, H, W = z.shape
+        assert Cc == 4
+        w_pix, w_tie = _weights(w_pix, w_tie, self.device, (H, W, ks, stride, int(f)))
+        img = torch.empty(B, self.config.vae_out_ch, H * f, W * f, device=self.device, dtype=torch.float32)
+        rc = self.lib.fgdm_vae_decode_patches(self.h, _ptr(z), B, H, W, float(scale), ks[0], ks[1], stride[0], stride[1], int(f),
+                                              _ptr(w_pix), _ptr(w_tie), int(max_crops_per_pass), _ptr(img), _stream())
+        self._check(rc, 'fgdm_vae_decode_patches')
+        return img
+
+    def apply_model_patches(self, x, t, ctx, ks, stride, w_pix, w_tie, max_crops_per_pass=0, flags=0):
+        """apply_model with split_input_params (ddpm.py:1046-1128, text branch): the UNet on every (kh, kw) crop of x with the
+        same t and context, blended with w_pix [kh, kw], w_tie [L].  The context is handed over explicitly on every call (the
+        engine's registered context, and this handle's cache policy, are left alone)."""
+        x = x.to(self.device, torch.float32).contiguous()
+        t_int = t_flt = None
+        if t.is_floating_point():
+            t_flt = t.to(self.device, torch.float32).contiguous()
+        else:
+            t_int = t.to(self.device, torch.int64).contiguous()
+        B, Cc, H, W = x.shape
+        if Cc != 4 or ctx.shape[0] != B or t.shape[0] != B:
+            raise ValueError(f'apply_model_patches: x {tuple(x.shape)}, t {tuple(t.shape)}, context {tuple(ctx.shape)} do not agree')
+        self.set_context_tokens(ctx.shape[1])
+        ctx = ctx.to(self.device, torch.float32).contiguous()
+        w_pix, w_tie = _weights(w_pix, w_tie, self.device, (H, W, ks, stride, 1))
+        eps = torch.empty_like(x)
+        rc = self.lib.fgdm_apply_model_patches(self.h, _ptr(x), _ptr(t_int), _ptr(t_flt), _ptr(ctx), B, H, W, ks[0], ks[1],
+                                               stride[0], stride[1], _ptr(w_pix), _ptr(w_tie), int(max_crops_per_pass),
+                                               int(flags), _ptr(eps), _stream())
+        self._check(rc, 'fgdm_apply_model_patches')
+        return eps
+
+    def unfold(self, x, ks, stride, l0=0, n=None, out=None):
+        return unfold(x.to(self.device), ks, stride, l0, n, out)
+
+    def fold_weighted(self, crops, w_pix, w_tie, size, stride, crops_per_pass=0, out=None):
+        return fold_weighted(crops.to(self.device), w_pix, w_tie, size, stride, crops_per_pass, out)
+
     def vae_encode(self, image):
         """AutoencoderKL.encode(image).parameters: fp32 NCHW images [B,3,H,W] in [-1,1] -> fp32 NCHW moments [B,8,H/8,W/8]
         (channels 0-3 the posterior mean, 4-7 its log-variance).  Needs an engine built with vae_encoder=True."""
@@ -475,6 +518,57 @@ def posterior_sample(moments, noise=None, scale=1.0):
     if rc != 0:
         raise RuntimeError(f'fgdm_posterior_sample failed: {rc}')
     return z
+
+
+def _weights(w_pix, w_tie, device, grid=None):
+    """the blending tables as contiguous fp32 on `device`; grid = (H, W, ks, stride, f): their sizes must match the crops the
+    native call will read them for (a grid the crops do not cover is left to the library to refuse)"""
+    w_pix, w_tie = w_pix.to(device, torch.float32).contiguous(), w_tie.to(device, torch.float32).contiguous()
+    if grid is not None:
+        H, W, (kh, kw), (sh, sw), f = grid
+        if tuple(w_pix.shape) != (kh * f, kw * f):
+            raise ValueError(f'w_pix {tuple(w_pix.shape)} must be {(kh * f, kw * f)}')
+        if min(sh, sw) >= 1 and kh <= H and kw <= W and w_tie.numel() < ((H - kh) // sh + 1) * ((W - kw) // sw + 1):
+            raise ValueError(f'w_tie has {w_tie.numel()} entries, fewer than the crops of the grid')
+    return w_pix, w_tie
+
+
+def unfold(x, ks, stride, l0=0, n=None, out=None):
+    """torch.nn.Unfold(ks, stride=stride) of x fp32 [B,C,H,W] (device), crops [l0, l0 + n) (default: all from l0) as fp32
+    [n,B,C,kh,kw]: crop l = ly * Lx + lx starts at (ly * stride[0], lx * stride[1])."""
+    lib = _lib.load()
+    x = x.to(torch.float32).contiguous()
+    B, Cc, H, W = x.shape
+    (kh, kw), (sh, sw) = ks, stride
+    if kh > H or kw > W or min(kh, kw, sh, sw) < 1:
+        raise ValueError(f'unfold: crop {tuple(ks)} / stride {tuple(stride)} do not fit {H} x {W}')
+    L = ((H - kh) // sh + 1) * ((W - kw) // sw + 1)
+    n = L - l0 if n is None else n
+    crops = torch.empty(n, B, Cc, kh, kw, device=x.device, dtype=torch.float32) if out is None else out
+    rc = lib.fgdm_unfold(_ptr(x), B, Cc, H, W, kh, kw, sh, sw, int(l0), int(n), _ptr(crops), _stream())
+    if rc != 0:
+        raise RuntimeError(f'fgdm_unfold failed: {rc}')
+    return crops
+
+
+def fold_weighted(crops, w_pix, w_tie, size, stride, crops_per_pass=0, out=None):
+    """fold(crops * weighting) / fold(weighting): crops fp32 [L,B,C,kh,kw] (device) of ALL crops -> fp32 [B,C,*size];
+    w_pix [kh,kw], w_tie [L] as fgdm_amd.patches.weights returns them."""
+    lib = _lib.load()
+    crops = crops.to(torch.float32).contiguous()
+    L, B, Cc, kh, kw = crops.shape
+    w_pix, w_tie = _weights(w_pix, w_tie, crops.device)
+    if tuple(w_pix.shape) != (kh, kw) or w_tie.numel() != L:
+        raise ValueError(f'fold_weighted: weights {tuple(w_pix.shape)}, {tuple(w_tie.shape)} do not match crops {tuple(crops.shape)}')
+    Ho, Wo = size
+    if kh > Ho or kw > Wo or min(stride) < 1 or L != ((Ho - kh) // stride[0] + 1) * ((Wo - kw) // stride[1] + 1):
+        raise ValueError(f'fold_weighted: {L} crops of {kh} x {kw} every {tuple(stride)} do not make a {Ho} x {Wo} grid')
+    y = torch.empty(B, Cc, Ho, Wo, device=crops.device, dtype=torch.float32) if out is None else out
+    rc = lib.fgdm_fold_weighted(_ptr(crops), _ptr(w_pix), _ptr(w_tie), B, Cc, Ho, Wo, kh, kw, stride[0], stride[1],
+                                int(crops_per_pass), _ptr(y), _stream())
+    if rc != 0:
+        raise RuntimeError(f'fgdm_fold_weighted failed: {rc}')
+    return y
 
 
 def cfg_combine(e_cond, e_uncond, cfg_scale):

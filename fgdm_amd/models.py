@@ -19,7 +19,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import _lib, config as _cfg, hack as _hack, schedule
+from . import _lib, config as _cfg, hack as _hack, patches as _patches, schedule
 from . import engine as _k
 
 
@@ -252,9 +252,14 @@ class LatentDiffusion(_Buffers):
         return self.engine.clip_encode(ids)
 
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False, n=None):
-        """ddpm.py:832-889 for an AutoencoderKL first stage: decode(z / scale_factor)."""
+        """ddpm.py:832-889 for an AutoencoderKL first stage: decode(z / scale_factor).  A model carrying `split_input_params`
+        with patch_distributed_vq decodes overlapping latent crops and blends them (ddpm.py:841-878); a non-square crop or a
+        grid the crops do not cover is a ValueError (fgdm_amd/patches.py)."""
         if predict_cids:
             raise NotImplementedError('predict_cids needs a VQ first stage; every shipped config uses AutoencoderKL')
+        sp = getattr(self, 'split_input_params', None)
+        if sp is not None and sp['patch_distributed_vq']:
+            return self._decode_patches(z, sp)
         if self.first_stage_decode is not None:
             return self.first_stage_decode(1. / self.scale_factor * z)
         if not self.engine.has_vae:
@@ -262,11 +267,35 @@ class LatentDiffusion(_Buffers):
                                       'model.first_stage_decode to a callable)')
         return self.engine.vae_decode(z, 1. / self.scale_factor)
 
+    def _patch_tables(self, kh, kw, Ly, Lx, sp):
+        """(w_pix, w_tie) on the model's device, computed once per geometry and clipping parameters"""
+        key = (kh, kw, Ly, Lx, bool(sp.get('tie_braker', False)), sp['clip_min_weight'], sp['clip_max_weight'],
+               sp.get('clip_min_tie_weight'), sp.get('clip_max_tie_weight'))
+        memo = self.__dict__.setdefault('_patch_tables_memo', {})
+        if key not in memo:
+            memo[key] = tuple(v.to(self.device) for v in _patches.weights(kh, kw, Ly, Lx, sp))
+        return memo[key]
+
+    def _decode_patches(self, z, sp):
+        (kh, kw), stride, Ly, Lx, f = _patches.decode_geometry(z.shape[2], z.shape[3], sp)
+        w_pix, w_tie = self._patch_tables(kh * f, kw * f, Ly, Lx, sp)
+        if self.first_stage_decode is not None:      # a caller's own decoder: its crops through the engine's unfold / fold
+            crops = _k.unfold((1. / self.scale_factor * z).to(self.device), (kh, kw), stride)
+            o = torch.stack([self.first_stage_decode(c) for c in crops])
+            return _k.fold_weighted(o, w_pix, w_tie, (z.shape[2] * f, z.shape[3] * f), (stride[0] * f, stride[1] * f))
+        if not self.engine.has_vae:
+            raise NotImplementedError('this model was built without first_stage_config; pass one (or set '
+                                      'model.first_stage_decode to a callable)')
+        return self.engine.vae_decode_patches(z, 1. / self.scale_factor, (kh, kw), stride, f, w_pix, w_tie,
+                                              getattr(self, 'max_crops_per_pass', 0))
+
     def encode_first_stage(self, x):
         """ddpm.py:952-996 for an AutoencoderKL first stage (plain branch): first_stage_model.encode(x), the posterior of an
         image batch fp32 NCHW [B,3,H,W] in [-1,1]."""
         if hasattr(self, 'split_input_params'):
-            raise NotImplementedError('split_input_params (patch-wise encoding of large images) is not supported')
+            raise NotImplementedError('split_input_params: patch-wise encoding cannot run with an AutoencoderKL first stage -- the '
+                                      "reference's branch (ddpm.py:957-984) multiplies the DiagonalGaussianDistribution that "
+                                      'encode() returns by the weighting tensor')
         if self.first_stage_encode is not None:
             return self.first_stage_encode(x)
         if not getattr(self.engine, 'has_vae_encoder', False):
@@ -307,7 +336,26 @@ class LatentDiffusion(_Buffers):
             self._ctx_cat_memo = memo = (key, list(cc), torch.cat(cc, 1))
         return memo[2]
 
+    def _apply_model_patches(self, x_noisy, t, cond, return_ids, sp):
+        """ddpm.py:1046-1128, text-conditioning branch: the UNet on every crop with the same t and cond, blended.  As in the
+        reference, **kwargs of apply_model (pcond, use_original, cfg_pairs, conds) are not forwarded to the crops (:1119)."""
+        ncond = len(cond) if isinstance(cond, dict) else 1       # a tensor or a list becomes {'c_crossattn': cond} (:1037-1044)
+        assert ncond == 1      # todo of the reference: can only deal with one conditioning
+        assert not return_ids
+        if getattr(self, 'cond_stage_key', None) in _patches.SPATIAL_COND_KEYS:
+            raise NotImplementedError(f"split_input_params with cond_stage_key '{self.cond_stage_key}' (a conditioning that is cut "
+                                      'into crops, or crop coordinates) is not supported: only the text branch is')
+        if getattr(self.engine, 'n_controlnets', 0):
+            raise NotImplementedError('split_input_params: ControlLDM.apply_model has no patch branch in the reference')
+        (kh, kw), stride, Ly, Lx = _patches.plan(x_noisy.shape[2], x_noisy.shape[3], sp['ks'], sp['stride'], clamp=False)
+        w_pix, w_tie = self._patch_tables(kh, kw, Ly, Lx, sp)
+        return self.engine.apply_model_patches(x_noisy, t, self._context(cond), (kh, kw), stride, w_pix, w_tie,
+                                               getattr(self, 'max_crops_per_pass', 0))
+
     def apply_model(self, x_noisy, t, cond, return_ids=False, **kwargs):
+        sp = getattr(self, 'split_input_params', None)
+        if sp is not None:
+            return self._apply_model_patches(x_noisy, t, cond, return_ids, sp)
         if return_ids:
             raise NotImplementedError('return_ids / return_conds needs a model with two outputs; no shipped model has one')
         flags = _lib.FLAG_NO_CONTROL

@@ -153,6 +153,50 @@ int fgdm_vae_encode(fgdm_engine* e, const float* image, int B, int H, int W, flo
 int fgdm_posterior_sample(const float* moments, const float* noise /* NULL: mode */, float scale, float* z,
                           int B, int zc, int HW, void* stream);
 
+/* Patch-wise evaluation of large images: the reference's `split_input_params` routes.  LatentDiffusion.get_fold_unfold
+ * (ldm/models/diffusion/ddpm.py:713-763) cuts a tensor [B,C,H,W] into Ly x Lx overlapping crops of (kh, kw) cells every (sh, sw)
+ * with torch.nn.Unfold -- crop l = ly * Lx + lx has its top-left corner at (ly * sh, lx * sw), Ly = (H-kh)/sh + 1, Lx = (W-kw)/sw
+ * + 1 -- runs a network on every crop, multiplies the results by `weighting` (get_weighting, ddpm.py:697-711), adds them up
+ * with torch.nn.Fold and divides by the folded weighting.  The weighting factors into w_pix fp32 [kh,kw] (clipped border
+ * distance of a cell in its crop) and w_tie fp32 [Ly*Lx] (all ones unless `tie_braker`); weighting[.., l] = w_pix * w_tie[l],
+ * rounded to fp32 once.  fgdm_amd/patches.py computes both tables; all pointers below are DEVICE pointers.
+ *
+ * fgdm_unfold: torch.nn.Unfold(kernel_size=(kh,kw), stride=(sh,sw)) and the view of ddpm.py:857-859 / 1056-1059, for the crops
+ *   [l0, l0 + n): x fp32 [B,C,H,W] -> crops fp32 [n,B,C,kh,kw] (crop-major: one pass is a contiguous NCHW batch of n*B rows).
+ * fgdm_fold_weighted: fold(o * weighting) / fold(weighting) (ddpm.py:871-877, 1123-1128) in one call: crops fp32 [L,B,C,kh,kw]
+ *   for ALL L = Ly*Lx crops -> out fp32 [B,C,Ho,Wo].  Per pixel the covering crops are added in ascending l; the accumulation
+ *   runs in passes of crops_per_pass crops (0: one pass) and gives the same bits for every pass size.  Unlike the reference,
+ *   which returns NaN pixels there, a grid that the crops do not cover ((Ho-kh) % sh, (Wo-kw) % sw non-zero, or a stride
+ *   larger than the crop) is FGDM_ERR_ARG.
+ * Both are stateless, asynchronous on `stream`; every argument error is FGDM_ERR_ARG before any launch. */
+int fgdm_unfold(const float* x, int B, int C, int H, int W, int kh, int kw, int sh, int sw, int l0, int n, float* crops,
+                void* stream);
+int fgdm_fold_weighted(const float* crops, const float* w_pix, const float* w_tie, int B, int C, int Ho, int Wo, int kh, int kw,
+                       int sh, int sw, int crops_per_pass, float* out, void* stream);
+/* LatentDiffusion.decode_first_stage with split_input_params['patch_distributed_vq'] (ddpm.py:841-878): z fp32 [B,4,H,W] is cut
+ * into (kh, kw) latent crops every (sh, sw), every crop is decoded by AutoencoderKL.decode(scale * crop) exactly as
+ * fgdm_vae_decode decodes an image of that size, and the (f kh, f kw) pixel crops are blended into image fp32
+ * [B, vae_out_ch, f H, f W] with w_pix fp32 [f kh, f kw] and w_tie [Ly*Lx] (the tables at IMAGE resolution: uf = vqf = f).
+ * f must equal the engine's 2^(vae_n_levels-1); kh * kw must be a multiple of 64 (the decoder's attention rule, as for
+ * fgdm_vae_encode); the crops must cover the latent grid.  Crops are decoded in passes of at most max_crops_per_pass crops
+ * (0: as many as fgdm_vae_decode's own images-per-pass rule allows for n*B crop images) and every pass is accumulated into
+ * `image`, which is finished at the end: the activation workspace is bounded by one pass, not by H x W. */
+int fgdm_vae_decode_patches(fgdm_engine* e, const float* z, int B, int H, int W, float scale, int kh, int kw, int sh, int sw,
+                            int f, const float* w_pix, const float* w_tie, int max_crops_per_pass, float* image, void* stream);
+/* LatentDiffusion.apply_model with split_input_params, text-conditioning branch (ddpm.py:1046-1059, 1115-1128): the UNet runs on
+ * every (kh, kw) crop of x fp32 [B,4,H,W] with the SAME timesteps and context (ddpm.py:1116,1119) and the crop results are
+ * blended into eps_out [B,4,H,W] with w_pix [kh,kw], w_tie [Ly*Lx].  A pass holds at most max_crops_per_pass crops (0: all) as
+ * one batch of n*B rows ordered (l, b); t / t_float [B] and ctx are repeated per crop on the device.
+ * ctx fp32 [B,77,context_dim] is REQUIRED (NULL: FGDM_ERR_ARG): a context registered with fgdm_set_context covers B rows, not
+ * the n*B rows of a pass, so the context is taken explicitly and converted / projected per pass; the registered one is left
+ * untouched.  flags: FGDM_FLAG_USE_ORIGINAL passes through; FGDM_FLAG_CFG_PAIRS is cleared (in (l, b) order the halves of the
+ * batch are not the CFG halves; results are unchanged, as the flag never changes results); the ControlNet flags are ignored.
+ * An engine with ControlNets is FGDM_ERR_ARG: ControlLDM.apply_model (controlnet/cldm/cldm.py:836-849) has no patch branch.
+ * No pcond / conds: the reference does not forward **kwargs to the crops (ddpm.py:1119). */
+int fgdm_apply_model_patches(fgdm_engine* e, const float* x, const int64_t* t, const float* t_float, const float* ctx, int B,
+                             int H, int W, int kh, int kw, int sh, int sw, const float* w_pix, const float* w_tie,
+                             int max_crops_per_pass, int flags, float* eps_out, void* stream);
+
 /* Stage boundary of the two-factor chain (device pointers; byte work, bit-exact to the reference's expressions):
  *  fgdm_image_to_uint8: fp32 NCHW image -> uint8 NHWC.  mode 0 = uint8(255 * clamp((x+1)/2, 0, 1))
  *      (scripts/txt2img_fgdm_inference.py:245,249-252); mode 1 = uint8(clip(x*127.5+127.5, 0, 255))

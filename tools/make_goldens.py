@@ -847,18 +847,85 @@ def g_clip_hack_tokens():
         json.dump(out, f)
     print(f'wrote {path}')
 
+# --------------------------------------------------------------------------- patch-wise routes (split_input_params)
+def _reference_split_ldm(params, diffusion_model=None, first_stage_model=None):
+    """The reference's LatentDiffusion carrying `split_input_params`, around already-built networks: the heavy constructor is
+    bypassed (as in g_samplers), get_fold_unfold / apply_model / decode_first_stage are the reference's own method bodies."""
+    import ldm.models.diffusion.ddpm as ddpm
+
+    class Wrapper(ddpm.DiffusionWrapper):
+        def __init__(s, m):
+            nn.Module.__init__(s)
+            s.diffusion_model = m
+            s.conditioning_key = 'crossattn'
+
+    class LD(ddpm.LatentDiffusion):
+        def __init__(s):
+            nn.Module.__init__(s)
+            s.split_input_params = dict(params)
+            s.cond_stage_key = 'caption'
+            s.scale_factor = 0.18215
+            if diffusion_model is not None:
+                s.model = Wrapper(diffusion_model)
+            if first_stage_model is not None:
+                s.first_stage_model = first_stage_model
+    return LD()
+
+
+def g_split_input_tables():
+    """weighting and normalization exactly as get_fold_unfold returns them (ddpm.py:713-763), for split_input_inputs.TABLES."""
+    import split_input_inputs as si
+    arrs = {}
+    for i, (h, w, ks, stride, uf, tie) in enumerate(si.TABLES):
+        ld = _reference_split_ldm(si.split_params(ks, stride, tie))
+        _, _, normalization, weighting = ld.get_fold_unfold(torch.zeros(1, 4, h, w), ks, stride, uf=uf)
+        arrs[f'weighting_{i}'] = weighting
+        arrs[f'normalization_{i}'] = normalization
+    save('split_input_tables', **arrs)
+
+
+def g_split_input_unet():
+    """LatentDiffusion.apply_model with split_input_params (ddpm.py:1046-1128, text branch) around the reduced UNet of
+    small_nets.npz (SMALL_CFG: SD widths, reduced depth -- the engine needs channel counts that are multiples of 64, which the
+    160-wide NARROW_CFG is not): x [2,4,24,32] in six 16 x 16 crops at stride 8."""
+    import split_input_inputs as si
+    from ldm.modules.diffusionmodules.openaimodel import UNetModel
+    m = UNetModel(**ref_cfg(gi.SMALL_CFG, no_prompting=True)).eval()
+    load_synth(m, 'small.')
+    ld = _reference_split_ldm(si.split_params(si.UNET_KS, si.UNET_STRIDE), diffusion_model=m)
+    t = torch.tensor(si.T, dtype=torch.long)
+    with torch.no_grad():
+        eps = ld.apply_model(si.unet_x(), t, si.unet_ctx())
+    save('split_input_unet', t=t, eps=eps.float())
+
+
+def g_split_input_vae():
+    """LatentDiffusion.decode_first_stage with split_input_params (ddpm.py:841-878): z [1,4,16,24] in fifteen 8 x 8 crops at
+    stride 4, decoded to 64 x 64 pixels each and folded into a 3 x 128 x 192 image."""
+    import contextlib
+    import io
+    import split_input_inputs as si
+    from ldm.models.autoencoder import AutoencoderKL
+    m = AutoencoderKL(ddconfig=vae_ddconfig(), lossconfig={'target': 'torch.nn.Identity'}, embed_dim=4).eval()
+    load_synth(m, 'first_stage_model.')
+    ld = _reference_split_ldm(si.split_params(si.VAE_KS, si.VAE_STRIDE), first_stage_model=m)
+    with torch.no_grad(), contextlib.redirect_stdout(io.StringIO()):
+        img = ld.decode_first_stage(si.vae_z())
+    save('split_input_vae', img=img.float())
+
 
 ALL = dict(schedule=g_schedule, ddpm_schedule=g_ddpm_schedule, param_keys=g_param_keys, ops=g_ops,
            unet_full=g_unet_full, controlnet_full=g_controlnet_full, small_nets=g_small_nets,
            samplers=g_samplers, samplers2=g_samplers2, samplers3=g_samplers3, sampler_unet=g_sampler_unet, vae=g_vae, clip=g_clip, adapt_unet=g_adapt_unet, full_size=g_full_size,
            full_size_check=g_full_size_check, vae_enc=g_vae_enc, long_context=g_long_context,
-           clip_hack_tokens=g_clip_hack_tokens)
+           clip_hack_tokens=g_clip_hack_tokens, split_input_tables=g_split_input_tables, split_input_unet=g_split_input_unet,
+           split_input_vae=g_split_input_vae)
 
 
 # generators that are ALSO run with the reference's modules under the emulated torch.autocast("cuda") policy
 # (scripts/txt2img_fgdm_inference.py:212-217 wraps the whole sampling loop in it) -> tests/golden/<name>_ac.npz
 AC = ('ops', 'unet_full', 'controlnet_full', 'small_nets', 'sampler_unet', 'adapt_unet', 'vae', 'clip', 'full_size', 'full_size_check',
-      'vae_enc', 'long_context')
+      'vae_enc', 'long_context', 'split_input_unet', 'split_input_vae')
 
 
 def main():
