@@ -28,6 +28,24 @@
 
 #pragma clang diagnostic ignored "-Winline-asm"     // M0 named as an asm clobber (att_dma16): reserved register, on purpose
 #define ATT_THR 8.0f
+#define ATT_SB() __builtin_amdgcn_sched_barrier(0)
+
+// XCD-aware mapping: workgroups b and b+8 share an XCD (and its 4 MiB L2).  Give every XCD a contiguous range of logical blocks, which
+// the kernels decode as (batch, head, q-block) triples with the q-block fastest, so all q-blocks of one (batch, head) stream the SAME
+// K / Vt through ONE L2 instead of eight (PMC: 389 MB fetched per launch against 252 MB of Q+K+V before).
+__device__ __forceinline__ int att_logical_block() {
+    const int nb = gridDim.x, bid = blockIdx.x, xcd = bid & 7, qd = nb >> 3, r = nb & 7;
+    return (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (bid >> 3);
+}
+// Maximum of mx over the two lane halves (the other key half of the same query: lane ^ 32).
+// Inline asm, not __builtin_amdgcn_permlane32_swap: hipcc folds fmaxf(r[0], r[1]) of the builtin's two results into r[0] (visible in the
+// IR; round 3 met the same fold) and the cross-half maximum silently disappears.  s_nop 1 = the two wait states between a vector-ALU
+// write of an operand and the swap that reads it
+__device__ __forceinline__ float att_max_cross(float mx) {
+    float lo = mx, hi = mx;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo), "+v"(hi));
+    return fmaxf(lo, hi);
+}
 
 template <int D>
 __global__ __launch_bounds__(256) void attn_kernel(const half_t* __restrict__ Q, int ldq,
@@ -51,16 +69,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const half_t* __restrict__ Q,
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lq = lane & 31, lh = lane >> 5;
-    // XCD-aware mapping: workgroups b and b+8 share an XCD (and its 4 MiB L2).  Give every XCD a contiguous range of
-    // (batch, head, q-block) triples with the q-block fastest, so all q-blocks of one (batch, head) stream the SAME
-    // K / Vt through ONE L2 instead of eight (PMC: 389 MB fetched per launch against 252 MB of Q+K+V before).
     const int nqb = (T + 127) / 128;
-    const int nb = gridDim.x;
-    int logical;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, qd = nb >> 3, r = nb & 7;
-        logical = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (bid >> 3);
-    }
+    const int logical = att_logical_block();
     // Cross-attention (Tk <= 128: K / Vt of a head are 6-25 KB, nothing to share) is bound by its Q reads and O writes, and a
     // head's slice of a token row is 2 D bytes of a 2 H D-byte row: there the HEAD runs fastest, so the H workgroups that touch
     // the same 128 rows are neighbours on one XCD and every 128-byte line of Q and O crosses the fabric once instead of once per
@@ -346,269 +356,30 @@ __global__ __launch_bounds__(256) void attn_kernel(const half_t* __restrict__ Q,
     }
 }
 
-
 // =====================================================================================================================
-// Cross-attention (64 < Tk <= 96: the 77 text tokens).  The kernel above gives every 128 queries their own workgroup, which
-// stages K / V^T tile by tile behind barriers: with two tiles of keys that is three dependent memory round trips and two barriers
-// for 50 MFMAs -- latency-bound at 2.2 TB/s of Q + O traffic (72 us at T = 4096, d = 40).  Here a workgroup stages ALL keys of its
-// (batch, head) once (K [96][DP], V^T [d][96] with the ones row), passes ONE barrier, and then each of its four waves walks CPW
-// chunks of 32 queries on its own: S^T = K Q^T for the three 32-key sub-tiles in one go, a plain (single-pass) softmax, O^T = V^T P^T;
-// the next chunk's Q rows are requested before the current chunk is computed.  Heads run fastest over workgroups (see above).
-template <int D>
+// Text cross-attention, key-resident (64 < Tk <= 256: one, two or three 77-token parts joined along the token axis, cldm.py:836-849 /
+// hack.py:23-68).  The kernel above gives every 128 queries their own workgroup, which stages K / V^T tile by tile behind barriers:
+// with two tiles of keys that is three dependent memory round trips and two barriers for 50 MFMAs -- latency-bound at 2.2 TB/s of
+// Q + O traffic (72 us at T = 4096, d = 40).  Here a workgroup stages ALL keys of its (batch, head) once (K [32 NS][DP], V^T [d][32 NS]
+// with the ones row), passes ONE barrier, and then each of its four waves walks cpw chunks of 32 queries on its own: S^T = K Q^T for
+// the NS 32-key sub-tiles in one go, a plain (single-pass) softmax -- the maximum over all NS score tiles before any exp2: a spike
+// may sit in any of them -- and O^T = V^T P^T; the next chunk's Q rows are requested before the current chunk is computed.  Heads run
+// fastest over workgroups (see above).
+// CONTRACT: NS == ceil(Tk / 32), so that only sub-tile NS - 1 can hold keys >= Tk and needs the mask (launch_cross returns
+// FGDM_ERR_ARG for anything else).
+// LDS: NS = 3 (the 77 text tokens) fits the static 64 KB; K / V^T for 256 keys need up to 123 KB (d = 80), so NS >= 4 is dynamic;
+// d = 160 fits up to NS = 7 (155 KB) and falls back to attn_kernel beyond.  At NS = 8 the scores alone are 128 fp32 registers per
+// lane: the kernel runs at one workgroup per CU by LDS anyway, so the 512-register budget of one wave per SIMD is its to use.
+constexpr int attn_cross_lds(int D, int NS) {
+    const int DP = (D + 15) / 16 * 16, DT = (D + 31) / 32, KEYS = NS * 32;
+    return KEYS * (DP * 2 + 16) + DT * 32 * (KEYS * 2 + 72) + (D <= 80 ? 4 * 32 * (D * 2 + 8) : 0);
+}
+template <int D, int NS>
 __global__ __launch_bounds__(256) void attn_cross_kernel(const half_t* __restrict__ Q, int ldq,
                                                          const half_t* __restrict__ K, int ldk,
                                                          const half_t* __restrict__ Vt, int ldvt,
                                                          half_t* __restrict__ O, int ldo,
                                                          int H, int T, int Tk, float sl2e, int cpw) {
-    constexpr int NS = 3, KEYS = NS * 32;
-    constexpr int DP = (D + 15) / 16 * 16, NKS = DP / 16, DT = (D + 31) / 32;
-    constexpr bool ONES = (DT * 32 > D);
-    constexpr bool FOLD = (DP > D) && (D % 8 == 0);      // same Q scaling rule as attn_kernel (the spare slot itself stays 0 here)
-    constexpr int KS = DP * 2 + 16;            // K row stride (bytes): odd multiple of 16
-    constexpr int VS = KEYS * 2 + 72;          // V^T row stride: 66 dwords = 2 mod 32 -> b64 reads conflict-free like the 34 above
-    constexpr int DC = D / 8;
-    // Q rows enter and O rows leave through a wave-private [32][D] LDS tile, so that global memory sees 16-byte pieces of whole
-    // 2 D-byte row slices (a lane per query row means 64 different lines per instruction, 8 bytes each on the way out)
-    constexpr bool RELAY = D <= 80;
-    constexpr int RS = D * 2 + 8;              // 22 / 42 dwords per row: 8-byte accesses of 16 consecutive rows hit 16 banks
-    constexpr int PCS = 32 * (D / 8), KP = (PCS + 63) / 64;      // 16-byte pieces of a 32-row chunk; per lane
-    __shared__ __attribute__((aligned(16))) char smem[KEYS * KS + DT * 32 * VS + (RELAY ? 4 * 32 * RS : 0)];
-    char* Ks = smem;
-    char* Vs = smem + KEYS * KS;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lq = lane & 31, lh = lane >> 5;
-    const int qpw = 128 * cpw;                               // queries per workgroup
-    const int ncb = (T + qpw - 1) / qpw;
-    const int nb = gridDim.x;
-    int logical;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, qd = nb >> 3, r = nb & 7;
-        logical = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (bid >> 3);
-    }
-    const int head = logical % H, rest = logical / H;
-    const int cblk = rest % ncb, b = rest / ncb;
-
-    const half_t* Kb = K + (size_t)b * Tk * ldk + head * D;
-    const half_t* Vb = Vt + ((size_t)b * H + head) * D * ldvt;
-    // ---- stage K (rows past Tk repeat the last valid one: their scores are masked) and V^T (rows are padded to 64-key multiples):
-    // every global load of the workgroup is issued before the first LDS store -- ONE memory round trip (as loops of load / store
-    // pairs the staging was 5-6 dependent round trips, most of a workgroup's life)
-    constexpr int KPC = KEYS * (DP / 8), VPC = DT * 32 * (KEYS / 8);
-    constexpr int KPT = (KPC + 255) / 256, VPT = (VPC + 255) / 256;
-    h8 kst[KPT], vst[VPT];
-#pragma unroll
-    for (int u = 0; u < KPT; ++u) {
-        const int i = tid + 256 * u, key = i / (DP / 8), c = i - key * (DP / 8);
-        kst[u] = (h8)(half_t)0;
-        if (i < KPC && c < DC) kst[u] = *(const h8*)(Kb + (size_t)min(key, Tk - 1) * ldk + c * 8);
-    }
-#pragma unroll
-    for (int u = 0; u < VPT; ++u) {
-        const int i = tid + 256 * u, r = i / (KEYS / 8), c = i - r * (KEYS / 8);
-        vst[u] = (r == D) ? (h8)(half_t)1 : (h8)(half_t)0;
-        if (i < VPC && r < D) vst[u] = *(const h8*)(Vb + (size_t)r * ldvt + c * 8);
-    }
-    char* scr = smem + KEYS * KS + DT * 32 * VS + (threadIdx.x >> 6) * 32 * RS;      // this wave's tile
-    // the chunk's Q rows: per-lane fragments straight from global memory, or (RELAY) 16-byte pieces in row order
-    constexpr int NQ = RELAY ? KP : NKS;
-    auto load_q = [&](int q0, h8 (&qr)[NQ]) {      // q0: first query of the chunk (wave-uniform)
-        if constexpr (RELAY) {
-#pragma unroll
-            for (int u = 0; u < KP; ++u) {
-                const int c = lane + 64 * u, row = c / (D / 8), ck = c - row * (D / 8);
-                qr[u] = (h8)(half_t)0;
-                if (c < PCS && q0 + row < T) qr[u] = *(const h8*)(Q + ((size_t)b * T + q0 + row) * ldq + head * D + ck * 8);
-            }
-        } else {
-#pragma unroll
-            for (int s2 = 0; s2 < NKS; ++s2) {
-                const int c = 16 * s2 + 8 * lh;
-                qr[s2] = (h8)(half_t)0;
-                if (c < D && q0 + lq < T) qr[s2] = *(const h8*)(Q + ((size_t)b * T + q0 + lq) * ldq + head * D + c);
-            }
-        }
-    };
-    const int q_first = cblk * qpw + wave * 32;              // chunk i of this wave: queries q_first + i * 128 + [0, 32)
-    h8 qn[NQ];
-    load_q(q_first, qn);
-#pragma unroll
-    for (int u = 0; u < KPT; ++u) {
-        const int i = tid + 256 * u, key = i / (DP / 8), c = i - key * (DP / 8);
-        if (i < KPC) *(h8*)(Ks + key * KS + c * 16) = kst[u];
-    }
-#pragma unroll
-    for (int u = 0; u < VPT; ++u) {
-        const int i = tid + 256 * u, r = i / (KEYS / 8), c = i - r * (KEYS / 8);
-        if (i < VPC) {
-            const h8 v = vst[u];
-            const h4 lo = {v[0], v[1], v[2], v[3]}, hi = {v[4], v[5], v[6], v[7]};
-            *(h4*)(Vs + r * VS + c * 16) = lo;
-            *(h4*)(Vs + r * VS + c * 16 + 8) = hi;
-        }
-    }
-    __syncthreads();
-
-    const int kfrag = lq * KS + 8 * lh * 2, vfrag = lq * VS + 4 * lh * 2;
-    for (int i = 0; i < cpw; ++i) {
-        const int q0 = __builtin_amdgcn_readfirstlane(q_first + i * 128);
-        if (q0 >= T) break;                                  // wave-uniform: this chunk starts past the end
-        const int q = q0 + lq;
-        h8 qf[NKS];
-        if constexpr (RELAY) {
-#pragma unroll
-            for (int u = 0; u < KP; ++u) {
-                const int c = lane + 64 * u, row = c / (D / 8), ck = c - row * (D / 8);
-                if (c < PCS) {
-                    const h4 lo = {qn[u][0], qn[u][1], qn[u][2], qn[u][3]}, hi = {qn[u][4], qn[u][5], qn[u][6], qn[u][7]};
-                    *(h4*)(scr + row * RS + ck * 16) = lo;
-                    *(h4*)(scr + row * RS + ck * 16 + 8) = hi;
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int s2 = 0; s2 < NKS; ++s2) {
-                const int c = 16 * s2 + 8 * lh;
-                qf[s2] = (h8)(half_t)0;
-                if (c < D) {
-                    const h4 lo = *(const h4*)(scr + lq * RS + c * 2), hi = *(const h4*)(scr + lq * RS + c * 2 + 8);
-                    qf[s2] = h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // fragments read before the tile is reused for O
-        } else {
-#pragma unroll
-            for (int s2 = 0; s2 < NKS; ++s2) qf[s2] = qn[s2];
-        }
-        if (i + 1 < cpw) load_q(q0 + 128, qn);
-        if constexpr (FOLD) {
-#pragma unroll
-            for (int s2 = 0; s2 < NKS; ++s2)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) qf[s2][j] = (half_t)((float)qf[s2][j] * sl2e);
-        }
-        // ---- S^T = K Q^T, all keys
-        f32x16 sacc[NS];
-#pragma unroll
-        for (int sub = 0; sub < NS; ++sub) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc[sub][r] = 0.f;
-#pragma unroll
-            for (int s2 = 0; s2 < NKS; ++s2) {
-                const h8 kf = *(const h8*)(Ks + kfrag + sub * 32 * KS + 16 * s2 * 2);
-                sacc[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s2], sacc[sub], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {           // only the last sub-tile can hold keys >= Tk (64 < Tk <= 96)
-            const int key = (NS - 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (key >= Tk) sacc[NS - 1][r] = -INFINITY;
-        }
-        float mx = sacc[0][0];
-#pragma unroll
-        for (int sub = 0; sub < NS; ++sub)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[sub][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float sc = FOLD ? 1.0f : sl2e;
-        float psum = 0.f;
-#pragma unroll
-        for (int sub = 0; sub < NS; ++sub)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pv = __builtin_amdgcn_exp2f((sacc[sub][r] - mx) * sc);
-                sacc[sub][r] = pv;
-                if constexpr (!ONES) psum += pv;
-            }
-        // ---- O^T = V^T P^T (row D of O^T: the sum of the fp16 probabilities)
-        f32x16 oacc[DT];
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
-#pragma unroll
-        for (int sub = 0; sub < NS; ++sub)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                h8 pf;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) pf[j] = (half_t)sacc[sub][8 * s2 + j];
-#pragma unroll
-                for (int t = 0; t < DT; ++t) {
-                    const char* vp = Vs + vfrag + t * 32 * VS + (sub * 32 + 16 * s2) * 2;
-                    const h4 v0 = *(const h4*)vp, v1 = *(const h4*)(vp + 16);
-                    const h8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                    oacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[t], 0, 0, 0);
-                }
-            }
-        float l_tot;
-        if constexpr (ONES) {
-            constexpr int rr = D % 32;
-            constexpr int reg = (rr & 3) + 4 * (rr >> 3);
-            constexpr int owner_half = (rr >> 2) & 1;
-            const float mine = oacc[D / 32][reg];
-            const float other = __shfl_xor(mine, 32);
-            l_tot = (lh == owner_half) ? mine : other;
-        } else {
-            l_tot = psum + __shfl_xor(psum, 32);
-        }
-        const float inv = 1.0f / l_tot;
-        if constexpr (RELAY) {
-#pragma unroll
-            for (int t = 0; t < DT; ++t)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int dd = t * 32 + 8 * g + 4 * lh;
-                    if (dd < D) {
-                        h4 pk = {(half_t)(oacc[t][4 * g] * inv), (half_t)(oacc[t][4 * g + 1] * inv),
-                                 (half_t)(oacc[t][4 * g + 2] * inv), (half_t)(oacc[t][4 * g + 3] * inv)};
-                        *(h4*)(scr + lq * RS + dd * 2) = pk;
-                    }
-                }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int u = 0; u < KP; ++u) {
-                const int c = lane + 64 * u, row = c / (D / 8), ck = c - row * (D / 8);
-                if (c < PCS && q0 + row < T) {
-                    const h4 lo = *(const h4*)(scr + row * RS + ck * 16), hi = *(const h4*)(scr + row * RS + ck * 16 + 8);
-                    *(h8*)(O + ((size_t)b * T + q0 + row) * ldo + head * D + ck * 8) = h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the tile is free for the next chunk's Q
-        } else if (q < T) {
-            half_t* op = O + ((size_t)b * T + q) * ldo + head * D;
-#pragma unroll
-            for (int t = 0; t < DT; ++t)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int dd = t * 32 + 8 * g + 4 * lh;
-                    if (dd < D) {
-                        h4 pk = {(half_t)(oacc[t][4 * g] * inv), (half_t)(oacc[t][4 * g + 1] * inv),
-                                 (half_t)(oacc[t][4 * g + 2] * inv), (half_t)(oacc[t][4 * g + 3] * inv)};
-                        *(h4*)(op + dd) = pk;
-                    }
-                }
-        }
-    }
-}
-
-// =====================================================================================================================
-// Long text contexts (96 < Tk <= 256: two or three 77-token parts joined along the token axis, cldm.py:836-849 / hack.py:23-68).
-// The design of attn_cross_kernel with NS sub-tiles of 32 keys: all keys of a (batch, head) staged once, ONE barrier, the maximum
-// over all NS score tiles before any exp2 (a spike may sit in any of them), every wave walking cpw chunks of 32 queries with the
-// next chunk's Q requested early.  K / V^T for 256 keys need up to 123 KB (d = 80), so the LDS is dynamic; d = 160 fits up to
-// NS = 7 (155 KB) and falls back to attn_kernel beyond.  At NS = 8 the scores alone are 128 fp32 registers per lane: the kernel
-// runs at one workgroup per CU by LDS anyway, so the 512-register budget of one wave per SIMD is its to use.
-constexpr int attn_cross_long_lds(int D, int NS) {
-    const int DP = (D + 15) / 16 * 16, DT = (D + 31) / 32, KEYS = NS * 32;
-    return KEYS * (DP * 2 + 16) + DT * 32 * (KEYS * 2 + 72) + (D <= 80 ? 4 * 32 * (D * 2 + 8) : 0);
-}
-template <int D, int NS>
-__global__ __launch_bounds__(256) void attn_cross_long_kernel(const half_t* __restrict__ Q, int ldq,
-                                                              const half_t* __restrict__ K, int ldk,
-                                                              const half_t* __restrict__ Vt, int ldvt,
-                                                              half_t* __restrict__ O, int ldo,
-                                                              int H, int T, int Tk, float sl2e, int cpw) {
     constexpr int KEYS = NS * 32;
     constexpr int DP = (D + 15) / 16 * 16, NKS = DP / 16, DT = (D + 31) / 32;
     constexpr bool ONES = (DT * 32 > D);
@@ -621,8 +392,15 @@ __global__ __launch_bounds__(256) void attn_cross_long_kernel(const half_t* __re
     constexpr bool RELAY = D <= 80;
     constexpr int RS = D * 2 + 8;              // 22 / 42 dwords per row: 8-byte accesses of 16 consecutive rows hit 16 banks
     constexpr int PCS = 32 * (D / 8), KP = (PCS + 63) / 64;      // 16-byte pieces of a 32-row chunk; per lane
-    static_assert(attn_cross_long_lds(D, NS) == KEYS * KS + DT * 32 * VS + (RELAY ? 4 * 32 * RS : 0), "LDS size formula");
-    extern __shared__ __attribute__((aligned(16))) char smem[];      // attn_cross_long_lds(D, NS) bytes: beyond the static 64 KB
+    static_assert(attn_cross_lds(D, NS) == KEYS * KS + DT * 32 * VS + (RELAY ? 4 * 32 * RS : 0), "LDS size formula");
+    char* smem;
+    if constexpr (NS == 3) {                   // static: its addresses are immediates (a dynamic base costs ~4 % more instructions)
+        __shared__ __attribute__((aligned(16))) char smem_static[attn_cross_lds(D, NS)];
+        smem = smem_static;
+    } else {                                   // beyond the static 64 KB
+        extern __shared__ __attribute__((aligned(16))) char smem_dynamic[];
+        smem = smem_dynamic;
+    }
     char* Ks = smem;
     char* Vs = smem + KEYS * KS;
 
@@ -630,12 +408,7 @@ __global__ __launch_bounds__(256) void attn_cross_long_kernel(const half_t* __re
     const int lq = lane & 31, lh = lane >> 5;
     const int qpw = 128 * cpw;                               // queries per workgroup
     const int ncb = (T + qpw - 1) / qpw;
-    const int nb = gridDim.x;
-    int logical;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, qd = nb >> 3, r = nb & 7;
-        logical = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (bid >> 3);
-    }
+    const int logical = att_logical_block();
     const int head = logical % H, rest = logical / H;
     const int cblk = rest % ncb, b = rest / ncb;
 
@@ -749,11 +522,13 @@ __global__ __launch_bounds__(256) void attn_cross_long_kernel(const half_t* __re
                 sacc[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s2], sacc[sub], 0, 0, 0);
             }
         }
-        // every sub-tile that can hold a key >= Tk is masked (the dispatch picks NS = ceil(Tk / 32), where that is the last one only;
-        // the test is wave-uniform, so full sub-tiles cost one scalar compare).  Sub-tile 0 always holds key 0 < Tk.
+        // Only the last sub-tile can hold keys >= Tk (the contract: NS == ceil(Tk / 32)), and it is masked without a test.  Three
+        // instantiations ran 0.3 - 3 % slower in that form than with every sub-tile from 1 on masked behind a wave-uniform test (the
+        // compiler schedules the chunk differently; profiles/attention_text_kernel_unified.txt): they keep the form with the test
+        constexpr int MASK_FROM = ((D == 160 && (NS == 5 || NS == 6)) || (D == 80 && NS == 8)) ? 1 : NS - 1;
 #pragma unroll
-        for (int sub = 1; sub < NS; ++sub)
-            if ((sub + 1) * 32 > Tk) {
+        for (int sub = MASK_FROM; sub < NS; ++sub)
+            if (MASK_FROM == NS - 1 || (sub + 1) * 32 > Tk) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -885,12 +660,7 @@ __global__ __launch_bounds__(512) void attn_pp_kernel(const half_t* __restrict__
     const int grp = wave >> 2;                      // 0 = A, 1 = B
     const int lq = lane & 31, lh = lane >> 5;
     const int nqb = (T + 255) / 256;
-    const int nb = gridDim.x;
-    int logical;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, qd = nb >> 3, r = nb & 7;
-        logical = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (bid >> 3);
-    }
+    const int logical = att_logical_block();
     const int qblk = logical % nqb, bh = logical / nqb;
     const int b = bh / H, head = bh - b * H;
     const int q = qblk * 256 + wave * 32 + lq;
@@ -1194,12 +964,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_dq_kernel(const half_t* __res
     const int n32 = lane & 31, h = lane >> 5;                // S^T layout: query on lane & 31, key half on lane >> 5
     const int n16 = lane & 15, g = lane >> 4;                // O^T layout: query on lane & 15, row quad on lane >> 4
     const int nqb = T / (NW * 64);
-    const int nb = gridDim.x;
-    int logical;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, qd = nb >> 3, r = nb & 7;
-        logical = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (bid >> 3);
-    }
+    const int logical = att_logical_block();
     const int qblk = logical % nqb, bh = logical / nqb;
     const int b = bh / H, head = bh - b * H;
     const int q0w = qblk * (NW * 64) + wave * 64;                  // first query of this wave; strand X: q0w + 32 X + [0, 32)
@@ -1280,7 +1045,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_dq_kernel(const half_t* __res
     f32x16 sacc[2][2];
     h8 kf[2][NKS], vf[DT][2], pb[2][2][2];
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define ATT_SB() __builtin_amdgcn_sched_barrier(0)
     auto rd_k = [&](const char* sl, int sub, int s) {
         const int ci0 = 2 * s;                               // piece index of lane half 0; half 1 reads ci0 + 1
         const char* p = sl + k_lane + sub * 32 * KROW + s * 32;
@@ -1312,14 +1076,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_dq_kernel(const half_t* __res
 #pragma unroll
         for (int r = 0; r < 16; r += 2) mx = fmaxf(fmaxf(mx, sacc[X][sub][r]), sacc[X][sub][r + 1]);
         return mx;
-    };
-    auto max_cross = [&](float mx) {                         // the other key half of the same query: lane ^ 32
-        // inline asm, not __builtin_amdgcn_permlane32_swap: hipcc folds fmaxf(r[0], r[1]) of the builtin's two results into r[0]
-        // (visible in the IR; round 3 met the same fold) and the cross-half maximum silently disappears.  s_nop 1 = the two wait
-        // states between a vector-ALU write of an operand and the swap that reads it
-        float lo = mx, hi = mx;
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo), "+v"(hi));
-        return fmaxf(lo, hi);
     };
     // the offset moves only when some query of the strand outgrew it by more than 2^ATT_THR (or on the first tile)
     auto decide = [&](int X, float mx, bool first) {
@@ -1397,7 +1153,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_dq_kernel(const half_t* __res
         float mx = sacc[0][0][0];                   // (sub-tile 0 first: its MFMAs retired three MFMAs ago)
         qk(1, 0, 0); mx = max_part(0, 0, mx); ATT_SB();
         qk(1, 0, 1); mx = max_part(0, 1, mx); ATT_SB();
-        qk(1, 0, 2 % NKS); mx = max_cross(mx); ATT_SB();
+        qk(1, 0, 2 % NKS); mx = att_max_cross(mx); ATT_SB();
 #pragma unroll
         for (int s = 3; s < NKS; ++s) { qk(1, 0, s); ATT_SB(); }
         decide(0, mx, first);
@@ -1421,7 +1177,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_dq_kernel(const half_t* __res
                 expo(0, 1, 16 * i / n, 16 * (i + 1) / n);
                 if (i == 1) mxb = max_part(1, 0, mxb);
                 if (i == 3) mxb = max_part(1, 1, mxb);
-                if (i == 4) mxb = max_cross(mxb);
+                if (i == 4) mxb = att_max_cross(mxb);
                 ATT_SB();
             }
         pack(0, 1);
@@ -1464,7 +1220,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_dq_kernel(const half_t* __res
         if (kt + 1 < nt) tile(kt + 1, std::integral_constant<int, 1>{});
         if (kt + 2 < nt) tile(kt + 2, std::integral_constant<int, 2>{});
     }
-#undef ATT_SB
 
     // ---- O = O^T / l: row D of O^T (tile D / 16, row D % 16: lane group (D % 16) / 4, register D % 4) is the denominator
     constexpr int LT = D / 16, LG = (D % 16) / 4, LR = D % 4;
@@ -1519,12 +1274,7 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n32 = lane & 31, h = lane >> 5;                // query (S^T, O^T) / row (fragments) on lane & 31, half on lane >> 5
     const int nqb = T / (NW * 64);
-    const int nb = gridDim.x;
-    int logical;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, qd = nb >> 3, r = nb & 7;
-        logical = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd) + (bid >> 3);
-    }
+    const int logical = att_logical_block();
     const int qblk = logical % nqb, bh = logical / nqb;
     const int b = bh / H, head = bh - b * H;
     const int q0w = qblk * (NW * 64) + wave * 64;            // first query of this wave; strand X: q0w + 32 X + [0, 32)
@@ -1614,7 +1364,6 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
     f32x16 sacc[2][2];
     h8 kf[2][NKS], vf[DT][2][2], pf[2][2][2];
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define ATT_SB() __builtin_amdgcn_sched_barrier(0)
     auto rd_k = [&](const char* sl, int sub, int s) {
         const int ci0 = 2 * s;                               // piece index of lane half 0; half 1 reads ci0 + 1
         const char* p = sl + k_lane[s] + sub * 32 * KROW;
@@ -1639,11 +1388,6 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
 #pragma unroll
         for (int r = 0; r < 16; r += 2) mx = fmaxf(fmaxf(mx, sacc[X][sub][r]), sacc[X][sub][r + 1]);
         return mx;
-    };
-    auto max_cross = [&](float mx) {                         // the other key half of the same query: lane ^ 32 (asm: see above)
-        float lo = mx, hi = mx;
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo), "+v"(hi));
-        return fmaxf(lo, hi);
     };
     auto decide = [&](int X, float mx, bool first) {
         if constexpr ((ABL & 2) != 0) return;
@@ -1704,7 +1448,7 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
         float mx = sacc[0][0][0];                            // (sub-tile 0 first: its MFMAs retired three MFMAs ago)
         qk(1, 0, 0); mx = max_part(0, 0, mx); ATT_SB();
         qk(1, 0, 1); mx = max_part(0, 1, mx); ATT_SB();
-        qk(1, 0, 2 % NKS); mx = max_cross(mx); ATT_SB();
+        qk(1, 0, 2 % NKS); mx = att_max_cross(mx); ATT_SB();
 #pragma unroll
         for (int s = 3; s < NKS; ++s) { qk(1, 0, s); ATT_SB(); }
         decide(0, mx, first);
@@ -1728,7 +1472,7 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
             expo(0, 1, 16 * i / NPV, 16 * (i + 1) / NPV);
             if (i == NPV - 3) mxb = max_part(1, 0, mxb);
             if (i == NPV - 2) mxb = max_part(1, 1, mxb);
-            if (i == NPV - 1) mxb = max_cross(mxb);
+            if (i == NPV - 1) mxb = att_max_cross(mxb);
             ATT_SB();
         }
         pack(0, 1);
@@ -1763,7 +1507,6 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
         if (kt + 1 < nt) tile(kt + 1, std::integral_constant<int, 1>{});
         if (kt + 2 < nt) tile(kt + 2, std::integral_constant<int, 2>{});
     }
-#undef ATT_SB
 
     // ---- O = O^T / l: row D of O^T lives in tile D / 32, register ((D % 32) & 3) + 4 ((D % 32) >> 3) of the half with 4 h == (D % 32) & 4
     constexpr int rr = D % 32, reg = (rr & 3) + 4 * (rr >> 3), owner_half = (rr >> 2) & 1;
@@ -1799,17 +1542,99 @@ static int att_launched(int kid) {
     return FGDM_OK;
 }
 
-template <int D, int NS>
-static int launch_cross_long(dim3 grid, const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
-                             int ldo, int H, int T, int Tk, float sl2e, int cpw, hipStream_t s) {
-    constexpr int smem = attn_cross_long_lds(D, NS);
-    static_assert(smem <= 160 * 1024, "does not fit the 160 KB of a CU");
-    constexpr auto k = attn_cross_long_kernel<D, NS>;
-    if (fgdm_dyn_lds<k>(smem) != FGDM_OK) return FGDM_ERR_HIP;
-    FGDM_LAUNCH(k, grid, dim3(256), smem, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw);
-    return att_launched(ATT_KID_CROSS_LONG);
+// ---- launch helpers.  AttnCall: what attention_launch was called with (sl2e: the factor the kernels multiply Q by)
+struct AttnCall {
+    const half_t* Q; int ldq;
+    const half_t* K; int ldk;
+    const half_t* Vt; int ldvt;
+    half_t* O; int ldo;
+    int B, H, T, Tk;
+    float sl2e;
+    hipStream_t s;
+};
+template <auto Kernel, class... Extra>
+static int att_launch(const AttnCall& c, dim3 grid, int threads, int lds, int kid, Extra... extra) {
+    FGDM_LAUNCH(Kernel, grid, dim3(threads), lds, c.s, c.Q, c.ldq, c.K, c.ldk, c.Vt, c.ldvt, c.O, c.ldo, c.H, c.T, c.Tk, c.sl2e, extra...);
+    return att_launched(kid);
+}
+// f(std::integral_constant<int, d>) for the head widths of the networks (320 ... 1280 channels over 8 heads)
+template <class F>
+static int by_head_width(int d, F&& f) {
+    switch (d) {
+        case 40: return f(std::integral_constant<int, 40>{});
+        case 80: return f(std::integral_constant<int, 80>{});
+        case 160: return f(std::integral_constant<int, 160>{});
+        default: return FGDM_ERR_ARG;
+    }
 }
 
+template <int D>
+static int launch_general(const AttnCall& c) {
+    return att_launch<attn_kernel<D>>(c, dim3(((c.T + 127) / 128) * c.H * c.B), 256, 0, ATT_KID_GENERAL);
+}
+template <int D>
+static int launch_pp(const AttnCall& c) {
+    return att_launch<attn_pp_kernel<D>>(c, dim3(((c.T + 255) / 256) * c.H * c.B), 512, 0, ATT_KID_PP);
+}
+
+// The two-strand kernels: whole 256-query blocks, whole 64-key tiles and at least two of them, and a tile's K / V^T byte offsets
+// (the 32-bit voffset of the LDS-DMA) below 2^31
+static bool two_strand_ok(const AttnCall& c, int d) {
+    return c.T % 256 == 0 && c.Tk % 64 == 0 && c.Tk >= 128 && (size_t)64 * c.ldk * 2 < (1u << 31) && (size_t)d * c.ldvt * 2 < (1u << 31);
+}
+template <auto Kernel>
+static int launch_two_strand(const AttnCall& c, int kid) {
+    return att_launch<Kernel>(c, dim3((c.T / 256) * c.H * c.B), 256, 0, kid);
+}
+// FGDM_ATTN_ABL (tools/bench_attention.py only; see ABL above): the d = 40 kernels with parts of their work removed
+template <int ABL>
+static int launch_ablation(const AttnCall& c, bool wide) {
+    return wide ? launch_two_strand<attn_dq32_kernel<40, 4, ABL>>(c, ATT_KID_DQ32) : launch_two_strand<attn_dq_kernel<40, 4, ABL>>(c, ATT_KID_DQ16);
+}
+static int launch_ablation_bits(const AttnCall& c, int abl, bool wide) {
+    switch (abl) {
+        case 1: return launch_ablation<1>(c, wide);
+        case 2: return launch_ablation<2>(c, wide);
+        case 3: return launch_ablation<3>(c, wide);
+        case 4: return launch_ablation<4>(c, wide);
+        case 7: return launch_ablation<7>(c, wide);
+        case 16: return launch_ablation<16>(c, wide);
+        case 32: return launch_ablation<32>(c, wide);
+        case 48: return launch_ablation<48>(c, wide);
+        case 51: return launch_ablation<51>(c, wide);
+        default: return FGDM_ERR_ARG;
+    }
+}
+
+// The key-resident text kernel with cpw query chunks per wave.  (d = 160, NS = 8) does not fit the 160 KB of a CU and is never built.
+template <int D, int NS>
+static int launch_cross(const AttnCall& c, int cpw) {
+    constexpr int lds = attn_cross_lds(D, NS), dyn = NS == 3 ? 0 : lds;      // NS = 3 keeps its LDS static
+    if constexpr (lds > 160 * 1024) {
+        return FGDM_ERR_ARG;
+    } else {
+        if ((c.Tk + 31) / 32 != NS || c.ldvt < NS * 32) return FGDM_ERR_ARG;      // the kernel's contract: it masks sub-tile NS - 1 only
+        constexpr auto k = attn_cross_kernel<D, NS>;
+        if (dyn && fgdm_dyn_lds<k>(dyn) != FGDM_OK) return FGDM_ERR_HIP;
+        const dim3 grid(((c.T + 128 * cpw - 1) / (128 * cpw)) * c.H * c.B);
+        return att_launch<k>(c, grid, 256, dyn, NS == 3 ? ATT_KID_CROSS : ATT_KID_CROSS_LONG, cpw);
+    }
+}
+template <int D>
+static int launch_cross_ns(const AttnCall& c, int ns, int cpw) {
+    switch (ns) {
+        case 3: return launch_cross<D, 3>(c, cpw);
+        case 4: return launch_cross<D, 4>(c, cpw);
+        case 5: return launch_cross<D, 5>(c, cpw);
+        case 6: return launch_cross<D, 6>(c, cpw);
+        case 7: return launch_cross<D, 7>(c, cpw);
+        case 8: return launch_cross<D, 8>(c, cpw);
+        default: return FGDM_ERR_ARG;
+    }
+}
+
+// The first condition that holds decides (tests/attention_dispatch.py states the same rules a second time); the knobs are read in
+// this order, each when its condition is reached.
 int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
                      int ldo, int B, int H, int T, int Tk, int d, int q_prescaled, hipStream_t s) {
     if (B <= 0 || H <= 0 || T <= 0 || Tk <= 0) return FGDM_ERR_ARG;
@@ -1817,83 +1642,32 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
     // q_prescaled: the to_q weights were packed with log2(e) d^-1/2 folded in (fgdm_finalize_weights), so Q arrives in the
     // log2 domain with ONE fp16 rounding; the kernels then multiply by exactly 1
     const float sl2e = q_prescaled ? 1.0f : 1.4426950408889634f / sqrtf((float)d);
-    // long self-attention: the eight-wave ping-pong kernel (256 queries per workgroup); FGDM_ATTN_PP=0 switches it off (A/B)
+    const AttnCall c{Q, ldq, K, ldk, Vt, ldvt, O, ldo, B, H, T, Tk, sl2e, s};
     const bool pp_on = knob_once(KNOB_ATTN_PP) != 0;
-    // ... and the two-strand kernels where their shape conditions hold.  FGDM_ATTN_DQ: 0 = off, 1 = 16-wide V^T P^T (the faster one
-    // on random operands: 756 vs 733 TF/s at B32 T4096), 3 = 32-wide V^T P^T (default: the faster one inside the network, where the
-    // activations toggle less and the chip holds its clock: attention family 357 vs 362 ms per sampling pass, 421 before)
+    // long self-attention, d = 40: the two-strand kernels.  FGDM_ATTN_DQ: 0 = off, 1 = 16-wide V^T P^T (the faster one on random
+    // operands), anything else = 32-wide (default 3: the faster one inside the network).  Under FGDM_ATTN_ABL the
+    // ablated 32-wide kernel is taken at FGDM_ATTN_DQ=3 only, the ablated 16-wide one otherwise
     const int dq = knob_once(KNOB_ATTN_DQ);
-    if (dq > 0 && d == 40 && T % 256 == 0 && Tk % 64 == 0 && Tk >= 128 && (size_t)64 * ldk * 2 < (1u << 31) &&
-        (size_t)d * ldvt * 2 < (1u << 31)) {
-        const dim3 gridq((T / 256) * H * B), blockq(256);
-        const int abl = knob_once(KNOB_ATTN_ABL);    // tools/bench_attention.py only
-        if (abl) {
-            switch (abl + (dq == 3 ? 1000 : 0)) {
-#define ATT_ABL_CASE(v) case v: FGDM_LAUNCH((attn_dq_kernel<40, 4, v>), gridq, blockq, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e); break; \
-                        case 1000 + v: FGDM_LAUNCH((attn_dq32_kernel<40, 4, v>), gridq, blockq, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e); break;
-                ATT_ABL_CASE(1) ATT_ABL_CASE(2) ATT_ABL_CASE(3) ATT_ABL_CASE(4) ATT_ABL_CASE(16) ATT_ABL_CASE(32) ATT_ABL_CASE(48) ATT_ABL_CASE(51) ATT_ABL_CASE(7)
-#undef ATT_ABL_CASE
-                default: return FGDM_ERR_ARG;
-            }
-            return att_launched(dq == 3 ? ATT_KID_DQ32 : ATT_KID_DQ16);
-        }
-        if (dq == 1) FGDM_LAUNCH((attn_dq_kernel<40, 4>), gridq, blockq, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
-        else FGDM_LAUNCH((attn_dq32_kernel<40, 4>), gridq, blockq, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
-        return att_launched(dq == 1 ? ATT_KID_DQ16 : ATT_KID_DQ32);
+    if (dq > 0 && d == 40 && two_strand_ok(c, d)) {
+        if (const int abl = knob_once(KNOB_ATTN_ABL)) return launch_ablation_bits(c, abl, dq == 3);
+        return dq == 1 ? launch_two_strand<attn_dq_kernel<40, 4>>(c, ATT_KID_DQ16) : launch_two_strand<attn_dq32_kernel<40, 4>>(c, ATT_KID_DQ32);
     }
-    // d = 80: the same kernel at one wave per SIMD (its two strands need ~280 registers); FGDM_ATTN_DQ80=0: the ping-pong kernel
+    // d = 80: the 32-wide kernel at one wave per SIMD (its two strands need ~280 registers); FGDM_ATTN_DQ80=0 switches it off (A/B)
     const int dq80 = knob_once(KNOB_ATTN_DQ80);
-    if (dq80 > 0 && d == 80 && T % 256 == 0 && Tk % 64 == 0 && Tk >= 128 && (size_t)64 * ldk * 2 < (1u << 31) &&
-        (size_t)d * ldvt * 2 < (1u << 31)) {
-        const dim3 gridq((T / 256) * H * B), blockq(256);
-        FGDM_LAUNCH((attn_dq32_kernel<80, 4>), gridq, blockq, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
-        return att_launched(ATT_KID_DQ32);
-    }
-    if (pp_on && T >= 256 && Tk >= 256 && (d == 40 || d == 80)) {
-        const dim3 grid2(((T + 255) / 256) * H * B), block2(512);
-        if (d == 40) FGDM_LAUNCH(attn_pp_kernel<40>, grid2, block2, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
-        else FGDM_LAUNCH(attn_pp_kernel<80>, grid2, block2, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e);
-        return att_launched(ATT_KID_PP);
-    }
-    // the text tokens: all keys staged once per workgroup, several query chunks per wave; FGDM_ATTN_CROSS=0 switches it off (A/B)
+    if (dq80 > 0 && d == 80 && two_strand_ok(c, d)) return launch_two_strand<attn_dq32_kernel<80, 4>>(c, ATT_KID_DQ32);
+    // every other long shape at d = 40 / 80: the eight-wave ping-pong kernel (256 queries per workgroup); FGDM_ATTN_PP=0 switches it off (A/B)
+    if (pp_on && T >= 256 && Tk >= 256 && (d == 40 || d == 80)) return d == 40 ? launch_pp<40>(c) : launch_pp<80>(c);
+    // one text part (64 < Tk <= 96, NS = 3): the key-resident kernel.  FGDM_ATTN_CROSS: query chunks per wave, 0 = off (A/B)
     const int cross = knob_once(KNOB_ATTN_CROSS);
-    if (cross > 0 && Tk > 64 && Tk <= 96 && ldvt >= 96 && T >= 128) {
-        const int cpw = std::min(cross, T / 128);
-        const dim3 gridc(((T + 128 * cpw - 1) / (128 * cpw)) * H * B), blockc(256);
-        switch (d) {
-            case 40: FGDM_LAUNCH(attn_cross_kernel<40>, gridc, blockc, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw); break;
-            case 80: FGDM_LAUNCH(attn_cross_kernel<80>, gridc, blockc, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw); break;
-            case 160: FGDM_LAUNCH(attn_cross_kernel<160>, gridc, blockc, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw); break;
-            default: return FGDM_ERR_ARG;
-        }
-        return att_launched(ATT_KID_CROSS);
-    }
-    // two or three text parts (96 < Tk <= 256): the key-resident kernel with NS = ceil(Tk / 32) sub-tiles, so that only the last one
-    // can hold a key >= Tk and NS * 32 <= ldvt.  FGDM_ATTN_CROSS_LONG: query chunks per wave, 0 = the general kernel (A/B).  Default 8:
-    // staging 154 - 256 keys costs as much traffic as the Q + O rows of 4 chunks, and at T = 1024 eight chunks make one workgroup
-    // per (batch, head) (measured: profiles/long_context_attention.txt; 4 chunks do not beat attn_kernel at d = 80)
-    const int cross_long = knob_once(KNOB_ATTN_CROSS_LONG);
-    if (cross_long > 0 && Tk > 96 && Tk <= 256 && T >= 128) {
-        const int ns = (Tk + 31) / 32;
-        if (ldvt >= ns * 32 && (d == 40 || d == 80 || (d == 160 && ns <= 7))) {
-            const int cpw = std::min(cross_long, T / 128);
-            const dim3 gridc(((T + 128 * cpw - 1) / (128 * cpw)) * H * B);
-#define ATT_XL(DD, NN) case NN: return launch_cross_long<DD, NN>(gridc, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e, cpw, s);
-            switch (d) {
-                case 40: switch (ns) { ATT_XL(40, 4) ATT_XL(40, 5) ATT_XL(40, 6) ATT_XL(40, 7) ATT_XL(40, 8) } break;
-                case 80: switch (ns) { ATT_XL(80, 4) ATT_XL(80, 5) ATT_XL(80, 6) ATT_XL(80, 7) ATT_XL(80, 8) } break;
-                case 160: switch (ns) { ATT_XL(160, 4) ATT_XL(160, 5) ATT_XL(160, 6) ATT_XL(160, 7) } break;
-            }
-#undef ATT_XL
-            return FGDM_ERR_ARG;
-        }
-    }
-    const dim3 grid(((T + 127) / 128) * H * B), block(256);
-    switch (d) {
-        case 40: FGDM_LAUNCH(attn_kernel<40>, grid, block, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e); break;
-        case 80: FGDM_LAUNCH(attn_kernel<80>, grid, block, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e); break;
-        case 160: FGDM_LAUNCH(attn_kernel<160>, grid, block, 0, s, Q, ldq, K, ldk, Vt, ldvt, O, ldo, H, T, Tk, sl2e); break;
-        default: return FGDM_ERR_ARG;
-    }
-    return att_launched(ATT_KID_GENERAL);
+    if (cross > 0 && Tk > 64 && Tk <= 96 && ldvt >= 96 && T >= 128)
+        return by_head_width(d, [&](auto dc) { return launch_cross<decltype(dc)::value, 3>(c, std::min(cross, T / 128)); });
+    // two or three text parts (96 < Tk <= 256): the same kernel with NS = ceil(Tk / 32) sub-tiles where NS * 32 <= ldvt and the LDS
+    // fits.  FGDM_ATTN_CROSS_LONG: query chunks per wave, 0 = off (A/B).  Default 8: staging 154 - 256 keys costs as much traffic as
+    // the Q + O rows of 4 chunks, and at T = 1024 eight chunks make one workgroup per (batch, head) (measured:
+    // profiles/long_context_attention.txt; 4 chunks do not beat attn_kernel at d = 80)
+    const int cross_long = knob_once(KNOB_ATTN_CROSS_LONG), ns = (Tk + 31) / 32;
+    if (cross_long > 0 && Tk > 96 && Tk <= 256 && T >= 128 && ldvt >= ns * 32 && (d == 40 || d == 80 || (d == 160 && ns <= 7)))
+        return by_head_width(d, [&](auto dc) { return launch_cross_ns<decltype(dc)::value>(c, ns, std::min(cross_long, T / 128)); });
+    // everything else: the general kernel
+    return by_head_width(d, [&](auto dc) { return launch_general<decltype(dc)::value>(c); });
 }

@@ -316,7 +316,7 @@ int fgdm_op_attention(const void* q, int ldq, const void* k, int ldk, const void
  * fgdm_op_attention_ex: fgdm_op_attention with the engine's q_prescaled flag passed through.  q_prescaled = 1: Q already carries
  * log2(e) d^-1/2 (the engine folds it into the to_q weights), so O = softmax(ln 2 * Q K^T) V and the kernels scale by exactly 1.
  * fgdm_debug_last_attention_kernel: which kernel the dispatch chose on the last successful attention call of this process:
- * 0 none yet, 1 general (attn_kernel), 2 text-token (attn_cross_kernel), 3 long-text (attn_cross_long_kernel), 4 ping-pong
+ * 0 none yet, 1 general (attn_kernel), 2 text-token (attn_cross_kernel<D, 3>), 3 long-text (attn_cross_kernel<D, 4 ... 8>), 4 ping-pong
  * (attn_pp_kernel), 5 two-strand 16-wide (attn_dq_kernel), 6 two-strand 32-wide (attn_dq32_kernel).
  * fgdm_op_small_attention: the text encoder's attention, softmax(q k^T d^-1/2 (j <= i when causal)) v with q | k | v as column
  * blocks of one fp16 [B T, ld] matrix (q at column 0, k at koff, v at voff; head h at columns [64 h, 64 h + 64) of its block),

@@ -36,10 +36,10 @@ def expected_kernel(T, Tk, d, env=None):
     # every other long shape at d = 40 / 80: the eight-wave ping-pong kernel
     if pp and T >= 256 and Tk >= 256 and d in (40, 80):
         return PING_PONG
-    # one text part (65 - 96 keys) against at least one 128-query chunk
+    # one text part (65 - 96 keys) against at least one 128-query chunk: the key-resident kernel with three 32-key sub-tiles
     if cross > 0 and 64 < Tk <= 96 and T >= 128:
         return TEXT_TOKEN
-    # two or three text parts (97 - 256 keys): key-resident with ceil(Tk / 32) sub-tiles; d = 160 fits seven of them
+    # two or three text parts (97 - 256 keys): the same kernel with ceil(Tk / 32) sub-tiles; d = 160 fits seven of them
     if cross_long > 0 and 96 < Tk <= 256 and T >= 128:
         ns = (Tk + 31) // 32
         if d in (40, 80) or (d == 160 and ns <= 7):

@@ -1,6 +1,6 @@
 """The attention kernels under the call the ENGINE makes, not only under the shapes it makes it with.
 
-tests/test_gpu_ops.py and tests/test_gpu_long_context.py cover the shapes of the six kernels of fgdm_amd/csrc/attention.hip with
+tests/test_gpu_ops.py and tests/test_gpu_long_context.py cover the shapes of the five kernels of fgdm_amd/csrc/attention.hip with
 compact buffers (ldq == ldk == ldo == heads * d), the unscaled-Q mode and unit-normal operands.  The engine calls them with Q and K
 as column halves of one [B T, 2 C] buffer (ldq = ldk = 2 C, ldo = C), with Q already in the log2 domain (q_prescaled = 1: the
 kernels scale by exactly 1) and with whatever logits the network produces.  Here:
@@ -62,10 +62,10 @@ KERNEL_CASES = [
     _c(AD.GENERAL, 2, 2, 64, 64, 40), _c(AD.GENERAL, 2, 2, 100, 333, 40), _c(AD.GENERAL, 2, 3, 100, 130, 80),
     _c(AD.GENERAL, 2, 2, 192, 64, 80), _c(AD.GENERAL, 2, 2, 256, 256, 160), _c(AD.GENERAL, 2, 3, 200, 321, 160),
     _c(AD.GENERAL, 2, 2, 300, 250, 160),
-    # text-token attn_cross_kernel (64 < Tk <= 96, T >= 128): one and several chunks per wave, ragged T, both key-count limits
+    # text-token attn_cross_kernel<D, 3> (64 < Tk <= 96, T >= 128): one and several chunks per wave, ragged T, both key-count limits
     _c(AD.TEXT_TOKEN, 2, 2, 128, 77, 40), _c(AD.TEXT_TOKEN, 2, 3, 700, 65, 40), _c(AD.TEXT_TOKEN, 2, 2, 1024, 77, 80),
     _c(AD.TEXT_TOKEN, 3, 2, 130, 96, 80), _c(AD.TEXT_TOKEN, 2, 2, 512, 77, 160), _c(AD.TEXT_TOKEN, 2, 2, 700, 96, 160),
-    # long-text attn_cross_long_kernel (96 < Tk <= 256, T >= 128): NS = ceil(Tk / 32) = 4 ... 8 (d = 160: 4 ... 7)
+    # long-text attn_cross_kernel<D, NS> (96 < Tk <= 256, T >= 128): NS = ceil(Tk / 32) = 4 ... 8 (d = 160: 4 ... 7)
     _c(AD.LONG_TEXT, 2, 2, 128, 97, 40), _c(AD.LONG_TEXT, 2, 2, 700, 129, 40), _c(AD.LONG_TEXT, 2, 3, 1024, 161, 40),
     _c(AD.LONG_TEXT, 2, 2, 300, 200, 40), _c(AD.LONG_TEXT, 2, 2, 130, 231, 40),
     _c(AD.LONG_TEXT, 2, 2, 700, 128, 80), _c(AD.LONG_TEXT, 2, 2, 128, 154, 80), _c(AD.LONG_TEXT, 2, 2, 300, 192, 80),
