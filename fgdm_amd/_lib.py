@@ -104,6 +104,7 @@ SIGNATURES = {
     'fgdm_op_transpose_pad': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgdm_op_timestep_embed': (_i, [_p, _p, _p, _i, _i, _i, _p]),
     'fgdm_op_add_f16': (_i, [_p, _p, _p, _i64, _p]),
+    'fgdm_op_ln_qkv': (_i, [_p] * 6 + [_i] * 5 + [_p, _p, _p]),
 }
 
 _lib = None

@@ -179,6 +179,45 @@ int fgdm_op_linear_ln_linear(const void* x, const float* w1, const float* b1, co
     return rc;
 }
 
+// Diagnostic entry of tests/test_gpu_qkv_projection.py; the product path does not call it.
+// to_q | to_k | to_v of a self-attention (attention.py:180-186, no bias) as the ONE GEMM Engine::attn_fwd launches: the stacked
+// [3C, C] weight over the raw tokens h with norm1 folded in (fold: statistics from row_stats_launch, gamma in the weight, beta W
+// in the bias), packed columns [0, 2C) row-major to qk [B T, 2C], [2C, 3C) transposed to vt [B, C, Tp].  vt is not cleared.
+int fgdm_op_ln_qkv(const void* h, const float* gamma, const float* beta, const float* wq, const float* wk, const float* wv,
+                   int B, int T, int C, int Tp, int fold, void* qk, void* vt, void* stream) {
+    if (!h || !wq || !wk || !wv || !qk || !vt) return FGDM_ERR_ARG;
+    if (B <= 0 || T <= 0 || C <= 0 || (C % 320) || Tp < T || (Tp & 7)) return FGDM_ERR_ARG;
+    if (fold ? (!gamma || !beta) : (gamma || beta)) return FGDM_ERR_ARG;
+    if ((long long)B * T > 0x7fffffffLL / (3 * C)) return FGDM_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    const int M = B * T, N = 3 * C;
+    const size_t cc = (size_t)C * C;
+    std::vector<float> w(3 * cc);
+    const float* src[3] = {wq, wk, wv};
+    for (int i = 0; i < 3; ++i)
+        if (hipMemcpy(&w[i * cc], src[i], cc * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
+    TmpDev tmp;
+    IgemmArgs a{};
+    int rc = op_pack(a, tmp, w.data(), nullptr, N, C, C, false, nullptr, fold ? gamma : nullptr, fold ? beta : nullptr);
+    if (rc != FGDM_OK) return rc;
+    a.A0 = (const half_t*)h; a.C0 = C; a.zero = g_zero_page();
+    if (!a.zero) return FGDM_ERR_NOMEM;
+    a.B = B; a.H = 1; a.W = T; a.Ho = 1; a.Wo = T; a.M = M; a.N = N; a.K = C; a.mode = IG_LINEAR; a.act = ACT_NONE;
+    a.out_kind = OUT_F16; a.out = qk; a.ld_out = 2 * C; a.rows_per_sample = T; a.scale = 1.f;
+    a.out2 = vt; a.out_kind2 = OUT_F16_T; a.ld_out2 = Tp; a.split_n = 2 * C;
+    if (fold) {
+        const int slots = row_stats_slots(C);
+        float* stats = tmp.alloc<float>((size_t)M * slots * 2);
+        if (!stats) return FGDM_ERR_NOMEM;
+        rc = row_stats_launch((const half_t*)h, M, C, stats, s);
+        if (rc != FGDM_OK) { (void)hipStreamSynchronize(s); return rc; }
+        a.ln_stats = stats; a.ln_slots = slots; a.ln_eps = 1e-5f;
+    }
+    rc = igemm_launch(a, s);
+    (void)hipStreamSynchronize(s);   // temporaries are freed on return
+    return rc;
+}
+
 int fgdm_debug_force_igemm_cfg(int cfg) { igemm_set_force_cfg(cfg); return FGDM_OK; }
 
 int fgdm_op_groupnorm(const void* x0, int C0, const void* x1, int C1, int B, int HW, const float* gamma, const float* beta,

@@ -366,6 +366,28 @@ int fgdm_op_transpose_pad(const void* v, void* vt, int B, int Tk, int C, int Tkp
 int fgdm_op_timestep_embed(const int64_t* t, const float* t_float, void* y, int B, int dim, int rows_pad, void* stream);
 int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream);
 
+/* Diagnostic entry (tests/test_gpu_qkv_projection.py); the product path does not call it.
+ *
+ * fgdm_op_ln_qkv: to_q | to_k | to_v of a self-attention (ldm/modules/attention.py:180-186: three Linear(C, C, bias=False)) behind
+ * norm1 (attention.py:238), as the ONE GEMM the engine launches for them (Engine::attn_fwd): the stacked weight [3C, C] over the
+ * tokens h with two destinations -- packed columns [0, 2C) row-major to qk, columns [2C, 3C) TRANSPOSED to vt (IgemmArgs::out2,
+ * out_kind2 = OUT_F16_T, ld_out2 = Tp, split_n = 2C, rows_per_sample = T, M = B T, N = 3C, K = C, no activation, scale 1) -- through
+ * igemm_launch, so the automatic tile choice and fgdm_debug_force_igemm_cfg both apply.
+ *   h fp16 [B T, C];  wq / wk / wv fp32 [C, C] in the reference's [out, in] layout (host or device), no bias;
+ *   qk fp16 [B T, 2C] (q at columns [0, C), k at [C, 2C));  vt fp16 [B, C, Tp], tokens contiguous.
+ * fold = 1: h holds the RAW tokens and LayerNorm(gamma, beta fp32 [C], eps 1e-5) is folded into the GEMM as in
+ *   fgdm_op_linear_ln_linear's consumer: weight fp16(gamma_k w_nk), the bias carries beta W, the per-row partial sums of h come
+ *   from the separate row-statistics pass (C / 160 slots) and (mean, rstd) are applied to the fp32 accumulator of BOTH destinations.
+ * fold = 0: gamma and beta must be NULL, h is taken as already normalised (the FGDM_LN_FOLD=0 engine) and the weights are packed
+ *   plain.
+ * The entry does NOT clear vt: the columns [T, Tp) of every V^T row are the caller's (the engine zeroes them once; the GEMM writes
+ * around them) and are left untouched.  FGDM_ERR_ARG before any launch for a NULL h / wq / wk / wv / qk / vt; B, T or C <= 0;
+ * C % 320 != 0 (split_n = 2C must be a multiple of 640, the launcher's rule); Tp < T; Tp % 8 != 0; gamma / beta not matching
+ * `fold`; B T 3C beyond 2^31 - 1.  A forced tile the launcher refuses for the shape (e.g. 256 x 256 tiles when 3C % 256 != 0) is
+ * FGDM_ERR_ARG as well, with qk and vt untouched. */
+int fgdm_op_ln_qkv(const void* h, const float* gamma, const float* beta, const float* wq, const float* wk, const float* wv,
+                   int B, int T, int C, int Tp, int fold, void* qk, void* vt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -587,6 +587,41 @@ def test_linear_f32_nchw_output(lib, N):
         lib.fgdm_debug_force_igemm_cfg(0)
 
 
+@pytest.mark.parametrize('N', [320, 1280])
+def test_linear_f16_transposed_output_on_pipelined_tiles(lib, N):
+    """out_kind 3 (OUT_F16_T) as the FIRST destination at real batch sizes: the cross-attention to_v over the text context
+    (Engine::cross_kv, rows_per_sample = 77) and the first-stage AttnBlock's v leave the GEMM as fp16 [B][N][ld], ld =
+    roundup(rows_per_sample, 64), by the pipelined kernel's direct 2-byte stores (PATH 0, phase-locked K loop) once the batch is
+    large enough for its tiles.  Ragged sample lengths whose boundaries fall inside row tiles (77), the 2-stage kernel's vector path
+    (100) and a length with no pad column (64); automatic tile, the 2-stage kernel, 256x320 / 128x320 / 64x160 tiles, 128x320 on the
+    phase-locked loop by request and, where N % 256 == 0, 256x256.  float64 reference; the pad columns stay untouched; every
+    configuration gives the same bits."""
+    K = 320
+    w, b = h16(rnd((N, K), 95, 1 / np.sqrt(K))), rnd((N,), 96, 0.1)
+    wd, bd = w.cuda(), b.cuda()
+    cfgs = (0, 1, 4, 6, 11, 6 + 16) + ((5,) if N == 1280 else ())
+    try:
+        for rps, Bt in ((77, 5), (100, 3), (64, 5)):
+            Mt = rps * Bt
+            ld = (rps + 63) // 64 * 64
+            x = h16(rnd((Mt, K), 97))
+            xd = din(x.half())
+            want = F.linear(x.double(), w.double(), b.double()).view(Bt, rps, N).permute(0, 2, 1).reshape(-1, rps).cuda()
+            outs = {}
+            for cfg in cfgs:
+                lib.fgdm_debug_force_igemm_cfg(cfg)
+                outT = guarded_out((Bt, N, ld), torch.half)
+                assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), None, Mt, K, N, 0, 3, rps, ld, _p(outT.t), _st()) == 0, (cfg, rps)
+                torch.cuda.synchronize()
+                check_transposed(outT, rps, ld)
+                close(f'linear V^T first destination N{N} rps {rps} cfg {cfg}', outT.t[:, :, :rps].reshape(-1, rps), want)
+                outs[cfg] = outT.t[:, :, :rps]
+            for cfg in cfgs[1:]:
+                assert torch.equal(outs[0], outs[cfg]), f'N{N} rps {rps}: automatic tile and cfg {cfg} differ'
+    finally:
+        lib.fgdm_debug_force_igemm_cfg(0)
+
+
 @pytest.mark.parametrize('M', [154, 201])
 def test_linear_quick_gelu(lib, M):
     """act 4, x sigmoid(1.702 x): the CLIP MLP's first projection (768 -> 3072, M = 2 x 77 tokens, and a ragged M); only the

@@ -140,6 +140,57 @@ def test_narrow_op_entries_refuse_bad_arguments(lib):
     assert lib.fgdm_op_add_f16(p, p, p, 0, null) < 0
 
 
+def test_ln_qkv_entry_refuses_bad_arguments(lib):
+    """fgdm_op_ln_qkv (tests/test_gpu_qkv_projection.py) returns FGDM_ERR_ARG before any launch or copy for every refusal
+    include/fgdm.h lists (so without a GPU too): the pointers below are never dereferenced."""
+    import ctypes as C
+    p, null = C.c_void_p(1 << 20), None
+    ERR_ARG = -1
+
+    def call(h=p, gamma=p, beta=p, wq=p, wk=p, wv=p, B=2, T=64, Cc=320, Tp=64, fold=1, qk=p, vt=p):
+        return lib.fgdm_op_ln_qkv(h, gamma, beta, wq, wk, wv, B, T, Cc, Tp, fold, qk, vt, null)
+
+    for name in ('h', 'wq', 'wk', 'wv', 'qk', 'vt'):
+        assert call(**{name: null}) == ERR_ARG, name
+    for name in ('B', 'T', 'Cc'):
+        for bad in (0, -1):
+            assert call(**{name: bad}) == ERR_ARG, (name, bad)
+    for bad in (64, 160, 256, 321, 960 + 64):            # C % 320 != 0
+        assert call(Cc=bad) == ERR_ARG, bad
+    assert call(T=100, Tp=96) == ERR_ARG                 # Tp < T
+    assert call(T=64, Tp=63) == ERR_ARG
+    assert call(T=100, Tp=100) == ERR_ARG                # Tp % 8 != 0
+    assert call(T=25, Tp=28) == ERR_ARG
+    # gamma / beta must match `fold`
+    assert call(fold=1, gamma=null) == ERR_ARG and call(fold=1, beta=null) == ERR_ARG
+    assert call(fold=1, gamma=null, beta=null) == ERR_ARG
+    assert call(fold=0) == ERR_ARG and call(fold=0, gamma=null) == ERR_ARG and call(fold=0, beta=null) == ERR_ARG
+    assert call(B=1 << 20, T=1 << 10, Cc=1280) == ERR_ARG          # B T 3C does not fit an int
+
+
+C_TO_CTYPES = {'const void*': 'c_void_p', 'void*': 'c_void_p', 'const float*': 'c_void_p', 'int': 'c_int'}
+
+
+def test_ln_qkv_header_and_binding_agree():
+    """The declaration of fgdm_op_ln_qkv in include/fgdm.h and its ctypes signature in fgdm_amd/_lib.py: the same argument
+    count and, argument by argument, the same kinds (every pointer a c_void_p, every int a c_int), int result; the header
+    states the contract next to the other diagnostic entries."""
+    hdr = open(os.path.join(ROOT, 'include', 'fgdm.h')).read()
+    m = re.search(r'\bint\s+fgdm_op_ln_qkv\s*\(([^)]*)\)\s*;', hdr)
+    assert m, 'fgdm_op_ln_qkv is not declared'
+    args = [re.sub(r'\s+', ' ', a).strip() for a in m.group(1).split(',')]
+    names = [a.split(' ')[-1] for a in args]
+    assert names == ['h', 'gamma', 'beta', 'wq', 'wk', 'wv', 'B', 'T', 'C', 'Tp', 'fold', 'qk', 'vt', 'stream'], names
+    kinds = [C_TO_CTYPES[a.rsplit(' ', 1)[0]] for a in args]
+    res, argtypes = _lib.SIGNATURES['fgdm_op_ln_qkv']
+    assert res.__name__ == 'c_int'
+    assert [t.__name__ for t in argtypes] == kinds
+    doc = re.sub(r'(\s|\*)+', ' ', hdr[hdr.rindex('/*', 0, m.start()):m.start()])       # the comment in front, as one line
+    assert 'the product path does not call it' in doc
+    for word in ('OUT_F16_T', 'split_n = 2C', 'does NOT clear vt', 'C % 320', 'Tp % 8', 'Tp < T', 'attention.py:180-186'):
+        assert word in doc, word
+
+
 CSRC = os.path.join(ROOT, 'fgdm_amd', 'csrc')
 
 
