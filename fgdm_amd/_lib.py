@@ -52,6 +52,7 @@ SIGNATURES = {
     'fgdm_load_tensor': (_i, [_p, C.c_char_p, _p, _i, C.POINTER(_i64), _i]),
     'fgdm_finalize_weights': (_i, [_p]),
     'fgdm_set_hint': (_i, [_p, _i, _p, _i, _i, _i, _p]),
+    'fgdm_set_concat': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgdm_set_adapter_conds': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgdm_set_context': (_i, [_p, _p, _i, _p]),
     'fgdm_apply_model': (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
@@ -100,6 +101,7 @@ SIGNATURES = {
     'fgdm_op_softmax_rows': (_i, [_p, _p, _i, _i, _p]),
     'fgdm_op_nchw_to_nhwc': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgdm_op_nhwc_to_nchw': (_i, [_p, _p, _i, _i, _i, _p]),
+    'fgdm_op_pack_xcat': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     'fgdm_op_avgpool2': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgdm_op_transpose_pad': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgdm_op_timestep_embed': (_i, [_p, _p, _p, _i, _i, _i, _p]),

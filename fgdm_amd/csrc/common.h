@@ -143,6 +143,8 @@ int attention_last_kernel();      // AttnKernelId (attention.hip) of the last su
 
 // ---------------------------------------------------------------- elementwise
 int nchw_f32_to_nhwc_f16(const float* x, half_t* y, int B, int C, int HW, int Cpad, hipStream_t s);
+// y [B, HW, Cpad] = x [B, 4, HW] fp32 | cc [Bc, HW, Cc] fp16 (row b % Bc; Bc = B or B / 2) | zeros; Cpad % 4 == 0, >= 4 + Cc
+int pack_xcat(const float* x, const half_t* cc, half_t* y, int B, int Bc, int Cc, int HW, int Cpad, hipStream_t s);
 int f32_to_f16(const float* x, half_t* y, size_t n, hipStream_t s);
 int silu_f32_to_f16(const float* x, half_t* y, size_t n, hipStream_t s);
 int nhwc_f16_to_nchw_f32(const half_t* x, float* y, int B, int C, int HW, hipStream_t s);

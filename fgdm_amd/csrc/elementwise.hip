@@ -26,6 +26,43 @@ int nchw_f32_to_nhwc_f16(const float* x, half_t* y, int B, int C, int HW, int Cp
     return LAUNCH_OK();
 }
 
+// First-layer input of a UNet fed cat([x] + c_concat, 1) (DiffusionWrapper 'hybrid', ldm/models/diffusion/ddpm.py:1838-1841):
+// x [B, 4, HW] fp32 | cc [Bc, HW, Cc] fp16 (the engine's cached c_concat)  ->  y [B, HW, Cpad] fp16: channels [0, 4) from x (rounded
+// as k_nchw_to_nhwc rounds), [4, 4 + Cc) from row b % Bc of cc (Bc = B, or B / 2: both halves of a CFG batch share a row),
+// [4 + Cc, Cpad) zero.  One thread per pixel row: the x loads of a wave are contiguous per channel; G halves per store
+// (G = 8 when Cpad % 8 == 0, else 4).
+template <int G>
+__global__ void k_pack_xcat(const float* __restrict__ x, const half_t* __restrict__ cc, half_t* __restrict__ y, int B, int Bc,
+                            int Cc, int HW, int Cpad) {
+    typedef half_t vec_t __attribute__((ext_vector_type(G)));
+    const size_t n = (size_t)B * HW;
+    EW_LOOP(i, n) {
+        const size_t b = i / HW, p = i - b * HW;
+        const float* xr = x + b * 4 * HW + p;
+        const half_t* cr = cc + ((b % Bc) * HW + p) * Cc;
+        half_t* yr = y + i * Cpad;
+        for (int c0 = 0; c0 < Cpad; c0 += G) {
+            vec_t v;
+#pragma unroll
+            for (int e = 0; e < G; ++e) {
+                const int c = c0 + e;
+                v[e] = c < 4 ? (half_t)xr[(size_t)c * HW] : (c < 4 + Cc ? cr[c - 4] : (half_t)0);
+            }
+            *(vec_t*)(yr + c0) = v;
+        }
+    }
+}
+int pack_xcat(const float* x, const half_t* cc, half_t* y, int B, int Bc, int Cc, int HW, int Cpad, hipStream_t s) {
+    if (B <= 0 || Bc <= 0 || Cc <= 0 || HW <= 0 || Cpad < 4 + Cc || (Cpad & 3) || !(Bc == B || (B % 2 == 0 && Bc == B / 2)))
+        return FGDM_ERR_ARG;
+    if ((Cpad & 7) == 0) {
+        FGDM_LAUNCH(k_pack_xcat<8>, dim3(ew_grid((size_t)B * HW)), dim3(EW_BLOCK), 0, s, x, cc, y, B, Bc, Cc, HW, Cpad);
+    } else {
+        FGDM_LAUNCH(k_pack_xcat<4>, dim3(ew_grid((size_t)B * HW)), dim3(EW_BLOCK), 0, s, x, cc, y, B, Bc, Cc, HW, Cpad);
+    }
+    return LAUNCH_OK();
+}
+
 __global__ void k_f32_to_f16(const float* __restrict__ x, half_t* __restrict__ y, size_t n) {
     EW_LOOP(i, n) y[i] = (half_t)x[i];
 }

@@ -301,6 +301,9 @@ struct fgdm_engine {
     std::unordered_map<const Layer*, CtxKV> ctx_cache;
     int ctx_B = 0, ctx_T = 0;
     int ctx_tokens = 77;                 // tokens behind every ctx / cond / uncond pointer (fgdm_set_context_tokens); 77 = one CLIP chunk
+    // c_concat of a UNet fed cat([x] + c_concat, 1) (in_channels > 4; fgdm_set_concat): loop-invariant, kept as fp16 NHWC
+    // [Bc, H W, in_channels - 4] (persistent hipMalloc, like a ControlNet's cached hint)
+    Tensor ccat;
     Arena arena;
     half_t* zero = nullptr;
     // packed weights in HBM, per component (state-dict prefix): re-packing a component frees its previous copy
@@ -610,8 +613,15 @@ struct fgdm_engine {
     int build() {
         if (cfg.n_levels < 1 || cfg.n_levels > FGDM_MAX_LEVELS || cfg.model_channels <= 0 || (cfg.model_channels & 63) ||
             cfg.num_heads <= 0 || cfg.n_controlnets < 0 || cfg.n_controlnets > FGDM_MAX_CONTROLNETS ||
-            (cfg.context_dim & 63) || cfg.in_channels != 4)
-            return fail(FGDM_ERR_ARG, "unsupported config (model_channels and context_dim must be multiples of 64, in_channels 4)");
+            (cfg.context_dim & 63) || cfg.in_channels < 4 || cfg.in_channels > 32)
+            return fail(FGDM_ERR_ARG, "unsupported config (model_channels and context_dim must be multiples of 64, 4 <= in_channels <= 32)");
+        // in_channels > 4: the UNet reads cat([x] + c_concat, 1) (DiffusionWrapper 'hybrid', ddpm.py:1838-1841)
+        if (cfg.in_channels != 4 && cfg.use_adapter)
+            return fail(FGDM_ERR_ARG, "in_channels != 4 with use_adapter: UNetModel.forward hands the concatenated input to an adapter built "
+                                      "for 4 channels (openaimodel.py:836-844); build the plain UNet (use_adapter = 0)");
+        if (cfg.in_channels != 4 && cfg.n_controlnets > 0)
+            return fail(FGDM_ERR_ARG, "in_channels != 4 with ControlNets: ControlLDM.apply_model never goes through DiffusionWrapper, its "
+                                      "c_concat is the hint (cldm.py:836-849)");
         for (int l = 0; l < cfg.n_levels; ++l) {
             const int ch = cfg.model_channels * cfg.channel_mult[l];
             if (ch % cfg.num_heads) return fail(FGDM_ERR_ARG, "channels not divisible by heads");
@@ -1726,11 +1736,23 @@ struct fgdm_engine {
         if (B <= 0 || H <= 0 || W <= 0) return fail(FGDM_ERR_ARG, "bad shape");
         Net& n = unet;
         const int HW = H * W;
-        Tensor x4 = talloc(B, H, W, 4), ctx16;
+        const int Cc = cfg.in_channels - 4;     // > 0: the first layer reads x | the c_concat cached by fgdm_set_concat
+        if (Cc > 0) {
+            if (!ccat.p) return fail(FGDM_ERR_STATE, "in_channels > 4 but no c_concat was registered (fgdm_set_concat)");
+            if (!(ccat.B == B || (B % 2 == 0 && 2 * ccat.B == B)))
+                return fail(FGDM_ERR_STATE, "the registered c_concat has " + std::to_string(ccat.B) + " rows: the batch must have as many, or twice as many");
+            if (ccat.H != H || ccat.W != W) return fail(FGDM_ERR_STATE, "the registered c_concat has another latent size than x");
+        }
+        Tensor x4 = talloc(B, H, W, Cc > 0 ? n.input[0][0].conv.cin_pad : 4), ctx16;
         if (ctx) ctx16 = talloc(B, 1, ctx_tokens, cfg.context_dim);
         else if (ctx_B != B) return fail(FGDM_ERR_STATE, "ctx is NULL but no context of this batch size was registered (fgdm_set_context)");
         if (!x4.p || (ctx && !ctx16.p)) return fail(FGDM_ERR_NOMEM, "workspace");
-        if (nchw_f32_to_nhwc_f16(x, x4.p, B, 4, HW, 4, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
+        const bool pairs = (flags & FGDM_FLAG_CFG_PAIRS) && (B % 2 == 0) && n.input.size() > 1;      // (see below)
+        if (Cc > 0) {      // only the rows the first layer reads: with CFG pairs the shared half, rows [0, B/2) of x and of the stored
+                           // c_concat, whether that holds B/2 rows or B (the caller's word that rows b and b + B/2 are equal)
+            const int rows = pairs ? B / 2 : B;
+            if (pack_xcat(x, ccat.p, x4.p, rows, std::min(ccat.B, rows), Cc, HW, x4.C, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "pack kernel");
+        } else if (nchw_f32_to_nhwc_f16(x, x4.p, B, 4, HW, 4, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
         if (ctx && f32_to_f16(ctx, ctx16.p, ctx16.numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "convert kernel");
         float* emb = nullptr;
         CHK(embed(n, t, tf, B, &emb));
@@ -1741,7 +1763,6 @@ struct fgdm_engine {
         // b + B/2 have the same x, t (and pcond / hint) and differ only in the context.  Everything before the first
         // cross-attention -- conv_in, the first ResBlock, the first self-attention, the adapter -- is computed once on
         // B/2 rows and duplicated where the context enters.  Per-sample results are unchanged bit for bit.
-        const bool pairs = (flags & FGDM_FLAG_CFG_PAIRS) && (B % 2 == 0) && n.input.size() > 1;
         const int Bs = pairs ? B / 2 : B;              // rows of the shared prefix
         Tensor x4s = x4; x4s.B = Bs;
         Tensor fa[4];
@@ -2090,15 +2111,39 @@ struct fgdm_engine {
         }
         return FGDM_OK;
     }
+
+    // c_concat of DiffusionWrapper's 'hybrid' mode (ddpm.py:1838-1841): the same tensor in every step of a sampling, so it is
+    // converted once -- fp32 NCHW [B, Cc, H, W] -> fp16 NHWC, rounded as x is -- and apply_model packs it behind x (k_pack_xcat)
+    void drop_concat() { if (ccat.p) (void)hipFree(ccat.p); ccat = Tensor{}; }
+    int set_concat(const float* cc, int B, int Cc, int H, int W) {
+        if (cfg.in_channels == 4) return fail(FGDM_ERR_ARG, "fgdm_set_concat: this engine's UNet takes x alone (in_channels = 4)");
+        if (!cc) { drop_concat(); return FGDM_OK; }
+        // a refused tensor leaves NOTHING stored: a caller who ignores the return code gets FGDM_ERR_STATE from apply_model, not the
+        // previous image
+        if (Cc != cfg.in_channels - 4) {
+            drop_concat();
+            return fail(FGDM_ERR_ARG, "fgdm_set_concat: c_concat must have in_channels - 4 = " + std::to_string(cfg.in_channels - 4) + " channels");
+        }
+        if (B <= 0 || H <= 0 || W <= 0) { drop_concat(); return fail(FGDM_ERR_ARG, "bad shape"); }
+        if (ccat.p && (ccat.B != B || ccat.H != H || ccat.W != W)) drop_concat();
+        if (!ccat.p) {
+            ccat.B = B; ccat.H = H; ccat.W = W; ccat.C = Cc;
+            if (hipMalloc(&ccat.p, ccat.numel() * sizeof(half_t)) != hipSuccess) { ccat = Tensor{}; return fail(FGDM_ERR_NOMEM, "hipMalloc (c_concat cache)"); }
+        }
+        if (nchw_f32_to_nhwc_f16(cc, ccat.p, B, Cc, H * W, Cc, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
+        return FGDM_OK;
+    }
 };
 
 // ================================================================================================ C ABI
 // (the op-level test entries are in ops_abi.hip, the micro-benchmark entries in bench_abi.hip)
+static std::string g_create_err;   // why the last fgdm_create / parameter-table query failed (there is no engine to ask): fgdm_last_error(NULL)
+
 static int make_desc(const fgdm_config* cfg, fgdm_engine** out) {
     fgdm_engine* e = new fgdm_engine();
     e->cfg = *cfg;
     const int rc = e->build();
-    if (rc != FGDM_OK) { delete e; return rc; }
+    if (rc != FGDM_OK) { g_create_err = "unsupported configuration: " + e->err; delete e; return rc; }
     *out = e;
     return FGDM_OK;
 }
@@ -2120,13 +2165,11 @@ template <typename F> static int scoped_call(fgdm_engine* e, void* stream, F f) 
 
 extern "C" {
 
-static std::string g_create_err;   // why the last fgdm_create failed (there is no engine to ask): fgdm_last_error(NULL)
-
 int fgdm_create(const fgdm_config* cfg, int device, fgdm_engine** out) {
     if (!cfg || !out) return FGDM_ERR_ARG;
     fgdm_engine* e = nullptr;
     int rc = make_desc(cfg, &e);
-    if (rc != FGDM_OK) { g_create_err = "unsupported configuration"; return rc; }
+    if (rc != FGDM_OK) return rc;      // make_desc left the reason in g_create_err
     e->device = device;
     e->ln_fold = knob_on(KNOB_LN_FOLD);
     rc = e->ensure_device();
@@ -2163,6 +2206,7 @@ void fgdm_destroy(fgdm_engine* e) {
     for (auto& kv : e->weight_allocs) for (void* p : kv.second) (void)hipFree(p);
     if (e->zero) (void)hipFree(e->zero);
     for (auto& n : e->cns) if (n.guided.p) (void)hipFree(n.guided.p);
+    e->drop_concat();
     e->drop_context();
     e->drop_adapter_conds();
     if (knob_text(KNOB_PAIR_DEBUG) && e->replayed_launches)
@@ -2314,6 +2358,11 @@ int fgdm_set_hint(fgdm_engine* e, int cn, const float* hint, int B, int Hh, int 
     return scoped_call(e, stream, [&] { return e->set_hint(cn, hint, B, Hh, Wh); });
 }
 
+int fgdm_set_concat(fgdm_engine* e, const float* c_concat, int B, int Cc, int H, int W, void* stream) {
+    if (!e) return FGDM_ERR_ARG;
+    return scoped_call(e, stream, [&] { return e->set_concat(c_concat, B, Cc, H, W); });
+}
+
 int fgdm_apply_model(fgdm_engine* e, const float* x, const int64_t* t, const float* t_float, const float* ctx,
                      const float* pcond, const float* control_scales, int B, int H, int W, int flags, float* eps_out,
                      void* stream) {
@@ -2409,6 +2458,9 @@ int fgdm_apply_model_patches(fgdm_engine* e, const float* x, const int64_t* t, c
         return e->fail(FGDM_ERR_ARG, "patch apply_model: null pointer or bad batch / pass size");
     if (!ctx) return e->fail(FGDM_ERR_ARG, "patch apply_model: ctx must be given (a registered context covers B rows, a pass has n*B)");
     if (!e->cns.empty()) return e->fail(FGDM_ERR_ARG, "patch apply_model: ControlLDM.apply_model has no patch branch (engine has ControlNets)");
+    if (e->cfg.in_channels != 4)
+        return e->fail(FGDM_ERR_ARG, "patch apply_model: in_channels != 4 -- the reference crops c_concat only for its spatial cond_stage_keys "
+                                     "(ddpm.py:1061-1071), which are refused");
     if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
     PatchGeom g{B, 4, H, W, kh, kw, sh, sw, 0, 0};
     if (patch_plan(H, W, kh, kw, sh, sw, true, &g.Ly, &g.Lx) != FGDM_OK)

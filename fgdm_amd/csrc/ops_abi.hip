@@ -283,6 +283,11 @@ int fgdm_op_nchw_to_nhwc(const float* x, void* y, int B, int C, int HW, int Cpad
     if (!x || !y || B <= 0 || C <= 0 || HW <= 0 || Cpad < C) return FGDM_ERR_ARG;
     return nchw_f32_to_nhwc_f16(x, (half_t*)y, B, C, HW, Cpad, as_stream(stream));
 }
+// Diagnostic entry of tests/test_gpu_hybrid.py: the engine's first-layer pack for in_channels > 4 on caller-owned buffers.
+int fgdm_op_pack_xcat(const float* x, const void* cc16, int B, int Bc, int Cc, int H, int W, int cin_pad, void* out, void* stream) {
+    if (!x || !cc16 || !out || H <= 0 || W <= 0) return FGDM_ERR_ARG;
+    return pack_xcat(x, (const half_t*)cc16, (half_t*)out, B, Bc, Cc, H * W, cin_pad, as_stream(stream));
+}
 int fgdm_op_nhwc_to_nchw(const void* x, float* y, int B, int C, int HW, void* stream) {
     if (!x || !y || B <= 0 || C <= 0 || HW <= 0) return FGDM_ERR_ARG;
     return nhwc_f16_to_nchw_f32((const half_t*)x, y, B, C, HW, as_stream(stream));

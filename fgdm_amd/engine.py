@@ -161,6 +161,9 @@ class Engine:
         self._ctx_policy = ContextCachePolicy()      # context tensor whose K/V projections the engine holds
         self._ctx_tokens = self.lib.fgdm_get_context_tokens(self.h)      # tokens per context (77 unless changed)
         self._conds_key, self._conds_keep = None, None
+        self._concat_key = None
+        self.concat_uploads = 0       # fgdm_set_concat calls that really stored a tensor (a repeated tensor is a cache hit)
+        self.pair_calls = 0           # apply_model calls that carried FLAG_CFG_PAIRS
         self.cache_context = os.environ.get('FGDM_CONTEXT_CACHE', '1') != '0'
 
     def close(self):
@@ -253,6 +256,25 @@ class Engine:
         self._check(self.lib.fgdm_set_adapter_conds(self.h, ptrs, len(dev), B, H, W, _stream()), 'fgdm_set_adapter_conds')
         self._conds_key, self._conds_keep = key, list(conds)
 
+    def set_concat(self, c_concat):
+        """c_concat of an engine whose UNet reads cat([x, c_concat], 1) (in_channels > 4; DiffusionWrapper 'hybrid', ddpm.py:1838-
+        1841): fp32 NCHW [B, in_channels - 4, H, W], stored once as fp16 NHWC and kept until a different tensor (object, version
+        or shape) is given; None drops it.  B is the batch of the later apply_model calls, or half of it (the two halves of a
+        classifier-free-guidance batch then share the rows).  The source object is kept alive with the key, as for set_hint."""
+        if c_concat is None:
+            self._check(self.lib.fgdm_set_concat(self.h, None, 0, 0, 0, 0, _stream()), 'fgdm_set_concat')
+            self._concat_key = None
+            return
+        key = (id(c_concat), c_concat.data_ptr(), c_concat._version, tuple(c_concat.shape))
+        if self._concat_key is not None and self._concat_key[0] == key:
+            return
+        self._concat_key = None       # a refused call leaves nothing that a later hit could vouch for
+        dev = c_concat.to(self.device, torch.float32).contiguous()
+        B, Cc, H, W = dev.shape
+        self._check(self.lib.fgdm_set_concat(self.h, _ptr(dev), B, Cc, H, W, _stream()), 'fgdm_set_concat')
+        self._concat_key = (key, c_concat)
+        self.concat_uploads += 1
+
     def set_context_tokens(self, tokens):
         """Token count of every context handed over from now on (cat(c_crossattn, 1) may hold several 77-token parts,
         ddpm.py:1835-1837 / hack.py:23-68).  A changed count drops the engine's registered projections, so the cache policy
@@ -302,6 +324,7 @@ class Engine:
         rc = self.lib.fgdm_apply_model(self.h, _ptr(x), _ptr(t_int), _ptr(t_flt), _ptr(ctx_arg), _ptr(pcond), sc_ptr, B, H, W,
                                        flags, _ptr(eps), _stream())
         self._check(rc, 'fgdm_apply_model')
+        self.pair_calls += bool(flags & _lib.FLAG_CFG_PAIRS)
         return eps
 
     def clip_encode(self, ids, clip_skip=0):

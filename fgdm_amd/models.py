@@ -91,16 +91,28 @@ class DiffusionWrapper:
         self.conditioning_key = conditioning_key
 
 
+# DiffusionWrapper.forward's modes (ddpm.py:1829-1846) the engine has no network for, each with its reason
+_REFUSED_KEYS = {
+    'concat': "conditioning_key='concat' hands the UNet cat([x] + c_concat, 1) WITHOUT a context (ddpm.py:1832-1834): the engine "
+              "builds UNets whose SpatialTransformers take a text context; use 'hybrid' (c_concat and c_crossattn)",
+    'adm': "conditioning_key='adm' hands the UNet class embeddings, y=c_crossattn[0] (ddpm.py:1842-1844): the engine has no "
+           'label embedding (num_classes is fixed to None)',
+    None: 'conditioning_key=None is the unconditional UNet (ddpm.py:1830-1831): the engine builds UNets whose SpatialTransformers '
+          'take a text context',
+}
+
+
 class LatentDiffusion(_Buffers):
-    def __init__(self, unet_config=None, engine=None, use_adapter=True, n_controlnets=0, num_prompts=1, timesteps=1000,
+    def __init__(self, unet_config=None, engine=None, use_adapter=None, n_controlnets=0, num_prompts=1, timesteps=1000,
                  beta_schedule='linear', linear_start=0.00085, linear_end=0.012, cosine_s=8e-3, given_betas=None,
                  v_posterior=0.0, parameterization='eps', conditioning_key='crossattn', scale_factor=0.18215,
                  channels=4, image_size=32, log_every_t=200, clip_denoised=False, device=0, first_stage_config=None,
                  cond_stage_config=None, first_stage_encoder=False, **ignored):
         if parameterization != 'eps':
             raise NotImplementedError('only eps-parameterization is used by the shipped configs (models/config.yaml)')
-        if conditioning_key != 'crossattn':
-            raise NotImplementedError("only conditioning_key='crossattn' is on the hot path (models/config.yaml:15)")
+        if conditioning_key not in ('crossattn', 'hybrid'):
+            raise NotImplementedError(_REFUSED_KEYS.get(conditioning_key, f'conditioning_key={conditioning_key!r}: DiffusionWrapper '
+                                                                          "knows None, 'concat', 'crossattn', 'hybrid', 'adm'"))
         self.engine = engine if engine is not None else _k.Engine(device=device, **self.engine_args(
             unet_config=unet_config, use_adapter=use_adapter, n_controlnets=n_controlnets, num_prompts=num_prompts,
             first_stage_config=first_stage_config, cond_stage_config=cond_stage_config, first_stage_encoder=first_stage_encoder))
@@ -129,17 +141,26 @@ class LatentDiffusion(_Buffers):
         self._finalized = False
 
     @classmethod
-    def engine_args(cls, unet_config=None, use_adapter=True, n_controlnets=0, num_prompts=1, first_stage_config=None,
+    def engine_args(cls, unet_config=None, use_adapter=None, n_controlnets=0, num_prompts=1, first_stage_config=None,
                     cond_stage_config=None, first_stage_encoder=False, **ignored):
         """Constructor arguments of the reference model -> keyword arguments of fgdm_amd.engine.Engine / make_config (a pure
         function: works without a GPU).  unet_config as the scripts pass it: {target: ...UNetModel, params: {...}}
         (models/config.yaml:33-48; OmegaConf or dict) or the bare parameter dict; the target and its flags select the
         adapter variant the engine builds."""
         kind, cfg, uflags = _cfg.unet_params(unet_config)
+        asked = bool(use_adapter)                     # the caller's own request; None: the FG-DM default, an adapter
+        use_adapter = True if use_adapter is None else use_adapter
         if kind == 'controlled' or uflags.get('no_prompting'):
             use_adapter = False                       # ControlledUnetModel / no_prompting: the plain SD UNet
         elif uflags.get('use_time_adapter'):
             use_adapter = 'time'
+        if cfg is not None and cfg['in_channels'] != 4 and use_adapter:
+            # a UNet fed cat([x] + c_concat, 1) ('hybrid'): UNetModel.forward would hand that input to an adapter built for 4
+            # channels (openaimodel.py:836-844), so such networks are the plain SD UNet apart from conv_in
+            if asked or uflags.get('use_time_adapter'):
+                raise NotImplementedError(f"in_channels={cfg['in_channels']} with an FG-DM adapter: the adapter takes the 4 latent "
+                                          'channels, the reference hands it the concatenated input (openaimodel.py:836-844)')
+            use_adapter = False
         if kind == 'adapt' or uflags.get('num_prompts', 1) > 1:
             num_prompts = max(num_prompts, int(uflags.get('num_prompts', num_prompts)))
         args = dict(cfg=cfg, use_adapter=use_adapter, n_controlnets=n_controlnets, num_prompts=num_prompts,
@@ -352,12 +373,48 @@ class LatentDiffusion(_Buffers):
         return self.engine.apply_model_patches(x_noisy, t, self._context(cond), (kh, kw), stride, w_pix, w_tie,
                                                getattr(self, 'max_crops_per_pass', 0))
 
+    def _concat(self, x_noisy, cond):
+        """xc = torch.cat([x] + c_concat, dim=1) (ddpm.py:1838-1841), the c_concat side: the channel-wise join of the parts, made
+        once per list of tensor objects (and _version) like _context's, so that the engine sees the SAME tensor in every step and
+        keeps its stored copy.  -> (joined tensor, may_pair): its rows are the batch, or half of it (a sampler's cat([x] * 2)
+        batch sharing one image); may_pair tells whether rows b and b + B/2 of the batch read equal c_concat rows."""
+        if not isinstance(cond, dict):
+            raise TypeError("conditioning_key='hybrid' needs a dict cond {'c_concat': [...], 'c_crossattn': [...]} (the reference "
+                            f'fails on [x] + None, ddpm.py:1840); got {type(cond).__name__}')
+        parts = cond.get('c_concat')
+        if not isinstance(parts, (list, tuple)) or not parts or 'c_crossattn' not in cond:
+            raise TypeError("conditioning_key='hybrid' needs cond['c_concat'] (a list of tensors) and cond['c_crossattn']")
+        if len(parts) == 1:
+            cc = parts[0]
+        else:
+            key = tuple((id(p), p._version) for p in parts)
+            memo = getattr(self, '_concat_cat_memo', None)
+            if memo is None or memo[0] != key:
+                self._concat_cat_memo = memo = (key, list(parts), torch.cat(list(parts), 1))
+            cc = memo[2]
+        B = x_noisy.shape[0]
+        if cc.dim() != 4 or tuple(cc.shape[2:]) != tuple(x_noisy.shape[2:]) or not (cc.shape[0] == B or 2 * cc.shape[0] == B):
+            raise ValueError(f'c_concat {tuple(cc.shape)} does not fit the latent batch {tuple(x_noisy.shape)}')
+        return cc, (2 * cc.shape[0] == B or self._halves_equal(cc))
+
     def apply_model(self, x_noisy, t, cond, return_ids=False, **kwargs):
         sp = getattr(self, 'split_input_params', None)
+        hybrid = self.model.conditioning_key == 'hybrid'
+        if hybrid and sp is not None:
+            raise NotImplementedError("split_input_params with conditioning_key='hybrid': the reference's patch branch crops c_concat "
+                                      'only for its spatial cond_stage_keys (ddpm.py:1061-1071), which are not supported')
         if sp is not None:
             return self._apply_model_patches(x_noisy, t, cond, return_ids, sp)
         if return_ids:
             raise NotImplementedError('return_ids / return_conds needs a model with two outputs; no shipped model has one')
+        if hybrid:
+            cc, may_pair = self._concat(x_noisy, cond)
+            self.engine.set_concat(cc)                # a no-op while the same tensor is handed over
+            flags = _lib.FLAG_NO_CONTROL | (_lib.FLAG_USE_ORIGINAL if kwargs.get('use_original', False) else 0)
+            # cfg_pairs (set by the samplers for cat([x] * 2) batches): honoured only if both halves read the same c_concat rows
+            if kwargs.get('cfg_pairs', False) and may_pair:
+                flags |= _lib.FLAG_CFG_PAIRS
+            return self.engine.apply_model(x_noisy, t, self._context(cond), flags=flags)
         flags = _lib.FLAG_NO_CONTROL
         if kwargs.get('use_original', False):
             flags |= _lib.FLAG_USE_ORIGINAL

@@ -481,6 +481,22 @@ class ControlDDIMSampler(DDIMSampler):
             return None      # e.g. a 231-token prompt against a 77-token negative prompt: two calls (ddim_hacked.py:190-191)
         return {'c_concat': hc, 'c_crossattn': [torch.cat([a, b]) for a, b in zip(uc['c_crossattn'], c['c_crossattn'])]}
 
+    def _batched_cond(self, uc, c):
+        """A model whose UNet reads cat([x] + c_concat, 1) (LatentDiffusion with conditioning_key='hybrid') takes c_concat per
+        ROW, unlike ControlLDM's hint: branches with different c_concat still make one 2B batch, with the parts concatenated
+        along the batch like the contexts (the model then finds the halves unequal and drops its cfg_pairs shortcut).  Branches
+        with the same c_concat keep the half-batch tensor of _cat_cond: one paired batch."""
+        c_in = super()._batched_cond(uc, c)
+        if c_in is None and getattr(getattr(getattr(self, 'model', None), 'model', None), 'conditioning_key', None) == 'hybrid' \
+                and isinstance(uc, dict) and isinstance(c, dict):
+            hu, hc, tu, tc = uc.get('c_concat'), c.get('c_concat'), uc['c_crossattn'], c['c_crossattn']
+            if hu is not None and hc is not None and len(hu) == len(hc) and len(tu) == len(tc) \
+                    and all(a.shape == b.shape for a, b in zip(hu, hc)) and all(a.shape[1:] == b.shape[1:] for a, b in zip(tu, tc)):
+                c_in = {'c_concat': [torch.cat([a, b]) for a, b in zip(hu, hc)],
+                        'c_crossattn': [torch.cat([a, b]) for a, b in zip(tu, tc)]}
+                self._cin_memo = (*self._cin_memo[:2], c_in)        # the same joined tensors in every step, like the base memo's
+        return c_in
+
 
 # ----------------------------------------------------------------------------------------------- DPM-Solver++
 class _DiscreteVPSchedule:

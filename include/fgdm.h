@@ -6,7 +6,8 @@
  *     fgdm_last_error() gives a message for the last failing call on that engine;
  *   - all tensor arguments are DEVICE pointers owned by the caller (e.g. torch tensor.data_ptr()), except
  *     fgdm_load_tensor which accepts host or device memory;
- *   - latents / eps are fp32 NCHW [B,4,H,W]; timesteps int64 [B]; context fp32 [B,77,ctx_dim] ("77" below: the engine's
+ *   - latents / eps are fp32 NCHW [B,4,H,W] (also for in_channels > 4: the further input channels come from the tensor registered
+ *     with the concat entry below, never through x); timesteps int64 [B]; context fp32 [B,77,ctx_dim] ("77" below: the engine's
  *     context token count, 77 unless fgdm_set_context_tokens changed it);
  *     hints fp32 NCHW [B,3,8H,8W] in [0,1];
  *   - the engine owns weights and workspace; one engine per device; not thread-safe; all work is enqueued on
@@ -120,6 +121,21 @@ int fgdm_set_context(fgdm_engine* e, const float* ctx, int B, void* stream);
  * All samples of a batch share the count.  No launch, no synchronisation beyond freeing the dropped projections. */
 int fgdm_set_context_tokens(fgdm_engine* e, int tokens);
 int fgdm_get_context_tokens(const fgdm_engine* e);
+/* UNets fed x | c_concat: DiffusionWrapper.forward in its 'hybrid' mode, xc = torch.cat([x] + c_concat, dim=1) handed to the
+ * UNet together with the text context (ldm/models/diffusion/ddpm.py:1838-1841) -- the SD-v1 inpainting checkpoints (in_channels 9:
+ * latent, mask, masked-image latent) and the InstructPix2Pix family (8).  An engine created with 4 < in_channels <= 32 is such a
+ * network: a plain SD UNet apart from conv_in; use_adapter and n_controlnets must be 0 (FGDM_ERR_ARG at creation otherwise, with
+ * the reason in the message).  c_concat is the same tensor in every step of a sampling, so the engine keeps it: this call
+ * stores c_concat fp32 NCHW [B, Cc, H, W] (device) once as fp16 NHWC [B, H W, Cc] in memory it owns (re-allocated when B, H or W
+ * change; c_concat NULL drops it), and every later apply_model call packs x in front of it for conv_in (one launch, k_pack_xcat).
+ * Cc must equal in_channels - 4 (FGDM_ERR_ARG otherwise, and like every refused tensor it leaves NOTHING stored: the previous
+ * c_concat is dropped, so a later apply_model is FGDM_ERR_STATE rather than a run on the old image); on an engine with in_channels == 4 the call is FGDM_ERR_ARG and changes
+ * nothing.  The stored rows may be the B of the later apply_model call, or B / 2 with B even: rows b and b + B / 2 then share
+ * row b (the cat([x] * 2) batch of a classifier-free-guidance step whose halves carry the same image).  An apply_model call
+ * without a stored c_concat, or with one whose rows or H, W do not fit, is FGDM_ERR_STATE before any launch.  With
+ * FGDM_FLAG_CFG_PAIRS and B stored rows only rows [0, B / 2) of c_concat are read, like those of x.  The patch-wise
+ * apply_model entry refuses such an engine (FGDM_ERR_ARG). */
+int fgdm_set_concat(fgdm_engine* e, const float* c_concat, int B, int Cc, int H, int W, void* stream);
 int fgdm_apply_model(fgdm_engine* e, const float* x, const int64_t* t, const float* t_float, const float* ctx,
                      const float* pcond, const float* control_scales, int B, int H, int W, int flags, float* eps_out,
                      void* stream);
@@ -351,6 +367,10 @@ int fgdm_op_vae_attention(const void* q, const void* k, const void* vt, void* ou
  *  fgdm_op_softmax_rows: P = fp16(softmax(S)) over the `cols` fp32 logits of each of `rows` rows (AttnBlock, model.py:190-192).
  *  fgdm_op_nchw_to_nhwc: x fp32 [B, C, HW] -> y fp16 [B, HW, Cpad], channels >= C exactly +0 (Cpad >= C).
  *  fgdm_op_nhwc_to_nchw: x fp16 [B, HW, C] -> y fp32 [B, C, HW].
+ *  fgdm_op_pack_xcat (tests/test_gpu_hybrid.py): the first-layer input of an engine with in_channels > 4, as apply_model packs it:
+ *      x fp32 [B, 4, H W] and cc16 fp16 [Bc, H W, Cc] (the layout the engine stores c_concat in) -> out fp16 [B, H W, cin_pad]:
+ *      channels [0, 4) x, [4, 4 + Cc) row b % Bc of cc16, [4 + Cc, cin_pad) exactly +0.  Bc = B, or B / 2 with B even; cin_pad a
+ *      multiple of 4 and >= 4 + Cc (the engine passes roundup(4 + Cc, 8) when 4 + Cc is a multiple of 8, else roundup(4 + Cc, 4)).
  *  fgdm_op_avgpool2: AvgPool2d(2) on fp16 NHWC [B, H, W, C] -> [B, H/2, W/2, C] (the adapter's Downsample with use_conv = False,
  *      ldm/modules/encoders/adapter.py:270-273); H, W even, C a multiple of 8.
  *  fgdm_op_transpose_pad: v fp16 [B, Tk, C] -> vt fp16 [B, C, Tkpad], columns [Tk, Tkpad) exactly zero (Tkpad >= Tk).
@@ -361,6 +381,7 @@ int fgdm_op_vae_attention(const void* q, const void* k, const void* vt, void* ou
 int fgdm_op_softmax_rows(const float* S, void* P, int rows, int cols, void* stream);
 int fgdm_op_nchw_to_nhwc(const float* x, void* y, int B, int C, int HW, int Cpad, void* stream);
 int fgdm_op_nhwc_to_nchw(const void* x, float* y, int B, int C, int HW, void* stream);
+int fgdm_op_pack_xcat(const float* x, const void* cc16, int B, int Bc, int Cc, int H, int W, int cin_pad, void* out, void* stream);
 int fgdm_op_avgpool2(const void* x, void* y, int B, int H, int W, int C, void* stream);
 int fgdm_op_transpose_pad(const void* v, void* vt, int B, int Tk, int C, int Tkpad, void* stream);
 int fgdm_op_timestep_embed(const int64_t* t, const float* t_float, void* y, int B, int dim, int rows_pad, void* stream);

@@ -914,18 +914,50 @@ def g_split_input_vae():
     save('split_input_vae', img=img.float())
 
 
+# --------------------------------------------------------------------------- hybrid conditioning (x | c_concat UNets)
+def g_hybrid():
+    """LatentDiffusion.apply_model with conditioning_key='hybrid' (ddpm.py:1035-1044, 1130-1136) through DiffusionWrapper.forward
+    (xc = torch.cat([x] + c_concat, dim=1), ddpm.py:1838-1841) around the full-width UNet with 9 (SD-v1 inpainting) and 8
+    (InstructPix2Pix) input channels, no_prompting: True, use_original=True.  Writes tests/golden/hybrid.npz only (a few KB of
+    outputs; the inputs come from tests/hybrid_inputs.py)."""
+    import hybrid_inputs as hi
+    import ldm.models.diffusion.ddpm as ddpm
+    from ldm.modules.diffusionmodules.openaimodel import UNetModel
+
+    class Wrapper(ddpm.DiffusionWrapper):
+        def __init__(s, m):
+            nn.Module.__init__(s)
+            s.diffusion_model = m
+            s.conditioning_key = 'hybrid'
+
+    class LD(ddpm.LatentDiffusion):      # the heavy constructor is bypassed (as in _reference_split_ldm); apply_model is the reference's
+        def __init__(s, m):
+            nn.Module.__init__(s)
+            s.model = Wrapper(m)
+
+    t = torch.tensor(hi.T, dtype=torch.long)
+    arrs = {'t': t}
+    with torch.no_grad():
+        for cin in hi.IN_CHANNELS:
+            m = UNetModel(**ref_cfg(hi.cfg(cin), no_prompting=True)).eval()
+            load_synth(m, hi.PREFIX)
+            cond = {'c_concat': [hi.c_concat(cin - 4)], 'c_crossattn': [hi.ctx()]}
+            arrs[f'eps{cin}'] = LD(m).apply_model(hi.x(), t, cond, use_original=True).float()
+    save('hybrid', **arrs)
+
+
 ALL = dict(schedule=g_schedule, ddpm_schedule=g_ddpm_schedule, param_keys=g_param_keys, ops=g_ops,
            unet_full=g_unet_full, controlnet_full=g_controlnet_full, small_nets=g_small_nets,
            samplers=g_samplers, samplers2=g_samplers2, samplers3=g_samplers3, sampler_unet=g_sampler_unet, vae=g_vae, clip=g_clip, adapt_unet=g_adapt_unet, full_size=g_full_size,
            full_size_check=g_full_size_check, vae_enc=g_vae_enc, long_context=g_long_context,
            clip_hack_tokens=g_clip_hack_tokens, split_input_tables=g_split_input_tables, split_input_unet=g_split_input_unet,
-           split_input_vae=g_split_input_vae)
+           split_input_vae=g_split_input_vae, hybrid=g_hybrid)
 
 
 # generators that are ALSO run with the reference's modules under the emulated torch.autocast("cuda") policy
 # (scripts/txt2img_fgdm_inference.py:212-217 wraps the whole sampling loop in it) -> tests/golden/<name>_ac.npz
 AC = ('ops', 'unet_full', 'controlnet_full', 'small_nets', 'sampler_unet', 'adapt_unet', 'vae', 'clip', 'full_size', 'full_size_check',
-      'vae_enc', 'long_context', 'split_input_unet', 'split_input_vae')
+      'vae_enc', 'long_context', 'split_input_unet', 'split_input_vae', 'hybrid')
 
 
 def main():
