@@ -83,6 +83,7 @@ SIGNATURES = {
     'fgdm_profile_end': (_i, [_p, C.POINTER(C.c_double)]),
     'fgdm_workspace_stats': (_i, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
     'fgdm_launch_stats': (_i, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    'fgdm_replay_plan': (_i, [_i, _p, _p, _p, _p, _i, _i, _p, _i, _p]),
     'fgdm_op_conv2d': (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p]),
     'fgdm_op_linear': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     'fgdm_debug_force_igemm_cfg': (_i, [_i]),

@@ -215,23 +215,22 @@ int fgdm_dyn_lds(int bytes) {
 
 // ---------------------------------------------------------------- deferred launches (twin-layer grouped launches)
 // While the engine RECORDS (engine.hip: apply_model with FGDM_PAIR_LAUNCH), nothing is enqueued: every launch site goes through
-// FGDM_LAUNCH, which then stores a closure (arguments by value) in the engine's list instead; the engine replays the lists of the
-// UNet encoder and of the ControlNets in lockstep and fuses launches of the same pipelined-GEMM instantiation and grid into ONE
-// grouped launch (igemm2.hip: igemm2_group_kernel; blockIdx.y selects the argument set: the UNet plus up to four ControlNets),
-// so that the half-empty grids of the 16x16 / 8x8 levels fill the chip.  Each net's launches keep their order, so the results do
-// not change by a bit.
+// FGDM_LAUNCH, which then stores a closure (arguments by value) in the walk's list instead (replay.h); the engine replays the lists
+// of the UNet encoder and of the ControlNets in lockstep and fuses launches that have the same grouped form, grid and shape into
+// ONE grouped launch (igemm2.hip: igemm2_pair_kernel, norm.hip: gn_*_group_kernel; blockIdx.y selects the argument set: the UNet
+// plus up to four ControlNets), so that the half-empty grids of the 16x16 / 8x8 levels fill the chip.  Each net's launches keep
+// their order, so the results do not change by a bit.
 #include <functional>
 #define FGDM_MAX_GROUP 5
-typedef int (*IgemmGroupFn)(const IgemmArgs* const* a, int n, unsigned grid_x, hipStream_t s);
 bool fgdm_recording();
-void fgdm_record(std::function<int(hipStream_t)> run, const void* pair_key = nullptr, IgemmGroupFn pair = nullptr,
-                 const IgemmArgs* ia = nullptr, unsigned grid_x = 0);
-// ... and the same for other kernels with twins (round 4, late: the single-pass GroupNorm kernels): a generic group function gets the
-// problems' argument blobs (<= FGDM_GROUP_BLOB bytes each, copied at record time); launches are matched by key, grid and a shape hash
-#define FGDM_GROUP_BLOB 96
-typedef int (*GenericGroupFn)(const void* const* args, int n, unsigned grid_x, hipStream_t s);
-void fgdm_record_generic(std::function<int(hipStream_t)> run, const void* key, GenericGroupFn fn, const void* args, size_t nbytes,
-                         unsigned grid_x, unsigned long long shape);
+void fgdm_record(std::function<int(hipStream_t)> run);      // a launch (or any other stream operation) without a twin
+// ... and one with a grouped form: `group` gets the argument blobs (<= FGDM_GROUP_BLOB bytes each, copied at record time) of 2 to
+// FGDM_MAX_GROUP launches recorded with the same `key`, `grid_x` and `shape` (0 where key and grid say it all) and launches them as
+// one grid of (grid_x, n).  group == nullptr records a plain launch.
+#define FGDM_GROUP_BLOB sizeof(IgemmArgs)      // the largest blob recorded; norm.hip static_asserts that its GnRec fits as well
+typedef int (*FgdmGroupFn)(const void* const* args, int n, unsigned grid_x, hipStream_t s);
+void fgdm_record(std::function<int(hipStream_t)> run, const void* key, FgdmGroupFn group, const void* args, size_t nbytes,
+                 unsigned grid_x, unsigned long long shape);
 #define FGDM_LAUNCH(kernel, grid, block, smem, stream, ...)                                                                  \
     do {                                                                                                                     \
         if (fgdm_recording()) {                                                                                              \

@@ -10,6 +10,7 @@
 //   ControlNet / ControlledUnet     controlnet/cldm/cldm.py:27-50, 545-813, 836-849
 #include "engine_shared.h"
 #include "knobs.h"
+#include "replay.h"
 
 #include <algorithm>
 #include <array>
@@ -191,24 +192,7 @@ struct Clip {
 // (the same stream the kernels run on), so per-kernel-class device time, launch counts and the ALGORITHMIC
 // flops / bytes of exactly those launches can be read back without an external profiler.
 enum ProfClass { PC_IGEMM = 0, PC_ATTN = 1, PC_NORM = 2, PC_ELEM = 3, PC_COUNT = 4 };
-// ---- deferred launches (common.h): one op per launch / copy / profiler bracket edge of a recorded network walk
-struct RecOp {
-    enum Kind { RUN, PROF_BEGIN, PROF_END } kind = RUN;
-    std::function<int(hipStream_t)> run;
-    const void* pair_key = nullptr;      // RUN of a pipelined-GEMM instantiation that has a two-problem twin
-    IgemmGroupFn pair = nullptr;
-    IgemmArgs ia{};
-    unsigned grid_x = 0;
-    GenericGroupFn gfn = nullptr;        // ... or of another kernel with a grouped form (GroupNorm): key in pair_key, arguments in gargs
-    unsigned long long gshape = 0;
-    alignas(8) char gargs[FGDM_GROUP_BLOB] = {0};
-    int cls = 0;                         // PROF_BEGIN
-    double w = 0, bytes = 0;
-    char tag[56] = {0};
-};
-thread_local std::vector<RecOp>* g_rec = nullptr;
-
-struct Prof {
+struct Prof final : LaunchTimer {
     bool on = false;
     std::vector<hipEvent_t> pool;
     size_t used = 0;
@@ -226,12 +210,9 @@ struct Prof {
     long counter = 0;
     bool armed = false;
     // bytes: algorithmic HBM bytes of the bracketed launch (counted only when the bracket is taken)
-    void begin(int cls, hipStream_t s, double w, const char* tag = "", double nbytes = 0.0) {
-        if (g_rec) {                                  // recording: the bracket becomes two ops around the launch it encloses
-            if (!on) return;
-            RecOp o; o.kind = RecOp::PROF_BEGIN; o.cls = cls; o.w = w; o.bytes = nbytes;
-            snprintf(o.tag, sizeof(o.tag), "%s", tag);
-            g_rec->push_back(std::move(o));
+    void begin(int cls, hipStream_t s, double w, const char* tag = "", double nbytes = 0.0) override {
+        if (fgdm_recording()) {                       // recording: the bracket becomes two ops around the launch it encloses
+            if (on) fgdm_record_bracket_begin(cls, w, nbytes, tag);
             return;
         }
         armed = false;
@@ -246,11 +227,9 @@ struct Prof {
         work[cls] += w;
         bytes[cls] += nbytes;
     }
-    void end(hipStream_t s) {
-        if (g_rec) {
-            if (!on) return;
-            RecOp o; o.kind = RecOp::PROF_END;
-            g_rec->push_back(std::move(o));
+    void end(hipStream_t s) override {
+        if (fgdm_recording()) {
+            if (on) fgdm_record_bracket_end();
             return;
         }
         if (!on || !armed || recs.empty()) return;
@@ -263,26 +242,6 @@ struct Prof {
 };
 
 }  // namespace
-
-bool fgdm_recording() { return g_rec != nullptr; }
-void fgdm_record(std::function<int(hipStream_t)> run, const void* pair_key, IgemmGroupFn pair, const IgemmArgs* ia, unsigned grid_x) {
-    RecOp o;
-    o.run = std::move(run);
-    o.pair_key = pair_key; o.pair = pair; o.grid_x = grid_x;
-    if (ia) o.ia = *ia;
-    g_rec->push_back(std::move(o));
-}
-
-void fgdm_record_generic(std::function<int(hipStream_t)> run, const void* key, GenericGroupFn fn, const void* args, size_t nbytes,
-                         unsigned grid_x, unsigned long long shape) {
-    RecOp o;
-    o.run = std::move(run);
-    if (fn && args && nbytes <= FGDM_GROUP_BLOB) {
-        o.pair_key = key; o.gfn = fn; o.grid_x = grid_x; o.gshape = shape;
-        memcpy(o.gargs, args, nbytes);
-    }
-    g_rec->push_back(std::move(o));
-}
 
 #define CHK0(x) do { int _rc0 = (x); if (_rc0 != FGDM_OK) return _rc0; } while (0)
 struct fgdm_engine {
@@ -327,11 +286,11 @@ struct fgdm_engine {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool twin_streams = false;
     // FGDM_PAIR_LAUNCH (default on): the UNet encoder + middle block and the ControlNets are RECORDED (common.h, "deferred
-    // launches") and replayed in lockstep on the one stream, twin GEMM launches fused into grouped launches (replay_zip)
+    // launches") and replayed in lockstep on the one stream, twin launches fused into grouped launches (replay.h: fgdm_replay)
     bool pair_launch = true;
     int group_max = FGDM_MAX_GROUP;      // FGDM_GROUP_MAX (read at fgdm_create): 2 = round 3's pairwise replay; the A/B knob
     bool gn_group = true;                // FGDM_GN_GROUP (read at fgdm_create): the twins' single-pass GroupNorm launches group too
-    long paired_launches = 0, replayed_launches = 0, paired_problems = 0;      // fused launches; all replayed launches; problems in fused launches
+    ReplayStats replay_stats;            // behind fgdm_launch_stats
     struct Deferred { const GemmW* w; Tensor src; int idx; float scale; Arena* owner; };
     Prof prof;
 
@@ -971,22 +930,16 @@ struct fgdm_engine {
     // ------------------------------------------------------------------------------------ runtime helpers
     // device-to-device copy / memset on the call's stream, deferred like every launch while a walk is being recorded
     int dcopy(void* dst, const void* src, size_t bytes) {
-        if (g_rec) {
-            RecOp o;
-            o.run = [=](hipStream_t rs) -> int { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, rs) == hipSuccess ? FGDM_OK : FGDM_ERR_HIP; };
-            g_rec->push_back(std::move(o));
-            return FGDM_OK;
-        }
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+        auto run = [=](hipStream_t rs) -> int { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, rs) == hipSuccess ? FGDM_OK : FGDM_ERR_HIP; };
+        if (!fgdm_recording()) return run(s);
+        fgdm_record(run);
+        return FGDM_OK;
     }
     int dzero(void* dst, size_t bytes) {
-        if (g_rec) {
-            RecOp o;
-            o.run = [=](hipStream_t rs) -> int { return hipMemsetAsync(dst, 0, bytes, rs) == hipSuccess ? FGDM_OK : FGDM_ERR_HIP; };
-            g_rec->push_back(std::move(o));
-            return FGDM_OK;
-        }
-        return hipMemsetAsync(dst, 0, bytes, s) == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
+        auto run = [=](hipStream_t rs) -> int { return hipMemsetAsync(dst, 0, bytes, rs) == hipSuccess ? FGDM_OK : FGDM_ERR_HIP; };
+        if (!fgdm_recording()) return run(s);
+        fgdm_record(run);
+        return FGDM_OK;
     }
     Tensor talloc(int B, int H, int W, int C) {
         Tensor t; t.B = B; t.H = H; t.W = W; t.C = C;
@@ -1562,92 +1515,6 @@ struct fgdm_engine {
         return FGDM_OK;
     }
 
-    // ControlNet.forward (cldm.py:792-813).  fused = true: every zero-conv output is scaled and ADDED in place into
-    // the UNet's skip tensor hs[i] / h_mid (cldm.py:40,46 + :846), so control residuals never hit HBM separately.
-    // fused = false: raw residuals are written as fp32 NCHW into out32 (test entry).
-    // ---- replay of recorded walks
-    int run_op(RecOp& o) {
-        switch (o.kind) {
-            case RecOp::PROF_BEGIN: prof.begin(o.cls, s, o.w, o.tag, o.bytes); return FGDM_OK;
-            case RecOp::PROF_END: prof.end(s); return FGDM_OK;
-            default: ++replayed_launches; return o.run(s);
-        }
-    }
-    // a unit = one op, or a profiler bracket around exactly one launch; `launch` = index of its fusable launch or -1
-    struct Unit { size_t first, last; long launch; };
-    static Unit unit_at(std::vector<RecOp>& v, size_t i) {
-        if (v[i].kind == RecOp::PROF_BEGIN && i + 2 < v.size() + 0 && v[i + 1].kind == RecOp::RUN && v[i + 2].kind == RecOp::PROF_END)
-            return Unit{i, i + 2, (v[i + 1].pair || v[i + 1].gfn) ? (long)(i + 1) : -1};
-        if (v[i].kind == RecOp::RUN) return Unit{i, i, (v[i].pair || v[i].gfn) ? (long)i : -1};
-        return Unit{i, i, -1};
-    }
-    int run_unit(std::vector<RecOp>& v, const Unit& u) {
-        for (size_t k = u.first; k <= u.last; ++k) CHK(run_op(v[k]));
-        return FGDM_OK;
-    }
-    // Recorded walks, replayed in lockstep (round 4: any number of them, one grouped launch for the UNet and ALL its ControlNets):
-    // each list keeps its order (the nets are independent of each other); a fusable GEMM launch of the leading list is fused with
-    // the next launch of the same instantiation and grid that each other list holds within a short look-ahead.  When the leading
-    // list runs out, the next one leads.
-    int replay_group(std::vector<std::vector<RecOp>*> L) {
-        constexpr int LOOK = 24;
-        while (L.size() > FGDM_MAX_GROUP) {      // (more walks than a grouped launch takes: the surplus replays on its own)
-            std::vector<RecOp>& v = *L.back();
-            for (size_t i = 0; i < v.size();) { const Unit u = unit_at(v, i); CHK(run_unit(v, u)); i = u.last + 1; }
-            L.pop_back();
-        }
-        std::vector<size_t> at(L.size(), 0);
-        for (size_t lead = 0; lead < L.size(); ++lead) {
-            std::vector<RecOp>& A = *L[lead];
-            while (at[lead] < A.size()) {
-                const Unit ua = unit_at(A, at[lead]);
-                size_t who[FGDM_MAX_GROUP];
-                Unit un[FGDM_MAX_GROUP];
-                int n = 0;
-                if (ua.launch >= 0) {
-                    who[n] = lead; un[n++] = ua;
-                    for (size_t m = lead + 1; m < L.size(); ++m) {
-                        std::vector<RecOp>& B = *L[m];
-                        size_t jj = at[m];
-                        for (int d = 0; d < LOOK && jj < B.size(); ++d) {
-                            const Unit u = unit_at(B, jj);
-                            if (u.launch >= 0 && B[u.launch].pair_key == A[ua.launch].pair_key && B[u.launch].grid_x == A[ua.launch].grid_x &&
-                                B[u.launch].gshape == A[ua.launch].gshape) {
-                                who[n] = m; un[n++] = u;
-                                break;
-                            }
-                            jj = u.last + 1;
-                        }
-                    }
-                }
-                if (n < 2) { CHK(run_unit(A, ua)); at[lead] = ua.last + 1; continue; }
-                // everything the partners hold in front of their member of the group runs first, in their own order
-                for (int k = 1; k < n; ++k) {
-                    std::vector<RecOp>& B = *L[who[k]];
-                    while (at[who[k]] < un[k].first) { const Unit u = unit_at(B, at[who[k]]); CHK(run_unit(B, u)); at[who[k]] = u.last + 1; }
-                }
-                // fused: one bracket (all the problems' work), one launch
-                const IgemmArgs* av[FGDM_MAX_GROUP];
-                const void* gv[FGDM_MAX_GROUP];
-                double w = 0.0, bytes = 0.0;
-                const RecOp* br = nullptr;
-                for (int k = 0; k < n; ++k) {
-                    std::vector<RecOp>& B = *L[who[k]];
-                    av[k] = &B[un[k].launch].ia;
-                    gv[k] = B[un[k].launch].gargs;
-                    if (un[k].first != un[k].last) { w += B[un[k].first].w; bytes += B[un[k].first].bytes; if (!br) br = &B[un[k].first]; }
-                }
-                if (br) prof.begin(br->cls, s, w, br->tag, bytes);
-                if (A[ua.launch].pair) CHK(A[ua.launch].pair(av, n, A[ua.launch].grid_x, s));
-                else CHK(A[ua.launch].gfn(gv, n, A[ua.launch].grid_x, s));
-                if (br) prof.end(s);
-                ++paired_launches; ++replayed_launches; paired_problems += n;
-                for (int k = 0; k < n; ++k) at[who[k]] = un[k].last + 1;
-            }
-        }
-        return FGDM_OK;
-    }
-
     // dst <- dst + scale (W src + b), in place (cldm.py:40,46,846 fused into the zero-conv's epilogue)
     int zero_conv_into(const GemmW& zw, const Tensor& src, Tensor& dst, float scale) {
         Epi e;
@@ -1664,11 +1531,44 @@ struct fgdm_engine {
         return linear(zw, src, e, nullptr);
     }
 
+    // While it lives, launches are recorded into `walk` (nullptr: enqueued as usual) and workspaces come from `arena`; whatever
+    // path leaves, both are as they were before.
+    struct RecordScope {
+        fgdm_engine& e;
+        Arena* const ar0;
+        RecWalk* const rec0;
+        RecordScope(fgdm_engine& e_, RecWalk* walk, Arena* arena) : e(e_), ar0(e_.ar), rec0(fgdm_record_into(walk)) { e.ar = arena; }
+        ~RecordScope() { e.ar = ar0; fgdm_record_into(rec0); }
+        RecordScope(const RecordScope&) = delete;
+    };
+    // What the GEMMs' tile and split-K choices are told about the layers walked while it lives: they have a same-shape twin in
+    // another net (igemm_set_twin_layers), and -- pair_mult > 0 -- their launches will be fused pair_mult at a time
+    // (igemm_set_pair_hint; 0 leaves the hint as it is).  Whatever path leaves, both are as they were before.
+    bool hint_twins = false;
+    int hint_pair = 1;
+    struct LayerHints {
+        fgdm_engine& e;
+        const bool twins0;
+        const int pair0;
+        LayerHints(fgdm_engine& e_, bool twins, int pair_mult = 0) : e(e_), twins0(e_.hint_twins), pair0(e_.hint_pair) {
+            e.set_hints(twins, pair_mult > 0 ? pair_mult : pair0);
+        }
+        ~LayerHints() { e.set_hints(twins0, pair0); }
+        LayerHints(const LayerHints&) = delete;
+    };
+    void set_hints(bool twins, int pair_mult) {
+        igemm_set_twin_layers(hint_twins = twins);
+        igemm_set_pair_hint(hint_pair = pair_mult);
+    }
+
+    // ControlNet.forward (cldm.py:792-813).  fused = true: every zero-conv output is scaled and ADDED in place into
+    // the UNet's skip tensor hs[i] / h_mid (cldm.py:40,46 + :846), so control residuals never hit HBM separately.
+    // fused = false: raw residuals are written as fp32 NCHW into out32 (test entry).
     int controlnet_fwd(Net& n, const Tensor& x4, const int64_t* t, const float* tf, const Tensor& ctx16, const float* scales,
                        std::vector<Tensor>* hs, Tensor* h_mid, bool only_mid, float* out32, int64_t out_cap, bool pairs = false,
                        std::vector<Deferred>* defer = nullptr) {
         const int B = x4.B;
-        struct TwinGuard { TwinGuard() { igemm_set_twin_layers(true); } ~TwinGuard() { igemm_set_twin_layers(false); } } twin_guard;
+        LayerHints twins(*this, true);
         // CFG pairs: rows b and b + B/2 carry the same x, t and hint -> input blocks 0 and 1 (up to the first
         // cross-attention) are evaluated once on B/2 rows
         const bool shared = pairs && !out32 && 2 * n.guided.B == B && n.input.size() > 1;
@@ -1730,6 +1630,18 @@ struct fgdm_engine {
         return FGDM_OK;
     }
 
+    // controlnet_fwd for every ControlNet of the engine (residuals into hs / h_mid, or deferred), each inside the scope that
+    // `per_net(c)` returns: the list that records it and the arena that serves it
+    template <class PerNet>
+    int controlnets_fwd(const Tensor& x4, const int64_t* t, const float* tf, const Tensor& ctx16, const float* scales, std::vector<Tensor>* hs,
+                        Tensor* h_mid, bool only_mid, bool pairs, std::vector<Deferred>* defer, PerNet per_net) {
+        for (size_t c = 0; c < cns.size(); ++c) {
+            RecordScope scope = per_net(c);
+            CHK(controlnet_fwd(cns[c], x4, t, tf, ctx16, scales ? scales + 13 * c : nullptr, hs, h_mid, only_mid, nullptr, 0, pairs, defer));
+        }
+        return FGDM_OK;
+    }
+
     int apply_model(const float* x, const int64_t* t, const float* tf, const float* ctx, const float* pcond,
                     const float* scales, int B, int H, int W, int flags, float* eps_out) {
         if (!finalized) return fail(FGDM_ERR_STATE, "weights not finalized");
@@ -1777,93 +1689,79 @@ struct fgdm_engine {
                 CHK(n.time_adapter ? time_adapter_fwd(n, x4s, ec, fa) : adapter_fwd(n, x4s, fa));
             }
         }
-        // ---- twin streams: the ControlNets start now, next to the UNet encoder
+        // ---- the ControlNets are independent of the UNet's encoder + middle block (cldm.py:40,46).  Twin streams: they run next to it
         const bool with_cn = !cns.empty() && !(flags & FGDM_FLAG_NO_CONTROL);
         const bool twin = twin_streams && with_cn && s2 && !(flags & FGDM_FLAG_ONLY_MID_CONTROL);
         std::vector<Deferred> deferred;
-        // ---- grouped twin launches: record the ControlNet walks now, the UNet encoder + middle block below, replay them together
+        // ---- grouped twin launches: record the ControlNet walks, then the UNet encoder + middle block, and replay them together
         const bool paired = pair_launch && with_cn && !twin && !(flags & FGDM_FLAG_ONLY_MID_CONTROL);
-        std::vector<std::vector<RecOp>> rec_cn(paired ? cns.size() : 0);
-        std::vector<RecOp> rec_un;
-        struct RecGuard { ~RecGuard() { g_rec = nullptr; igemm_set_pair_hint(1); } } rec_guard;   // whatever path leaves: recording ends
-        if (paired) {
-            const bool fat = knob_once(KNOB_PAIR_FAT_TILES) != 0;      // A/B knob
-            if (fat) igemm_set_pair_hint(std::min<int>(group_max, 1 + (int)cns.size()));
-            groupnorm_set_group(gn_group);
-            int rc = FGDM_OK;
-            for (size_t c = 0; c < cns.size() && rc == FGDM_OK; ++c) {
-                ar = cn_arena[c].get();           // an arena per walk: see cn_arena
-                g_rec = &rec_cn[c];
-                rc = controlnet_fwd(cns[c], x4, t, tf, ctx16, scales ? scales + 13 * c : nullptr, nullptr, nullptr, false, nullptr, 0, pairs,
-                                    &deferred);
-            }
-            g_rec = nullptr;
-            ar = &arena;
-            if (rc != FGDM_OK) return rc;
-            g_rec = &rec_un;
-        }
-        if (twin) {
-            if (hipEventRecord(ev_fork, s) != hipSuccess || hipStreamWaitEvent(s2, ev_fork, 0) != hipSuccess) return fail(FGDM_ERR_HIP, "stream fork");
-            hipStream_t main_s = s;
-            s = s2; ar = cn_arena[0].get();
-            int rc = FGDM_OK;
-            for (size_t c = 0; c < cns.size() && rc == FGDM_OK; ++c)
-                rc = controlnet_fwd(cns[c], x4, t, tf, ctx16, scales ? scales + 13 * c : nullptr, nullptr, nullptr, false, nullptr, 0, pairs,
-                                    &deferred);
-            s = main_s; ar = &arena;
-            if (rc != FGDM_OK) return rc;
-            if (hipEventRecord(ev_join, s2) != hipSuccess) return fail(FGDM_ERR_HIP, "stream join");
-        }
         // ---- encoder (openaimodel.py:849-858); the adapter feature is added BEFORE the skip is recorded
-        struct TwinOff { ~TwinOff() { igemm_set_twin_layers(false); } } twin_off;      // whatever path leaves
-        igemm_set_twin_layers(with_cn);             // encoder + middle block: the ControlNets' twins (a ControlNet walk ends with it off)
         std::vector<Tensor> hs;
-        Tensor h;
-        int k = 0;
-        Tensor h0s;        // input block 0 on the shared rows (CFG pairs)
-        for (size_t i = 0; i < n.input.size(); ++i) {
-            Tensor nxt;
-            if (pairs && i == 0) {
-                CHK(block_fwd(n.input[0], x4s, false, nullptr, ec, ctx16, nullptr, &h0s));
-                CHK(dup_rows(h0s, &nxt));                                        // the skip tensor hs[0] needs all B rows
-            } else if (pairs && i == 1) {
-                CHK(block_fwd_shared(n.input[1], h0s, true, ec, ctx16, &nxt));   // B/2 rows in, B rows out
-            } else {
-                CHK(block_fwd(n.input[i], i == 0 ? x4 : h, false, nullptr, ec, ctx16, nullptr, &nxt));
-            }
-            if (use_adapter && (i + 1) % 3 == 0) {
-                // the adapter features cover Bs rows; with CFG pairs each is added to both halves
-                if (k >= 4 || fa[k].numel() * (size_t)(B / Bs) != nxt.numel()) return fail(FGDM_ERR_ARG, "adapter feature shape mismatch (latent size must be divisible by 8)");
-                for (int half = 0; half < B / Bs; ++half) {
-                    half_t* dst = nxt.p + (size_t)half * fa[k].numel();
-                    if (n.xad_valid) {   // h = h + fk + fa[adapter_idx] (openaimodel.py:1301-1305): fk first, like the reference's sum order
-                        if (n.xad_sum[k].numel() != nxt.numel()) return fail(FGDM_ERR_ARG, "registered adapter conds do not match this batch / latent size");
-                        const half_t* xs = n.xad_sum[k].p + (size_t)half * fa[k].numel();
-                        if (add_f16(dst, xs, dst, fa[k].numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "add kernel");
-                    }
-                    if (add_f16(dst, fa[k].p, dst, fa[k].numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "add kernel");
+        Tensor h, hm;
+        auto encoder = [&]() -> int {
+            LayerHints twins(*this, with_cn);                // encoder + middle block: the ControlNets' twins
+            int k = 0;
+            Tensor h0s;        // input block 0 on the shared rows (CFG pairs)
+            for (size_t i = 0; i < n.input.size(); ++i) {
+                Tensor nxt;
+                if (pairs && i == 0) {
+                    CHK(block_fwd(n.input[0], x4s, false, nullptr, ec, ctx16, nullptr, &h0s));
+                    CHK(dup_rows(h0s, &nxt));                                        // the skip tensor hs[0] needs all B rows
+                } else if (pairs && i == 1) {
+                    CHK(block_fwd_shared(n.input[1], h0s, true, ec, ctx16, &nxt));   // B/2 rows in, B rows out
+                } else {
+                    CHK(block_fwd(n.input[i], i == 0 ? x4 : h, false, nullptr, ec, ctx16, nullptr, &nxt));
                 }
-                tfree(fa[k]);
-                ++k;
+                if (use_adapter && (i + 1) % 3 == 0) {
+                    // the adapter features cover Bs rows; with CFG pairs each is added to both halves
+                    if (k >= 4 || fa[k].numel() * (size_t)(B / Bs) != nxt.numel()) return fail(FGDM_ERR_ARG, "adapter feature shape mismatch (latent size must be divisible by 8)");
+                    for (int half = 0; half < B / Bs; ++half) {
+                        half_t* dst = nxt.p + (size_t)half * fa[k].numel();
+                        if (n.xad_valid) {   // h = h + fk + fa[adapter_idx] (openaimodel.py:1301-1305): fk first, like the reference's sum order
+                            if (n.xad_sum[k].numel() != nxt.numel()) return fail(FGDM_ERR_ARG, "registered adapter conds do not match this batch / latent size");
+                            const half_t* xs = n.xad_sum[k].p + (size_t)half * fa[k].numel();
+                            if (add_f16(dst, xs, dst, fa[k].numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "add kernel");
+                        }
+                        if (add_f16(dst, fa[k].p, dst, fa[k].numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "add kernel");
+                    }
+                    tfree(fa[k]);
+                    ++k;
+                }
+                h = nxt;
+                hs.push_back(h);
             }
-            h = nxt;
-            hs.push_back(h);
-        }
-        Tensor hm;
-        CHK(block_fwd(n.middle, h, false, nullptr, ec, ctx16, nullptr, &hm));
-        igemm_set_twin_layers(false);
-        // ---- ControlNets: residuals accumulate in place into hs / hm (cldm.py:40,46,846)
+            CHK(block_fwd(n.middle, h, false, nullptr, ec, ctx16, nullptr, &hm));
+            return FGDM_OK;
+        };
         if (paired) {
-            g_rec = nullptr;
-            igemm_set_pair_hint(1);
-            // the UNet and ALL its ControlNets in one lockstep replay (FGDM_GROUP_MAX=2: pairwise, as in round 3)
-            std::vector<std::vector<RecOp>*> lists{&rec_un};
-            for (size_t c = 0; c < rec_cn.size(); ++c) {
-                if ((int)lists.size() == group_max) { CHK(replay_group(lists)); lists.clear(); }
-                lists.push_back(&rec_cn[c]);
+            std::vector<RecWalk> walks(1 + cns.size());      // the UNet's, then one per ControlNet
+            {
+                const bool fat = knob_once(KNOB_PAIR_FAT_TILES) != 0;      // A/B knob
+                LayerHints fused(*this, false, fat ? std::min<int>(group_max, 1 + (int)cns.size()) : 0);
+                groupnorm_set_group(gn_group);
+                CHK(controlnets_fwd(x4, t, tf, ctx16, scales, nullptr, nullptr, false, pairs, &deferred,         // an arena per walk: see cn_arena
+                                    [&](size_t c) { return RecordScope(*this, &walks[1 + c], cn_arena[c].get()); }));
+                RecordScope rec(*this, &walks[0], &arena);
+                CHK(encoder());
             }
-            CHK(replay_group(lists));
+            // the UNet and ALL its ControlNets in one lockstep replay (FGDM_GROUP_MAX=2: pairwise, as in round 3)
+            std::vector<RecWalk*> lists;
+            for (RecWalk& w : walks) lists.push_back(&w);
+            CHK(fgdm_replay(lists, group_max, s, prof, replay_stats));
+        } else {
+            if (twin) {      // the ControlNets start now, on the second stream, next to the UNet encoder
+                if (hipEventRecord(ev_fork, s) != hipSuccess || hipStreamWaitEvent(s2, ev_fork, 0) != hipSuccess) return fail(FGDM_ERR_HIP, "stream fork");
+                hipStream_t main_s = s;
+                s = s2;
+                const int rc = controlnets_fwd(x4, t, tf, ctx16, scales, nullptr, nullptr, false, pairs, &deferred,
+                                               [&](size_t) { return RecordScope(*this, nullptr, cn_arena[0].get()); });
+                s = main_s;
+                if (rc != FGDM_OK) return rc;
+                if (hipEventRecord(ev_join, s2) != hipSuccess) return fail(FGDM_ERR_HIP, "stream join");
+            }
+            CHK(encoder());
         }
+        // ---- ControlNets: residuals accumulate in place into hs / hm (cldm.py:40,46,846)
         if (twin || paired) {
             if (twin && hipStreamWaitEvent(s, ev_join, 0) != hipSuccess) return fail(FGDM_ERR_HIP, "stream join");
             for (const Deferred& d : deferred) CHK(zero_conv_into(*d.w, d.src, d.idx < 0 ? hm : hs[d.idx], d.scale));
@@ -1871,9 +1769,8 @@ struct fgdm_engine {
             // waits for that call's fork event, recorded behind these zero-convs
             for (Deferred& d : deferred) { d.owner->release(d.src.p); d.src.p = nullptr; }
         } else if (with_cn) {
-            for (size_t c = 0; c < cns.size(); ++c)
-                CHK(controlnet_fwd(cns[c], x4, t, tf, ctx16, scales ? scales + 13 * c : nullptr, &hs, &hm,
-                                   (flags & FGDM_FLAG_ONLY_MID_CONTROL) != 0, nullptr, 0, pairs));
+            CHK(controlnets_fwd(x4, t, tf, ctx16, scales, &hs, &hm, (flags & FGDM_FLAG_ONLY_MID_CONTROL) != 0, pairs, nullptr,
+                                [&](size_t) { return RecordScope(*this, nullptr, &arena); }));
         }
         // ---- decoder (openaimodel.py:868-870): virtual concat [h, skip]
         h = hm;
@@ -2209,8 +2106,8 @@ void fgdm_destroy(fgdm_engine* e) {
     e->drop_concat();
     e->drop_context();
     e->drop_adapter_conds();
-    if (knob_text(KNOB_PAIR_DEBUG) && e->replayed_launches)
-        fprintf(stderr, "[fgdm] grouped twin launches: %ld of %ld replayed launches were fused (%ld problems)\n", e->paired_launches, e->replayed_launches, e->paired_problems);
+    if (knob_text(KNOB_PAIR_DEBUG) && e->replay_stats.replayed)
+        fprintf(stderr, "[fgdm] grouped twin launches: %ld of %ld replayed launches were fused (%ld problems)\n", e->replay_stats.fused, e->replay_stats.replayed, e->replay_stats.problems);
     if (e->s2) { (void)hipStreamSynchronize(e->s2); (void)hipStreamDestroy(e->s2); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
@@ -2347,9 +2244,9 @@ int fgdm_workspace_stats(fgdm_engine* e, int64_t* peak_bytes, int64_t* reserved_
 
 int fgdm_launch_stats(fgdm_engine* e, int64_t* replayed_launches, int64_t* fused_launches, int64_t* fused_problems) {
     if (!e || !replayed_launches || !fused_launches || !fused_problems) return FGDM_ERR_ARG;
-    *replayed_launches = (int64_t)e->replayed_launches;
-    *fused_launches = (int64_t)e->paired_launches;
-    *fused_problems = (int64_t)e->paired_problems;
+    *replayed_launches = (int64_t)e->replay_stats.replayed;
+    *fused_launches = (int64_t)e->replay_stats.fused;
+    *fused_problems = (int64_t)e->replay_stats.problems;
     return FGDM_OK;
 }
 

@@ -1192,15 +1192,16 @@ int launch2p(const IgemmArgs& a, hipStream_t s) {
         if constexpr (PIPE != 0 && PATH != 0 && !SPLIT && !ABL && MS == 16) {
             constexpr auto kp = igemm2_pair_kernel<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>;
             if (fgdm_dyn_lds<kp>(smem) != FGDM_OK) return FGDM_ERR_HIP;
-            IgemmGroupFn pf = [](const IgemmArgs* const* av, int n, unsigned grid_x, hipStream_t rs) -> int {
+            static_assert(sizeof(IgemmArgs) <= FGDM_GROUP_BLOB, "the recorded blob holds an IgemmArgs");
+            FgdmGroupFn pf = [](const void* const* av, int n, unsigned grid_x, hipStream_t rs) -> int {
                 if (n < 2 || n > FGDM_MAX_GROUP) return FGDM_ERR_ARG;
                 IgemmArgsG pg;
-                for (int i = 0; i < FGDM_MAX_GROUP; ++i) pg.g[i] = *av[i < n ? i : 0];
+                for (int i = 0; i < FGDM_MAX_GROUP; ++i) pg.g[i] = *(const IgemmArgs*)av[i < n ? i : 0];
                 hipLaunchKernelGGL((igemm2_pair_kernel<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>), dim3(grid_x, n),
                                    dim3(WM * WN * 64), smem, rs, pg);
                 return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
             };
-            fgdm_record(single, (const void*)kp, pf, &a, gx);
+            fgdm_record(single, (const void*)kp, pf, &a, sizeof(a), gx, 0);      // shape 0: key and grid say it all
         } else {
             fgdm_record(single);
         }

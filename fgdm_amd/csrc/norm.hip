@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
 // launch disappears (these calls were latency-bound: 24 us for a 5 MB tensor at the 8x8 level).  Same fixed-order
 // reductions as the two-kernel path -> bitwise independent of the batch.
 // Twin layers (the UNet encoder's and every ControlNet's GroupNorm of the same shape) share ONE launch of the single-pass kernels:
-// blockIdx.y selects the problem (engine.hip: replay_group).  Same bodies -> same bits.
+// blockIdx.y selects the problem (replay.h: fgdm_replay).  Same bodies -> same bits.
 struct GnProb { const half_t* x0; const half_t* x1; const float* gamma; const float* beta; half_t* out; };
 struct GnArgsG { GnProb p[FGDM_MAX_GROUP]; int C0, C1, B, HW, NG, silu; float eps; };
 struct GnRec { GnProb p; int C0, C1, B, HW, NG, silu; float eps; int np_sel; unsigned smem; };     // what a recorded launch keeps (<= FGDM_GROUP_BLOB)
@@ -433,8 +433,9 @@ static int gn_single_pass_launch(const GnRec& r, unsigned grid_x, hipStream_t s)
     const void* args[1] = {&r};
     if (!fgdm_recording()) return gn_group_fn(args, 1, grid_x, s);
     const GnRec rc = r;
-    fgdm_record_generic([rc, grid_x](hipStream_t rs) -> int { const void* a1[1] = {&rc}; return gn_group_fn(a1, 1, grid_x, rs); },
-                        (const void*)&gn_group_fn, g_gn_group ? gn_group_fn : nullptr, &r, sizeof(r), grid_x, gn_shape_hash(r, r.np_sel));
+    static_assert(sizeof(GnRec) <= FGDM_GROUP_BLOB, "the recorded blob holds a GnRec");
+    fgdm_record([rc, grid_x](hipStream_t rs) -> int { const void* a1[1] = {&rc}; return gn_group_fn(a1, 1, grid_x, rs); },
+                (const void*)&gn_group_fn, g_gn_group ? gn_group_fn : nullptr, &r, sizeof(r), grid_x, gn_shape_hash(r, r.np_sel));
     return FGDM_OK;
 }
 

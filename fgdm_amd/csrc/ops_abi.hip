@@ -2,6 +2,7 @@
 // buffers, for the per-kernel parity tests.  No engine: they restate the weight packing and the IgemmArgs on their own, and
 // share with engine.hip only the launch sequences of engine_shared.h (im2col_conv, vattn_core, conv3_kmap).
 #include "engine_shared.h"
+#include "replay_plan.h"
 
 // The host-side packing of every entry below.  w [N][Ks] and bias [N] (or null), fp32 on the host or the device, become what the
 // GEMM kernels read: a.Wt [igemm_npad(N)][K] fp16 and a.bias [npad] fp32 on the device (owned by `tmp`; pad rows and columns zero).
@@ -307,6 +308,23 @@ int fgdm_op_timestep_embed(const int64_t* t, const float* t_float, void* y, int 
 int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream) {
     if (!a || !b || !y || n <= 0 || (n & 7)) return FGDM_ERR_ARG;
     return add_f16((const half_t*)a, (const half_t*)b, (half_t*)y, (size_t)n, as_stream(stream));
+}
+
+// Host-only entry of tests/test_replay_plan.py: the planner of replay_plan.h on caller-made walks.  Never touches the device.
+int fgdm_replay_plan(int n_walks, const int32_t* lens, const uint64_t* key, const uint32_t* grid_x, const uint64_t* shape, int group_max,
+                     int chunk, int32_t* out, int out_cap, int* limits) {
+    if (limits) { limits[0] = REPLAY_LOOK; limits[1] = FGDM_MAX_GROUP; }
+    if (n_walks < 0 || group_max < 1 || out_cap < 0 || (n_walks && !lens) || (out_cap && !out)) return FGDM_ERR_ARG;
+    std::vector<PlanWalk> walks(n_walks);
+    size_t u = 0;
+    for (int w = 0; w < n_walks; ++w) {
+        if (lens[w] < 0 || (lens[w] && (!key || !grid_x || !shape))) return FGDM_ERR_ARG;
+        for (int i = 0; i < lens[w]; ++i, ++u) walks[w].push_back(PlanUnit{key[u], grid_x[u], shape[u]});
+    }
+    std::vector<int32_t> steps;
+    replay_plan_chunked(walks.data(), n_walks, chunk, group_max, REPLAY_LOOK, steps);
+    for (size_t i = 0; i < steps.size() && i < (size_t)out_cap; ++i) out[i] = steps[i];
+    return (int)steps.size();
 }
 
 }  // extern "C"

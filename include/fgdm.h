@@ -283,6 +283,15 @@ int fgdm_workspace_stats(fgdm_engine* e, int64_t* peak_bytes, int64_t* reserved_
  * layer shape): launches replayed from recorded walks since fgdm_create, how many of them were fused launches, and how many
  * problems those carried.  Diagnostic: the tests assert that the fused kernel really ran. */
 int fgdm_launch_stats(fgdm_engine* e, int64_t* replayed_launches, int64_t* fused_launches, int64_t* fused_problems);
+/* The order in which recorded walks replay, without a device (the planner behind those grouped launches, for the tests).  Walk w has
+ * lens[w] units; unit u (walks concatenated) is (key[u], grid_x[u], shape[u]), key 0 = it has no grouped form.  The walks are cut
+ * into runs of `chunk` (<= 0: one run) as fgdm_apply_model cuts them by FGDM_GROUP_MAX, and every run is scheduled for grouped
+ * launches of up to `group_max` (>= 1) members.  out receives the steps, each  n, (walk, unit) x n : n == 1 a unit on its own,
+ * n >= 2 one grouped launch; at most out_cap values are written.  Returns the number of values of the whole schedule (< 0: bad
+ * arguments); limits (may be NULL) receives [0] how many of a walk's pending units are searched for a group's member and [1] the
+ * largest group the engine launches (FGDM_MAX_GROUP). */
+int fgdm_replay_plan(int n_walks, const int32_t* lens, const uint64_t* key, const uint32_t* grid_x, const uint64_t* shape,
+                     int group_max, int chunk, int32_t* out, int out_cap, int* limits);
 
 /* Per-kernel entry points used by the parity tests (tests/test_gpu_ops.py); weights given in the reference's
  * native layouts (fp32, [Cout,Cin,kh,kw] / [N,K]) and packed on the fly.  Activations fp16 NHWC.
