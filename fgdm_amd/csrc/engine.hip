@@ -1,14 +1,14 @@
-// FG-DM sampling engine: model graph (SD-v1.x UNet + FG-DM adapter + ControlNet twin encoders), weight
-// repacking into kernel layouts, activation workspace, and the forward passes, all as launches of the
+// FG-DM sampling engine: weight repacking of the model graph (model.h: SD-v1.x UNet + FG-DM adapter + ControlNet twin encoders,
+// first stage, text encoder) into kernel layouts, activation workspace, and the forward passes, all as launches of the
 // hand-written gfx950 kernels in this directory.  No torch, no BLAS: only the HIP runtime.
 //
 // Reference structure being reproduced (file:line in the reference checkout):
-//   UNetModel.__init__/forward      ldm/modules/diffusionmodules/openaimodel.py:469-734, 808-884 (753-806 original)
+//   UNetModel.forward               ldm/modules/diffusionmodules/openaimodel.py:808-884 (753-806 original)
 //   ResBlock._forward               openaimodel.py:275-301
 //   SpatialTransformer & friends    ldm/modules/attention.py:152-292
 //   Adapter                         ldm/modules/encoders/adapter.py:280-346
 //   ControlNet / ControlledUnet     controlnet/cldm/cldm.py:27-50, 545-813, 836-849
-#include "engine_shared.h"
+#include "model.h"
 #include "knobs.h"
 #include "replay.h"
 
@@ -87,107 +87,6 @@ struct Arena {
     }
 };
 
-struct Tensor {
-    half_t* p = nullptr;
-    int B = 0, H = 0, W = 0, C = 0;
-    size_t numel() const { return (size_t)B * H * W * C; }
-    int rows() const { return B * H * W; }
-};
-
-struct ParamSlot {
-    std::vector<int64_t> shape;
-    std::vector<float> host;
-    bool loaded = false;
-    size_t numel() const { size_t n = 1; for (auto d : shape) n *= (size_t)d; return n; }
-};
-
-struct GemmW {              // packed [npad][K] fp16 weight + fp32 bias (packed column order)
-    half_t* w = nullptr;
-    float* bias = nullptr;
-    int N = 0, K = 0;
-    bool im2col = false;    // conv3x3 whose Cin is not a multiple of 64: K = roundup64(9 * cin_pad)
-    int cin_pad = 0;
-    int k_real = 0;         // un-padded contraction length (algorithmic flop accounting)
-    float* ln_u = nullptr;  // LayerNorm folded in: u[n] = sum_k W'[n][k] (packed order); bias then holds sum_k beta_k W_nk + b_n
-    float ln_eps = 1e-5f;
-};
-struct NormW { float* g = nullptr; float* b = nullptr; int C = 0; };
-
-enum LType { L_CONV, L_RES, L_ATTN, L_DOWN, L_UP };
-struct Layer {
-    LType type = L_CONV;
-    int cin = 0, cout = 0, heads = 0;
-    bool down = false;                                     // L_RES with AvgPool2d(2) on both branches (TimeAdapter)
-    std::string pre;
-    GemmW conv;                                            // L_CONV / L_DOWN / L_UP
-    NormW gn1, gn2; GemmW c1, c2, skip; int emb_off = 0;   // L_RES
-    NormW gn, ln1, ln2, ln3;                               // L_ATTN
-    GemmW pin, pout, qkv1, o1, q2, k2, v2, o2, ffp, ffo;     // qkv1: attn1's to_q | to_k | to_v stacked (one GEMM)
-};
-typedef std::vector<Layer> Block;
-
-struct AdapterBlk { int ic = 0, oc = 0; bool down = false; std::string pre; GemmW in_conv, b1, b2; };
-
-struct Net {
-    std::string prefix;
-    bool control = false;
-    GemmW time0, time2, emb_all;
-    int emb_total = 0;
-    std::vector<Block> input, output;
-    Block middle;
-    NormW out_gn; GemmW out_conv;                          // UNet only
-    bool has_adapter = false;                              // UNet only
-    GemmW ad_conv_in; std::vector<AdapterBlk> ad_body;
-    // AdaptUNetModel (openaimodel.py:993-999): num_prompts - 1 further Adapters over extra condition images; their
-    // features do not depend on x or t, so their sum is computed once per set of conds (fgdm_set_adapter_conds)
-    std::vector<GemmW> xad_conv_in; std::vector<std::vector<AdapterBlk>> xad_body;
-    Tensor xad_sum[4]; bool xad_valid = false;
-    bool time_adapter = false; Block tad_body;             // TimeAdapter: time-conditioned ResBlocks (adapter.py:387-417)
-    std::vector<GemmW> zero_convs; GemmW mid_out;          // ControlNet only
-    std::vector<int> zero_ch;
-    GemmW hint_convs[8];
-    Tensor guided;                                         // cached input_hint_block output (persistent hipMalloc)
-};
-
-// First-stage decoder (AutoencoderKL.decode; ldm/modules/diffusionmodules/model.py:462-560)
-struct VRes { int cin = 0, cout = 0; std::string pre; NormW n1, n2; GemmW c1, c2, nin; };
-struct VLevel { std::vector<VRes> blocks; bool up = false; std::string up_pre; GemmW upconv; };
-struct VAttn { std::string pre; NormW norm; GemmW q, k, v, o; };      // AttnBlock (model.py:146-203)
-// First-stage encoder (AutoencoderKL.encode; model.py:368-460), present when fgdm_config::vae_encoder is set
-struct VDown { std::vector<VRes> blocks; bool down = false; std::string down_pre; GemmW downconv; };
-struct VEnc {
-    bool on = false;
-    GemmW conv_in, conv_out;
-    std::vector<VDown> levels;             // execution order: full resolution first
-    VRes mid1, mid2;
-    VAttn attn;
-    NormW norm_out;
-    float* qc = nullptr;                   // quant_conv: 64 weights [co][ci] + 8 biases
-};
-struct Vae {
-    bool on = false, packed = false;
-    std::string prefix;
-    int top = 0, factor = 1;
-    GemmW conv_in, conv_out;
-    VRes mid1, mid2;
-    VAttn attn;
-    std::vector<VLevel> levels;            // execution order: deepest level first
-    NormW norm_out;
-    float* pq = nullptr;                   // post_quant_conv: 16 weights [co][ci] + 4 biases
-    VEnc enc;
-};
-
-// CLIP text encoder (transformers.CLIPTextModel behind FrozenCLIPEmbedder; ldm/modules/encoders/modules.py:137-162)
-struct ClipLayer { std::string pre; NormW ln1, ln2; GemmW qkv, o, fc1, fc2; };
-struct Clip {
-    bool on = false, packed = false;
-    std::string prefix;
-    float* tok = nullptr;     // [vocab][W] fp32 (nn.Embedding is not an autocast op: the residual stream starts in fp32)
-    float* pos = nullptr;     // [max_len][W] fp32
-    std::vector<ClipLayer> layers;
-    NormW final_ln;
-};
-
 // Built-in kernel timer: when enabled, every launch is bracketed by HIP events recorded on the launch stream
 // (the same stream the kernels run on), so per-kernel-class device time, launch counts and the ALGORITHMIC
 // flops / bytes of exactly those launches can be read back without an external profiler.
@@ -243,18 +142,9 @@ struct Prof final : LaunchTimer {
 
 }  // namespace
 
-#define CHK0(x) do { int _rc0 = (x); if (_rc0 != FGDM_OK) return _rc0; } while (0)
-struct fgdm_engine {
-    fgdm_config cfg{};
+struct fgdm_engine : Model {
     int device = -1;
     bool device_ready = false, finalized = false;
-    std::string err;
-    std::vector<std::string> order;
-    std::unordered_map<std::string, ParamSlot> params;
-    Net unet;
-    std::vector<Net> cns;
-    Vae vae;
-    Clip clip;
     // cross-attention K / V^T of a registered context (fgdm_set_context): constant over the denoising steps
     struct CtxKV { Tensor k, vt; };
     std::unordered_map<const Layer*, CtxKV> ctx_cache;
@@ -265,10 +155,7 @@ struct fgdm_engine {
     Tensor ccat;
     Arena arena;
     half_t* zero = nullptr;
-    // packed weights in HBM, per component (state-dict prefix): re-packing a component frees its previous copy
-    std::unordered_map<std::string, std::vector<void*>> weight_allocs;
-    std::unordered_map<std::string, bool> comp_dirty, comp_packed;
-    std::string cur_comp;
+    int cur_comp = -1;            // the component being packed: its Component::allocs takes the uploads
     // LayerNorms of the transformer blocks folded into the GEMMs they feed (default) or run as kernels of their own
     // (FGDM_LN_FOLD=0 at fgdm_create: the A/B switch for tools/ab_bench.sh; numerics differ only in rounding points)
     bool ln_fold = true;
@@ -294,313 +181,6 @@ struct fgdm_engine {
     struct Deferred { const GemmW* w; Tensor src; int idx; float scale; Arena* owner; };
     Prof prof;
 
-    int fail(int code, const std::string& m) { err = m; return code; }
-
-    // ------------------------------------------------------------------------------------ graph + registry
-    void reg(const std::string& name, std::vector<int64_t> shape) {
-        order.push_back(name);
-        params[name].shape = std::move(shape);
-    }
-    void reg_wb(const std::string& pre, std::vector<int64_t> wshape) {
-        const int64_t n = wshape[0];
-        reg(pre + ".weight", std::move(wshape));
-        reg(pre + ".bias", {n});
-    }
-    void reg_res(const std::string& p, int cin, int cout, int temb) {
-        reg_wb(p + "in_layers.0", {cin});
-        reg_wb(p + "in_layers.2", {cout, cin, 3, 3});
-        reg_wb(p + "emb_layers.1", {cout, temb});
-        reg_wb(p + "out_layers.0", {cout});
-        reg_wb(p + "out_layers.3", {cout, cout, 3, 3});
-        if (cin != cout) reg_wb(p + "skip_connection", {cout, cin, 1, 1});
-    }
-    void reg_attn(const std::string& p, int ch, int ctx) {
-        reg_wb(p + "norm", {ch});
-        reg_wb(p + "proj_in", {ch, ch, 1, 1});
-        const std::string t = p + "transformer_blocks.0.";
-        reg(t + "attn1.to_q.weight", {ch, ch});
-        reg(t + "attn1.to_k.weight", {ch, ch});
-        reg(t + "attn1.to_v.weight", {ch, ch});
-        reg_wb(t + "attn1.to_out.0", {ch, ch});
-        reg_wb(t + "ff.net.0.proj", {8 * ch, ch});
-        reg_wb(t + "ff.net.2", {ch, 4 * ch});
-        reg(t + "attn2.to_q.weight", {ch, ch});
-        reg(t + "attn2.to_k.weight", {ch, ctx});
-        reg(t + "attn2.to_v.weight", {ch, ctx});
-        reg_wb(t + "attn2.to_out.0", {ch, ch});
-        reg_wb(t + "norm1", {ch});
-        reg_wb(t + "norm2", {ch});
-        reg_wb(t + "norm3", {ch});
-        reg_wb(p + "proj_out", {ch, ch, 1, 1});
-    }
-    void reg_block(const std::string& pre, Block& blk, int temb, int ctx) {
-        for (size_t j = 0; j < blk.size(); ++j) {
-            Layer& l = blk[j];
-            l.pre = pre + std::to_string(j) + ".";
-            switch (l.type) {
-                case L_CONV: reg_wb(l.pre.substr(0, l.pre.size() - 1), {l.cout, l.cin, 3, 3}); break;
-                case L_RES: reg_res(l.pre, l.cin, l.cout, temb); break;
-                case L_ATTN: reg_attn(l.pre, l.cin, ctx); break;
-                case L_DOWN: reg_wb(l.pre + "op", {l.cin, l.cin, 3, 3}); break;
-                case L_UP: reg_wb(l.pre + "conv", {l.cin, l.cin, 3, 3}); break;
-            }
-        }
-    }
-    static Layer mk(LType t, int cin, int cout, int heads = 0) {
-        Layer l; l.type = t; l.cin = cin; l.cout = cout; l.heads = heads; return l;
-    }
-    bool in_ares(int ds) const {
-        for (int i = 0; i < cfg.n_attention_resolutions; ++i) if (cfg.attention_resolutions[i] == ds) return true;
-        return false;
-    }
-    // openaimodel.py:558-718 / cldm.py:640-787
-    void build_net(Net& n, const std::string& prefix, bool control, int adapter_kind) {
-        const bool adapter = adapter_kind == 1;
-        n.prefix = prefix; n.control = control; n.has_adapter = adapter_kind != 0; n.time_adapter = adapter_kind == 2;
-        const int mc = cfg.model_channels, temb = 4 * mc, ctx = cfg.context_dim, heads = cfg.num_heads;
-        reg_wb(prefix + "time_embed.0", {temb, mc});
-        reg_wb(prefix + "time_embed.2", {temb, temb});
-        if (adapter) {   // registration order of the reference: adapter precedes input_blocks (openaimodel.py:551-558)
-            static const int chs[4] = {320, 640, 1280, 1280};
-            const std::string ap = prefix + "adapter.";
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 2; ++j) {
-                    AdapterBlk b;
-                    b.down = (i != 0 && j == 0);
-                    b.ic = b.down ? chs[i - 1] : chs[i];
-                    b.oc = chs[i];
-                    b.pre = ap + "body." + std::to_string(i * 2 + j) + ".";
-                    if (b.ic != b.oc) reg_wb(b.pre + "in_conv", {b.oc, b.ic, 1, 1});
-                    reg_wb(b.pre + "block1", {b.oc, b.oc, 3, 3});
-                    reg_wb(b.pre + "block2", {b.oc, b.oc, 1, 1});
-                    n.ad_body.push_back(b);
-                }
-            reg_wb(ap + "conv_in", {chs[0], cfg.in_channels, 3, 3});
-            const int nx = control ? 0 : cfg.n_extra_adapters;
-            n.xad_conv_in.resize(nx); n.xad_body.resize(nx);
-            for (int kk = 0; kk < nx; ++kk) {
-                const std::string xp = prefix + "adapters." + std::to_string(kk) + ".";
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 2; ++j) {
-                        AdapterBlk b;
-                        b.down = (i != 0 && j == 0);
-                        b.ic = b.down ? chs[i - 1] : chs[i];
-                        b.oc = chs[i];
-                        b.pre = xp + "body." + std::to_string(i * 2 + j) + ".";
-                        if (b.ic != b.oc) reg_wb(b.pre + "in_conv", {b.oc, b.ic, 1, 1});
-                        reg_wb(b.pre + "block1", {b.oc, b.oc, 3, 3});
-                        reg_wb(b.pre + "block2", {b.oc, b.oc, 1, 1});
-                        n.xad_body[kk].push_back(b);
-                    }
-                reg_wb(xp + "conv_in", {chs[0], cfg.in_channels, 3, 3});
-            }
-        }
-        if (n.time_adapter) {   // TimeAdapter(cin, [320,640,1280,1280], nums_rb=2, use_conv=False): openaimodel.py:554
-            static const int chs[4] = {320, 640, 1280, 1280};
-            const std::string ap = prefix + "adapter.";
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 2; ++j) {
-                    const bool down = (i != 0 && j == 0);
-                    Layer l = mk(L_RES, down ? chs[i - 1] : chs[i], chs[i]);
-                    l.down = down;
-                    l.pre = ap + "body." + std::to_string(i * 2 + j) + ".";
-                    reg_res(l.pre, l.cin, l.cout, temb);
-                    n.tad_body.push_back(l);
-                }
-            reg_wb(ap + "conv_in", {chs[0], cfg.in_channels, 3, 3});
-        }
-        std::vector<int> chans;
-        int ch = mc, ds = 1;
-        n.input.push_back({mk(L_CONV, cfg.in_channels, mc)});
-        chans.push_back(mc);
-        for (int level = 0; level < cfg.n_levels; ++level) {
-            const int mult = cfg.channel_mult[level];
-            for (int r = 0; r < cfg.num_res_blocks; ++r) {
-                Block b{mk(L_RES, ch, mult * mc)};
-                ch = mult * mc;
-                if (in_ares(ds)) b.push_back(mk(L_ATTN, ch, ch, heads));
-                n.input.push_back(b);
-                chans.push_back(ch);
-            }
-            if (level != cfg.n_levels - 1) {
-                n.input.push_back({mk(L_DOWN, ch, ch)});
-                chans.push_back(ch);
-                ds *= 2;
-            }
-        }
-        n.middle = {mk(L_RES, ch, ch), mk(L_ATTN, ch, ch, heads), mk(L_RES, ch, ch)};
-        for (size_t i = 0; i < n.input.size(); ++i) reg_block(prefix + "input_blocks." + std::to_string(i) + ".", n.input[i], temb, ctx);
-        if (control) {
-            for (size_t i = 0; i < n.input.size(); ++i) {
-                const int zc = n.input[i].back().type == L_DOWN ? n.input[i].back().cin : n.input[i][0].cout;
-                n.zero_ch.push_back(zc);
-                reg_wb(prefix + "zero_convs." + std::to_string(i) + ".0", {zc, zc, 1, 1});
-            }
-            static const int hc[7] = {16, 16, 32, 32, 96, 96, 256};
-            int prev = cfg.hint_channels;
-            for (int k = 0; k < 8; ++k) {
-                const int oc = k < 7 ? hc[k] : mc;
-                reg_wb(prefix + "input_hint_block." + std::to_string(2 * k), {oc, prev, 3, 3});
-                prev = oc;
-            }
-            reg_block(prefix + "middle_block.", n.middle, temb, ctx);
-            reg_wb(prefix + "middle_block_out.0", {ch, ch, 1, 1});
-            return;
-        }
-        reg_block(prefix + "middle_block.", n.middle, temb, ctx);
-        for (int level = cfg.n_levels - 1; level >= 0; --level) {
-            const int mult = cfg.channel_mult[level];
-            for (int i = 0; i <= cfg.num_res_blocks; ++i) {
-                const int ich = chans.back();
-                chans.pop_back();
-                Block b{mk(L_RES, ch + ich, mc * mult)};
-                ch = mc * mult;
-                if (in_ares(ds)) b.push_back(mk(L_ATTN, ch, ch, heads));
-                if (level && i == cfg.num_res_blocks) { b.push_back(mk(L_UP, ch, ch)); ds /= 2; }
-                n.output.push_back(b);
-            }
-        }
-        for (size_t i = 0; i < n.output.size(); ++i) reg_block(prefix + "output_blocks." + std::to_string(i) + ".", n.output[i], temb, ctx);
-        reg_wb(prefix + "out.0", {mc});
-        reg_wb(prefix + "out.2", {cfg.out_channels, mc, 3, 3});
-    }
-    void reg_vres(VRes& r, const std::string& pre, int cin, int cout) {
-        r.cin = cin; r.cout = cout; r.pre = pre;
-        reg_wb(pre + "norm1", {cin});
-        reg_wb(pre + "conv1", {cout, cin, 3, 3});
-        reg_wb(pre + "norm2", {cout});
-        reg_wb(pre + "conv2", {cout, cout, 3, 3});
-        if (cin != cout) reg_wb(pre + "nin_shortcut", {cout, cin, 1, 1});
-    }
-    void reg_vattn(VAttn& at, const std::string& pre, int c) {
-        at.pre = pre;
-        reg_wb(pre + "norm", {c});
-        for (const char* n : {"q", "k", "v", "proj_out"}) reg_wb(pre + n, {c, c, 1, 1});
-    }
-    // Encoder.__init__ (model.py:368-435) with double_z = True and in_channels = 3; keys in module-registration order
-    void build_vae_encoder() {
-        const int L = cfg.vae_n_levels, ch = cfg.vae_ch, nrb = cfg.vae_num_res_blocks;
-        VEnc& en = vae.enc;
-        en.on = true;
-        const std::string d = vae.prefix + "encoder.";
-        reg_wb(d + "conv_in", {ch, 3, 3, 3});
-        int block_in = ch;
-        en.levels.resize(L);
-        for (int lvl = 0; lvl < L; ++lvl) {
-            const std::string lp = d + "down." + std::to_string(lvl) + ".";
-            const int block_out = ch * cfg.vae_ch_mult[lvl];
-            VDown& lv = en.levels[lvl];
-            lv.blocks.resize(nrb);
-            for (int i = 0; i < nrb; ++i) { reg_vres(lv.blocks[i], lp + "block." + std::to_string(i) + ".", block_in, block_out); block_in = block_out; }
-            lv.down = lvl != L - 1;
-            if (lv.down) { lv.down_pre = lp + "downsample.conv"; reg_wb(lv.down_pre, {block_in, block_in, 3, 3}); }
-        }
-        reg_vres(en.mid1, d + "mid.block_1.", block_in, block_in);
-        reg_vattn(en.attn, d + "mid.attn_1.", block_in);
-        reg_vres(en.mid2, d + "mid.block_2.", block_in, block_in);
-        reg_wb(d + "norm_out", {block_in});
-        reg_wb(d + "conv_out", {2 * cfg.vae_z_channels, block_in, 3, 3});
-    }
-    // Decoder.__init__ (model.py:486-530) + post_quant_conv (autoencoder.py:303); keys in module-registration order.  With
-    // vae_encoder the whole AutoencoderKL (autoencoder.py:298-303): encoder.*, decoder.*, quant_conv.*, post_quant_conv.*
-    int build_vae() {
-        const int L = cfg.vae_n_levels, ch = cfg.vae_ch, nrb = cfg.vae_num_res_blocks;
-        if (L < 1 || L > FGDM_MAX_LEVELS || (ch & 63) || nrb < 0 || cfg.vae_z_channels != 4 || cfg.vae_out_ch < 1 || cfg.vae_out_ch > 8)
-            return fail(FGDM_ERR_ARG, "unsupported first-stage decoder config (ch multiple of 64, z_channels 4, no attention at up levels)");
-        Vae& v = vae;
-        v.on = true;
-        v.prefix = "first_stage_model.";
-        v.factor = 1 << (L - 1);
-        if (cfg.vae_encoder) build_vae_encoder();
-        const std::string d = v.prefix + "decoder.";
-        v.top = ch * cfg.vae_ch_mult[L - 1];
-        reg_wb(d + "conv_in", {v.top, 4, 3, 3});
-        reg_vres(v.mid1, d + "mid.block_1.", v.top, v.top);
-        reg_vattn(v.attn, d + "mid.attn_1.", v.top);
-        reg_vres(v.mid2, d + "mid.block_2.", v.top, v.top);
-        std::vector<VLevel> asc(L);
-        int block_in = v.top;
-        for (int lvl = L - 1; lvl >= 0; --lvl) {      // channel bookkeeping in execution order (model.py:501-511)
-            const int block_out = ch * cfg.vae_ch_mult[lvl];
-            for (int i = 0; i <= nrb; ++i) { VRes r; r.cin = block_in; r.cout = block_out; asc[lvl].blocks.push_back(r); block_in = block_out; }
-            asc[lvl].up = lvl != 0;
-        }
-        for (int lvl = 0; lvl < L; ++lvl) {           // registration order: `self.up.insert(0, up)` -> ascending
-            const std::string lp = d + "up." + std::to_string(lvl) + ".";
-            for (size_t i = 0; i < asc[lvl].blocks.size(); ++i) {
-                VRes& r = asc[lvl].blocks[i];
-                reg_vres(r, lp + "block." + std::to_string(i) + ".", r.cin, r.cout);
-            }
-            if (asc[lvl].up) {
-                const int c = asc[lvl].blocks.back().cout;
-                asc[lvl].up_pre = lp + "upsample.conv";
-                reg_wb(asc[lvl].up_pre, {c, c, 3, 3});
-            }
-        }
-        for (int lvl = L - 1; lvl >= 0; --lvl) v.levels.push_back(asc[lvl]);
-        const int c0 = ch * cfg.vae_ch_mult[0];
-        reg_wb(d + "norm_out", {c0});
-        reg_wb(d + "conv_out", {cfg.vae_out_ch, c0, 3, 3});
-        if (v.enc.on) reg_wb(v.prefix + "quant_conv", {2 * cfg.vae_z_channels, 2 * cfg.vae_z_channels, 1, 1});
-        reg_wb(v.prefix + "post_quant_conv", {4, 4, 1, 1});
-        return FGDM_OK;
-    }
-    // CLIPTextModel state-dict keys in module-registration order, under the reference checkpoints' prefix
-    int build_clip() {
-        const int W = cfg.clip_width, I = cfg.clip_mlp;
-        if (cfg.clip_layers > 64 || (W & 63) || (I & 63) || cfg.clip_heads <= 0 || W != 64 * cfg.clip_heads ||
-            cfg.clip_vocab <= 0 || cfg.clip_max_len <= 0 || cfg.clip_max_len > 128)
-            return fail(FGDM_ERR_ARG, "unsupported text-encoder config (head dim must be 64, width/mlp multiples of 64, <= 128 tokens)");
-        Clip& c = clip;
-        c.on = true;
-        c.prefix = "cond_stage_model.transformer.text_model.";
-        reg(c.prefix + "embeddings.token_embedding.weight", {cfg.clip_vocab, W});
-        reg(c.prefix + "embeddings.position_embedding.weight", {cfg.clip_max_len, W});
-        c.layers.resize(cfg.clip_layers);
-        for (int i = 0; i < cfg.clip_layers; ++i) {
-            ClipLayer& l = c.layers[i];
-            l.pre = c.prefix + "encoder.layers." + std::to_string(i) + ".";
-            for (const char* n : {"k_proj", "v_proj", "q_proj", "out_proj"}) reg_wb(l.pre + "self_attn." + n, {W, W});
-            reg_wb(l.pre + "layer_norm1", {W});
-            reg_wb(l.pre + "mlp.fc1", {I, W});
-            reg_wb(l.pre + "mlp.fc2", {W, I});
-            reg_wb(l.pre + "layer_norm2", {W});
-        }
-        reg_wb(c.prefix + "final_layer_norm", {W});
-        return FGDM_OK;
-    }
-    int build() {
-        if (cfg.n_levels < 1 || cfg.n_levels > FGDM_MAX_LEVELS || cfg.model_channels <= 0 || (cfg.model_channels & 63) ||
-            cfg.num_heads <= 0 || cfg.n_controlnets < 0 || cfg.n_controlnets > FGDM_MAX_CONTROLNETS ||
-            (cfg.context_dim & 63) || cfg.in_channels < 4 || cfg.in_channels > 32)
-            return fail(FGDM_ERR_ARG, "unsupported config (model_channels and context_dim must be multiples of 64, 4 <= in_channels <= 32)");
-        // in_channels > 4: the UNet reads cat([x] + c_concat, 1) (DiffusionWrapper 'hybrid', ddpm.py:1838-1841)
-        if (cfg.in_channels != 4 && cfg.use_adapter)
-            return fail(FGDM_ERR_ARG, "in_channels != 4 with use_adapter: UNetModel.forward hands the concatenated input to an adapter built "
-                                      "for 4 channels (openaimodel.py:836-844); build the plain UNet (use_adapter = 0)");
-        if (cfg.in_channels != 4 && cfg.n_controlnets > 0)
-            return fail(FGDM_ERR_ARG, "in_channels != 4 with ControlNets: ControlLDM.apply_model never goes through DiffusionWrapper, its "
-                                      "c_concat is the hint (cldm.py:836-849)");
-        for (int l = 0; l < cfg.n_levels; ++l) {
-            const int ch = cfg.model_channels * cfg.channel_mult[l];
-            if (ch % cfg.num_heads) return fail(FGDM_ERR_ARG, "channels not divisible by heads");
-        }
-        if (cfg.use_adapter && !(cfg.model_channels == 320 && cfg.n_levels == 4 && cfg.num_res_blocks == 2))
-            return fail(FGDM_ERR_ARG, "FG-DM adapter requires the SD-v1 topology (openaimodel.py:554-556,855-859)");
-        if (cfg.use_adapter < 0 || cfg.use_adapter > 2) return fail(FGDM_ERR_ARG, "use_adapter: 0 none, 1 Adapter, 2 TimeAdapter");
-        if (cfg.n_extra_adapters < 0 || cfg.n_extra_adapters > 7 || (cfg.n_extra_adapters && cfg.use_adapter != 1))
-            return fail(FGDM_ERR_ARG, "n_extra_adapters (AdaptUNetModel num_prompts - 1) needs use_adapter = 1");
-        build_net(unet, "model.diffusion_model.", false, cfg.use_adapter);
-        cns.resize(cfg.n_controlnets);
-        for (int k = 0; k < cfg.n_controlnets; ++k)
-            build_net(cns[k], k == 0 ? std::string("control_model.") : "control_model_" + std::to_string(k) + ".", true, 0);
-        if (cfg.vae_encoder < 0 || cfg.vae_encoder > 1 || (cfg.vae_encoder && cfg.vae_ch <= 0))
-            return fail(FGDM_ERR_ARG, "vae_encoder: 0 none, 1 first-stage encoder (needs the first-stage config: vae_ch > 0)");
-        if (cfg.vae_ch > 0) CHK0(build_vae());
-        if (cfg.clip_layers > 0) CHK0(build_clip());
-        return FGDM_OK;
-    }
-
     // ------------------------------------------------------------------------------------ weight packing
     const ParamSlot* slot(const std::string& name) {
         auto it = params.find(name);
@@ -611,41 +191,8 @@ struct fgdm_engine {
         T* d = nullptr;
         if (hipMalloc(&d, std::max<size_t>(h.size() * sizeof(T), 256)) != hipSuccess) return nullptr;
         if (hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        weight_allocs[cur_comp].push_back(d);
+        comps[cur_comp].allocs.push_back(d);
         return d;
-    }
-    // component (network) a state-dict key belongs to: the longest registered prefix it starts with
-    std::vector<std::string> components() const {
-        std::vector<std::string> c{unet.prefix};
-        for (auto& n : cns) c.push_back(n.prefix);
-        if (vae.on) c.push_back(vae.prefix);
-        if (clip.on) c.push_back(clip.prefix);
-        return c;
-    }
-    std::string component_of(const std::string& key) const {
-        std::string best;
-        for (auto& c : components()) if (key.compare(0, c.size(), c) == 0 && c.size() > best.size()) best = c;
-        return best;
-    }
-    // (re)pack one component if it was never packed or tensors of it were loaded since: the old packed copy is freed
-    template <typename F> int repack(const std::string& comp, F pack) {
-        if (comp_packed[comp] && !comp_dirty[comp]) return FGDM_OK;
-        for (auto& name : order)
-            if (component_of(name) == comp) {
-                const ParamSlot& ps = params[name];
-                if (ps.loaded && ps.host.empty())
-                    return fail(FGDM_ERR_STATE, "tensor " + name + " was released after packing: reload every tensor of " + comp +
-                                                " before finalizing again");
-            }
-        for (void* p : weight_allocs[comp]) (void)hipFree(p);
-        weight_allocs[comp].clear();
-        cur_comp = comp;
-        const int rc = pack();
-        cur_comp.clear();
-        if (rc != FGDM_OK) return rc;
-        comp_packed[comp] = true;
-        comp_dirty[comp] = false;
-        return FGDM_OK;
     }
     // rows: list of (source float*, n_rows) stacked along N; each source is [n][K_src] row-major;
     // kmap(k_packed) -> k_src or -1.  row_perm maps packed row -> stacked source row (GEGLU interleave).
@@ -749,113 +296,6 @@ struct fgdm_engine {
         n.b = upload(b->host);
         return (n.g && n.b) ? FGDM_OK : fail(FGDM_ERR_NOMEM, "hipMalloc failed");
     }
-#define CHK(x) do { int _rc = (x); if (_rc != FGDM_OK) return _rc; } while (0)
-    int pack_block(Block& blk) {
-        for (Layer& l : blk) {
-            const std::string& p = l.pre;
-            switch (l.type) {
-                case L_CONV: CHK(pack_conv3(l.conv, p.substr(0, p.size() - 1))); break;
-                case L_DOWN: CHK(pack_conv3(l.conv, p + "op")); break;
-                case L_UP: CHK(pack_conv3(l.conv, p + "conv")); break;
-                case L_RES:
-                    CHK(pack_norm(l.gn1, p + "in_layers.0"));
-                    CHK(pack_conv3(l.c1, p + "in_layers.2"));
-                    CHK(pack_norm(l.gn2, p + "out_layers.0"));
-                    CHK(pack_conv3(l.c2, p + "out_layers.3"));
-                    if (l.cin != l.cout) CHK(pack_linear(l.skip, p + "skip_connection", true));
-                    break;
-                case L_ATTN: {
-                    const std::string t = p + "transformer_blocks.0.";
-                    CHK(pack_norm(l.gn, p + "norm"));
-                    CHK(pack_linear(l.pin, p + "proj_in", true));
-                    CHK(pack_linear(l.pout, p + "proj_out", true));
-                    // softmax(q k^T d^-1/2) is evaluated as exp2 of (q log2(e) d^-1/2) k^T: the constant is folded into the
-                    // to_q weights here, in fp32, so the scaled query carries ONE fp16 rounding (attention.py:190-193)
-                    const float qs = 1.4426950408889634f / sqrtf((float)(l.cin / l.heads));
-                    // norm1 / norm2 / norm3 are folded into the Linears they feed (no normalised copy of the tokens is ever stored)
-                    const std::string n1 = ln_fold ? t + "norm1" : "", n2 = ln_fold ? t + "norm2" : "", n3 = ln_fold ? t + "norm3" : "";
-                    if (!ln_fold) { CHK(pack_norm(l.ln1, t + "norm1")); CHK(pack_norm(l.ln2, t + "norm2")); CHK(pack_norm(l.ln3, t + "norm3")); }
-                    CHK(pack_stack(l.qkv1, {t + "attn1.to_q", t + "attn1.to_k", t + "attn1.to_v"}, false, {qs, 1.f, 1.f}, n1));
-                    CHK(pack_linear(l.o1, t + "attn1.to_out.0", true));
-                    CHK(pack_linear(l.q2, t + "attn2.to_q", false, false, qs, n2));
-                    CHK(pack_linear(l.k2, t + "attn2.to_k", false));
-                    CHK(pack_linear(l.v2, t + "attn2.to_v", false));
-                    CHK(pack_linear(l.o2, t + "attn2.to_out.0", true));
-                    CHK(pack_linear(l.ffp, t + "ff.net.0.proj", true, true, 1.f, n3));
-                    CHK(pack_linear(l.ffo, t + "ff.net.2", true));
-                    break;
-                }
-            }
-        }
-        return FGDM_OK;
-    }
-    int pack_net(Net& n) {
-        CHK(pack_linear(n.time0, n.prefix + "time_embed.0", true));
-        CHK(pack_linear(n.time2, n.prefix + "time_embed.2", true));
-        // every ResBlock's emb_layers Linear stacked into one GEMM per evaluation (openaimodel.py:238-244, 290)
-        std::vector<std::string> embs;
-        int off = 0;
-        auto collect = [&](Block& b) {
-            for (Layer& l : b) if (l.type == L_RES) { l.emb_off = off; off += l.cout; embs.push_back(l.pre + "emb_layers.1"); }
-        };
-        for (auto& b : n.input) collect(b);
-        collect(n.middle);
-        for (auto& b : n.output) collect(b);
-        collect(n.tad_body);
-        n.emb_total = off;
-        CHK(pack_stack(n.emb_all, embs, true));
-        for (auto& b : n.input) CHK(pack_block(b));
-        CHK(pack_block(n.middle));
-        for (auto& b : n.output) CHK(pack_block(b));
-        if (!n.control) {
-            CHK(pack_norm(n.out_gn, n.prefix + "out.0"));
-            CHK(pack_conv3(n.out_conv, n.prefix + "out.2"));
-            if (n.time_adapter) CHK(pack_block(n.tad_body));
-            if (n.has_adapter) {
-                CHK(pack_conv3(n.ad_conv_in, n.prefix + "adapter.conv_in"));
-                for (auto& b : n.ad_body) {
-                    if (b.ic != b.oc) CHK(pack_linear(b.in_conv, b.pre + "in_conv", true));
-                    CHK(pack_conv3(b.b1, b.pre + "block1"));
-                    CHK(pack_linear(b.b2, b.pre + "block2", true));
-                }
-                for (size_t kk = 0; kk < n.xad_body.size(); ++kk) {
-                    CHK(pack_conv3(n.xad_conv_in[kk], n.prefix + "adapters." + std::to_string(kk) + ".conv_in"));
-                    for (auto& b : n.xad_body[kk]) {
-                        if (b.ic != b.oc) CHK(pack_linear(b.in_conv, b.pre + "in_conv", true));
-                        CHK(pack_conv3(b.b1, b.pre + "block1"));
-                        CHK(pack_linear(b.b2, b.pre + "block2", true));
-                    }
-                }
-            }
-        } else {
-            n.zero_convs.resize(n.input.size());
-            for (size_t i = 0; i < n.input.size(); ++i)
-                CHK(pack_linear(n.zero_convs[i], n.prefix + "zero_convs." + std::to_string(i) + ".0", true));
-            CHK(pack_linear(n.mid_out, n.prefix + "middle_block_out.0", true));
-            for (int k = 0; k < 8; ++k) CHK(pack_conv3(n.hint_convs[k], n.prefix + "input_hint_block." + std::to_string(2 * k)));
-        }
-        // staging for this net is no longer needed
-        for (auto& name : order)
-            if (name.compare(0, n.prefix.size(), n.prefix) == 0) { auto& ps = params[name]; std::vector<float>().swap(ps.host); }
-        return FGDM_OK;
-    }
-
-    int pack_vres(VRes& r) {
-        CHK(pack_norm(r.n1, r.pre + "norm1"));
-        CHK(pack_conv3(r.c1, r.pre + "conv1"));
-        CHK(pack_norm(r.n2, r.pre + "norm2"));
-        CHK(pack_conv3(r.c2, r.pre + "conv2"));
-        if (r.cin != r.cout) CHK(pack_linear(r.nin, r.pre + "nin_shortcut", true));
-        return FGDM_OK;
-    }
-    int pack_vattn(VAttn& at) {
-        CHK(pack_norm(at.norm, at.pre + "norm"));
-        CHK(pack_linear(at.q, at.pre + "q", true));
-        CHK(pack_linear(at.k, at.pre + "k", true));
-        CHK(pack_linear(at.v, at.pre + "v", true));
-        CHK(pack_linear(at.o, at.pre + "proj_out", true));
-        return FGDM_OK;
-    }
     // fp32 [co][ci] weights of a 1x1 convolution followed by its biases, for the per-pixel kernels (vae_prequant, vae_moments)
     int pack_pointwise(float** dst, const std::string& pre) {
         const ParamSlot* w = slot(pre + ".weight");
@@ -866,67 +306,63 @@ struct fgdm_engine {
         *dst = upload(wb);
         return *dst ? FGDM_OK : fail(FGDM_ERR_NOMEM, "hipMalloc failed");
     }
-    int pack_vae_encoder() {
-        VEnc& en = vae.enc;
-        const std::string d = vae.prefix + "encoder.";
-        CHK(pack_conv3(en.conv_in, d + "conv_in"));          // Cin = 3: the im2col layout, cin_pad 4
-        for (auto& lv : en.levels) {
-            for (auto& r : lv.blocks) CHK(pack_vres(r));
-            if (lv.down) CHK(pack_conv3(lv.downconv, lv.down_pre));
-        }
-        CHK(pack_vres(en.mid1));
-        CHK(pack_vattn(en.attn));
-        CHK(pack_vres(en.mid2));
-        CHK(pack_norm(en.norm_out, d + "norm_out"));
-        CHK(pack_conv3(en.conv_out, d + "conv_out"));
-        return pack_pointwise(&en.qc, vae.prefix + "quant_conv");
+    // fp32 table as it is (CLIP's embeddings)
+    int pack_table(float** dst, const std::string& name) {
+        const ParamSlot* w = slot(name);
+        if (!w) return FGDM_ERR_STATE;
+        *dst = upload(w->host);
+        return *dst ? FGDM_OK : fail(FGDM_ERR_NOMEM, "hipMalloc failed");
     }
-    int pack_vae() {
-        Vae& v = vae;
-        if (v.enc.on) CHK(pack_vae_encoder());
-        const std::string d = v.prefix + "decoder.";
-        CHK(pack_conv3(v.conv_in, d + "conv_in"));
-        CHK(pack_vres(v.mid1));
-        CHK(pack_vattn(v.attn));
-        CHK(pack_vres(v.mid2));
-        for (auto& lv : v.levels) {
-            for (auto& r : lv.blocks) CHK(pack_vres(r));
-            if (lv.up) CHK(pack_conv3(lv.upconv, lv.up_pre));
+    // The packing visitor of model.h's traversals: every call lands in one of the pack_* above; after the first failure the rest
+    // of the walk does nothing.  What depends on the engine's knobs is decided here, at pack time: ln_fold is read at fgdm_create.
+    struct Packer {
+        fgdm_engine& e;
+        int rc = FGDM_OK;
+        template <class F> void run(F pack) { if (rc == FGDM_OK) rc = pack(); }
+        // softmax(q k^T d^-1/2) is evaluated as exp2 of (q log2(e) d^-1/2) k^T: the constant is folded into the to_q weights
+        // here, in fp32, so the scaled query carries ONE fp16 rounding (attention.py:190-193)
+        static float qscale(const LinOpt& o) { return o.q_head_dim ? 1.4426950408889634f / sqrtf((float)o.q_head_dim) : 1.f; }
+        // norm1 / norm2 / norm3 are folded into the Linears they feed (no normalised copy of the tokens is ever stored) ...
+        std::string fold(const LinOpt& o) const { return e.ln_fold ? o.ln : std::string(); }
+        // ... or, FGDM_LN_FOLD=0, packed as norms of their own
+        void layernorm(NormW& n, const std::string& pre, int C) { if (!e.ln_fold) norm(n, pre, C); }
+        void norm(NormW& n, const std::string& pre, int) { run([&] { return e.pack_norm(n, pre); }); }
+        void conv3(GemmW& g, const std::string& pre, int, int) { run([&] { return e.pack_conv3(g, pre); }); }
+        void pointwise(float*& dst, const std::string& pre, int, int) { run([&] { return e.pack_pointwise(&dst, pre); }); }
+        void table(float*& dst, const std::string& key, int, int) { run([&] { return e.pack_table(&dst, key); }); }
+        void source(const std::string&, int, int, bool) {}
+        void linear(GemmW& g, const std::string& pre, int, int, bool, bool bias, const LinOpt& o = LinOpt()) {
+            run([&] { return e.pack_linear(g, pre, bias, o.geglu, qscale(o), fold(o)); });
         }
-        CHK(pack_norm(v.norm_out, d + "norm_out"));
-        CHK(pack_conv3(v.conv_out, d + "conv_out"));
-        CHK(pack_pointwise(&v.pq, v.prefix + "post_quant_conv"));
-        for (auto& name : order)
-            if (name.compare(0, v.prefix.size(), v.prefix) == 0) { auto& ps = params[name]; std::vector<float>().swap(ps.host); }
-        v.packed = true;
+        void stack(GemmW& g, const std::vector<std::string>& pres, bool bias, const LinOpt& o = LinOpt()) {
+            run([&] { return e.pack_stack(g, pres, bias, o.q_head_dim ? std::vector<float>{qscale(o)} : std::vector<float>(), fold(o)); });
+        }
+    };
+    // (re)pack one component if it was never packed or tensors of it were loaded since: the old packed copy is freed, the
+    // component's traversal (model.h) is run with the Packer, and the host staging is released
+    int repack(int c) {
+        Component& comp = comps[c];
+        if (comp.packed && !comp.dirty) return FGDM_OK;
+        for (auto& name : order) {
+            const ParamSlot& ps = params[name];
+            if (ps.comp == c && ps.loaded && ps.host.empty())
+                return fail(FGDM_ERR_STATE, "tensor " + name + " was released after packing: reload every tensor of " + comp.prefix +
+                                            " before finalizing again");
+        }
+        for (void* p : comp.allocs) (void)hipFree(p);
+        comp.allocs.clear();
+        cur_comp = c;
+        Packer pk{*this};
+        visit_component(c, pk);
+        cur_comp = -1;
+        if (pk.rc != FGDM_OK) return pk.rc;
+        for (auto& name : order) { ParamSlot& ps = params[name]; if (ps.comp == c) std::vector<float>().swap(ps.host); }
+        comp.packed = true;
+        comp.dirty = false;
         return FGDM_OK;
     }
 
-    int pack_clip() {
-        Clip& c = clip;
-        auto up32 = [&](const std::string& name, float** dst) -> int {
-            const ParamSlot* w = slot(name);
-            if (!w) return FGDM_ERR_STATE;
-            *dst = upload(w->host);
-            return *dst ? FGDM_OK : fail(FGDM_ERR_NOMEM, "hipMalloc failed");
-        };
-        CHK(up32(c.prefix + "embeddings.token_embedding.weight", &c.tok));
-        CHK(up32(c.prefix + "embeddings.position_embedding.weight", &c.pos));
-        for (ClipLayer& l : c.layers) {
-            CHK(pack_norm(l.ln1, l.pre + "layer_norm1"));
-            CHK(pack_norm(l.ln2, l.pre + "layer_norm2"));
-            CHK(pack_stack(l.qkv, {l.pre + "self_attn.q_proj", l.pre + "self_attn.k_proj", l.pre + "self_attn.v_proj"}, true));
-            CHK(pack_linear(l.o, l.pre + "self_attn.out_proj", true));
-            CHK(pack_linear(l.fc1, l.pre + "mlp.fc1", true));
-            CHK(pack_linear(l.fc2, l.pre + "mlp.fc2", true));
-        }
-        CHK(pack_norm(c.final_ln, c.prefix + "final_layer_norm"));
-        for (auto& name : order)
-            if (name.compare(0, c.prefix.size(), c.prefix) == 0) { auto& ps = params[name]; std::vector<float>().swap(ps.host); }
-        c.packed = true;
-        return FGDM_OK;
-    }
-
+#define CHK(x) do { int _rc = (x); if (_rc != FGDM_OK) return _rc; } while (0)
     // ------------------------------------------------------------------------------------ runtime helpers
     // device-to-device copy / memset on the call's stream, deferred like every launch while a walk is being recorded
     int dcopy(void* dst, const void* src, size_t bytes) {
@@ -1083,10 +519,11 @@ struct fgdm_engine {
     // ------------------------------------------------------------------------------------ layers
     struct EmbCtx { const float* emb_all; int stride; };
 
-    // ResBlock._forward (openaimodel.py:275-301); x1 = skip tensor of the decoder's channel concat
+    // ResBlock._forward (openaimodel.py:275-301); x1 = skip tensor of the decoder's channel concat.  Also the first stage's
+    // ResnetBlock.forward with temb = None (model.py:121-141): no timestep row, GroupNorm eps 1e-6
     int res_fwd(const Layer& l, const Tensor& x, const Tensor* x1, const EmbCtx& ec, Tensor* out) {
         Tensor g1, h, g2, sk, xp;
-        CHK(gnorm(l.gn1, x, x1, 1e-5f, true, &g1));
+        CHK(gnorm(l.gn1, x, x1, l.eps, true, &g1));
         const Tensor* xs = &x;       // the tensor the skip path reads
         if (l.down) {                // ResBlock(down=True, use_conv=False): AvgPool2d(2) on h and on x (openaimodel.py:276-282)
             if (x1) return fail(FGDM_ERR_ARG, "down ResBlock with a concatenated input");
@@ -1099,10 +536,11 @@ struct fgdm_engine {
             g1 = gp;
             xs = &xp;
         }
-        Epi e1; e1.rowvec = ec.emb_all + l.emb_off; e1.rv_stride = ec.stride;
+        Epi e1;
+        if (l.emb_off >= 0) { e1.rowvec = ec.emb_all + l.emb_off; e1.rv_stride = ec.stride; }
         CHK(conv3(l.c1, g1, nullptr, 1, false, e1, &h));
         tfree(g1);
-        CHK(gnorm(l.gn2, h, nullptr, 1e-5f, true, &g2));
+        CHK(gnorm(l.gn2, h, nullptr, l.eps, true, &g2));
         tfree(h);
         Epi e2;
         if (l.cin != l.cout) {
@@ -1156,14 +594,8 @@ struct fgdm_engine {
                 if (l.type == L_ATTN) { CtxKV kv; CHK(cross_kv(l, ctx16, true, &kv.k, &kv.vt)); ctx_cache[&l] = kv; }
             return FGDM_OK;
         };
-        auto walk_net = [&](const Net& n) -> int {
-            for (auto& b : n.input) CHK(walk(b));
-            CHK(walk(n.middle));
-            for (auto& b : n.output) CHK(walk(b));
-            return FGDM_OK;
-        };
-        CHK(walk_net(unet));
-        for (auto& n : cns) CHK(walk_net(n));
+        CHK(for_each_block(unet, false, walk));
+        for (auto& n : cns) CHK(for_each_block(n, false, walk));
         tfree(ctx16);
         ctx_B = B; ctx_T = ctx_tokens;
         return FGDM_OK;
@@ -1422,26 +854,24 @@ struct fgdm_engine {
         if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(FGDM_ERR_ARG, "bad shape");
         Net* net = nullptr;
         const Block* blk = nullptr;
+        Block single;                // the prefix may also name ONE layer of a block ("...input_blocks.4.1.")
         auto scan = [&](Net& n) {
-            auto chk = [&](const Block& b) {
-                if (b.empty() || blk) return;
+            for_each_block(n, false, [&](const Block& b) {
+                if (blk || b.empty()) return FGDM_OK;
                 const std::string& lp = b[0].pre;                       // "<block prefix>0."
                 if (lp.size() >= 2 && lp.compare(0, lp.size() - 2, prefix) == 0 && lp.size() - 2 == prefix.size()) { blk = &b; net = &n; }
-            };
-            for (auto& b : n.input) chk(b);
-            chk(n.middle);
-            for (auto& b : n.output) chk(b);
+                return FGDM_OK;
+            });
+        };
+        auto scan1 = [&](Net& n) {
+            for_each_block(n, false, [&](const Block& b) {
+                for (const Layer& l : b) if (single.empty() && l.pre == prefix) { single.push_back(l); net = &n; }
+                return FGDM_OK;
+            });
         };
         scan(unet);
         for (auto& n : cns) scan(n);
-        Block single;                // the prefix may also name ONE layer of a block ("...input_blocks.4.1.")
         if (!blk) {
-            auto scan1 = [&](Net& n) {
-                auto chk = [&](const Block& b) { for (const Layer& l : b) if (single.empty() && l.pre == prefix) { single.push_back(l); net = &n; } };
-                for (auto& b : n.input) chk(b);
-                chk(n.middle);
-                for (auto& b : n.output) chk(b);
-            };
             scan1(unet);
             for (auto& n : cns) scan1(n);
             if (!single.empty()) blk = &single;
@@ -1800,7 +1230,7 @@ struct fgdm_engine {
     // of layer L - k + 1 of L, so the last clip_skip - 1 layers are not run
     int clip_encode(const int64_t* ids, int B, int T, float* out, int clip_skip = 0) {
         if (!clip.on) return fail(FGDM_ERR_STATE, "engine was created without a text encoder (clip_layers = 0)");
-        if (!clip.packed) return fail(FGDM_ERR_STATE, "weights not finalized");
+        if (!comps[clip_comp].packed) return fail(FGDM_ERR_STATE, "weights not finalized");
         if (B <= 0 || T <= 0 || T > cfg.clip_max_len) return fail(FGDM_ERR_ARG, "bad shape (T must be <= clip_max_len)");
         if (clip_skip > cfg.clip_layers + 1) return fail(FGDM_ERR_ARG, "clip_skip exceeds the number of hidden states");
         const int n_run = cfg.clip_layers - (clip_skip > 1 ? clip_skip - 1 : 0);
@@ -1848,22 +1278,6 @@ struct fgdm_engine {
     }
 
     // ------------------------------------------------------------------------------------ first-stage decoder
-    // ResnetBlock.forward with temb = None (model.py:121-141); Normalize = GroupNorm(32, eps 1e-6), swish = SiLU
-    int vres_fwd(const VRes& r, const Tensor& x, Tensor* out) {
-        Tensor g1, h, g2, sk;
-        CHK(gnorm(r.n1, x, nullptr, 1e-6f, true, &g1));
-        CHK(conv3(r.c1, g1, nullptr, 1, false, Epi{}, &h));
-        tfree(g1);
-        CHK(gnorm(r.n2, h, nullptr, 1e-6f, true, &g2));
-        tfree(h);
-        Epi e2;
-        if (r.cin != r.cout) { CHK(linear(r.nin, x, Epi{}, &sk)); e2.resid = sk.p; e2.ld_res = sk.C; }
-        else { e2.resid = x.p; e2.ld_res = x.C; }
-        CHK(conv3(r.c2, g2, nullptr, 1, false, e2, out));
-        tfree(g2);
-        if (sk.p) tfree(sk);
-        return FGDM_OK;
-    }
     // AttnBlock.forward (model.py:176-203): ONE head over all C channels.  d = C = 512 does not fit the flash kernel's
     // register budget, so per image: S = C^-1/2 Q K^T (fp32, GEMM with K as the "weight"), row softmax, O = P V
     // (GEMM with V^T, written transposed by the v projection's epilogue, as the weight).
@@ -1902,10 +1316,11 @@ struct fgdm_engine {
     // Decoder.forward (model.py:532-560).  z fp32 NCHW [B,4,H,W] -> image fp32 NCHW [B,out_ch,f*H,f*W]
     int vae_decode(const float* z, int B, int H, int W, float scale, float* out) {
         if (!vae.on) return fail(FGDM_ERR_STATE, "engine was created without a first-stage decoder (vae_ch = 0)");
-        if (!vae.packed) return fail(FGDM_ERR_STATE, "weights not finalized");
+        if (!comps[vae_comp].packed) return fail(FGDM_ERR_STATE, "weights not finalized");
         if (B <= 0 || H <= 0 || W <= 0) return fail(FGDM_ERR_ARG, "bad shape");
         const Vae& v = vae;
         const int f = v.factor, HW = H * W;
+        const EmbCtx no_emb{nullptr, 0};
         const size_t out_per_img = (size_t)cfg.vae_out_ch * H * f * W * f;
         // images per pass: ~8 live full-resolution tensors of `ch` channels must fit comfortably in one slab
         const size_t big = (size_t)H * f * W * f * cfg.vae_ch * sizeof(half_t) * 8;
@@ -1917,11 +1332,11 @@ struct fgdm_engine {
             if (vae_prequant(z + (size_t)b0 * 4 * HW, v.pq, scale, z4.p, nb, HW, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "prequant kernel");
             CHK(conv3(v.conv_in, z4, nullptr, 1, false, Epi{}, &h));
             tfree(z4);
-            CHK(vres_fwd(v.mid1, h, &t)); tfree(h); h = t;
+            CHK(res_fwd(v.mid1, h, nullptr, no_emb, &t)); tfree(h); h = t;
             CHK(vattn_fwd(v.attn, h, &t)); tfree(h); h = t;
-            CHK(vres_fwd(v.mid2, h, &t)); tfree(h); h = t;
+            CHK(res_fwd(v.mid2, h, nullptr, no_emb, &t)); tfree(h); h = t;
             for (const VLevel& lv : v.levels) {
-                for (const VRes& r : lv.blocks) { CHK(vres_fwd(r, h, &t)); tfree(h); h = t; }
+                for (const Layer& r : lv.blocks) { CHK(res_fwd(r, h, nullptr, no_emb, &t)); tfree(h); h = t; }
                 if (lv.up) { CHK(conv3(lv.upconv, h, nullptr, 1, true, Epi{}, &t)); tfree(h); h = t; }
             }
             Tensor g;
@@ -1938,9 +1353,10 @@ struct fgdm_engine {
     // Encoder.forward (model.py:436-460) + quant_conv.  image fp32 NCHW [B,3,H,W] -> moments fp32 NCHW [B,2*z_channels,H/f,W/f]
     int vae_encode(const float* image, int B, int H, int W, float* moments) {
         if (!vae.on || !vae.enc.on) return fail(FGDM_ERR_STATE, "engine was created without a first-stage encoder (vae_encoder = 0)");
-        if (!vae.packed) return fail(FGDM_ERR_STATE, "weights not finalized");
+        if (!comps[vae_comp].packed) return fail(FGDM_ERR_STATE, "weights not finalized");
         const VEnc& en = vae.enc;
         const int f = vae.factor;
+        const EmbCtx no_emb{nullptr, 0};
         if (B <= 0 || H <= 0 || W <= 0 || H % f || W % f || (((H / f) * (W / f)) & 63))
             return fail(FGDM_ERR_ARG, "first-stage encoder: H and W must be multiples of " + std::to_string(f) + " and (H/" + std::to_string(f) +
                                       ")*(W/" + std::to_string(f) + ") a multiple of 64 (smallest image 64 x 64)");
@@ -1956,12 +1372,12 @@ struct fgdm_engine {
             CHK(conv3(en.conv_in, x4, nullptr, 1, false, Epi{}, &h));
             tfree(x4);
             for (const VDown& lv : en.levels) {
-                for (const VRes& r : lv.blocks) { CHK(vres_fwd(r, h, &t)); tfree(h); h = t; }
+                for (const Layer& r : lv.blocks) { CHK(res_fwd(r, h, nullptr, no_emb, &t)); tfree(h); h = t; }
                 if (lv.down) { CHK(conv3(lv.downconv, h, nullptr, FGDM_STRIDE2_PAD_BR, false, Epi{}, &t)); tfree(h); h = t; }
             }
-            CHK(vres_fwd(en.mid1, h, &t)); tfree(h); h = t;
+            CHK(res_fwd(en.mid1, h, nullptr, no_emb, &t)); tfree(h); h = t;
             CHK(vattn_fwd(en.attn, h, &t)); tfree(h); h = t;
-            CHK(vres_fwd(en.mid2, h, &t)); tfree(h); h = t;
+            CHK(res_fwd(en.mid2, h, nullptr, no_emb, &t)); tfree(h); h = t;
             Tensor g;
             CHK(gnorm(en.norm_out, h, nullptr, 1e-6f, true, &g));
             tfree(h);
@@ -2100,7 +1516,7 @@ int fgdm_create(const fgdm_config* cfg, int device, fgdm_engine** out) {
 void fgdm_destroy(fgdm_engine* e) {
     if (!e) return;
     for (hipEvent_t ev : e->prof.pool) (void)hipEventDestroy(ev);
-    for (auto& kv : e->weight_allocs) for (void* p : kv.second) (void)hipFree(p);
+    for (auto& c : e->comps) for (void* p : c.allocs) (void)hipFree(p);
     if (e->zero) (void)hipFree(e->zero);
     for (auto& n : e->cns) if (n.guided.p) (void)hipFree(n.guided.p);
     e->drop_concat();
@@ -2163,7 +1579,7 @@ int fgdm_load_tensor(fgdm_engine* e, const char* key, const void* data, int dtyp
         return e->fail(FGDM_ERR_ARG, "unsupported dtype");
     }
     ps.loaded = true;
-    e->comp_dirty[e->component_of(key)] = true;
+    e->comps[ps.comp].dirty = true;
     e->finalized = false;
     return FGDM_OK;
 }
@@ -2177,11 +1593,7 @@ int fgdm_finalize_weights(fgdm_engine* e) {
     for (auto& n : e->cns) if (n.guided.p) { (void)hipFree(n.guided.p); n.guided = Tensor{}; }
     // only components whose tensors changed since the last call are packed again (their previous HBM copy is freed
     // first): loading the base checkpoint and then a ControlNet checkpoint does not re-pack or leak the UNet
-    rc = e->repack(e->unet.prefix, [&] { return e->pack_net(e->unet); });
-    if (rc != FGDM_OK) return rc;
-    for (auto& n : e->cns) { rc = e->repack(n.prefix, [&] { return e->pack_net(n); }); if (rc != FGDM_OK) return rc; }
-    if (e->vae.on) { rc = e->repack(e->vae.prefix, [&] { return e->pack_vae(); }); if (rc != FGDM_OK) return rc; }
-    if (e->clip.on) { rc = e->repack(e->clip.prefix, [&] { return e->pack_clip(); }); if (rc != FGDM_OK) return rc; }
+    for (int c = 0; c < (int)e->comps.size(); ++c) { rc = e->repack(c); if (rc != FGDM_OK) return rc; }
     e->finalized = true;
     return FGDM_OK;
 }
@@ -2316,7 +1728,7 @@ int fgdm_vae_decode_patches(fgdm_engine* e, const float* z, int B, int H, int W,
     if (!e) return FGDM_ERR_ARG;
     if (!z || !w_pix || !w_tie || !image || B <= 0 || max_crops_per_pass < 0) return e->fail(FGDM_ERR_ARG, "patch decode: null pointer or bad batch / pass size");
     if (!e->vae.on) return e->fail(FGDM_ERR_STATE, "engine was created without a first-stage decoder (vae_ch = 0)");
-    if (!e->vae.packed) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    if (!e->comps[e->vae_comp].packed) return e->fail(FGDM_ERR_STATE, "weights not finalized");
     if (f != e->vae.factor) return e->fail(FGDM_ERR_ARG, "patch decode: f (vqf) must equal the decoder's upscaling factor " + std::to_string(e->vae.factor));
     PatchGeom gz{B, 4, H, W, kh, kw, sh, sw, 0, 0};
     if (patch_plan(H, W, kh, kw, sh, sw, true, &gz.Ly, &gz.Lx) != FGDM_OK)

@@ -444,3 +444,36 @@ def test_grouped_twin_launches_and_second_stream_are_bit_identical(knob, off, on
     if knob == 'FGDM_GROUP_MAX':
         assert stats[0]['fused_launches'] > 0 and stats[0]['fused_problems'] == 2 * stats[0]['fused_launches'], stats
         assert stats[1]['fused_problems'] >= (1 + ncn) * 50 and stats[1]['fused_launches'] < stats[0]['fused_launches'], stats
+
+
+def test_refinalize_repacks_only_reloaded_components():
+    """fgdm_finalize_weights packs a component (state-dict prefix) again only when tensors of it were loaded since, and a packed
+    component's host staging is gone: reloading the ControlNet alone finalizes (the UNet is not packed again) and gives the same
+    bits; one reloaded UNet tensor is refused ('released after packing'); the whole UNet reloaded is packed again, same bits."""
+    from fgdm_amd.engine import Engine
+    e = Engine(gi.SMALL_CFG, n_controlnets=1)
+    try:
+        sd = {k: synth.make_tensor(small_rename(k), s) for k, s in e.param_shapes().items()}
+        unet = [k for k in sd if k.startswith('model.diffusion_model.')]
+        cn = [k for k in sd if k.startswith('control_model.')]
+        assert unet and cn and len(unet) + len(cn) == len(sd)
+        x, ctx = gi.get('small/x')[:, :, :8, :8].contiguous(), gi.get('small/ctx')
+        t = torch.tensor([981, 21])
+        hint = gi.hint(2, 64, seed=5)
+
+        def run(keys):
+            for k in keys:
+                e.load_tensor(k, sd[k])
+            e.finalize()
+            e.set_hint(0, hint)
+            return e.apply_model(x, t, ctx).cpu()
+
+        out0 = run(sd)
+        assert torch.isfinite(out0).all()
+        assert torch.equal(run(cn), out0)                   # the UNet's staging was released: it was not packed again
+        e.load_tensor(unet[0], sd[unet[0]])
+        with pytest.raises(RuntimeError, match='released after packing'):
+            e.finalize()
+        assert torch.equal(run(unet), out0)
+    finally:
+        e.close()
