@@ -50,6 +50,16 @@ __device__ __forceinline__ float silu_f(float x, float k = 1.0f) {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * k * x));
 }
 
+// The folded LayerNorm's fix-up of a GEMM accumulator, rstd (acc - mean u): one fma and one multiply as inline asm -- with
+// -ffp-contract=fast the backend fuses a multiply into the bias add that follows whatever the source says.  One definition for
+// both GEMM kernels (igemm.hip, igemm2.hip): WHICH of them evaluates a layer must not change a bit of its output.
+__device__ __forceinline__ float ln_scale(float acc, float mean, float rstd, float u) {
+    float t, w;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(t) : "v"(-mean), "v"(u), "v"(acc));
+    asm("v_mul_f32 %0, %1, %2" : "=v"(w) : "v"(rstd), "v"(t));
+    return w;
+}
+
 #define FGDM_OK 0
 #define FGDM_ERR_ARG -1
 #define FGDM_ERR_HIP -2

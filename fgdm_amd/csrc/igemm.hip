@@ -24,16 +24,6 @@ __device__ __forceinline__ void glds16(const void* g, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const GLB_AS void*)g, (LDS_AS void*)lds_wave_base, 16, 0, 0);
 }
 
-
-// rstd (acc - mean u): one fma and one multiply that must NOT be contracted with the bias add that follows -- the pipelined
-// kernel (igemm2.hip ln_fix) rounds in exactly this sequence, and which kernel runs a layer must not change a bit
-__device__ __forceinline__ float ln_scale(float acc, float mean, float rstd, float u) {
-    float t, w;      // inline asm: opaque to the backend's multiply-add fusion (-ffp-contract=fast)
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(t) : "v"(-mean), "v"(u), "v"(acc));
-    asm("v_mul_f32 %0, %1, %2" : "=v"(w) : "v"(rstd), "v"(t));
-    return w;
-}
-
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(WM * WN * 64) void igemm_kernel(const IgemmArgs a) {
     constexpr int T = WM * WN * 64;

@@ -43,16 +43,6 @@ __device__ __forceinline__ void glds16_sv(unsigned voff, const void* sbase, unsi
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_wave_addr) : "memory", "m0");
 }
 __device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(LDS_AS const void*)p; }
-// rstd (acc - mean u): one fma and one multiply as inline asm -- with -ffp-contract=fast the backend fuses a multiply into the
-// bias add that follows whatever the source says; the 2-stage kernel (igemm.hip) rounds in exactly this sequence, and WHICH
-// kernel evaluates a layer must not change a bit of its output
-__device__ __forceinline__ float ln_scale(float acc, float mean, float rstd, float u) {
-    float t, w;
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(t) : "v"(-mean), "v"(u), "v"(acc));
-    asm("v_mul_f32 %0, %1, %2" : "=v"(w) : "v"(rstd), "v"(t));
-    return w;
-}
-
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
@@ -662,7 +652,7 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
     if constexpr (LN) {
         // LayerNorm folded into this GEMM: acc <- rstd_m (acc - mean_m u_n), IN PLACE and before anything else (the bias, which
         // carries beta W, is added by the ordinary epilogue below): one column quad of u and one row's (mean, rstd) live at a time,
-        // so the fix-up costs no registers next to the accumulators.  fma + mul as inline asm: see ln_scale.
+        // so the fix-up costs no registers next to the accumulators.  fma + mul as inline asm: see ln_scale (common.h).
         const float* uw = u_l + wn * TN;
 #pragma unroll
         for (int j = 0; j < NI; ++j)

@@ -560,6 +560,30 @@ def test_linear_pipelined_tile_edges(lib, cfg):
         lib.fgdm_debug_force_igemm_cfg(0)
 
 
+@pytest.mark.parametrize('cfg', [c + p for p in (0, 16) for c in PIPE_TILES])
+def test_linear_pipelined_short_k(lib, cfg):
+    """The drain of the pipelined K loop: K = 64 is two K-steps (no step refills, two of the three draining arms), K = 128 four
+    (one refilling step -- an odd count, so the fragment double buffer changes sides -- then all three draining arms), K = 192 six
+    (the two-step loop once, then the odd one).  This entry takes K in multiples of 64 only, so one and three K-steps and an even
+    count of refilling steps (K-steps minus three) are reached through split K alone.  One column tile, one row past a row tile."""
+    BM, BN = PIPE_TILES[cfg & 15]
+    M, N = BM + 1, BN
+    res = h16(rnd((M, N), 93))
+    resd = din(res.half())
+    try:
+        lib.fgdm_debug_force_igemm_cfg(cfg)
+        for K in (64, 128, 192):
+            x, w, b = h16(rnd((M, K), 90)), h16(rnd((N, K), 91, 1 / np.sqrt(K))), rnd((N,), 92, 0.1)
+            xd, wd, bd = din(x.half()), w.cuda(), b.cuda()
+            out = guarded_out((M, N), torch.half)
+            assert lib.fgdm_op_linear(_p(xd), _p(wd), _p(bd), _p(resd), M, K, N, 0, 0, 0, 0, _p(out.t), _st()) == 0
+            ref = h16(h16(F.linear(x, w, b)) + res)
+            assert relerr(out.check().float().cpu(), ref) < TOL, K
+            close(f'pipelined linear cfg {cfg} K{K}', out.t, ref)
+    finally:
+        lib.fgdm_debug_force_igemm_cfg(0)
+
+
 @pytest.mark.parametrize('N', [4, 320, 1280])
 def test_linear_f32_nchw_output(lib, N):
     """out_kind 2 (OUT_F32_NCHW): the UNet's eps, the ControlNet residuals of the inspection entry and the VAE output leave the
@@ -771,6 +795,8 @@ LN_CASES = [
     (2048, 1280, 1280, 1280, 0, True, 0, 8),    # the 8x8 level: 64x160 four-wave tiles (automatic), statistics from their epilogue
     (4100, 1280, 1280, 1280, 0, True, 0, 8),    # ragged M on the 64x160 tiles (the 16x16 level at 8 prompts per GPU, plus four rows)
     (2050, 1280, 1280, 1280, 0, True, 27, 8),   # the 64x160 tile on the phase-locked K loop emits them the same way
+    (6600, 320, 320, 2560, 3, True, 0, 2),      # the smallest consumer on the persistent GEGLU kernel: 26 row tiles (the last ragged) x 10
+                                                # column tiles = 260 > 256 (test_persistent_walk_modes runs it under both tile walks)
 ]
 
 
@@ -840,6 +866,24 @@ def test_layernorm_folded_into_consumer_gemm(lib, case):
         a, g = z32.chunk(2, dim=-1)
         z32 = a * F.gelu(g)
     assert relerr(y.float().cpu(), z32) < TOL
+
+
+@pytest.mark.parametrize('mode', ['2', '0'])
+def test_persistent_walk_modes(mode):
+    """FGDM_IGEMM_PERSIST=2 (contiguous runs instead of the default round-robin walk) and =0 (one workgroup per tile) stay selectable
+    for same-box A/B runs, so they stay under the same cases.  With 260 tiles, mode 2 gives the workgroups of four XCDs runs of two
+    tiles: some stay in one row block (the next tile's (mean, rstd) are COPIED from the other operand set), some cross into the next
+    (they are recomputed); the LayerNorm case holds either bitwise against the 2-stage kernel.  The knob is read once per process:
+    a fresh interpreter runs that case and the smaller persistent-kernel case under each value."""
+    import os
+    import subprocess
+    import sys
+    env = dict(os.environ, FGDM_IGEMM_PERSIST=mode)
+    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-q', '-x', '-m', 'gpu', '-k',
+                        '(test_layernorm_folded_into_consumer_gemm and M6600_) or (test_geglu_persistent_kernel and L1)'],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert '2 passed' in r.stdout, r.stdout[-3000:]
 
 
 @pytest.mark.parametrize('offset', [8.0, 32.0], ids=lambda o: f'row_mean_{int(o)}_std')
