@@ -37,6 +37,14 @@ class FgdmConfig(C.Structure):
     ]
 
 
+class FgdmConfig2(FgdmConfig):
+    """fgdm_config as include/fgdm.h declares it today: the 208-byte struct above (whose last four bytes, `reserved0` in the
+    header, were its tail padding) followed by the SD-2.x fields.  A ctypes subclass lays its own fields out after the WHOLE base,
+    padding included, which is exactly where the header puts them (offsets 208 and 212); zero in both means the networks the
+    208-byte struct described."""
+    _fields_ = [('num_head_channels', C.c_int32), ('use_linear_in_transformer', C.c_int32)]
+
+
 _p = C.c_void_p
 _f = C.c_float
 _i = C.c_int

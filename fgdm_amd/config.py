@@ -25,14 +25,37 @@ _UNET_TARGETS = {
 # UNetModel / ControlNet kwargs the engine implements with exactly one value (the shipped configs')
 _FIXED = {'use_spatial_transformer': True, 'transformer_depth': 1, 'legacy': False, 'dims': 2, 'num_classes': None,
           'use_scale_shift_norm': False, 'resblock_updown': False, 'conv_resample': True, 'use_new_attention_order': False,
-          'num_head_channels': -1, 'num_heads_upsample': -1, 'n_embed': None, 'dropout': 0, 'use_fp16': False,
-          'disable_self_attentions': None, 'num_attention_blocks': None, 'disable_middle_self_attn': False,
-          'use_linear_in_transformer': False}
+          'num_heads_upsample': -1, 'n_embed': None, 'dropout': 0, 'use_fp16': False,
+          'disable_self_attentions': None, 'num_attention_blocks': None, 'disable_middle_self_attn': False}
 # ... and the ones without numerical meaning on the sampling path
 _IGNORED = {'image_size', 'use_checkpoint', 'hint_channels', 'no_prompting', 'use_time_adapter', 'num_prompts',
             'return_conds', 'distill', 'freeze_backbone'}
 _NET_KEYS = ('in_channels', 'out_channels', 'model_channels', 'attention_resolutions', 'num_res_blocks', 'channel_mult',
              'num_heads', 'context_dim')
+# The SD-2.x switches (openaimodel.py:469-511; ldm/modules/attention.py:262-267): a fixed head width instead of a fixed head count,
+# and nn.Linear proj_in / proj_out.  They enter the engine cfg only when set, so an SD-v1 node yields the dict it always did.
+_SD2_KEYS = {'num_head_channels': -1, 'use_linear_in_transformer': False}
+SD2_LIMIT = ('of the SD-2.x family the engine runs the eps-prediction networks (SD-2.1-base and its ControlNets: num_head_channels, '
+             'use_linear_in_transformer, context_dim 1024) with the context handed in as a tensor or by a cond_stage_model callable')
+
+
+def _head_params(p):
+    """num_heads / num_head_channels of a node -> the pair the engine takes; exactly one of them is set (-1: unset)."""
+    nh, nhc = p.get('num_heads', -1), p.get('num_head_channels', -1)
+    nh, nhc = (-1 if nh is None else int(nh)), (-1 if nhc is None else int(nhc))
+    if nh != -1 and nhc != -1:
+        raise NotImplementedError(f'num_heads={nh} and num_head_channels={nhc} are both set: set one and leave the other at -1')
+    if nh == -1 and nhc == -1:
+        raise NotImplementedError('Either num_heads or num_head_channels has to be set (openaimodel.py:507-511)')
+    if nhc != -1:
+        if nhc <= 0 or nhc % 8:
+            raise NotImplementedError(f'num_head_channels={nhc}: the head width must be a positive multiple of 8')
+        bad = [int(p['model_channels']) * int(m) for m in p['channel_mult'] if int(p['model_channels']) * int(m) % nhc]
+        if bad:
+            raise NotImplementedError(f'num_head_channels={nhc} does not divide the channel counts {bad}')
+    elif nh <= 0:
+        raise NotImplementedError(f'num_heads={nh}: a positive head count (or -1 with num_head_channels)')
+    return nh, nhc
 
 
 def to_dict(node):
@@ -73,14 +96,22 @@ def unet_params(node, default=None):
     for k, want in _FIXED.items():
         if k in p and p[k] != want and not (want in (0, None, False) and not p[k]):
             raise NotImplementedError(f'{k}={p[k]!r}: the engine implements {k}={want!r} (the shipped configs)')
-    unknown = [k for k in p if k not in _FIXED and k not in _IGNORED and k not in _NET_KEYS]
+    if p.get('parameterization', 'eps') != 'eps':         # (a LatentDiffusion key; refused here too when it strays into the node)
+        raise NotImplementedError(f"parameterization={p['parameterization']!r}: {SD2_LIMIT}; v-prediction is not implemented")
+    unknown = [k for k in p if k not in _FIXED and k not in _IGNORED and k not in _NET_KEYS and k not in _SD2_KEYS]
     if unknown:
         raise NotImplementedError(f'unsupported UNet parameters {unknown}')
-    missing = [k for k in _NET_KEYS if k not in p and not (k == 'out_channels' and kind == 'controlnet')]
+    missing = [k for k in _NET_KEYS if k not in p and not (k == 'out_channels' and kind == 'controlnet')
+               and k != 'num_heads']       # absent: -1, the reference's default; _head_params asks for one of the pair
     if missing:
         raise KeyError(f'UNet config lacks {missing}')
     cfg = {k: (tuple(p[k]) if isinstance(p[k], (list, tuple)) else p[k]) for k in _NET_KEYS if k in p}
     cfg.setdefault('out_channels', cfg['in_channels'])
+    cfg['num_heads'], nhc = _head_params(p)
+    if nhc != -1:
+        cfg['num_head_channels'] = nhc
+    if p.get('use_linear_in_transformer'):
+        cfg['use_linear_in_transformer'] = True
     flags = {k: p[k] for k in ('no_prompting', 'use_time_adapter', 'num_prompts', 'hint_channels') if k in p}
     return kind, cfg, flags
 

@@ -1266,8 +1266,11 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
     // K row stride: 4 mod 8 dwords makes sixteen consecutive rows tile the banks (d = 40: 80-byte rows).  d = 80 (160-byte rows: rows
     // r and r + 8 would meet in the same banks): the 16-byte pieces of rows with (r >> 3) & 1 are ROTATED by ROT = 5 positions,
     // half a row, on the source side -- sixteen consecutive rows then tile the banks again
-    constexpr int ROT = (KROW / 4) % 8 == 4 ? 0 : DC / 2;
-    static_assert(ROT == 0 || ((KROW / 4) % 16 == 8 && DC % 2 == 0), "K row stride");
+    // d = 64 (128-byte rows, exactly the V^T row: rows r and r + 2 would meet): the pieces are XOR-swizzled by (r >> 1) & 7 on the
+    // source side, as those of V^T are -- a K fragment read has the very bank pattern of a V^T fragment read
+    constexpr bool KXOR = KROW == 128;
+    constexpr int ROT = (KXOR || (KROW / 4) % 8 == 4) ? 0 : DC / 2;
+    static_assert(KXOR || ROT == 0 || ((KROW / 4) % 16 == 8 && DC % 2 == 0), "K row stride");
     __shared__ __attribute__((aligned(1024))) char smem[NSLOT * SLOT + 64];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1310,7 +1313,7 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
             const int L = 64 * j + lane, rp = L / DC, c = L - rp * DC;
             const int rho = rp & 31, a = rho >> 3;
             const int key = (rp & 32) + 16 * (a >> 1) + 8 * ((rho >> 2) & 1) + 4 * (a & 1) + (rho & 3);
-            const int cs = (c + DC - ROT * ((rho >> 3) & 1)) % DC;           // LDS position c of this row holds source piece cs
+            const int cs = KXOR ? (c ^ ((rho >> 1) & 7)) : (c + DC - ROT * ((rho >> 3) & 1)) % DC;      // LDS position c of this row holds source piece cs
             voff[u] = (unsigned)(key * ldk + cs * 8) * 2u;
         } else {
             const int L = 64 * (j - KBYTES / 1024) + lane, d = L >> 3, x = L & 7;
@@ -1353,7 +1356,8 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
     // pieces >= DC are the constants.  V^T: row 32 t + n32, source piece 4 sub + 2 s2 + h at position (that) ^ ((n32 >> 1) & 7).
     int k_lane[NKS];                                         // byte offset of piece 2 s + h in this lane's row (rotated rows: see ROT)
 #pragma unroll
-    for (int s2 = 0; s2 < NKS; ++s2) k_lane[s2] = n32 * KROW + ((2 * s2 + h + ROT * ((n32 >> 3) & 1)) % DC) * 16;
+    for (int s2 = 0; s2 < NKS; ++s2)      // (the fold slot's pieces, 2 s2 + h >= DC, are the constants: its k_lane is never used)
+        k_lane[s2] = n32 * KROW + (KXOR ? ((2 * s2 + h) & 7) ^ ((n32 >> 1) & 7) : (2 * s2 + h + ROT * ((n32 >> 3) & 1)) % DC) * 16;
     int v_lane[2][2];
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub)
@@ -1557,11 +1561,13 @@ static int att_launch(const AttnCall& c, dim3 grid, int threads, int lds, int ki
     FGDM_LAUNCH(Kernel, grid, dim3(threads), lds, c.s, c.Q, c.ldq, c.K, c.ldk, c.Vt, c.ldvt, c.O, c.ldo, c.H, c.T, c.Tk, c.sl2e, extra...);
     return att_launched(kid);
 }
-// f(std::integral_constant<int, d>) for the head widths of the networks (320 ... 1280 channels over 8 heads)
+// f(std::integral_constant<int, d>) for the head widths of the networks (320 ... 1280 channels over 8 heads: 40 / 80 / 160; a fixed
+// head width, num_head_channels = 64: 5 ... 20 heads)
 template <class F>
 static int by_head_width(int d, F&& f) {
     switch (d) {
         case 40: return f(std::integral_constant<int, 40>{});
+        case 64: return f(std::integral_constant<int, 64>{});
         case 80: return f(std::integral_constant<int, 80>{});
         case 160: return f(std::integral_constant<int, 160>{});
         default: return FGDM_ERR_ARG;
@@ -1607,6 +1613,8 @@ static int launch_ablation_bits(const AttnCall& c, int abl, bool wide) {
 }
 
 // The key-resident text kernel with cpw query chunks per wave.  (d = 160, NS = 8) does not fit the 160 KB of a CU and is never built.
+static_assert(attn_cross_lds(64, 3) <= 64 * 1024 && attn_cross_lds(64, 8) <= 160 * 1024, "d = 64: NS = 3 static, every NS form fits a CU's LDS");
+static_assert(attn_cross_lds(160, 7) <= 160 * 1024 && attn_cross_lds(160, 8) > 160 * 1024, "d = 160: up to NS = 7");
 template <int D, int NS>
 static int launch_cross(const AttnCall& c, int cpw) {
     constexpr int lds = attn_cross_lds(D, NS), dyn = NS == 3 ? 0 : lds;      // NS = 3 keeps its LDS static
@@ -1655,8 +1663,11 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
     // d = 80: the 32-wide kernel at one wave per SIMD (its two strands need ~280 registers); FGDM_ATTN_DQ80=0 switches it off (A/B)
     const int dq80 = knob_once(KNOB_ATTN_DQ80);
     if (dq80 > 0 && d == 80 && two_strand_ok(c, d)) return launch_two_strand<attn_dq32_kernel<80, 4>>(c, ATT_KID_DQ32);
-    // every other long shape at d = 40 / 80: the eight-wave ping-pong kernel (256 queries per workgroup); FGDM_ATTN_PP=0 switches it off (A/B)
-    if (pp_on && T >= 256 && Tk >= 256 && (d == 40 || d == 80)) return d == 40 ? launch_pp<40>(c) : launch_pp<80>(c);
+    // d = 64 (SD-2.x: a fixed head width): the 32-wide kernel as well, one wave per SIMD like d = 80 and behind the same switch --
+    // FGDM_ATTN_DQ80=0 sends both to the ping-pong kernel (A/B; the measurement behind the default: profiles/attention_d64.txt)
+    if (dq80 > 0 && d == 64 && two_strand_ok(c, d)) return launch_two_strand<attn_dq32_kernel<64, 4>>(c, ATT_KID_DQ32);
+    // every other long shape at d = 40 / 64 / 80: the eight-wave ping-pong kernel (256 queries per workgroup); FGDM_ATTN_PP=0 switches it off (A/B)
+    if (pp_on && T >= 256 && Tk >= 256 && (d == 40 || d == 64 || d == 80)) return d == 40 ? launch_pp<40>(c) : d == 64 ? launch_pp<64>(c) : launch_pp<80>(c);
     // one text part (64 < Tk <= 96, NS = 3): the key-resident kernel.  FGDM_ATTN_CROSS: query chunks per wave, 0 = off (A/B)
     const int cross = knob_once(KNOB_ATTN_CROSS);
     if (cross > 0 && Tk > 64 && Tk <= 96 && ldvt >= 96 && T >= 128)
@@ -1666,7 +1677,7 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
     // the Q + O rows of 4 chunks, and at T = 1024 eight chunks make one workgroup per (batch, head) (measured:
     // profiles/long_context_attention.txt; 4 chunks do not beat attn_kernel at d = 80)
     const int cross_long = knob_once(KNOB_ATTN_CROSS_LONG), ns = (Tk + 31) / 32;
-    if (cross_long > 0 && Tk > 96 && Tk <= 256 && T >= 128 && ldvt >= ns * 32 && (d == 40 || d == 80 || (d == 160 && ns <= 7)))
+    if (cross_long > 0 && Tk > 96 && Tk <= 256 && T >= 128 && ldvt >= ns * 32 && (d == 40 || d == 64 || d == 80 || (d == 160 && ns <= 7)))
         return by_head_width(d, [&](auto dc) { return launch_cross_ns<decltype(dc)::value>(c, ns, std::min(cross_long, T / 128)); });
     // everything else: the general kernel
     return by_head_width(d, [&](auto dc) { return launch_general<decltype(dc)::value>(c); });

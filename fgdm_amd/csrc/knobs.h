@@ -21,7 +21,7 @@
 #define FGDM_KNOBS(X)                                                                                                          \
     X(ATTN_PP, "FGDM_ATTN_PP", "1", "0: the four-wave attention kernel where the eight-wave ping-pong one would run")           \
     X(ATTN_DQ, "FGDM_ATTN_DQ", "3", "long self-attention, d = 40: 3 = two-strand kernel, 32-wide V^T P^T; 1 = 16-wide; 0 = off") \
-    X(ATTN_DQ80, "FGDM_ATTN_DQ80", "1", "0: the ping-pong kernel instead of the two-strand one at d = 80")                      \
+    X(ATTN_DQ80, "FGDM_ATTN_DQ80", "1", "0: the ping-pong kernel instead of the two-strand one at d = 64 / 80")                 \
     X(ATTN_ABL, "FGDM_ATTN_ABL", "0", "ablation instantiations of the two-strand kernel (tools/bench_attention.py only)")       \
     X(ATTN_CROSS, "FGDM_ATTN_CROSS", "4", "query chunks per wave of the text-token kernel (65 - 96 keys); 0 = off")             \
     X(ATTN_CROSS_LONG, "FGDM_ATTN_CROSS_LONG", "8", "query chunks per wave of the key-resident kernel (97 - 256 keys); 0 = off") \

@@ -186,7 +186,8 @@ struct Model {
         const std::string q = t + "attn1.to_q", k = t + "attn1.to_k", vv = t + "attn1.to_v", n1 = t + "norm1", n2 = t + "norm2", n3 = t + "norm3";
         const int ch = l.cin, d = ch / l.heads;
         v.norm(l.gn, p + "norm", ch);
-        v.linear(l.pin, p + "proj_in", ch, ch, true, true);
+        const bool conv_proj = !cfg.use_linear_in_transformer;      // nn.Conv2d(C, C, 1) or nn.Linear(C, C): the same GEMM over NHWC rows
+        v.linear(l.pin, p + "proj_in", ch, ch, conv_proj, true);
         v.source(q, ch, ch, false);
         v.source(k, ch, ch, false);
         v.source(vv, ch, ch, false);
@@ -201,7 +202,7 @@ struct Model {
         v.layernorm(l.ln1, n1, ch);
         v.layernorm(l.ln2, n2, ch);
         v.layernorm(l.ln3, n3, ch);
-        v.linear(l.pout, p + "proj_out", ch, ch, true, true);
+        v.linear(l.pout, p + "proj_out", ch, ch, conv_proj, true);
     }
     template <class V> void visit_block(V& v, Block& blk, int temb, std::vector<std::string>* embs) {
         for (Layer& l : blk)
@@ -378,7 +379,10 @@ struct Model {
     // openaimodel.py:558-718 / cldm.py:640-787
     void build_net(Net& n, const std::string& prefix, bool control, int adapter_kind) {
         n.prefix = prefix; n.control = control; n.has_adapter = adapter_kind != 0; n.time_adapter = adapter_kind == 2;
-        const int mc = cfg.model_channels, heads = cfg.num_heads;
+        const int mc = cfg.model_channels;
+        // heads of a SpatialTransformer at `c` channels: c / num_head_channels when the head WIDTH is fixed (openaimodel.py:603-606,
+        // 659-662, 709-712), else num_heads at every level
+        auto heads_at = [&](int c) { return cfg.num_head_channels > 0 ? c / cfg.num_head_channels : cfg.num_heads; };
         auto blocks = [](const std::string& ap) {
             std::vector<AdapterBlk> body;
             adapter_body(ap, [&](int ic, int oc, bool down, const std::string& pre) {
@@ -403,7 +407,7 @@ struct Model {
             for (int r = 0; r < cfg.num_res_blocks; ++r) {
                 Block b{mk(L_RES, ch, mult * mc)};
                 ch = mult * mc;
-                if (in_ares(ds)) b.push_back(mk(L_ATTN, ch, ch, heads));
+                if (in_ares(ds)) b.push_back(mk(L_ATTN, ch, ch, heads_at(ch)));
                 n.input.push_back(b);
                 chans.push_back(ch);
             }
@@ -413,7 +417,7 @@ struct Model {
                 ds *= 2;
             }
         }
-        n.middle = {mk(L_RES, ch, ch), mk(L_ATTN, ch, ch, heads), mk(L_RES, ch, ch)};
+        n.middle = {mk(L_RES, ch, ch), mk(L_ATTN, ch, ch, heads_at(ch)), mk(L_RES, ch, ch)};
         if (control) n.zero_convs.resize(n.input.size());
         for (int level = cfg.n_levels - 1; level >= 0 && !control; --level) {
             const int mult = cfg.channel_mult[level];
@@ -422,7 +426,7 @@ struct Model {
                 chans.pop_back();
                 Block b{mk(L_RES, ch + ich, mc * mult)};
                 ch = mc * mult;
-                if (in_ares(ds)) b.push_back(mk(L_ATTN, ch, ch, heads));
+                if (in_ares(ds)) b.push_back(mk(L_ATTN, ch, ch, heads_at(ch)));
                 if (level && i == cfg.num_res_blocks) { b.push_back(mk(L_UP, ch, ch)); ds /= 2; }
                 n.output.push_back(b);
             }
@@ -500,7 +504,7 @@ struct Model {
     }
     int build() {
         if (cfg.n_levels < 1 || cfg.n_levels > FGDM_MAX_LEVELS || cfg.model_channels <= 0 || (cfg.model_channels & 63) ||
-            cfg.num_heads <= 0 || cfg.n_controlnets < 0 || cfg.n_controlnets > FGDM_MAX_CONTROLNETS ||
+            cfg.n_controlnets < 0 || cfg.n_controlnets > FGDM_MAX_CONTROLNETS ||
             (cfg.context_dim & 63) || cfg.in_channels < 4 || cfg.in_channels > 32)
             return fail(FGDM_ERR_ARG, "unsupported config (model_channels and context_dim must be multiples of 64, 4 <= in_channels <= 32)");
         // in_channels > 4: the UNet reads cat([x] + c_concat, 1) (DiffusionWrapper 'hybrid', ddpm.py:1838-1841)
@@ -510,9 +514,20 @@ struct Model {
         if (cfg.in_channels != 4 && cfg.n_controlnets > 0)
             return fail(FGDM_ERR_ARG, "in_channels != 4 with ControlNets: ControlLDM.apply_model never goes through DiffusionWrapper, its "
                                       "c_concat is the hint (cldm.py:836-849)");
+        // num_heads XOR num_head_channels (openaimodel.py:507-511); -1, the reference's "unset", and 0, a zeroed struct, both mean unset
+        const bool fixed_width = cfg.num_head_channels > 0, fixed_count = cfg.num_heads > 0;
+        if (cfg.reserved0 != 0) return fail(FGDM_ERR_ARG, "fgdm_config::reserved0 must be 0");
+        if (fixed_width == fixed_count)
+            return fail(FGDM_ERR_ARG, fixed_width ? "num_heads and num_head_channels are both set: set one, leave the other -1"
+                                                  : "either num_heads or num_head_channels has to be set");
+        if (cfg.num_head_channels < -1 || cfg.num_heads < -1 || (fixed_width && (cfg.num_head_channels & 7)))
+            return fail(FGDM_ERR_ARG, "num_head_channels must be a positive multiple of 8 (or -1), num_heads positive (or -1)");
+        if (cfg.use_linear_in_transformer < 0 || cfg.use_linear_in_transformer > 1)
+            return fail(FGDM_ERR_ARG, "use_linear_in_transformer: 0 (1x1 convolutions) or 1 (nn.Linear proj_in / proj_out)");
         for (int l = 0; l < cfg.n_levels; ++l) {
             const int ch = cfg.model_channels * cfg.channel_mult[l];
-            if (ch % cfg.num_heads) return fail(FGDM_ERR_ARG, "channels not divisible by heads");
+            if (fixed_width ? ch % cfg.num_head_channels : ch % cfg.num_heads)
+                return fail(FGDM_ERR_ARG, fixed_width ? "channels not divisible by num_head_channels" : "channels not divisible by heads");
         }
         if (cfg.use_adapter && !(cfg.model_channels == 320 && cfg.n_levels == 4 && cfg.num_res_blocks == 2))
             return fail(FGDM_ERR_ARG, "FG-DM adapter requires the SD-v1 topology (openaimodel.py:554-556,855-859)");

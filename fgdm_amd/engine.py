@@ -24,7 +24,8 @@ SD_CLIP = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hi
 
 def make_config(cfg=None, use_adapter=False, n_controlnets=0, hint_channels=3, workspace_bytes=0, vae=None, clip=None,
                 num_prompts=1, vae_encoder=False):
-    """fgdm_config from the reference's UNetModel kwargs (models/config.yaml:33-48); `vae`: None (no first-stage
+    """fgdm_config from the reference's UNetModel kwargs (models/config.yaml:33-48; SD-2.x nodes carry `num_head_channels` with
+    `num_heads=-1`, and `use_linear_in_transformer`); `vae`: None (no first-stage
     decoder), True (SD_VAE) or the AutoencoderKL `ddconfig` dict; `clip`: None, True (SD_CLIP) or a CLIPTextConfig-style
     dict (text encoder in the engine); `vae_encoder`: also the first-stage ENCODER of that `vae` (AutoencoderKL.encode: the
     parameter table then lists the whole AutoencoderKL.state_dict(), encoder.* and quant_conv.* included)."""
@@ -34,7 +35,7 @@ def make_config(cfg=None, use_adapter=False, n_controlnets=0, hint_channels=3, w
         from . import config as _cfgmod          # {target, params} node / OmegaConf / dict with extra UNetModel kwargs
         cfg = _cfgmod.unet_params(cfg)[1]
     cfg = dict(SD_V1 if cfg is None else cfg)
-    c = _lib.FgdmConfig()
+    c = _lib.FgdmConfig2()
     c.in_channels = cfg['in_channels']
     c.out_channels = cfg['out_channels']
     c.model_channels = cfg['model_channels']
@@ -48,6 +49,9 @@ def make_config(cfg=None, use_adapter=False, n_controlnets=0, hint_channels=3, w
     for i, v in enumerate(ar):
         c.attention_resolutions[i] = v
     c.num_heads = cfg['num_heads']
+    # SD-2.x networks: a fixed head WIDTH (then num_heads is -1) and nn.Linear proj_in / proj_out; absent: the SD-v1 values
+    c.num_head_channels = cfg.get('num_head_channels', -1)
+    c.use_linear_in_transformer = int(bool(cfg.get('use_linear_in_transformer', False)))
     c.context_dim = cfg['context_dim']
     c.use_adapter = 2 if use_adapter in ('time', 2) else int(bool(use_adapter))      # 'time' -> TimeAdapter
     c.n_controlnets = int(n_controlnets)

@@ -109,7 +109,8 @@ class LatentDiffusion(_Buffers):
                  channels=4, image_size=32, log_every_t=200, clip_denoised=False, device=0, first_stage_config=None,
                  cond_stage_config=None, first_stage_encoder=False, **ignored):
         if parameterization != 'eps':
-            raise NotImplementedError('only eps-parameterization is used by the shipped configs (models/config.yaml)')
+            raise NotImplementedError(f'parameterization={parameterization!r}: only eps-parameterization is implemented (the shipped '
+                                      f'configs, models/config.yaml; {_cfg.SD2_LIMIT}; v-prediction checkpoints are refused)')
         if conditioning_key not in ('crossattn', 'hybrid'):
             raise NotImplementedError(_REFUSED_KEYS.get(conditioning_key, f'conditioning_key={conditioning_key!r}: DiffusionWrapper '
                                                                           "knows None, 'concat', 'crossattn', 'hybrid', 'adm'"))
@@ -192,6 +193,10 @@ class LatentDiffusion(_Buffers):
             return True
         cc = dict(cond_stage_config)
         if 'target' in cc:
+            if 'OpenCLIP' in str(cc['target']):
+                raise NotImplementedError(f"cond_stage_config target {cc['target']}: the OpenCLIP text encoder is not in the engine; "
+                                          f'{_cfg.SD2_LIMIT} (build the model without cond_stage_config and set its '
+                                          'cond_stage_model, or pass c_crossattn tensors [B, tokens, 1024])')
             if not str(cc['target']).endswith('FrozenCLIPEmbedder'):
                 raise NotImplementedError(f"cond_stage_config target {cc['target']}: only FrozenCLIPEmbedder is shipped")
             return True
@@ -544,7 +549,9 @@ class ControlLDM(LatentDiffusion):
         ckind, ccfg, cflags = _cfg.unet_params(control_stage_config)
         _, ucfg, _ = _cfg.unet_params(unet_config)
         ucfg = dict(_k.SD_V1 if ucfg is None else ucfg)
-        diff = [k for k in ccfg if k != 'out_channels' and tuple(np.atleast_1d(ccfg[k])) != tuple(np.atleast_1d(ucfg[k]))]
+        sd2 = _cfg._SD2_KEYS       # absent from a cfg when unset: compared by their defaults, so a twin must match in them too
+        diff = [k for k in list(ccfg) + [k for k in sd2 if k not in ccfg] if k != 'out_channels' and
+                tuple(np.atleast_1d(ccfg.get(k, sd2.get(k)))) != tuple(np.atleast_1d(ucfg.get(k, sd2.get(k))))]
         if ckind not in (None, 'controlnet') or diff or cflags.get('hint_channels', 3) != 3:
             raise NotImplementedError(f'control_stage_config must be a ControlNet matching unet_config (differs in {diff})')
 

@@ -54,6 +54,17 @@ typedef struct fgdm_config {
                                 * quant_conv.*, post_quant_conv.*, with double_z = True and in_channels = 3 (models/config.yaml:55-69)
                                 * and the ch / ch_mult / num_res_blocks / z_channels above.  Needs vae_ch > 0.  (Appended last: the
                                 * offsets of the earlier fields are those of engines built before the encoder existed.) */
+    int32_t reserved0;         /* must be 0.  Offset 204: the tail padding of the 208-byte struct that ended with vae_encoder, so
+                                * the fields below start where that struct ended and none of its bytes changes meaning. */
+    /* The second Stable-Diffusion family (SD-2.x UNets and their ControlNets; UNetModel.__init__, openaimodel.py:469-734).  Both
+     * fields zero (or -1 / 0): the networks above, unchanged.
+     * num_head_channels > 0: every SpatialTransformer at `ch` channels has ch / num_head_channels heads of that width (64 in
+     *   SD-2.x: 5 / 10 / 20 / 20 heads) and num_heads must be -1 or 0; a multiple of 8 that divides every level's channel count,
+     *   and a width the attention kernels are built for (40, 64, 80, 160).  0 or -1: num_heads heads at every level.
+     * use_linear_in_transformer = 1: SpatialTransformer.proj_in / proj_out are nn.Linear, so their weights are [C, C] in the
+     *   parameter table instead of [C, C, 1, 1] (ldm/modules/attention.py:262-267,285-291).  The arithmetic is the same GEMM. */
+    int32_t num_head_channels;
+    int32_t use_linear_in_transformer;
 } fgdm_config;
 
 #define FGDM_DTYPE_F32 0
@@ -334,7 +345,7 @@ int fgdm_op_layernorm(const void* x, int rows, int C, const float* gamma, const 
  * vt [B, heads * d, ldvt], keys contiguous, ldvt a multiple of 8 and >= roundup(Tk, 64).  Contract for the columns of a V^T row:
  * [0, Tk) the values; [Tk, roundup(Tk, 64)) must be ZERO (the kernels load whole 32- / 64-key tiles and multiply the pad
  * columns by probabilities that are exactly 0, so anything finite would do, a NaN or Inf would not); columns >=
- * roundup(Tk, 64) are read by no kernel and may hold anything.  d is 40, 80 or 160. */
+ * roundup(Tk, 64) are read by no kernel and may hold anything.  d is 40, 64, 80 or 160. */
 int fgdm_op_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo,
                       int B, int heads, int T, int Tk, int d, void* stream);
 /* Diagnostic entries (tests/test_gpu_attention_calls.py); the product path does not call them.
