@@ -61,6 +61,14 @@ int fgdm_bench_igemm(int B, int H, int W, int C0, int C1, int Cout, int ksize, i
     a.B = B; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.mode = mode;
     a.M = (int)M; a.N = Cout; a.K = K; a.act = act; a.out_kind = OUT_F16; a.out = out; a.ld_out = nout;
     a.rows_per_sample = Ho * Wo; a.scale = 1.f; a.force_cfg = cfg & 0xff; a.debug = (cfg >> 8) & 0xff;
+    if (igemm_up_phase(a)) {        // the engine's dispatch: four 2x2 phase GEMMs in one launch, on random phase kernels [4][npad][4 C]
+        std::vector<half_t> hp(4 * npad * (size_t)(4 * Cin));
+        const float ps = 1.0f / sqrtf(2.25f * Cin);       // a phase tap sums 1 / 2 / 4 of the 3x3 taps: 2.25 on average
+        for (auto& v : hp) v = (half_t)(rnd() * ps * 3.0f);
+        const half_t* wph = tmp.up(hp);
+        if (!wph) return FGDM_ERR_NOMEM;
+        a = igemm_phase_args(a, wph);
+    }
     if ((cfg & 0xff) == 0 && plan_splitk(a, tmp) != FGDM_OK) return FGDM_ERR_NOMEM;
     return time_launches(3, iters, avg_ms, [&]() { return igemm_launch(a, nullptr); });
 }

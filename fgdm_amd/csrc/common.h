@@ -70,7 +70,11 @@ __device__ __forceinline__ float ln_scale(float acc, float mean, float rstd, flo
 // out[m, n] = epilogue( sum_k A[m, k] * W[n, k] ),  m = (b, oy, ox) output pixel, k = (tap, cin)
 // IG_CONV3_S2_BR: stride 2 with the zero padding on the bottom / right only (the first-stage encoder's Downsample, ldm/modules/
 // diffusionmodules/model.py:72-76: F.pad(x, (0,1,0,1)) then conv3x3 stride 2 padding 0): taps at iy = 2 oy + ky, ix = 2 ox + kx
-enum IgemmMode { IG_LINEAR = 0, IG_CONV3 = 1, IG_CONV3_S2 = 2, IG_CONV3_UP2 = 3, IG_CONV3_S2_BR = 4 };
+// IG_CONV2_PHASE: the IG_CONV3_UP2 layer as four 2x2 convolutions over the SOURCE image, one per output phase (pa, pb) = (oy & 1,
+// ox & 1): the 3x3 window over a nearest-2x upsampled image touches a 2x2 block of source pixels, so the taps that land on the same
+// pixel are summed beforehand (engine_shared.h: up_phase_pack) and an output pixel costs 4 C MACs instead of 9 C.  M = B H W source
+// pixels, K = 4 C0, Wt = [4 phases][Npad][K]; all four phases are one launch (igemm2.hip).  igemm_up_phase says which layers take it.
+enum IgemmMode { IG_LINEAR = 0, IG_CONV3 = 1, IG_CONV3_S2 = 2, IG_CONV3_UP2 = 3, IG_CONV3_S2_BR = 4, IG_CONV2_PHASE = 5 };
 enum IgemmAct { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4 /* x * sigmoid(1.702 x), CLIP MLP */ };
 enum IgemmOut { OUT_F16 = 0, OUT_F32 = 1, OUT_F32_NCHW = 2, OUT_F16_T = 3 };
 
@@ -119,6 +123,11 @@ struct IgemmArgs {
 };
 
 int igemm_launch(const IgemmArgs& a, hipStream_t s);
+// Does the IG_CONV3_UP2 problem `a` run as IG_CONV2_PHASE?  Layer geometry and process-wide knobs only (FGDM_IGEMM_UP_PHASE, a forced
+// 2-stage tile) -- never the batch: a sample's bits must not depend on the batch it is evaluated in.
+bool igemm_up_phase(const IgemmArgs& a);
+// ... and `a` rewritten for it: mode, M, K, rows_per_sample and the phase weights `wt_phase` ([4][Npad][4 C0], up_phase_pack)
+IgemmArgs igemm_phase_args(const IgemmArgs& a, const half_t* wt_phase);
 void igemm_set_force_cfg(int cfg);   // process-wide override of the tile choice (0 = automatic)
 void igemm_set_twin_layers(bool on);  // the layers walked from now on have a same-shape twin in another net of this engine (UNet
                                        // encoder / middle block and the ControlNets): igemm_splitk_factor leaves their K = 11520

@@ -276,7 +276,9 @@ struct fgdm_engine : Model {
         return pack_rows(g, srcs, K, K, {}, biases, false, scales, lg ? lg->host.data() : nullptr, lb ? lb->host.data() : nullptr);
     }
     // conv3x3 [Cout, Cin, 3, 3] -> k = tap * Cin + c (implicit GEMM) or im2col layout with padded Cin / K
-    int pack_conv3(GemmW& g, const std::string& pre) {
+    // up: the conv of an Upsample layer -- where the phase form can serve it (igemm_up_phase's geometry) the four summed 2x2 kernels
+    // are packed NEXT TO the 3x3 pack (FGDM_IGEMM_UP_PHASE switches between them in one build), from the fp32 weights, rounded once
+    int pack_conv3(GemmW& g, const std::string& pre, bool up = false) {
         const ParamSlot* w = slot(pre + ".weight");
         const ParamSlot* b = slot(pre + ".bias");
         if (!w || !b) return FGDM_ERR_STATE;
@@ -285,6 +287,11 @@ struct fgdm_engine : Model {
         const std::vector<int> kmap = conv3_kmap(Cin, &cp);      // source row layout is [Cin][3][3]
         g.im2col = (Cin % 64) != 0;
         g.cin_pad = cp;
+        g.wph = nullptr;
+        if (up && Cin % 64 == 0 && N % 320 == 0) {
+            g.wph = upload(up_phase_pack(w->host.data(), N, Cin, igemm_npad(N)));
+            if (!g.wph) return fail(FGDM_ERR_NOMEM, "hipMalloc failed while packing weights");
+        }
         return pack_rows(g, {{w->host.data(), N}}, Cin * 9, (int)kmap.size(), kmap, {b->host.data()}, false);
     }
     int pack_norm(NormW& n, const std::string& pre) {
@@ -328,6 +335,7 @@ struct fgdm_engine : Model {
         void layernorm(NormW& n, const std::string& pre, int C) { if (!e.ln_fold) norm(n, pre, C); }
         void norm(NormW& n, const std::string& pre, int) { run([&] { return e.pack_norm(n, pre); }); }
         void conv3(GemmW& g, const std::string& pre, int, int) { run([&] { return e.pack_conv3(g, pre); }); }
+        void conv3_up(GemmW& g, const std::string& pre, int, int) { run([&] { return e.pack_conv3(g, pre, true); }); }
         void pointwise(float*& dst, const std::string& pre, int, int) { run([&] { return e.pack_pointwise(&dst, pre); }); }
         void table(float*& dst, const std::string& key, int, int) { run([&] { return e.pack_table(&dst, key); }); }
         void source(const std::string&, int, int, bool) {}
@@ -422,6 +430,8 @@ struct fgdm_engine : Model {
         const int taps = mode == IG_LINEAR ? 1 : 9;
         if (taps * (a.C0 + a.C1) != a.K) return fail(FGDM_ERR_ARG, "gemm: K mismatch");
         if (!a.out) return fail(FGDM_ERR_NOMEM, "gemm: null output (workspace exhausted?)");
+        // an Upsample conv whose geometry the phase form serves (and whose phase kernels were packed) runs as four 2x2 phase GEMMs
+        if (w.wph && !e.stats && !e.ln && igemm_up_phase(a)) a = igemm_phase_args(a, w.wph);
         char tag[56] = "";
         // (l: LayerNorm folded in, s: emits LayerNorm partial sums, r: residual, v: per-sample emb row)
         if (prof.on) snprintf(tag, sizeof(tag), "igemm M%d N%d K%d mode%d act%d out%d l%ds%dr%dv%d", a.M, a.N, a.K, a.mode, a.act, a.out_kind,
@@ -449,7 +459,7 @@ struct fgdm_engine : Model {
             const double out_b = (double)a.M * nout * (e.out_kind == OUT_F16 || e.out_kind == OUT_F16_T ? 2.0 : 4.0);
             nbytes = in_b + 2.0 * (double)w.N * w.K + out_b + (e.resid ? 2.0 * (double)a.M * nout : 0.0);
         }
-        prof.begin(PC_IGEMM, s, 2.0 * (double)a.M * (double)w.N * (double)w.k_real, tag, nbytes);
+        prof.begin(PC_IGEMM, s, 2.0 * (double)x0.B * Ho * Wo * (double)w.N * (double)w.k_real, tag, nbytes);    // (algorithmic flops)
         int rc = igemm_launch(a, s);
         prof.end(s);
         if (a.ws) ar->release(a.ws);

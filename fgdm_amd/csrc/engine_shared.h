@@ -30,6 +30,35 @@ static std::vector<int> conv3_kmap(int Cin, int* cin_pad) {
     return kmap;
 }
 
+// Upsample = nearest-2x, then conv3x3 (openaimodel.py: Upsample.forward).  Rows 2 i + a - 1 .. 2 i + a + 1 of the upsampled image are
+// source rows {i - 1, i, i} (a = 0) or {i, i, i + 1} (a = 1), columns likewise with b: output phase (a, b) is a 2x2 convolution over
+// the source at displacement (a - 1 + ty, b - 1 + tx) whose tap (ty, tx) is the SUM of the 3x3 taps that land on that source pixel
+//     a = 0: ty 0 = w[0], ty 1 = w[1] + w[2]        a = 1: ty 0 = w[0] + w[1], ty 1 = w[2]        (columns: b, tx, kx alike)
+// and the zero padding of the upsampled image is "source index -1 or H reads zero".  w [N][Cin][3][3] fp32 -> [4 phases][npad][4 Cin]
+// fp16, phase = 2 a + b, k = (2 ty + tx) Cin + c; the sums are taken in fp32 (ky-major order) and rounded ONCE.
+// One function for Engine::pack_conv3 and fgdm_op_conv2d.
+static std::vector<half_t> up_phase_pack(const float* w, int N, int Cin, size_t npad) {
+    const size_t K = 4 * (size_t)Cin;
+    std::vector<half_t> pk(4 * npad * K, (half_t)0);
+    for (int phs = 0; phs < 4; ++phs) {
+        const int a = phs >> 1, b = phs & 1;
+        for (int n = 0; n < N; ++n)
+            for (int c = 0; c < Cin; ++c) {
+                const float* src = w + ((size_t)n * Cin + c) * 9;
+                for (int t = 0; t < 4; ++t) {
+                    const int ty = t >> 1, tx = t & 1;
+                    const int ky0 = ty == 0 ? 0 : (a == 0 ? 1 : 2), ky1 = ty == 0 ? (a == 0 ? 0 : 1) : 2;
+                    const int kx0 = tx == 0 ? 0 : (b == 0 ? 1 : 2), kx1 = tx == 0 ? (b == 0 ? 0 : 1) : 2;
+                    float sum = 0.f;
+                    for (int ky = ky0; ky <= ky1; ++ky)
+                        for (int kx = kx0; kx <= kx1; ++kx) sum += src[ky * 3 + kx];
+                    pk[((size_t)phs * npad + n) * K + (size_t)t * Cin + c] = (half_t)sum;
+                }
+            }
+    }
+    return pk;
+}
+
 // The im2col route of a conv3x3 (padding 1, stride 1 or 2): A[m][tap * C + c] into the caller's workspace A [B Ho Wo, K], then
 // `gemm_rows(A, B, Ho, Wo, K, rows_per_sample)`: the caller's LINEAR GEMM over the rows of A viewed as [B, Ho, Wo, K], the rows
 // of one sample being its Ho Wo output pixels.  One sequence for Engine::conv3 (whose GEMM goes through the engine's arena and

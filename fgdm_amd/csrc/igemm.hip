@@ -324,6 +324,10 @@ static int pick_force(const IgemmArgs& a) {
     }
     const bool small_tiles = knob_once(KNOB_IGEMM_SMALL_TILES) != 0;        // A/B knob
     const bool other_widths = knob_once(KNOB_IGEMM_OTHER_WIDTHS) != 0;   // A/B knob
+    if (a.mode == IG_CONV2_PHASE) {             // four phases per launch: 256 x 320 tiles once they fill the chip, else 128 x 320
+        if (force >= 4) return force;
+        return (long)((a.M + 255) / 256) * (a.N / 320) * 4 * g_pair_mult >= 192 ? 4 : 6;
+    }
     if (force == 0) {
         const bool geglu = a.act == ACT_GEGLU;
         if (!geglu && a.N % 320 == 0) {
@@ -369,12 +373,36 @@ int igemm_stats_slots(const IgemmArgs& a) {
     return (tile == 0 || tile == 2 || tile == 3 || tile == 5 || (tile == 7 && stats64)) ? a.N / 160 : 0;
 }
 
+// The phase form serves the UNets' Upsample layers: one source whose width is a multiple of 64, N a multiple of 320 (the tiles of the
+// pipelined kernel that pick_force gives it), the plain fp16 output without a per-sample emb row.  The first-stage decoder's widths (128 / 256 / 512) stay on
+// the 3x3 walk.  A forced 2-stage tile (cfg 1..3: tests, tools) has no phase form.
+bool igemm_up_phase(const IgemmArgs& a) {
+    if (!knob_once(KNOB_IGEMM_UP_PHASE)) return false;
+    const int force = a.force_cfg ? a.force_cfg : g_force_cfg;
+    if (force >= 1 && force <= 3) return false;
+    // sources below 8 x 8 (the deepest levels of reduced-size latents: a few rows per sample, launch-bound either way) keep the 3x3 walk
+    if (a.H * a.W < 64) return false;
+    return a.mode == IG_CONV3_UP2 && !a.C1 && a.C0 > 0 && !(a.C0 & 63) && a.K == 9 * a.C0 && a.N % 320 == 0 && a.out_kind == OUT_F16 &&
+           a.act != ACT_GEGLU && a.act != ACT_QGELU && !a.rowvec && !a.stats_out && !a.out2 && !a.ln_stats;
+}
+IgemmArgs igemm_phase_args(const IgemmArgs& a, const half_t* wt_phase) {
+    IgemmArgs p = a;
+    p.mode = IG_CONV2_PHASE;
+    p.Wt = wt_phase;
+    p.K = 4 * a.C0;
+    p.M = a.B * a.H * a.W;                  // rows are SOURCE pixels; Ho / Wo stay the output's
+    p.rows_per_sample = a.H * a.W;
+    p.splitk = 1; p.ws = nullptr;
+    return p;
+}
+
 int igemm_launch(const IgemmArgs& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K & 63) || (a.C0 & 63) || (a.C1 & 63)) return FGDM_ERR_ARG;
     if (a.act == ACT_GEGLU && (a.N & 63)) return FGDM_ERR_ARG;
     if (a.ln_stats && (a.mode != IG_LINEAR || a.C1 || a.ln_slots <= 0 || !a.ln_u)) return FGDM_ERR_ARG;
     if (a.stats_out && igemm_stats_slots(a) == 0) return FGDM_ERR_ARG;
     if (a.out2 && (a.act == ACT_GEGLU || a.splitk > 1 || a.stats_out || a.split_n <= 0 || a.split_n >= a.N || (a.split_n % 640))) return FGDM_ERR_ARG;
+    if (a.mode == IG_CONV2_PHASE && (a.splitk > 1 || a.N % 320)) return FGDM_ERR_ARG;
     if (a.splitk > 1) {        // split-K plan made by the caller (igemm_splitk_factor): 128x320 tiles + reduction pass
         if (!a.ws || a.ln_stats) return FGDM_ERR_ARG;
         // 256 x 320 tiles once they fill the chip (eight-way splits at B = 32), else 128 x 320: the tile changes no sum's order

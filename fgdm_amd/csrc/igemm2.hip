@@ -66,10 +66,11 @@ template <int BM, int BN, int STAGES, int PIPE> constexpr int ring_bytes() {
 // than random ones), measured +3..9 % on the conv shapes (tools/bench_igemm.py cfg 4 vs 7).
 // LN: the consumer side of a folded LayerNorm (IgemmArgs::ln_stats) is its own instantiation, so every other layer pays nothing
 // for it (as a run-time branch inside the register stage it cost the 256x320 tile 208 bytes of scratch per lane)
+// CONV: 0 = LINEAR, 1 = the 3x3 convolution modes, 2 = IG_CONV2_PHASE (its own instantiation: the hot 3x3 kernels keep their registers)
 // PIPE: 0 = every K-step reads its 14 fragments, then runs its 40 MFMAs (all eight waves in the same phase); 1 = software-pipelined
 // K loop (see there).  ABL: the ablation switches of IgemmArgs::debug exist only in the instantiations tools/bench_igemm.py asks for.
-template <int BM, int BN, int WM, int WN, int STAGES, bool CONV, bool GEGLU, bool SPLIT, int MS, bool LN, int PATH, int PIPE, bool ABL>
-__device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
+template <int BM, int BN, int WM, int WN, int STAGES, int CONV, bool GEGLU, bool SPLIT, int MS, bool LN, int PATH, int PIPE, bool ABL>
+__device__ __forceinline__ void igemm2_body(const IgemmArgs& a, const int yb) {
     constexpr int NW = WM * WN, T = NW * 64;
     constexpr int TM = BM / WM, TN = BN / WN;
     constexpr int MI = TM / MS, NI = TN / MS;
@@ -128,6 +129,16 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
     const int br = (CONV && a.mode == IG_CONV3_S2_BR) ? 1 : 0;
     const int sy = (CONV && (a.mode == IG_CONV3_S2 || a.mode == IG_CONV3_S2_BR)) ? 2 : 1;
     const int up = (CONV && a.mode == IG_CONV3_UP2) ? 1 : 0;
+    // IG_CONV2_PHASE (common.h): phase yb = 2 pa + pb of the nearest-2x upsample + 3x3 convolution as a 2x2 convolution over the
+    // SOURCE image.  Rows are source pixels (img, i, j); tap t = 2 ty + tx reads source pixel (i + pa - 1 + ty, j + pb - 1 + tx) (zero
+    // outside the image) against the phase's summed weights [phase][Npad][4 C], k = t C + c; the row is stored to output pixel
+    // (img, 2 i + pa, 2 j + pb).  The walk is the 3x3 one with four taps: 64-channel chunk, tap, 32-channel half.
+    // The phase form is its own instantiation (CONV = 2): every other kernel compiles exactly as it did without it.
+    constexpr bool ph = CONV == 2;
+    const int pa = ph ? (yb >> 1) : 0, pb = ph ? (yb & 1) : 0;
+    const int NT = ph ? 4 : 9;                                  // taps of the walk
+    const int Wq = ph ? a.W : a.Wo, hwq = ph ? a.H * a.W : a.Ho * a.Wo;      // the image a row index walks
+    const half_t* const Wt = ph ? a.Wt + (size_t)yb * (size_t)((a.N + 127) / 128 * 128) * (size_t)a.K : a.Wt;
 #pragma unroll
     for (int i = 0; i < LA; ++i) {
         const int q = (wave + i * NW) * 64 + lane, r = q >> 2, s = q & 3;
@@ -138,9 +149,8 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
             if (!CONV) {
                 a_pix[i] = m;
             } else {
-                const int hw = a.Ho * a.Wo;
-                const int b = m / hw, rem = m - b * hw;
-                const int oy = rem / a.Wo, ox = rem - oy * a.Wo;
+                const int b = m / hwq, rem = m - b * hwq;
+                const int oy = rem / Wq, ox = rem - oy * Wq;
                 a_pix[i] = b * a.H * a.W;
                 a_yx[i] = ((oy * sy + br) << 16) | (ox * sy + br);
             }
@@ -173,9 +183,8 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
                 unsigned cen = (unsigned)m;
                 a_msk[i] = 1;
                 if (CONV) {
-                    const int hw = a.Ho * a.Wo;
-                    const int b = m / hw, rem = m - b * hw;
-                    const int oy = (rem / a.Wo) * sy + br, ox = (rem - (rem / a.Wo) * a.Wo) * sy + br;
+                    const int b = m / hwq, rem = m - b * hwq;
+                    const int oy = (rem / Wq) * sy + br, ox = (rem - (rem / Wq) * Wq) * sy + br;
                     // nearest-2x upsampled input (up = 1): (oy, ox) are coordinates of the upsampled image, the centre is the
                     // source pixel (oy >> 1, ox >> 1), and a tap's source displacement depends on the parity of oy / ox:
                     // bits 16 / 17 of the mask say "oy even" / "ox even"
@@ -183,8 +192,8 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
                     unsigned msk = 0;
 #pragma unroll
                     for (int t = 0; t < 9; ++t) {
-                        const int uy = oy + t / 3 - 1, ux = ox + t % 3 - 1;
-                        if ((unsigned)uy < Hu && (unsigned)ux < Wu) msk |= 1u << t;
+                        const int uy = oy + (ph ? pa - 1 + (t >> 1) : t / 3 - 1), ux = ox + (ph ? pb - 1 + (t & 1) : t % 3 - 1);
+                        if ((!ph || t < 4) && (unsigned)uy < Hu && (unsigned)ux < Wu) msk |= 1u << t;
                     }
                     if (up) msk |= ((oy & 1) ? 0u : 1u << 16) | ((ox & 1) ? 0u : 1u << 17);
                     a_msk[i] = msk;
@@ -209,7 +218,7 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
             const half_t* src = a.A0;
             int Cs = a.C0, co = cc;
             if (co >= a.C0) { src = a.A1; Cs = a.C1; co -= a.C0; }
-            const int ky = tap / 3 - 1, kx = tap - (tap / 3) * 3 - 1;
+            const int ky = ph ? pa - 1 + (tap >> 1) : tap / 3 - 1, kx = ph ? pb - 1 + (tap & 1) : tap - (tap / 3) * 3 - 1;
             const half_t* ptr = a.zero;
             if (!CONV) {
                 if (a_pix[i] >= 0) ptr = src + (size_t)a_pix[i] * Cs + co + a_off[i];
@@ -223,7 +232,7 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
             glds16(ptr, base + (wave + i * NW) * 1024);
         } else {
             const int i = p - LA;
-            const half_t* ptr = a.Wt + (size_t)b_off[i] + ((size_t)(k_begin + kt) << 5);
+            const half_t* ptr = Wt + (size_t)b_off[i] + (ph ? (size_t)(tap * a.C0 + cc) : ((size_t)(k_begin + kt) << 5));
             if constexpr (ABL) { if (a.debug & 8) ptr = a.zero; }
             glds16(ptr, base + b_lds[i]);
         }
@@ -251,11 +260,11 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
 
     // ---- prologue: STAGES-1 stages in flight
     int tap = 0, cc = k_begin << 5;      // tap index, channel offset of the next stage to issue
-    if (CONV) { const int q = k_begin >> 1; tap = q % 9; cc = (q / 9) * 64 + (k_begin & 1) * 32; }
+    if (CONV) { const int q = k_begin >> 1; tap = q % NT; cc = (q / NT) * 64 + (k_begin & 1) * 32; }
     auto advance = [&]() {
         if (!CONV) { cc += 32; return; }
         if (cc & 32) {                       // second half of the 64-chunk done: next tap (or next chunk)
-            if (++tap == 9) { tap = 0; cc += 32; } else { cc -= 32; }
+            if (++tap == NT) { tap = 0; cc += 32; } else { cc -= 32; }
         } else {
             cc += 32;
         }
@@ -268,7 +277,7 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
         const half_t* src = sc.s1 ? a.A1 : a.A0;
         const int Cs = sc.s1 ? a.C1 : a.C0;
         int disp = sc.s1 ? cc - a.C0 : cc;                    // halfs: channel offset (+ the tap's pixel displacement)
-        const int ky = tap / 3 - 1, kx = tap - (tap / 3) * 3 - 1;
+        const int ky = ph ? pa - 1 + (tap >> 1) : tap / 3 - 1, kx = ph ? pb - 1 + (tap & 1) : tap - (tap / 3) * 3 - 1;
         sc.dyE = sc.dyO = sc.dxE = sc.dxO = 0;
         if (CONV) {
             if (!up) {
@@ -279,7 +288,8 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
             }
         }
         sc.sbase = (const char*)src + (ptrdiff_t)disp * 2;
-        sc.wbase = (const char*)a.Wt + ((size_t)(k_begin + kn) << 6);
+        // (the phase weights keep k = tap C + c: a stage's weight piece is addressed by the walk, not by the step count)
+        sc.wbase = (const char*)Wt + (ph ? ((size_t)(tap * a.C0 + cc) << 1) : ((size_t)(k_begin + kn) << 6));
         sc.lbase = __builtin_amdgcn_readfirstlane(lds_addr(smem) + (kn & 3) * STAGE_BYTES);
         sc.tap = tap;
         return sc;
@@ -301,7 +311,7 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
     };
     auto advance_bf = [&]() {       // the same walk as advance(), branch-free
         if (!CONV) { cc += 32; return; }
-        const bool second = (cc & 32) != 0, wrap = second && tap == 8;
+        const bool second = (cc & 32) != 0, wrap = second && tap == NT - 1;
         cc = second ? (wrap ? cc + 32 : cc - 32) : cc + 32;
         tap = second ? (wrap ? 0 : tap + 1) : tap;
     };
@@ -801,12 +811,17 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
                 const int grow = m0 + wm * TM + ip * 32 + pr;
                 const int gcol = ocol0 + ck * 8;
                 ok[it] = c < 32 * CPR && grow < a.M && gcol < nvalid;
-                goff[it] = (size_t)grow * ldo + gcol;
+                size_t orow = (size_t)grow;              // row of the destination (and of the residual)
+                if (ph) {                                // source pixel (img, i, j) -> output pixel (img, 2 i + pa, 2 j + pb)
+                    const int img = grow / hwq, rem = grow - img * hwq, si = rem / a.W, sj = rem - si * a.W;
+                    orow = ((size_t)img * a.Ho + (size_t)(2 * si + pa)) * a.Wo + (size_t)(2 * sj + pb);
+                }
+                goff[it] = orow * ldo + gcol;
                 if (ok[it]) {
                     const char* sp = cst + pr * PITCH + ck * 16;
                     const h4 lo = *(const h4*)sp, hi = *(const h4*)(sp + 8);
                     v[it] = h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    if (a.resid) rr[it] = *(const h8*)(a.resid + (size_t)grow * a.ld_res + gcol);
+                    if (a.resid) rr[it] = *(const h8*)(a.resid + orow * a.ld_res + gcol);
                 }
             }
             bool want_stats = false;
@@ -878,16 +893,16 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& a) {
     }   // !SPLIT
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES, bool CONV, bool GEGLU, bool SPLIT, int MS, bool LN, int PATH, int PIPE, bool ABL>
+template <int BM, int BN, int WM, int WN, int STAGES, int CONV, bool GEGLU, bool SPLIT, int MS, bool LN, int PATH, int PIPE, bool ABL>
 __global__ __launch_bounds__(WM * WN * 64) void igemm2_kernel(const IgemmArgs a) {
-    igemm2_body<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>(a);
+    igemm2_body<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>(a, (int)blockIdx.y);     // y: IG_CONV2_PHASE's phase
 }
 // Up to FGDM_MAX_GROUP problems of the same instantiation and grid in ONE launch (twin layers of the UNet encoder and the
 // ControlNets: common.h, "deferred launches"): blockIdx.y selects the argument set, everything else is the kernel above.
 struct IgemmArgsG { IgemmArgs g[FGDM_MAX_GROUP]; };
-template <int BM, int BN, int WM, int WN, int STAGES, bool CONV, bool GEGLU, bool SPLIT, int MS, bool LN, int PATH, int PIPE, bool ABL>
+template <int BM, int BN, int WM, int WN, int STAGES, int CONV, bool GEGLU, bool SPLIT, int MS, bool LN, int PATH, int PIPE, bool ABL>
 __global__ __launch_bounds__(WM * WN * 64) void igemm2_pair_kernel(const IgemmArgsG p) {
-    igemm2_body<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>(p.g[blockIdx.y]);
+    igemm2_body<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>(p.g[blockIdx.y], 0);
 }
 
 // =====================================================================================================================
@@ -1164,7 +1179,7 @@ int launch_geglu_persist(const IgemmArgs& a, int ntiles, int contiguous, hipStre
     return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES, bool CONV, bool GEGLU, bool SPLIT, int MS, bool LN, int PATH, int PIPE, bool ABL>
+template <int BM, int BN, int WM, int WN, int STAGES, int CONV, bool GEGLU, bool SPLIT, int MS, bool LN, int PATH, int PIPE, bool ABL>
 int launch2p(const IgemmArgs& a, hipStream_t s) {
     constexpr int ring = ring_bytes<BM, BN, STAGES, PIPE>();
     constexpr int smem = ring + (1 + RV_MAX) * BN * 4 + (2 * BM + BN) * 4;      // + staged bias, emb rows, LayerNorm (mean, rstd), u
@@ -1173,11 +1188,16 @@ int launch2p(const IgemmArgs& a, hipStream_t s) {
     if (fgdm_dyn_lds<k>(smem) != FGDM_OK) return FGDM_ERR_HIP;
     const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
     const unsigned gx = (unsigned)(ntm * ntn * (SPLIT ? a.splitk : 1));
+    // the four phases of an IG_CONV2_PHASE problem are ONE launch: the phase on blockIdx.y (the decoder's Upsample layers have no
+    // twin in another net, so the y axis the grouped launches use for their argument sets is free)
+    constexpr bool phases = CONV == 2;
+    const unsigned gy = phases ? 4u : 1u;
     if (fgdm_recording()) {
         auto single = [=](hipStream_t rs) -> int {
-            hipLaunchKernelGGL(k, dim3(gx), dim3(WM * WN * 64), smem, rs, a);
+            hipLaunchKernelGGL(k, dim3(gx, gy), dim3(WM * WN * 64), smem, rs, a);
             return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
         };
+        if (phases) { fgdm_record(single); return FGDM_OK; }
         // the hot instantiations (pipelined loop, straight-line epilogue) have a twin that takes two argument sets
         if constexpr (PIPE != 0 && PATH != 0 && !SPLIT && !ABL && MS == 16) {
             constexpr auto kp = igemm2_pair_kernel<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, PATH, PIPE, ABL>;
@@ -1197,7 +1217,7 @@ int launch2p(const IgemmArgs& a, hipStream_t s) {
         }
         return FGDM_OK;
     }
-    hipLaunchKernelGGL(k, dim3(gx), dim3(WM * WN * 64), smem, s, a);
+    hipLaunchKernelGGL(k, dim3(gx, gy), dim3(WM * WN * 64), smem, s, a);
     return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
 }
 // Which epilogue PATH serves `a` (see igemm2_kernel): 1 / 2 need the fp16 row-major output without an activation (GEGLU is
@@ -1218,7 +1238,7 @@ int epilogue_path(const IgemmArgs& a) {
 // for PATH 1 / 2 (every layer of the sampling loop but a handful); the general epilogue keeps the phase-locked loop (its register
 // stage and the pipelined loop's fragment ring do not fit 256 VGPRs together).  a.debug != 0 (only tools/bench_igemm.py sets
 // it) takes the ablation instantiation: PATH 1 of the FAST non-LayerNorm tiles.
-template <int BM, int BN, int WM, int WN, int STAGES, bool CONV, bool GEGLU, bool SPLIT, int MS, bool LN, bool FAST, int PIPE>
+template <int BM, int BN, int WM, int WN, int STAGES, int CONV, bool GEGLU, bool SPLIT, int MS, bool LN, bool FAST, int PIPE>
 int launch2(const IgemmArgs& a, hipStream_t s) {
     const bool fast_on = knob_once(KNOB_IGEMM_EPI_PATHS) != 0;   // A/B knob
     if constexpr (FAST && !SPLIT && !LN) {
@@ -1232,17 +1252,23 @@ int launch2(const IgemmArgs& a, hipStream_t s) {
     if constexpr (FAST && !SPLIT) {
         switch (fast_on ? epilogue_path<BM, GEGLU, LN>(a) : 0) {
             case 1: return launch2p<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, 1, PIPE, false>(a, s);
-            case 2: if constexpr (!GEGLU && !LN) return launch2p<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, 2, PIPE, false>(a, s);
+            case 2: if constexpr (!GEGLU && !LN && CONV != 2) return launch2p<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, 2, PIPE, false>(a, s);
             default: break;
         }
     }
-    return launch2p<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, 0, 0, false>(a, s);
+    // (the phase form with the general epilogue does not fit 256 x 320 tiles without spilling: 128 x 320 tiles, the same sums)
+    if constexpr (CONV == 2 && BM == 256 && BN == 320 && MS == 16) return launch2p<128, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, 0, 0, false>(a, s);
+    else return launch2p<BM, BN, WM, WN, STAGES, CONV, GEGLU, SPLIT, MS, LN, 0, 0, false>(a, s);
 }
 template <int BM, int BN, bool GEGLU, int MS, int PIPE, int WM, int WN>
 int launch2m(const IgemmArgs& a, hipStream_t s) {
     constexpr int PL = PIPE == 2 ? 1 : PIPE;        // the halo loop is a convolution's
-    return a.mode == IG_LINEAR ? launch2<BM, BN, WM, WN, 4, false, GEGLU, false, MS, false, MS == 16, PL>(a, s)
-                               : launch2<BM, BN, WM, WN, 4, true, GEGLU, false, MS, false, MS == 16, (GEGLU ? PL : PIPE)>(a, s);
+    if (a.mode == IG_CONV2_PHASE) {                 // CONV = 2: the four 2x2 phase GEMMs of an Upsample conv (never the halo loop)
+        if constexpr (!GEGLU) return launch2<BM, BN, WM, WN, 4, 2, false, false, MS, false, MS == 16, PL>(a, s);
+        else return FGDM_ERR_ARG;
+    }
+    return a.mode == IG_LINEAR ? launch2<BM, BN, WM, WN, 4, 0, GEGLU, false, MS, false, MS == 16, PL>(a, s)
+                               : launch2<BM, BN, WM, WN, 4, 1, GEGLU, false, MS, false, MS == 16, (GEGLU ? PL : PIPE)>(a, s);
 }
 // consumer of a folded LayerNorm: always a LINEAR GEMM
 template <int BM, int BN, bool GEGLU, int MS, int PIPE, int WM, int WN>
@@ -1300,6 +1326,7 @@ void igemm_set_twin_layers(bool on) { g_twin_layers = on; }
 
 int igemm_splitk_factor(const IgemmArgs& a) {
     if (a.force_cfg || a.act == ACT_GEGLU || a.out_kind != OUT_F16 || a.N % 320 || (a.K & 31)) return 1;
+    if (a.mode == IG_CONV2_PHASE) return 1;     // four phases per launch fill the chip; the reduction pass knows no phase rows
     const int nk = a.K >> 5;
     const bool fat = knob_once(KNOB_SPLITK_FAT) != 0;          // A/B knob
     // the decoder's convolutions of the 16x16 level (they have no ControlNet twin to share a launch with): two ways, so that at
@@ -1341,6 +1368,10 @@ int igemm2_launch(const IgemmArgs& a, int cfg, hipStream_t s) {
     const size_t px = a.mode == IG_LINEAR ? (size_t)a.M : (size_t)a.B * a.H * a.W;
     const bool small = px * (size_t)std::max(a.C0, a.C1) * 2 < (1ull << 32) && (size_t)(a.N + 320) * a.K * 2 < (1ull << 32);
     const bool pipe = (psel == 0 ? pipe_default != 0 : psel == 2) && small;
+    // the phase mode: what igemm_up_phase (igemm.hip) promises, and 32-bit byte offsets on either loop's weight walk
+    if (a.mode == IG_CONV2_PHASE && (a.splitk > 1 || a.C1 || a.out_kind != OUT_F16 || a.stats_out || a.out2 || a.ln_stats || a.act == ACT_GEGLU ||
+                                     a.Ho != 2 * a.H || a.Wo != 2 * a.W || a.K != 4 * a.C0 || a.M != a.B * a.H * a.W || !small))
+        return FGDM_ERR_ARG;
     // the halo loop (PIPE = 2) where the geometry allows it (halo_geometry).  FGDM_IGEMM_HALO=0: A/B knob
     const bool halo = knob_once(KNOB_IGEMM_HALO) != 0 && pipe && halo_geometry(a);
     const int bn = (tile == 1 || tile == 4) ? 256 : tile == 6 ? 128 : tile == 7 ? 160 : 320;

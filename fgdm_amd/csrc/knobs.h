@@ -31,6 +31,7 @@
     X(IGEMM_OTHER_WIDTHS, "FGDM_IGEMM_OTHER_WIDTHS", "1", "0: widths 128 / 256 / 512 back on the 2-stage kernel")               \
     X(IGEMM_PERSIST, "FGDM_IGEMM_PERSIST", "1", "GEGLU projections: 1 = persistent, tiles round-robin; 2 = contiguous runs; 0 = off") \
     X(IGEMM_PIPE, "FGDM_IGEMM_PIPE", "1", "0: the phase-locked K loop instead of the software-pipelined one")                   \
+    X(IGEMM_UP_PHASE, "FGDM_IGEMM_UP_PHASE", "1", "0: Upsample convs as the 3x3 walk over the virtual upsampled image, not four 2x2 phase GEMMs") \
     X(IGEMM_SMALL_M, "FGDM_IGEMM_SMALL_M", "1", "0: linears with a thin 128-row grid stay on 128 x 320 tiles")                  \
     X(IGEMM_SMALL_TILES, "FGDM_IGEMM_SMALL_TILES", "1", "0: the 8x8 level's linears back on the 2-stage kernel")                \
     X(IGEMM_STATS64, "FGDM_IGEMM_STATS64", "1", "0: the 64 x 160 tile leaves the LayerNorm partial sums to the row-statistics pass") \

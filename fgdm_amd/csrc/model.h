@@ -44,6 +44,7 @@ struct GemmW {              // packed [npad][K] fp16 weight + fp32 bias (packed 
     bool im2col = false;    // conv3x3 whose Cin is not a multiple of 64: K = roundup64(9 * cin_pad)
     int cin_pad = 0;
     int k_real = 0;         // un-padded contraction length (algorithmic flop accounting)
+    half_t* wph = nullptr;  // Upsample convs of the UNets: the four 2x2 phase kernels [4][npad][4 Cin] next to the 3x3 pack (IG_CONV2_PHASE)
     float* ln_u = nullptr;  // LayerNorm folded in: u[n] = sum_k W'[n][k] (packed order); bias then holds sum_k beta_k W_nk + b_n
     float ln_eps = 1e-5f;
 };
@@ -211,7 +212,7 @@ struct Model {
                 case L_RES: visit_res(v, l, UNET_RES, temb, embs); break;
                 case L_ATTN: visit_attn(v, l); break;
                 case L_DOWN: v.conv3(l.conv, l.pre + "op", l.cin, l.cin); break;
-                case L_UP: v.conv3(l.conv, l.pre + "conv", l.cin, l.cin); break;
+                case L_UP: v.conv3_up(l.conv, l.pre + "conv", l.cin, l.cin); break;
             }
     }
     // Adapter (adapter.py:280-332): the 8 ResnetBlocks (or, TimeAdapter, `tad` ResBlocks), then conv_in
@@ -347,6 +348,7 @@ struct Model {
         void norm(NormW&, const std::string& pre, int C) { wb(pre, {C}); }
         void layernorm(NormW&, const std::string& pre, int C) { wb(pre, {C}); }
         void conv3(GemmW&, const std::string& pre, int cout, int cin) { wb(pre, {cout, cin, 3, 3}); }
+        void conv3_up(GemmW& g, const std::string& pre, int cout, int cin) { conv3(g, pre, cout, cin); }
         void pointwise(float*&, const std::string& pre, int co, int ci) { wb(pre, {co, ci, 1, 1}); }
         void table(float*&, const std::string& key, int rows, int W) { reg(key, {rows, W}); }
         void source(const std::string& pre, int N, int K, bool bias) { wb(pre, {N, K}, bias); }

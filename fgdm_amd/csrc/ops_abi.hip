@@ -115,6 +115,13 @@ int fgdm_op_conv2d(const void* x0, int C0, const void* x1, int C1, const float* 
     a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = K;
     a.act = act; a.out_kind = OUT_F16; a.out = out; a.ld_out = Cout;
     a.rows_per_sample = a.Ho * a.Wo; a.scale = scale;
+    if (igemm_up_phase(a)) {        // the engine's dispatch (Engine::gemm): the four summed 2x2 kernels, packed as Engine::pack_conv3 does
+        std::vector<float> wh((size_t)Cout * K);
+        if (hipMemcpy(wh.data(), w, wh.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return FGDM_ERR_HIP;
+        const half_t* wph = tmp.up(up_phase_pack(wh.data(), Cout, Cin, igemm_npad(Cout)));
+        if (!wph) return FGDM_ERR_NOMEM;
+        a = igemm_phase_args(a, wph);
+    }
     if (plan_splitk(a, tmp) != FGDM_OK) return FGDM_ERR_NOMEM;
     const int rc = igemm_launch(a, s);
     (void)hipStreamSynchronize(s);   // temporaries are freed on return

@@ -4,6 +4,8 @@ The denoising path has no cross-sample dependence (GroupNorm is per sample; no B
 never talk during sampling.  The only collective is the broadcast of the frozen weights from rank 0
 at start-up -- over RCCL/xGMI on GPUs ("nccl" backend), over gloo in the CPU tests.
 """
+import re
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -28,14 +30,17 @@ def shard(t, rank, world):
 # encoder keeps its token / position embeddings in fp32 (fp32 residual stream), the first stage its 4x4 post_quant_conv.
 _FP32_SUFFIXES = ('attn1.to_q.weight', 'attn1.to_k.weight', 'attn1.to_v.weight', 'attn2.to_q.weight', 'ff.net.0.proj.weight',
                   'token_embedding.weight', 'position_embedding.weight', 'post_quant_conv.weight')
+# ... and the UNets' Upsample convs (output_blocks.<i>.<j>.conv): their 3x3 taps are summed into four 2x2 phase kernels in fp32 and
+# rounded once (csrc/engine_shared.h: up_phase_pack).  The first-stage decoder's upsample convs keep the 3x3 form and ship as fp16.
+_FP32_PATTERN = re.compile(r'output_blocks\.\d+\.\d+\.conv\.weight$')
 
 
 def _ships_as_fp16(key, shape):
     """Tensors the engine stores as fp16 UNCHANGED may travel as fp16: every >= 2-D weight except the ones listed in
-    _FP32_SUFFIXES.  1-D tensors (biases, norm affine) stay fp32 in the engine and travel as fp32.  With this rule a rank fed
+    _FP32_SUFFIXES / matched by _FP32_PATTERN.  1-D tensors (biases, norm affine) stay fp32 in the engine and travel as fp32.  With this rule a rank fed
     from the broadcast holds bit-identical packed weights to one that loaded the fp32 state dict directly
     (tests/test_gpu_nets.py::test_broadcast_layout_is_bit_identical_to_fp32_load)."""
-    return len(shape) >= 2 and not key.endswith(_FP32_SUFFIXES)
+    return len(shape) >= 2 and not key.endswith(_FP32_SUFFIXES) and not _FP32_PATTERN.search(key)
 
 
 def broadcast_weights(shapes, make_tensor, rank, world, device, timing=None, force=False):

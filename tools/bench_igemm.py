@@ -34,6 +34,10 @@ SHAPES = [
     ('L3 geglu 1280->10240', 32, 8, 8, 1280, 0, 10240, 1, 1, 0, 3, 0),
     ('L1 down s2 320->320', 32, 64, 64, 320, 0, 320, 3, 2, 0, 0, 0),
     ('L0 up 640->640', 32, 32, 32, 640, 0, 640, 3, 1, 1, 0, 0),
+    # the other two Upsample layers of the decoder (FGDM_IGEMM_UP_PHASE=0 / 1: the 3x3 walk / four 2x2 phase GEMMs in one launch;
+    # the TF/s column counts the 3x3 form's flops either way)
+    ('L1 up 1280->1280', 32, 16, 16, 1280, 0, 1280, 3, 1, 1, 0, 0),
+    ('L2 up 1280->1280', 32, 8, 8, 1280, 0, 1280, 3, 1, 1, 0, 0),
     # the same GEMMs as the L0 / L1 / L2 convolutions without the 3x3 gather (what the addressing and the tap re-reads cost)
     ('L0 lin 2880->320', 32, 64, 64, 2880, 0, 320, 1, 1, 0, 0, 1),
     ('L1 lin 5760->640', 32, 32, 32, 5760, 0, 640, 1, 1, 0, 0, 1),
