@@ -45,6 +45,15 @@ class FgdmConfig2(FgdmConfig):
     _fields_ = [('num_head_channels', C.c_int32), ('use_linear_in_transformer', C.c_int32)]
 
 
+class FgdmDdimParams(C.Structure):
+    """fgdm_ddim_params of include/fgdm.h (fgdm_sample_ddim_ex); struct_size must be ctypes.sizeof of this class."""
+    _fields_ = [('struct_size', C.c_int64)] + [(name, C.c_void_p) for name in (
+        'x', 'cond', 'uncond', 'timesteps', 'alphas', 'alphas_prev', 'sqrt_one_minus_alphas', 'control_scales', 'sigmas',
+        'cfg_scales', 'step_noise', 'mask', 'x0', 'q_noise', 'sqrt_alphas_cumprod_t', 'sqrt_one_minus_alphas_cumprod_t',
+        'log_steps', 'x_inter_out', 'pred_x0_out')] + [('cfg_scale', C.c_float)] + [(name, C.c_int32) for name in (
+            'S', 'B', 'H', 'W', 'flags', 'n_log', 'reserved0')]
+
+
 _p = C.c_void_p
 _f = C.c_float
 _i = C.c_int
@@ -87,6 +96,8 @@ SIGNATURES = {
     'fgdm_ancestral_step': (_i, [_p, _p, _f, _f, _f, _f, _f, _p, _p, _i64, _p]),
     'fgdm_sample_ddim': (_i, [_p, _p, _p, _p, _f, _i, C.POINTER(_i64), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
                               _p, _i, _i, _i, _i, _p]),
+    'fgdm_sample_ddim_ex': (_i, [_p, C.POINTER(FgdmDdimParams), _p]),
+    'fgdm_op_ddim_loop_step': (_i, [_p, _p, _p, _f, _f, _f, _f, _f, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _i64, _p]),
     'fgdm_profile_begin': (_i, [_p, _i]),
     'fgdm_profile_end': (_i, [_p, C.POINTER(C.c_double)]),
     'fgdm_workspace_stats': (_i, [_p, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -193,6 +193,17 @@ int transpose_pad_keys(const half_t* v, half_t* vt, int B, int Tk, int C, int Tk
 int ddim_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale,
               float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, const float* noise,
               float* x_prev, float* pred_x0, float* e_out, size_t n, hipStream_t s);
+// One step of the device DDIM loop (k_ddim_loop_step): ddim_step's update, then the NEXT step's inpainting blend
+// x = q m + (1 - m) x_prev with q = sa_next x0 + s1m_next qnoise (mask NULL: x = x_prev), stored to x_out and to the two halves
+// of the network's input (each may be NULL); log_x / log_p0 receive x_prev and pred_x0 of a logged step.  ec NULL: no update
+// (x_prev = x): the blend and the input copies in front of the first step.  x_out may alias x; nothing else may overlap.
+struct DdimLoopStep {
+    const float *x, *ec, *eu, *noise, *mask, *x0, *qnoise;
+    float *x_out, *xin_a, *xin_b, *log_x, *log_p0;
+    float cfg, a_t, a_prev, sigma, s1m, sa_next, s1m_next;
+    size_t n;
+};
+int ddim_loop_step(const DdimLoopStep& a, hipStream_t s);
 int plms_combine(const float* e_t, const float* e1, const float* e2, const float* e3, int order,
                  float* e_prime, size_t n, hipStream_t s);
 int axpby(const float* a, float ca, const float* b, float cb, float* y, size_t n, hipStream_t s);

@@ -248,6 +248,53 @@ int ddim_step(const float* x, const float* e_cond, const float* e_uncond, float 
     return LAUNCH_OK();
 }
 
+// One step of the device DDIM loop (fgdm_sample_ddim_ex), one pass over the n elements:
+//   e = e_u + s (e_c - e_u); pred_x0, x_prev as k_ddim_step (sigma * noise included)                    ddim.py:243,259-268
+//   mask given (there is a next step): x = q m + (1 - m) x_prev, q = sa_next x0 + s1m_next qnoise        ddim.py:151-154
+// and x goes to the state and to both halves of the network's cat([x] * 2) input; a logged step also stores x_prev and pred_x0
+// (the intermediates hold x_prev BEFORE the next step's blend, as the per-step loop appends them).  ec NULL: no update, x_prev = x
+// (the blend and the input copies in front of the first step).  x_out may be x; every other buffer is distinct.
+// The results must be the bits of k_ddim_step, then k_axpby, then k_mask_blend, and this file is compiled with -ffp-contract=fast,
+// under which the backend fuses any product into a following sum (a `*` behind __fmul_rn included).  So every rounding is spelled
+// out as those three kernels perform it: fmaf where they fuse, mul_rn where they round the product on its own.
+// Which of the two each term gets is read off the three kernels' disassembly under the current toolchain (k_ddim_step and
+// k_mask_blend round their two products in one v_pk_mul_f32, k_axpby is v_mul then v_fmac); their source does not pin it.  When
+// tests/test_gpu_ddim_loop.py starts failing after a compiler change, disassemble them again and re-derive the pattern below.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+    float p = a * b;
+    asm volatile("" : "+v"(p));     // no instruction: the product is a value in a register, so it cannot become the multiplicand of an FMA
+    return p;
+}
+__global__ void k_ddim_loop_step(const DdimLoopStep a) {
+    const float sa = sqrtf(a.a_t), sp = sqrtf(a.a_prev), dir = sqrtf(__builtin_fmaf(-a.sigma, a.sigma, 1.0f - a.a_prev));
+    EW_LOOP(i, a.n) {
+        float xp = a.x[i], p0 = 0.f;
+        if (a.ec) {
+            float e = a.ec[i];
+            if (a.eu) { const float u = a.eu[i]; e = __builtin_fmaf(a.cfg, e - u, u); }
+            p0 = __builtin_fmaf(-a.s1m, e, xp) / sa;
+            xp = mul_rn(dir, e) + mul_rn(sp, p0);
+            if (a.noise) xp = __builtin_fmaf(a.sigma, a.noise[i], xp);
+            if (a.log_x) a.log_x[i] = xp;
+            if (a.log_p0) a.log_p0[i] = p0;
+        }
+        float xn = xp;
+        if (a.mask) {
+            const float m = a.mask[i];
+            const float q = __builtin_fmaf(a.sa_next, a.x0[i], mul_rn(a.s1m_next, a.qnoise[i]));     // k_axpby
+            xn = mul_rn(q, m) + mul_rn(1.0f - m, xp);                                                // k_mask_blend
+        }
+        if (a.x_out) a.x_out[i] = xn;
+        if (a.xin_a) a.xin_a[i] = xn;
+        if (a.xin_b) a.xin_b[i] = xn;
+    }
+}
+int ddim_loop_step(const DdimLoopStep& a, hipStream_t s) {
+    if (!a.x || a.n == 0 || (a.mask && (!a.x0 || !a.qnoise)) || (a.eu && !a.ec)) return FGDM_ERR_ARG;
+    FGDM_LAUNCH(k_ddim_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
+    return LAUNCH_OK();
+}
+
 // Adams-Bashforth combinations of plms.py:224-232; order = number of old eps available (1..3)
 __global__ void k_plms(const float* __restrict__ e, const float* __restrict__ e1, const float* __restrict__ e2,
                        const float* __restrict__ e3, int order, float* __restrict__ out, size_t n) {

@@ -1872,45 +1872,110 @@ int fgdm_uint8_to_hint(const uint8_t* src, int B, int H, int W, int C, float* hi
     return u8_to_hint(src, hint, B, H * W, C, as_stream(stream));
 }
 
-int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* uncond, float cfg_scale, int S,
-                     const int64_t* timesteps, const float* alphas, const float* alphas_prev,
-                     const float* sqrt_one_minus_alphas, const float* control_scales, int B, int H, int W, int flags,
-                     void* stream) {
-    if (!e || !x || !cond || !timesteps || !alphas || !alphas_prev || !sqrt_one_minus_alphas || S <= 0) return FGDM_ERR_ARG;
+// Host-side checks of fgdm_sample_ddim_ex, in front of any launch; nullptr: the parameters are consistent.
+static const char* ddim_params_error(const fgdm_ddim_params* p) {
+    if (p->reserved0 != 0) return "reserved0 must be 0";
+    if (!p->x || !p->cond || !p->timesteps || !p->alphas || !p->alphas_prev || !p->sqrt_one_minus_alphas) return "x, cond or a schedule table is NULL";
+    if (p->S <= 0 || p->B <= 0 || p->H <= 0 || p->W <= 0) return "S, B, H and W must be positive";
+    if (p->mask && (!p->x0 || !p->q_noise || !p->sqrt_alphas_cumprod_t || !p->sqrt_one_minus_alphas_cumprod_t))
+        return "mask needs x0, q_noise and q_sample's two coefficient tables";
+    if (p->sigmas && !p->step_noise)
+        for (int k = 0; k < p->S; ++k)
+            if (p->sigmas[k] != 0.f) return "a sigma is not 0 and step_noise is NULL";
+    if (p->n_log < 0 || (p->n_log > 0 && !p->log_steps)) return "n_log < 0, or log steps without log_steps";
+    for (int j = 0; j < p->n_log; ++j)
+        if (p->log_steps[j] < 0 || p->log_steps[j] >= p->S || (j > 0 && p->log_steps[j] <= p->log_steps[j - 1]))
+            return "log_steps must be strictly ascending walk positions in [0, S)";
+    return nullptr;
+}
+
+int fgdm_sample_ddim_ex(fgdm_engine* e, const fgdm_ddim_params* caller, void* stream) {
+    if (!e || !caller) return FGDM_ERR_ARG;
+    // The caller's struct may be any version this library knows: at least the first one, at most this one; the fields its
+    // version did not have yet read as zero (absent).  A larger size holds fields this library cannot honour.
+    const int64_t size = caller->struct_size;
+    if (size < FGDM_DDIM_PARAMS_SIZE_V1 || size > (int64_t)sizeof(fgdm_ddim_params))
+        return e->fail(FGDM_ERR_ARG, "fgdm_sample_ddim_ex: struct_size is not the sizeof(fgdm_ddim_params) of a known header version");
+    fgdm_ddim_params known{};
+    memcpy(&known, caller, (size_t)size);
+    const fgdm_ddim_params* p = &known;
+    if (const char* why = ddim_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_ddim_ex: ") + why);
     if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
     hipStream_t s = as_stream(stream);
     return scoped_call(e, stream, [&]() -> int {
-    const bool cfg_on = uncond && cfg_scale != 1.0f;
+    const int S = p->S, B = p->B, H = p->H, W = p->W;
+    bool cfg_on = false;      // one decision for the whole walk: the registered context has Bm rows
+    if (p->uncond)
+        for (int i = 0; i < S && !cfg_on; ++i) cfg_on = (p->cfg_scales ? p->cfg_scales[i] : p->cfg_scale) != 1.0f;
     const int Bm = cfg_on ? 2 * B : B;
     const size_t n = (size_t)B * 4 * H * W, nctx = (size_t)B * e->ctx_tokens * e->cfg.context_dim;
+    float* x = p->x;
     float* x2 = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
     float* eps = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
     float* c2 = (float*)e->arena.alloc(Bm * (size_t)e->ctx_tokens * e->cfg.context_dim * sizeof(float));
     int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * Bm * sizeof(int64_t));
     if (!x2 || !eps || !c2 || !tdev) return e->fail(FGDM_ERR_NOMEM, "workspace");
     std::vector<int64_t> th((size_t)S * Bm);
-    for (int i = 0; i < S; ++i) for (int b = 0; b < Bm; ++b) th[(size_t)i * Bm + b] = timesteps[i];
+    for (int i = 0; i < S; ++i) for (int b = 0; b < Bm; ++b) th[(size_t)i * Bm + b] = p->timesteps[i];
     HIP_TRY(hipMemcpyAsync(tdev, th.data(), th.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));   // th is a local: the copy must finish before it goes out of scope
     if (cfg_on) {   // c_in = cat([uncond, cond])  (ddim.py:226)
-        HIP_TRY(hipMemcpyAsync(c2, uncond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c2 + nctx, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c2, p->uncond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c2 + nctx, p->cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
     } else {
-        HIP_TRY(hipMemcpyAsync(c2, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c2, p->cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     int rc = e->set_context(c2, Bm);   // the conditioning is loop-invariant: project it once, pass ctx = NULL below
+    // the blend in front of step `i` (index k = S - 1 - i), done by the kernel of the step before it
+    auto blend = [&](DdimLoopStep& a, int i) {
+        if (!p->mask) return;
+        const int k = S - 1 - i;
+        a.mask = p->mask; a.x0 = p->x0; a.qnoise = p->q_noise + (size_t)i * n;
+        a.sa_next = p->sqrt_alphas_cumprod_t[k]; a.s1m_next = p->sqrt_one_minus_alphas_cumprod_t[k];
+    };
+    if (rc == FGDM_OK) {                // in front of the first step: its blend, and x into the network's input
+        DdimLoopStep a{};
+        a.x = x; a.n = n; a.xin_a = x2; a.xin_b = cfg_on ? x2 + n : nullptr;
+        blend(a, 0);
+        a.x_out = p->mask ? x : nullptr;
+        rc = ddim_loop_step(a, s);
+    }
+    int logged = 0;
     for (int i = 0; i < S && rc == FGDM_OK; ++i) {
         const int index = S - 1 - i;   // reversed walk (ddim.py:137,148)
-        HIP_TRY(hipMemcpyAsync(x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (cfg_on) HIP_TRY(hipMemcpyAsync(x2 + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        rc = e->apply_model(x2, tdev + (size_t)index * Bm, nullptr, nullptr, nullptr, control_scales, Bm, H, W, flags, eps);
+        rc = e->apply_model(x2, tdev + (size_t)index * Bm, nullptr, nullptr, nullptr, p->control_scales, Bm, H, W, p->flags, eps);
         if (rc != FGDM_OK) break;
-        rc = ddim_step(x, cfg_on ? eps + n : eps, cfg_on ? eps : nullptr, cfg_scale, alphas[index], alphas_prev[index], 0.f,
-                       sqrt_one_minus_alphas[index], nullptr, x, nullptr, nullptr, n, s);
+        DdimLoopStep a{};
+        a.x = x; a.n = n; a.ec = cfg_on ? eps + n : eps; a.eu = cfg_on ? eps : nullptr;
+        a.cfg = p->cfg_scales ? p->cfg_scales[i] : p->cfg_scale;
+        a.a_t = p->alphas[index]; a.a_prev = p->alphas_prev[index]; a.s1m = p->sqrt_one_minus_alphas[index];
+        a.sigma = p->sigmas ? p->sigmas[index] : 0.f;
+        a.noise = a.sigma != 0.f ? p->step_noise + (size_t)i * n : nullptr;
+        a.x_out = x;
+        if (i + 1 < S) { blend(a, i + 1); a.xin_a = x2; a.xin_b = cfg_on ? x2 + n : nullptr; }
+        if (logged < p->n_log && p->log_steps[logged] == i) {
+            a.log_x = p->x_inter_out ? p->x_inter_out + (size_t)logged * n : nullptr;
+            a.log_p0 = p->pred_x0_out ? p->pred_x0_out + (size_t)logged * n : nullptr;
+            ++logged;
+        }
+        rc = ddim_loop_step(a, s);
     }
     e->arena.release(x2); e->arena.release(eps); e->arena.release(c2); e->arena.release(tdev);
     return rc;
     });
+}
+
+int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* uncond, float cfg_scale, int S,
+                     const int64_t* timesteps, const float* alphas, const float* alphas_prev,
+                     const float* sqrt_one_minus_alphas, const float* control_scales, int B, int H, int W, int flags,
+                     void* stream) {
+    if (!e || !x || !cond || !timesteps || !alphas || !alphas_prev || !sqrt_one_minus_alphas || S <= 0) return FGDM_ERR_ARG;
+    fgdm_ddim_params p{};
+    p.struct_size = sizeof(p);
+    p.x = x; p.cond = cond; p.uncond = uncond; p.cfg_scale = cfg_scale; p.S = S; p.timesteps = timesteps;
+    p.alphas = alphas; p.alphas_prev = alphas_prev; p.sqrt_one_minus_alphas = sqrt_one_minus_alphas;
+    p.control_scales = control_scales; p.B = B; p.H = H; p.W = W; p.flags = flags;
+    return fgdm_sample_ddim_ex(e, &p, stream);
 }
 
 }  // extern "C"

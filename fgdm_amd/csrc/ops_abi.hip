@@ -317,6 +317,20 @@ int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stre
     return add_f16((const half_t*)a, (const half_t*)b, (half_t*)y, (size_t)n, as_stream(stream));
 }
 
+// Diagnostic entry of tests/test_gpu_ddim_loop.py: one launch of the device DDIM loop's step kernel on caller-owned buffers.
+int fgdm_op_ddim_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float a_t, float a_prev,
+                           float sigma_t, float sqrt_one_minus_at, const float* noise, const float* mask, const float* x0,
+                           const float* q_noise, float sqrt_ac_next, float sqrt_one_minus_ac_next, float* x_out, float* xin_a,
+                           float* xin_b, float* log_x, float* log_pred_x0, int64_t n, void* stream) {
+    if (!x || n <= 0 || (e_uncond && !e_cond) || (mask && (!x0 || !q_noise))) return FGDM_ERR_ARG;
+    DdimLoopStep a{};
+    a.x = x; a.ec = e_cond; a.eu = e_uncond; a.noise = noise; a.mask = mask; a.x0 = x0; a.qnoise = q_noise;
+    a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.log_x = log_x; a.log_p0 = log_pred_x0;
+    a.cfg = cfg_scale; a.a_t = a_t; a.a_prev = a_prev; a.sigma = sigma_t; a.s1m = sqrt_one_minus_at;
+    a.sa_next = sqrt_ac_next; a.s1m_next = sqrt_one_minus_ac_next; a.n = (size_t)n;
+    return ddim_loop_step(a, as_stream(stream));
+}
+
 // Host-only entry of tests/test_replay_plan.py: the planner of replay_plan.h on caller-made walks.  Never touches the device.
 int fgdm_replay_plan(int n_walks, const int32_t* lens, const uint64_t* key, const uint32_t* grid_x, const uint64_t* shape, int group_max,
                      int chunk, int32_t* out, int out_cap, int* limits) {

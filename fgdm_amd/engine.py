@@ -513,6 +513,62 @@ class Engine:
         self._check(rc, 'fgdm_sample_ddim')
         return x
 
+    def sample_ddim_ex(self, x_T, cond, uncond, cfg_scale, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, sigmas=None,
+                       cfg_scales=None, step_noise=None, mask=None, x0=None, q_noise=None, sqrt_alphas_cumprod_t=None,
+                       sqrt_one_minus_alphas_cumprod_t=None, log_steps=(), control_scales=None, flags=0, out=None,
+                       x_inter_out=None, pred_x0_out=None):
+        """The whole DDIM loop on the device with every option of fgdm_sample_ddim_ex (include/fgdm.h): the S-entry schedule
+        tables (timesteps ... sigmas, and q_sample's two coefficient tables with a mask) in ddim_timesteps order like
+        sample_ddim's; cfg_scales [S], step_noise / q_noise [S, B,4,H,W] and log_steps in WALK order (slot i: the i-th step that
+        runs).  Returns (x, x_inter, pred_x0): the final latent and the two [len(log_steps), B,4,H,W] intermediates (None without
+        log steps).  x_T is not modified; out / x_inter_out / pred_x0_out: caller-owned device buffers to use instead of new ones."""
+        dev = lambda v: None if v is None else v.to(self.device, torch.float32).contiguous()
+        x = x_T.to(self.device, torch.float32).clone().contiguous() if out is None else out.copy_(x_T)
+        cond, uncond = dev(cond), dev(uncond)
+        if uncond is not None and tuple(uncond.shape) != tuple(cond.shape):      # one cat([uncond, cond]) batch (ddim.py:222-226)
+            raise ValueError(f'sample_ddim_ex: cond {tuple(cond.shape)} and uncond {tuple(uncond.shape)} must agree')
+        self.set_context_tokens(cond.shape[1])
+        B, _, H, W = x.shape
+        S, n_log = len(timesteps), len(log_steps)
+        step_noise, q_noise, mask, x0 = dev(step_noise), dev(q_noise), dev(mask), dev(x0)
+        for name, v, shape in (('step_noise', step_noise, (S, *x.shape)), ('q_noise', q_noise, (S, *x.shape)),
+                               ('mask', mask, tuple(x.shape)), ('x0', x0, tuple(x.shape))):
+            if v is not None and tuple(v.shape) != tuple(shape):
+                raise ValueError(f'sample_ddim_ex: {name} {tuple(v.shape)} must be {tuple(shape)}')
+        keep = []      # host arrays the struct points into
+
+        def table(a, ctype=C.c_float, conv=float, count=S):
+            if a is None:
+                return None
+            if len(a) != count:
+                raise ValueError(f'sample_ddim_ex: a table of {len(a)} entries where {count} are needed')
+            keep.append((ctype * count)(*[conv(v) for v in a]))
+            return C.cast(keep[-1], C.c_void_p)
+
+        if n_log:
+            x_inter = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if x_inter_out is None else x_inter_out
+            pred_x0 = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if pred_x0_out is None else pred_x0_out
+        else:
+            x_inter = pred_x0 = None
+        p = _lib.FgdmDdimParams()
+        p.struct_size = C.sizeof(p)
+        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
+        p.timesteps = table(timesteps, C.c_int64, int)
+        p.alphas, p.alphas_prev, p.sqrt_one_minus_alphas = table(alphas), table(alphas_prev), table(sqrt_one_minus_alphas)
+        p.sigmas, p.cfg_scales = table(sigmas), table(cfg_scales)
+        p.sqrt_alphas_cumprod_t, p.sqrt_one_minus_alphas_cumprod_t = table(sqrt_alphas_cumprod_t), table(sqrt_one_minus_alphas_cumprod_t)
+        if control_scales is not None:
+            keep.append(np.asarray(control_scales, dtype=np.float32).ravel().copy())
+            p.control_scales = keep[-1].ctypes.data_as(C.c_void_p)
+        p.step_noise, p.mask, p.x0, p.q_noise = _ptr(step_noise), _ptr(mask), _ptr(x0), _ptr(q_noise)
+        p.log_steps = table(log_steps, C.c_int32, int, n_log) if n_log else None
+        p.x_inter_out, p.pred_x0_out = _ptr(x_inter), _ptr(pred_x0)
+        p.cfg_scale, p.S, p.B, p.H, p.W, p.flags, p.n_log = float(cfg_scale), S, B, H, W, int(flags), n_log
+        rc = self.lib.fgdm_sample_ddim_ex(self.h, C.byref(p), _stream())
+        self._ctx_policy = ContextCachePolicy()      # the device-side loop registered its own context
+        self._check(rc, 'fgdm_sample_ddim_ex')
+        return x, x_inter, pred_x0
+
 
 # ---------------------------------------------------------------------- fused sampler updates
 def ddim_step(x, e_cond, e_uncond, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise=None,

@@ -10,6 +10,11 @@ every per-step tensor update is one fused HIP kernel (csrc/elementwise.hip) and 
 (cat([uncond, cond])) like ddim.py:222-243; the ControlNet sampler's two sequential calls
 (ddim_hacked.py:190-192) are batched the same way when both branches use the same hint (identical math).
 Not carried over (dead or unreachable in the reference): inference_loss / return_conds / x2.
+
+DDIMSampler / ControlDDIMSampler(model, device_loop=True) hand a whole sample() / ddim_sampling() / decode() to the engine's device
+loop (fgdm_sample_ddim_ex) when nothing asked for needs the host between steps; the noise is drawn beforehand by the same calls in
+the same order, so either route gives the same bits from the same generator state.  Everything else, and the default, is the
+per-step loop below.
 """
 import numpy as np
 import torch
@@ -160,6 +165,91 @@ class _SamplerBase:
 
 
 class DDIMSampler(_SamplerBase):
+    def __init__(self, model, schedule="linear", device_loop=False, **kwargs):
+        super().__init__(model, schedule, **kwargs)
+        self.device_loop = bool(device_loop)
+
+    # ---- the device loop: what it can take over, and the hand-over
+    def _loop_cond(self, c, uc, cfg_on):
+        """(ctx, uctx, flags, control_scales) the engine's loop needs for this conditioning, after registering the hints as
+        apply_model would -- or None: a conditioning the loop does not take (the per-step route then treats it as before)."""
+        from . import _lib, models
+        m = self.model
+        pair = _lib.FLAG_CFG_PAIRS if cfg_on else 0
+        if isinstance(m, models.ControlLDM):
+            if type(m).apply_model is not models.ControlLDM.apply_model:
+                return None                                                   # a subclass with its own apply_model
+            if cfg_on and not isinstance(self, ControlDDIMSampler):
+                return None                                                   # only that sampler's _cat_cond joins dict conds
+            if not isinstance(c, dict) or len(c.get('c_crossattn') or ()) != 1 or not torch.is_tensor(c['c_crossattn'][0]):
+                return None
+            if cfg_on and (not isinstance(uc, dict) or self._cat_cond(uc, c) is None):
+                return None                                                   # branches that cannot share one batch: two calls per step
+            hints = c.get('c_concat')
+            flags = pair | (_lib.FLAG_ONLY_MID_CONTROL if m.only_mid_control else 0)
+            ctx, uctx = c['c_crossattn'][0], uc['c_crossattn'][0] if cfg_on else None
+            if hints is None:
+                return ctx, uctx, flags | _lib.FLAG_NO_CONTROL, None
+            if m.n_controlnets == 1:
+                hints = [hints[0] if len(hints) == 1 else torch.cat(hints, 1)]
+            if len(hints) != m.n_controlnets:
+                return None
+            for k, h in enumerate(hints):
+                m.engine.set_hint(k, h)
+            return ctx, uctx, flags, m._scales()
+        if type(m).apply_model is not models.LatentDiffusion.apply_model or m.model.conditioning_key != 'crossattn':
+            return None                                                       # hybrid c_concat, or a model with its own apply_model
+        if not torch.is_tensor(c) or getattr(m.engine, '_conds_key', None) is not None:
+            return None
+        if cfg_on and (not torch.is_tensor(uc) or tuple(uc.shape) != tuple(c.shape)):
+            return None
+        return c, uc if cfg_on else None, _lib.FLAG_NO_CONTROL | pair, None
+
+    def _loop_plan(self, cond, uc, scales, mask, x0, img, host_hooks, kwargs):
+        """None (per-step route), or the conditioning part of the device loop's arguments.  `scales`: the guidance scale of
+        every step of the walk; host_hooks: whether anything asked for runs on the host between steps.  Draws no noise."""
+        m = self.model
+        eng = getattr(m, 'engine', None)
+        if not self.device_loop or eng is None or not hasattr(eng, 'sample_ddim_ex') or host_hooks or kwargs:
+            return None
+        if getattr(m, 'split_input_params', None) is not None or getattr(self, '_dyn', None) is not None:
+            return None
+        if getattr(m, 'parameterization', 'eps') != 'eps' or not hasattr(m, '_host') or img.dim() != 4 or img.shape[1] != 4:
+            return None
+        on = [uc is not None and s != 1. for s in scales]
+        if any(on) != all(on):
+            return None                 # a ucg_schedule that is 1 at some steps: those steps run without the unconditional half
+        if mask is not None and (x0 is None or tuple(x0.shape) != tuple(img.shape)):
+            return None
+        return self._loop_cond(cond, uc, all(on))
+
+    def _device_loop(self, plan, img, timesteps, tabs, scales, mask, x0, temperature, log_steps):
+        """Draw the walk's noise as the per-step route would (per step: q_sample's if there is a mask, then the step's, which is
+        drawn and dropped where sigma is 0), then one engine call.  timesteps / tabs in ddim_timesteps order, S entries."""
+        ctx, uctx, flags, control_scales = plan
+        S = len(timesteps)
+        alphas, alphas_prev, s1m, sigmas = (np.asarray(t)[:S] for t in tabs)
+        qn, sn = [], []
+        for i in range(S):
+            if mask is not None:
+                qn.append(torch.randn_like(x0))                               # q_sample(x0, ts)
+            noise = _randn(img.shape, img.device)
+            if float(sigmas[S - 1 - i]) != 0.0 and temperature != 1.:
+                noise = noise * temperature
+            if sigmas.any():
+                sn.append(noise)
+        kw = {}
+        if mask is not None:
+            h = self.model._host
+            kw = dict(mask=mask.to(img.dtype).expand_as(img).contiguous(), x0=x0, q_noise=torch.stack(qn),
+                      sqrt_alphas_cumprod_t=[h['sqrt_alphas_cumprod'][int(t)] for t in timesteps],
+                      sqrt_one_minus_alphas_cumprod_t=[h['sqrt_one_minus_alphas_cumprod'][int(t)] for t in timesteps])
+        cfg_on = uctx is not None
+        return self.model.engine.sample_ddim_ex(img, ctx, uctx, scales[0] if cfg_on else 1.0, [int(t) for t in timesteps], alphas,
+                                                alphas_prev, s1m, sigmas=sigmas, cfg_scales=scales if cfg_on else None,
+                                                step_noise=torch.stack(sn) if sn else None, log_steps=log_steps,
+                                                control_scales=control_scales, flags=flags, **kw)
+
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0.,
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
@@ -197,6 +287,21 @@ class DDIMSampler(_SamplerBase):
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         time_range = list(reversed(range(0, timesteps))) if ddim_use_original_steps else np.flip(timesteps)
         total_steps = timesteps if ddim_use_original_steps else timesteps.shape[0]
+        ucg = getattr(self, '_ucg', None)
+        scales = [unconditional_guidance_scale if ucg is None else ucg[i] for i in range(total_steps)] \
+            if ucg is None or len(ucg) >= total_steps else None
+        hooks = bool(callback or img_callback or score_corrector is not None or noise_dropout > 0. or quantize_denoised
+                     or inference_loss)
+        plan = None if scales is None or total_steps < 1 else \
+            self._loop_plan(cond, unconditional_conditioning, scales, mask, x0, img, hooks, kwargs)
+        if plan is not None:
+            log_steps = [i for i in range(total_steps)
+                         if (total_steps - i - 1) % log_every_t == 0 or i == 0]       # `index % log_every_t == 0 or index == total_steps - 1`
+            img, x_inter, pred = self._device_loop(plan, img, list(reversed([int(t) for t in time_range])),
+                                                   self._tables(ddim_use_original_steps), scales, mask, x0, temperature, log_steps)
+            intermediates['x_inter'] += list(x_inter)
+            intermediates['pred_x0'] += list(pred)
+            return img, intermediates
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -260,6 +365,13 @@ class DDIMSampler(_SamplerBase):
         timesteps = timesteps[:t_start]
         total_steps = timesteps.shape[0]
         x_dec = x_latent
+        # (ControlDDIMSampler.p_sample_ddim reads a ucg_schedule left by an earlier ddim_sampling at i = 0: per-step route)
+        plan = None if total_steps < 1 or getattr(self, '_ucg', None) is not None else \
+            self._loop_plan(cond, unconditional_conditioning, [unconditional_guidance_scale] * total_steps, None, None, x_latent,
+                            bool(callback), {})
+        if plan is not None:
+            return self._device_loop(plan, x_latent, [int(t) for t in timesteps], self._tables(use_original_steps),
+                                     [unconditional_guidance_scale] * total_steps, None, None, 1., ())[0]
         for i, step in enumerate(np.flip(timesteps)):
             index = total_steps - i - 1
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)

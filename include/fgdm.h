@@ -275,11 +275,77 @@ int fgdm_ancestral_step(const float* x, const float* eps, float sqrt_recip_ac, f
 /* Whole DDIM loop on the device (DDIMSampler.sample with eta = 0 and no host callbacks, ddim.py:58-177;
  * ddim_hacked.py:55-178).  alphas/alphas_prev/sqrt_one_minus_alphas: S floats (host) in ddim_timesteps order,
  * timesteps: S int64 (host).  cond/uncond ctx fp32 [B,77,ctx]; uncond NULL or cfg_scale == 1 disables CFG.
- * CFG runs as ONE 2B batch (cat([uncond, cond]), ddim.py:222-226); x is updated in place. */
+ * CFG runs as ONE 2B batch (cat([uncond, cond]), ddim.py:222-226); x is updated in place.
+ * The entry is fgdm_sample_ddim_ex (below) with every optional field absent: same results, and the same refusals -- B, H or W <= 0
+ * is FGDM_ERR_ARG with a message in fgdm_last_error(), before any launch. */
 int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* uncond, float cfg_scale, int S,
                      const int64_t* timesteps, const float* alphas, const float* alphas_prev,
                      const float* sqrt_one_minus_alphas, const float* control_scales, int B, int H, int W,
                      int flags, void* stream);
+
+/* The whole of DDIMSampler.sample / ddim_sampling / decode without host callbacks (ldm/models/diffusion/ddim.py:58-177,
+ * 395-412; controlnet/cldm/ddim_hacked.py:55-178,298-317): fgdm_sample_ddim plus stochastic steps (eta > 0, temperature), the
+ * inpainting blend by mask / x0 (ddim.py:151-154), a per-step guidance scale (ucg_schedule, ddim_hacked.py:159-161) and the
+ * x_inter / pred_x0 intermediates (ddim.py:171-173).  decode() from t_start is a call whose tables hold the first t_start entries.
+ * fgdm_sample_ddim is this call with every optional pointer NULL.
+ *
+ * Per step the loop runs the network on cat([x] * 2) (or x, CFG off) and then ONE elementwise kernel (k_ddim_loop_step): CFG
+ * combine, pred_x0, x_prev (+ sigma * noise), the NEXT step's blend, and the stores of x to the state and to both halves of the
+ * network's input.  The arithmetic is that of fgdm_ddim_step, fgdm_axpby (q_sample) and fgdm_mask_blend, rounding for rounding:
+ * the loop gives the bits of the per-step route of fgdm_amd/samplers.py fed the same noise.
+ *
+ * struct_size: sizeof(fgdm_ddim_params) of the CALLER's header.  Fields are only ever appended, so the library accepts every size
+ * from FGDM_DDIM_PARAMS_SIZE_V1 (the struct below) up to its own sizeof and takes the fields a shorter struct lacks as zero (absent);
+ * a smaller or a larger size is FGDM_ERR_ARG.  reserved0 must be 0.
+ * Host tables of S entries, entry k belonging to timesteps[k] (ddim_timesteps order; the walk visits k = S-1 ... 0, ddim.py:137,148):
+ *   timesteps (int64), alphas, alphas_prev, sqrt_one_minus_alphas as for fgdm_sample_ddim; sigmas (NULL: all 0, eta = 0);
+ *   sqrt_alphas_cumprod_t / sqrt_one_minus_alphas_cumprod_t: q_sample's coefficients at timesteps[k] (ddpm.py:342-345), with mask only.
+ * In WALK order, slot i belonging to the i-th step that runs (i = 0 is the largest timestep):
+ *   cfg_scales [S] (host; NULL: cfg_scale at every step): ucg_schedule[i].  CFG is on when uncond is given and some scale is not 1;
+ *     it then runs at every step, so a schedule that is 1 at SOME steps does not give the bits of a sampler that drops the
+ *     unconditional half at those steps (fgdm_amd/samplers.py keeps such schedules on the per-step route);
+ *   step_noise [S, B,4,H,W] (device): noise_like(x.shape) * temperature of step i (ddim.py:265-268), read at the steps whose sigma
+ *     is not 0; NULL requires every sigma to be 0;
+ *   mask [B,4,H,W] (device, already expanded to the latent's shape; NULL: no blending), x0 [B,4,H,W], q_noise [S, B,4,H,W]
+ *     (device): in front of step i, x = q_sample(x0, t_i; q_noise[i]) * mask + (1 - mask) * x;
+ *   log_steps [n_log] (host, strictly ascending walk positions in [0, S)), x_inter_out / pred_x0_out [n_log, B,4,H,W] (device, each
+ *     may be NULL): slot j receives x_prev and pred_x0 of step log_steps[j] (x_prev before the next step's blend, as ddim.py:171-173
+ *     appends it).  Nothing outside the n_log slots is written.
+ * FGDM_ERR_ARG before any launch (x untouched): a struct_size outside that range, reserved0 != 0; a NULL x / cond / table, S, B, H or W <= 0; mask without x0,
+ * q_noise or the two q_sample tables; a sigma that is not 0 without step_noise; n_log < 0, n_log > 0 without log_steps, a log step
+ * outside [0, S) or not above its predecessor. */
+#define FGDM_DDIM_PARAMS_SIZE_V1 192
+typedef struct fgdm_ddim_params {
+    int64_t struct_size;
+    float* x;                           /* device [B,4,H,W]: x_T (or the latent decode() starts from) in, the sample out */
+    const float* cond;                  /* device [B,tokens,context_dim] */
+    const float* uncond;                /* device, or NULL */
+    const int64_t* timesteps;
+    const float* alphas;
+    const float* alphas_prev;
+    const float* sqrt_one_minus_alphas;
+    const float* control_scales;        /* host, n_controlnets * 13, or NULL */
+    const float* sigmas;
+    const float* cfg_scales;
+    const float* step_noise;
+    const float* mask;
+    const float* x0;
+    const float* q_noise;
+    const float* sqrt_alphas_cumprod_t;
+    const float* sqrt_one_minus_alphas_cumprod_t;
+    const int32_t* log_steps;
+    float* x_inter_out;
+    float* pred_x0_out;
+    float cfg_scale;
+    int32_t S;
+    int32_t B;
+    int32_t H;
+    int32_t W;
+    int32_t flags;                      /* FGDM_FLAG_* as for fgdm_apply_model */
+    int32_t n_log;
+    int32_t reserved0;                  /* 0 */
+} fgdm_ddim_params;
+int fgdm_sample_ddim_ex(fgdm_engine* e, const fgdm_ddim_params* p, void* stream);
 
 /* Built-in kernel timer (no reference counterpart: the reference only prints wall-clock, scripts/txt2img.py:381-396).
  * Between begin and end every stride-th kernel launch is bracketed by HIP events on the launch stream
@@ -406,6 +472,21 @@ int fgdm_op_avgpool2(const void* x, void* y, int B, int H, int W, int C, void* s
 int fgdm_op_transpose_pad(const void* v, void* vt, int B, int Tk, int C, int Tkpad, void* stream);
 int fgdm_op_timestep_embed(const int64_t* t, const float* t_float, void* y, int B, int dim, int rows_pad, void* stream);
 int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream);
+
+/* Diagnostic entry (tests/test_gpu_ddim_loop.py); only fgdm_sample_ddim_ex's loop launches this kernel in the product path.
+ *
+ * fgdm_op_ddim_loop_step: one launch of k_ddim_loop_step, the per-step kernel of fgdm_sample_ddim_ex, on n fp32 elements:
+ *   e = e_uncond + cfg_scale (e_cond - e_uncond) (e_uncond NULL: e_cond); pred_x0 and x_prev exactly as fgdm_ddim_step (ddim.py:243,
+ *   254-268; noise NULL: no sigma term) -> log_pred_x0, log_x (each may be NULL);
+ *   mask given: x = q mask + (1 - mask) x_prev with q = sqrt_ac_next x0 + sqrt_one_minus_ac_next q_noise (ddim.py:151-154: the blend
+ *   in front of the NEXT step, fgdm_axpby then fgdm_mask_blend rounding for rounding); mask NULL: x = x_prev;
+ *   x -> x_out, xin_a, xin_b (each may be NULL; x_out may be x itself, no other buffers may overlap).
+ *   e_cond NULL: no update, x_prev = x (the launch in front of the first step).
+ * FGDM_ERR_ARG before any launch: x NULL, n <= 0, e_uncond without e_cond, mask without x0 or q_noise. */
+int fgdm_op_ddim_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float a_t, float a_prev,
+                           float sigma_t, float sqrt_one_minus_at, const float* noise, const float* mask, const float* x0,
+                           const float* q_noise, float sqrt_ac_next, float sqrt_one_minus_ac_next, float* x_out, float* xin_a,
+                           float* xin_b, float* log_x, float* log_pred_x0, int64_t n, void* stream);
 
 /* Diagnostic entry (tests/test_gpu_qkv_projection.py); the product path does not call it.
  *
