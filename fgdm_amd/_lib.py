@@ -54,6 +54,25 @@ class FgdmDdimParams(C.Structure):
             'S', 'B', 'H', 'W', 'flags', 'n_log', 'reserved0')]
 
 
+class FgdmPlmsParams(C.Structure):
+    """fgdm_plms_params of include/fgdm.h (fgdm_sample_plms); struct_size must be ctypes.sizeof of this class."""
+    _fields_ = [('struct_size', C.c_int64)] + [(name, C.c_void_p) for name in (
+        'x', 'cond', 'uncond', 'timesteps', 'alphas', 'alphas_prev', 'sqrt_one_minus_alphas', 'control_scales', 'mask', 'x0',
+        'q_noise', 'sqrt_alphas_cumprod_t', 'sqrt_one_minus_alphas_cumprod_t', 'log_steps', 'x_inter_out', 'pred_x0_out')] + [
+            ('cfg_scale', C.c_float)] + [(name, C.c_int32) for name in ('S', 'B', 'H', 'W', 'flags', 'n_log', 'reserved0')]
+
+
+class FgdmDpmppParams(C.Structure):
+    """fgdm_dpmpp_params of include/fgdm.h (fgdm_sample_dpmpp); struct_size must be ctypes.sizeof of this class."""
+    _fields_ = [('struct_size', C.c_int64)] + [(name, C.c_void_p) for name in (
+        'x', 'cond', 'uncond', 'control_scales', 't_float', 'inv_alpha', 'neg_sigma_over_alpha', 'update_kind', 'c1', 'cm0',
+        'cm1')] + [('cfg_scale', C.c_float)] + [(name, C.c_int32) for name in (
+            'n_eval', 'B', 'H', 'W', 'flags', 'reserved0', 'reserved1')]
+
+
+DPMPP_FIRST, DPMPP_SECOND = 1, 2      # FGDM_DPMPP_FIRST / FGDM_DPMPP_SECOND
+PLMS_PROBE, PLMS_FINISH_FIRST, PLMS_MULTISTEP = 0, 1, 2      # the modes of fgdm_op_plms_loop_step
+
 _p = C.c_void_p
 _f = C.c_float
 _i = C.c_int
@@ -98,6 +117,11 @@ SIGNATURES = {
                               _p, _i, _i, _i, _i, _p]),
     'fgdm_sample_ddim_ex': (_i, [_p, C.POINTER(FgdmDdimParams), _p]),
     'fgdm_op_ddim_loop_step': (_i, [_p, _p, _p, _f, _f, _f, _f, _f, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _i64, _p]),
+    'fgdm_sample_plms': (_i, [_p, C.POINTER(FgdmPlmsParams), _p]),
+    'fgdm_sample_dpmpp': (_i, [_p, C.POINTER(FgdmDpmppParams), _p]),
+    'fgdm_op_plms_loop_step': (_i, [_p, _p, _p, _f, _i, _i, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p,
+                                    _i64, _p]),
+    'fgdm_op_dpmpp_loop_step': (_i, [_p, _p, _p, _f, _f, _f, _p, _i, _f, _f, _f, _p, _p, _p, _p, _i64, _p]),
     'fgdm_profile_begin': (_i, [_p, _i]),
     'fgdm_profile_end': (_i, [_p, C.POINTER(C.c_double)]),
     'fgdm_workspace_stats': (_i, [_p, C.POINTER(_i64), C.POINTER(_i64)]),

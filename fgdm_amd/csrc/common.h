@@ -204,6 +204,36 @@ struct DdimLoopStep {
     size_t n;
 };
 int ddim_loop_step(const DdimLoopStep& a, hipStream_t s);
+// One launch per network evaluation of the device PLMS loop (k_plms_loop_step).  mode:
+//   PLMS_PROBE        e_t = CFG(ec, eu) -> e_out; x_prev = step(e_t) -> xin_a / xin_b only (plms.py:219-221)
+//   PLMS_FINISH_FIRST e' = (e1 + CFG(ec, eu)) / 2 as axpby(e1, 0.5, e_next, 0.5): e1 is the probe's e_t (plms.py:222-223)
+//   PLMS_MULTISTEP    e_t = CFG(ec, eu) -> e_out; e' = plms_combine(e_t, e1, e2, e3, order), order 1..3 (plms.py:224-232)
+// and, but for the probe, DdimLoopStep's tail with sigma = 0: pred_x0 / x_prev from e', the logged stores, the NEXT step's blend,
+// x to x_out and the two input halves.  ec NULL: the blend and the stores in front of the first step.  x_out may alias x, and
+// e_out may alias e3 (each element is read before it is written, by the same thread); nothing else may overlap.
+enum { PLMS_PROBE = 0, PLMS_FINISH_FIRST = 1, PLMS_MULTISTEP = 2 };
+struct PlmsLoopStep {
+    const float *x, *ec, *eu, *e1, *e2, *e3, *mask, *x0, *qnoise;
+    float *e_out, *x_out, *xin_a, *xin_b, *log_x, *log_p0;
+    float cfg, a_t, a_prev, s1m, sa_next, s1m_next;
+    int mode, order;
+    size_t n;
+};
+int plms_loop_step(const PlmsLoopStep& a, hipStream_t s);
+// One launch per network evaluation of the device DPM-Solver++ loop (k_dpmpp_loop_step): the data prediction
+// m0 = axpby(x, inv_alpha, CFG(ec, eu), neg_sigma_over_alpha) -> m0_out, then the update to the next time:
+//   DPMPP_FIRST   x = axpby(x, c1, m0, cm0)                              (dpm_solver.py:504-528)
+//   DPMPP_SECOND  x = axpby(axpby(x, c1, m0, cm0), 1, m1, cm1)           (dpm_solver.py:755-789; two roundings, two axpby)
+// and x to x_out and the two input halves (each may be NULL).  x_out may alias x; nothing else may overlap.
+enum { DPMPP_FIRST = 1, DPMPP_SECOND = 2 };
+struct DpmppLoopStep {
+    const float *x, *ec, *eu, *m1;
+    float *m0_out, *x_out, *xin_a, *xin_b;
+    float cfg, inv_alpha, neg_sigma_over_alpha, c1, cm0, cm1;
+    int kind;
+    size_t n;
+};
+int dpmpp_loop_step(const DpmppLoopStep& a, hipStream_t s);
 int plms_combine(const float* e_t, const float* e1, const float* e2, const float* e3, int order,
                  float* e_prime, size_t n, hipStream_t s);
 int axpby(const float* a, float ca, const float* b, float cb, float* y, size_t n, hipStream_t s);

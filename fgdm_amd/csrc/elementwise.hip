@@ -295,6 +295,99 @@ int ddim_loop_step(const DdimLoopStep& a, hipStream_t s) {
     return LAUNCH_OK();
 }
 
+// The tail the two multistep loop kernels share with k_ddim_loop_step: the next step's blend (k_axpby, then k_mask_blend) and the
+// stores of x to the state and to both halves of the network's input.
+__device__ __forceinline__ void loop_blend_store(float xp, size_t i, const float* mask, const float* x0, const float* qnoise,
+                                                 float sa_next, float s1m_next, float* x_out, float* xin_a, float* xin_b) {
+    float xn = xp;
+    if (mask) {
+        const float m = mask[i];
+        const float q = __builtin_fmaf(sa_next, x0[i], mul_rn(s1m_next, qnoise[i]));
+        xn = mul_rn(q, m) + mul_rn(1.0f - m, xp);
+    }
+    if (x_out) x_out[i] = xn;
+    if (xin_a) xin_a[i] = xn;
+    if (xin_b) xin_b[i] = xn;
+}
+
+// One launch per network evaluation of the device PLMS loop (fgdm_sample_plms; plms.py:178-236), one pass over the n elements.
+//   probe         e_t = CFG -> e_out;  x_prev = step(e_t) -> the two input halves only              plms.py:219-221
+//   finish-first  e' = (e1 + CFG) / 2 with e1 the probe's e_t, as k_axpby(e1, 0.5, e_next, 0.5)     plms.py:222-223
+//   multistep     e_t = CFG -> e_out;  e' = k_plms(e_t, e1, e2, e3, order)                          plms.py:224-232
+// then (not the probe) pred_x0 / x_prev from e' as k_ddim_step with sigma = 0, the logged stores, the next step's blend and the
+// stores of x, as k_ddim_loop_step.  ec NULL: the blend and the stores in front of the first step.  e_out may be e3: element i
+// of e3 is read before element i of e_out is written, by the same thread.
+// Every rounding is that of the kernel it replaces under the current toolchain (see k_ddim_loop_step): k_ddim_step fuses
+// u + s (e - u) and x - s1m e and rounds sp p0 and dir e on their own; k_axpby is v_mul (cb b) then v_fmac (ca a); k_plms compiles
+// order 1 to fma(3, e, -e1) * 0.5, order 2 to (fma(-16, e1, rn(23 e)) + rn(5 e2)) / 12 and order 3 to four rounded products
+// summed left to right, / 24 (IEEE divisions).  After a compiler change: disassemble k_plms / k_axpby and re-derive.
+__global__ void k_plms_loop_step(const PlmsLoopStep a) {
+    const float sa = sqrtf(a.a_t), sp = sqrtf(a.a_prev), dir = sqrtf(1.0f - a.a_prev);
+    EW_LOOP(i, a.n) {
+        float xp = a.x[i];
+        if (a.ec) {
+            float e = a.ec[i];
+            if (a.eu) { const float u = a.eu[i]; e = __builtin_fmaf(a.cfg, e - u, u); }
+            float ep = e;      // the probe steps with e_t itself
+            if (a.mode == PLMS_FINISH_FIRST) {
+                ep = __builtin_fmaf(0.5f, a.e1[i], mul_rn(0.5f, e));
+            } else if (a.mode == PLMS_MULTISTEP) {
+                if (a.order == 1) ep = mul_rn(__builtin_fmaf(3.f, e, -a.e1[i]), 0.5f);
+                else if (a.order == 2) ep = (__builtin_fmaf(-16.f, a.e1[i], mul_rn(23.f, e)) + mul_rn(5.f, a.e2[i])) / 12.f;
+                else ep = (((mul_rn(55.f, e) - mul_rn(59.f, a.e1[i])) + mul_rn(37.f, a.e2[i])) - mul_rn(9.f, a.e3[i])) / 24.f;
+            }
+            if (a.e_out) a.e_out[i] = e;
+            const float p0 = __builtin_fmaf(-a.s1m, ep, xp) / sa;
+            xp = mul_rn(dir, ep) + mul_rn(sp, p0);
+            if (a.mode == PLMS_PROBE) {
+                if (a.xin_a) a.xin_a[i] = xp;
+                if (a.xin_b) a.xin_b[i] = xp;
+                continue;
+            }
+            if (a.log_x) a.log_x[i] = xp;
+            if (a.log_p0) a.log_p0[i] = p0;
+        }
+        loop_blend_store(xp, i, a.mask, a.x0, a.qnoise, a.sa_next, a.s1m_next, a.x_out, a.xin_a, a.xin_b);
+    }
+}
+int plms_loop_step(const PlmsLoopStep& a, hipStream_t s) {
+    if (!a.x || a.n == 0 || (a.mask && (!a.x0 || !a.qnoise)) || (a.eu && !a.ec)) return FGDM_ERR_ARG;
+    if (a.ec) {
+        if (a.mode != PLMS_PROBE && a.mode != PLMS_FINISH_FIRST && a.mode != PLMS_MULTISTEP) return FGDM_ERR_ARG;
+        if (a.mode == PLMS_FINISH_FIRST && !a.e1) return FGDM_ERR_ARG;
+        if (a.mode == PLMS_MULTISTEP && (a.order < 1 || a.order > 3 || !a.e1 || (a.order >= 2 && !a.e2) || (a.order >= 3 && !a.e3)))
+            return FGDM_ERR_ARG;
+    }
+    FGDM_LAUNCH(k_plms_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
+    return LAUNCH_OK();
+}
+
+// One launch per network evaluation of the device DPM-Solver++ loop (fgdm_sample_dpmpp; dpm_solver.py:386-399, 504-528, 755-789):
+//   m0 = k_axpby(x, inv_alpha, CFG, neg_sigma_over_alpha) -> m0_out
+//   first order   x = k_axpby(x, c1, m0, cm0)
+//   second order  x = k_axpby(k_axpby(x, c1, m0, cm0), 1, m1, cm1)
+// and x to the state and to both halves of the network's input.  Every k_axpby is v_mul (cb b), then v_fmac (ca a).
+__global__ void k_dpmpp_loop_step(const DpmppLoopStep a) {
+    EW_LOOP(i, a.n) {
+        const float xi = a.x[i];
+        float e = a.ec[i];
+        if (a.eu) { const float u = a.eu[i]; e = __builtin_fmaf(a.cfg, e - u, u); }
+        const float m0 = __builtin_fmaf(a.inv_alpha, xi, mul_rn(a.neg_sigma_over_alpha, e));
+        if (a.m0_out) a.m0_out[i] = m0;
+        float xn = __builtin_fmaf(a.c1, xi, mul_rn(a.cm0, m0));
+        if (a.kind == DPMPP_SECOND) xn = __builtin_fmaf(1.0f, xn, mul_rn(a.cm1, a.m1[i]));
+        if (a.x_out) a.x_out[i] = xn;
+        if (a.xin_a) a.xin_a[i] = xn;
+        if (a.xin_b) a.xin_b[i] = xn;
+    }
+}
+int dpmpp_loop_step(const DpmppLoopStep& a, hipStream_t s) {
+    if (!a.x || !a.ec || a.n == 0 || (a.kind != DPMPP_FIRST && a.kind != DPMPP_SECOND) || (a.kind == DPMPP_SECOND && !a.m1))
+        return FGDM_ERR_ARG;
+    FGDM_LAUNCH(k_dpmpp_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
+    return LAUNCH_OK();
+}
+
 // Adams-Bashforth combinations of plms.py:224-232; order = number of old eps available (1..3)
 __global__ void k_plms(const float* __restrict__ e, const float* __restrict__ e1, const float* __restrict__ e2,
                        const float* __restrict__ e3, int order, float* __restrict__ out, size_t n) {

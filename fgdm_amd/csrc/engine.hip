@@ -1978,4 +1978,196 @@ int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* u
     return fgdm_sample_ddim_ex(e, &p, stream);
 }
 
+// ---- the two multistep loops (fgdm_sample_plms, fgdm_sample_dpmpp)
+// The caller's struct in the library's layout, as fgdm_sample_ddim_ex reads its own: every size from the first version up to this
+// library's sizeof is accepted and the fields a shorter struct lacks read as zero.  false: a size this library does not know.
+static bool read_params(const void* caller, int64_t size_v1, void* known, size_t size_lib) {
+    int64_t size;
+    memcpy(&size, caller, sizeof(size));      // struct_size leads every parameter struct
+    if (size < size_v1 || size > (int64_t)size_lib) return false;
+    memset(known, 0, size_lib);
+    memcpy(known, caller, (size_t)size);
+    return true;
+}
+
+// What both loops hold while they run: the network's input (Bm rows), its output, and the loop-invariant context
+// cat([uncond, cond]) (ddim.py:226), registered once so that every evaluation passes ctx = NULL.
+struct LoopWork {
+    float *x2 = nullptr, *eps = nullptr, *c2 = nullptr;
+    int Bm = 0;
+    size_t n = 0;
+};
+static int loop_begin(fgdm_engine* e, const float* cond, const float* uncond, bool cfg_on, int B, int H, int W, hipStream_t s, LoopWork* w) {
+    w->Bm = cfg_on ? 2 * B : B;
+    w->n = (size_t)B * 4 * H * W;
+    const size_t nctx = (size_t)B * e->ctx_tokens * e->cfg.context_dim;
+    w->x2 = (float*)e->arena.alloc(w->Bm * 4 * (size_t)H * W * sizeof(float));
+    w->eps = (float*)e->arena.alloc(w->Bm * 4 * (size_t)H * W * sizeof(float));
+    w->c2 = (float*)e->arena.alloc(w->Bm * (size_t)e->ctx_tokens * e->cfg.context_dim * sizeof(float));
+    if (!w->x2 || !w->eps || !w->c2) return e->fail(FGDM_ERR_NOMEM, "workspace");
+    if (cfg_on) {
+        HIP_TRY(hipMemcpyAsync(w->c2, uncond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w->c2 + nctx, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+    } else {
+        HIP_TRY(hipMemcpyAsync(w->c2, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    return e->set_context(w->c2, w->Bm);
+}
+static void loop_end(fgdm_engine* e, LoopWork* w) {
+    e->arena.release(w->x2); e->arena.release(w->eps); e->arena.release(w->c2);
+}
+
+static const char* plms_params_error(const fgdm_plms_params* p) {
+    if (p->reserved0 != 0) return "reserved0 must be 0";
+    if (!p->x || !p->cond || !p->timesteps || !p->alphas || !p->alphas_prev || !p->sqrt_one_minus_alphas) return "x, cond or a schedule table is NULL";
+    if (p->S <= 0 || p->B <= 0 || p->H <= 0 || p->W <= 0) return "S, B, H and W must be positive";
+    if (p->mask && (!p->x0 || !p->q_noise || !p->sqrt_alphas_cumprod_t || !p->sqrt_one_minus_alphas_cumprod_t))
+        return "mask needs x0, q_noise and q_sample's two coefficient tables";
+    if (p->n_log < 0 || (p->n_log > 0 && !p->log_steps)) return "n_log < 0, or log steps without log_steps";
+    for (int j = 0; j < p->n_log; ++j)
+        if (p->log_steps[j] < 0 || p->log_steps[j] >= p->S || (j > 0 && p->log_steps[j] <= p->log_steps[j - 1]))
+            return "log_steps must be strictly ascending walk positions in [0, S)";
+    return nullptr;
+}
+
+int fgdm_sample_plms(fgdm_engine* e, const fgdm_plms_params* caller, void* stream) {
+    if (!e || !caller) return FGDM_ERR_ARG;
+    fgdm_plms_params known;
+    if (!read_params(caller, FGDM_PLMS_PARAMS_SIZE_V1, &known, sizeof(known)))
+        return e->fail(FGDM_ERR_ARG, "fgdm_sample_plms: struct_size is not the sizeof(fgdm_plms_params) of a known header version");
+    const fgdm_plms_params* p = &known;
+    if (const char* why = plms_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_plms: ") + why);
+    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_sample_plms: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    hipStream_t s = as_stream(stream);
+    return scoped_call(e, stream, [&]() -> int {
+    const int S = p->S, B = p->B, H = p->H, W = p->W;
+    const bool cfg_on = p->uncond && p->cfg_scale != 1.0f;
+    const int flags = cfg_on ? p->flags | FGDM_FLAG_CFG_PAIRS : p->flags & ~FGDM_FLAG_CFG_PAIRS;
+    LoopWork w;
+    int rc = loop_begin(e, p->cond, p->uncond, cfg_on, B, H, W, s, &w);
+    const int Bm = w.Bm;
+    const size_t n = w.n;
+    float* x = p->x;
+    float* hist = (float*)e->arena.alloc(3 * n * sizeof(float));      // e_t of step j lives in plane j % 3
+    int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * Bm * sizeof(int64_t));
+    if (rc == FGDM_OK && (!hist || !tdev)) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
+    if (rc != FGDM_OK) return rc;
+    std::vector<int64_t> th((size_t)S * Bm);
+    for (int i = 0; i < S; ++i) for (int b = 0; b < Bm; ++b) th[(size_t)i * Bm + b] = p->timesteps[i];
+    HIP_TRY(hipMemcpyAsync(tdev, th.data(), th.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));   // th is a local: the copy must finish before it goes out of scope
+    auto plane = [&](int step) { return hist + (size_t)(step % 3) * n; };
+    // the blend in front of step `i` (index k = S - 1 - i), done by the kernel of the step before it
+    auto blend = [&](PlmsLoopStep& a, int i) {
+        if (!p->mask) return;
+        const int k = S - 1 - i;
+        a.mask = p->mask; a.x0 = p->x0; a.qnoise = p->q_noise + (size_t)i * n;
+        a.sa_next = p->sqrt_alphas_cumprod_t[k]; a.s1m_next = p->sqrt_one_minus_alphas_cumprod_t[k];
+    };
+    auto inputs = [&](PlmsLoopStep& a) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; };
+    auto eval = [&](int index) {
+        return e->apply_model(w.x2, tdev + (size_t)index * Bm, nullptr, nullptr, nullptr, p->control_scales, Bm, H, W, flags, w.eps);
+    };
+    {                                   // in front of the first step: its blend, and x into the network's input
+        PlmsLoopStep a{};
+        a.x = x; a.n = n; inputs(a);
+        blend(a, 0);
+        a.x_out = p->mask ? x : nullptr;
+        rc = plms_loop_step(a, s);
+    }
+    int logged = 0;
+    for (int i = 0; i < S && rc == FGDM_OK; ++i) {
+        const int index = S - 1 - i;   // reversed walk (plms.py:138,150)
+        rc = eval(index);
+        if (rc != FGDM_OK) break;
+        PlmsLoopStep a{};
+        a.x = x; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr; a.cfg = p->cfg_scale;
+        a.a_t = p->alphas[index]; a.a_prev = p->alphas_prev[index]; a.s1m = p->sqrt_one_minus_alphas[index];
+        if (i == 0) {                   // pseudo improved Euler (plms.py:219-223): probe, second evaluation at t_next, finish
+            PlmsLoopStep probe = a;
+            probe.mode = PLMS_PROBE; probe.e_out = plane(0); inputs(probe);
+            rc = plms_loop_step(probe, s);
+            if (rc == FGDM_OK) rc = eval(S >= 2 ? S - 2 : 0);
+            if (rc != FGDM_OK) break;
+            a.mode = PLMS_FINISH_FIRST; a.e1 = plane(0);
+        } else {                        // Adams-Bashforth over the last min(i, 3) planes (plms.py:224-232)
+            a.mode = PLMS_MULTISTEP; a.order = i < 3 ? i : 3;
+            a.e_out = plane(i); a.e1 = plane(i - 1);
+            if (i >= 2) a.e2 = plane(i - 2);
+            if (i >= 3) a.e3 = plane(i - 3);      // the plane e_out replaces
+        }
+        a.x_out = x;
+        if (i + 1 < S) { blend(a, i + 1); inputs(a); }
+        if (logged < p->n_log && p->log_steps[logged] == i) {
+            a.log_x = p->x_inter_out ? p->x_inter_out + (size_t)logged * n : nullptr;
+            a.log_p0 = p->pred_x0_out ? p->pred_x0_out + (size_t)logged * n : nullptr;
+            ++logged;
+        }
+        rc = plms_loop_step(a, s);
+    }
+    loop_end(e, &w); e->arena.release(hist); e->arena.release(tdev);
+    return rc;
+    });
+}
+
+static const char* dpmpp_params_error(const fgdm_dpmpp_params* p) {
+    if (p->reserved0 != 0 || p->reserved1 != 0) return "reserved0 and reserved1 must be 0";
+    if (!p->x || !p->cond || !p->t_float || !p->inv_alpha || !p->neg_sigma_over_alpha || !p->update_kind || !p->c1 || !p->cm0 || !p->cm1)
+        return "x, cond or a table is NULL";
+    if (p->n_eval <= 0 || p->B <= 0 || p->H <= 0 || p->W <= 0) return "n_eval, B, H and W must be positive";
+    for (int k = 0; k < p->n_eval; ++k)
+        if (p->update_kind[k] != FGDM_DPMPP_FIRST && p->update_kind[k] != FGDM_DPMPP_SECOND)
+            return "update_kind must be FGDM_DPMPP_FIRST or FGDM_DPMPP_SECOND";
+    if (p->update_kind[0] == FGDM_DPMPP_SECOND) return "update_kind[0] is second-order: there is no earlier data prediction";
+    return nullptr;
+}
+
+int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* caller, void* stream) {
+    if (!e || !caller) return FGDM_ERR_ARG;
+    fgdm_dpmpp_params known;
+    if (!read_params(caller, FGDM_DPMPP_PARAMS_SIZE_V1, &known, sizeof(known)))
+        return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpmpp: struct_size is not the sizeof(fgdm_dpmpp_params) of a known header version");
+    const fgdm_dpmpp_params* p = &known;
+    if (const char* why = dpmpp_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_dpmpp: ") + why);
+    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpmpp: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    hipStream_t s = as_stream(stream);
+    return scoped_call(e, stream, [&]() -> int {
+    const int K = p->n_eval, B = p->B, H = p->H, W = p->W;
+    const bool cfg_on = p->uncond && p->cfg_scale != 1.0f;
+    const int flags = cfg_on ? p->flags | FGDM_FLAG_CFG_PAIRS : p->flags & ~FGDM_FLAG_CFG_PAIRS;
+    LoopWork w;
+    int rc = loop_begin(e, p->cond, p->uncond, cfg_on, B, H, W, s, &w);
+    const int Bm = w.Bm;
+    const size_t n = w.n;
+    float* x = p->x;
+    float* m = (float*)e->arena.alloc(2 * n * sizeof(float));         // the data prediction of evaluation k lives in plane k % 2
+    float* tdev = (float*)e->arena.alloc((size_t)K * Bm * sizeof(float));
+    if (rc == FGDM_OK && (!m || !tdev)) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
+    if (rc != FGDM_OK) return rc;
+    std::vector<float> th((size_t)K * Bm);
+    for (int k = 0; k < K; ++k) for (int b = 0; b < Bm; ++b) th[(size_t)k * Bm + b] = p->t_float[k];
+    HIP_TRY(hipMemcpyAsync(tdev, th.data(), th.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));   // th is a local: the copy must finish before it goes out of scope
+    HIP_TRY(hipMemcpyAsync(w.x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));      // x_T into the network's input, once
+    if (cfg_on) HIP_TRY(hipMemcpyAsync(w.x2 + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    for (int k = 0; k < K && rc == FGDM_OK; ++k) {
+        rc = e->apply_model(w.x2, nullptr, tdev + (size_t)k * Bm, nullptr, nullptr, p->control_scales, Bm, H, W, flags, w.eps);
+        if (rc != FGDM_OK) break;
+        DpmppLoopStep a{};
+        a.x = x; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr; a.cfg = p->cfg_scale;
+        a.inv_alpha = p->inv_alpha[k]; a.neg_sigma_over_alpha = p->neg_sigma_over_alpha[k];
+        a.kind = p->update_kind[k]; a.c1 = p->c1[k]; a.cm0 = p->cm0[k]; a.cm1 = p->cm1[k];
+        a.m0_out = m + (size_t)(k % 2) * n;
+        a.m1 = k > 0 ? m + (size_t)((k - 1) % 2) * n : nullptr;
+        a.x_out = x;
+        if (k + 1 < K) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; }
+        rc = dpmpp_loop_step(a, s);
+    }
+    loop_end(e, &w); e->arena.release(m); e->arena.release(tdev);
+    return rc;
+    });
+}
+
 }  // extern "C"

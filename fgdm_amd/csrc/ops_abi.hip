@@ -331,6 +331,33 @@ int fgdm_op_ddim_loop_step(const float* x, const float* e_cond, const float* e_u
     return ddim_loop_step(a, as_stream(stream));
 }
 
+// Diagnostic entries of tests/test_gpu_multistep_loop.py: one launch of the device PLMS / DPM-Solver++ loop's step kernel on
+// caller-owned buffers.
+int fgdm_op_plms_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, int mode, int order,
+                           const float* e1, const float* e2, const float* e3, float* e_out, float a_t, float a_prev,
+                           float sqrt_one_minus_at, const float* mask, const float* x0, const float* q_noise, float sqrt_ac_next,
+                           float sqrt_one_minus_ac_next, float* x_out, float* xin_a, float* xin_b, float* log_x, float* log_pred_x0,
+                           int64_t n, void* stream) {
+    if (n <= 0) return FGDM_ERR_ARG;
+    PlmsLoopStep a{};
+    a.x = x; a.ec = e_cond; a.eu = e_uncond; a.e1 = e1; a.e2 = e2; a.e3 = e3; a.mask = mask; a.x0 = x0; a.qnoise = q_noise;
+    a.e_out = e_out; a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.log_x = log_x; a.log_p0 = log_pred_x0;
+    a.cfg = cfg_scale; a.a_t = a_t; a.a_prev = a_prev; a.s1m = sqrt_one_minus_at; a.sa_next = sqrt_ac_next;
+    a.s1m_next = sqrt_one_minus_ac_next; a.mode = mode; a.order = order; a.n = (size_t)n;
+    return plms_loop_step(a, as_stream(stream));
+}
+
+int fgdm_op_dpmpp_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float inv_alpha,
+                            float neg_sigma_over_alpha, const float* m1, int update_kind, float c1, float cm0, float cm1,
+                            float* m0_out, float* x_out, float* xin_a, float* xin_b, int64_t n, void* stream) {
+    if (n <= 0) return FGDM_ERR_ARG;
+    DpmppLoopStep a{};
+    a.x = x; a.ec = e_cond; a.eu = e_uncond; a.m1 = m1; a.m0_out = m0_out; a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b;
+    a.cfg = cfg_scale; a.inv_alpha = inv_alpha; a.neg_sigma_over_alpha = neg_sigma_over_alpha; a.c1 = c1; a.cm0 = cm0; a.cm1 = cm1;
+    a.kind = update_kind; a.n = (size_t)n;
+    return dpmpp_loop_step(a, as_stream(stream));
+}
+
 // Host-only entry of tests/test_replay_plan.py: the planner of replay_plan.h on caller-made walks.  Never touches the device.
 int fgdm_replay_plan(int n_walks, const int32_t* lens, const uint64_t* key, const uint32_t* grid_x, const uint64_t* shape, int group_max,
                      int chunk, int32_t* out, int out_cap, int* limits) {

@@ -14,7 +14,8 @@ Not carried over (dead or unreachable in the reference): infer
 DDIMSampler / ControlDDIMSampler(model, device_loop=True) hand a whole sample() / ddim_sampling() / decode() to the engine's device
 loop (fgdm_sample_ddim_ex) when nothing asked for needs the host between steps; the noise is drawn beforehand by the same calls in
 the same order, so either route gives the same bits from the same generator state.  Everything else, and the default, is the
-per-step loop below.
+per-step loop below.  PLMSSampler and DPMSolverSampler take the same keyword and the same rule (_loop_plan / _loop_cond) for
+fgdm_sample_plms and fgdm_sample_dpmpp; the DPM-Solver++ coefficients of both routes come from dpmpp_tables.
 """
 import numpy as np
 import torch
@@ -164,12 +165,7 @@ class _SamplerBase:
         return _k.axpby(x0.contiguous(), float(sa[ti.flat[0]]), noise.contiguous(), float(s1m[ti.flat[0]]))
 
 
-class DDIMSampler(_SamplerBase):
-    def __init__(self, model, schedule="linear", device_loop=False, **kwargs):
-        super().__init__(model, schedule, **kwargs)
-        self.device_loop = bool(device_loop)
-
-    # ---- the device loop: what it can take over, and the hand-over
+    # ---- the device loops (DDIM, PLMS, DPM-Solver++): what they can take over
     def _loop_cond(self, c, uc, cfg_on):
         """(ctx, uctx, flags, control_scales) the engine's loop needs for this conditioning, after registering the hints as
         apply_model would -- or None: a conditioning the loop does not take (the per-step route then treats it as before)."""
@@ -205,12 +201,13 @@ class DDIMSampler(_SamplerBase):
             return None
         return c, uc if cfg_on else None, _lib.FLAG_NO_CONTROL | pair, None
 
-    def _loop_plan(self, cond, uc, scales, mask, x0, img, host_hooks, kwargs):
+    def _loop_plan(self, cond, uc, scales, mask, x0, img, host_hooks, kwargs, entry='sample_ddim_ex'):
         """None (per-step route), or the conditioning part of the device loop's arguments.  `scales`: the guidance scale of
-        every step of the walk; host_hooks: whether anything asked for runs on the host between steps.  Draws no noise."""
+        every step of the walk; host_hooks: whether anything asked for runs on the host between steps; entry: the engine
+        method that runs the loop.  Draws no noise."""
         m = self.model
         eng = getattr(m, 'engine', None)
-        if not self.device_loop or eng is None or not hasattr(eng, 'sample_ddim_ex') or host_hooks or kwargs:
+        if not getattr(self, 'device_loop', False) or eng is None or not hasattr(eng, entry) or host_hooks or kwargs:
             return None
         if getattr(m, 'split_input_params', None) is not None or getattr(self, '_dyn', None) is not None:
             return None
@@ -222,6 +219,17 @@ class DDIMSampler(_SamplerBase):
         if mask is not None and (x0 is None or tuple(x0.shape) != tuple(img.shape)):
             return None
         return self._loop_cond(cond, uc, all(on))
+
+    @staticmethod
+    def _log_steps(total_steps, log_every_t):
+        """walk positions whose x_prev / pred_x0 the loops log: `index % log_every_t == 0 or index == total_steps - 1`"""
+        return [i for i in range(total_steps) if (total_steps - i - 1) % log_every_t == 0 or i == 0]
+
+
+class DDIMSampler(_SamplerBase):
+    def __init__(self, model, schedule="linear", device_loop=False, **kwargs):
+        super().__init__(model, schedule, **kwargs)
+        self.device_loop = bool(device_loop)
 
     def _device_loop(self, plan, img, timesteps, tabs, scales, mask, x0, temperature, log_steps):
         """Draw the walk's noise as the per-step route would (per step: q_sample's if there is a mask, then the step's, which is
@@ -295,8 +303,7 @@ class DDIMSampler(_SamplerBase):
         plan = None if scales is None or total_steps < 1 else \
             self._loop_plan(cond, unconditional_conditioning, scales, mask, x0, img, hooks, kwargs)
         if plan is not None:
-            log_steps = [i for i in range(total_steps)
-                         if (total_steps - i - 1) % log_every_t == 0 or i == 0]       # `index % log_every_t == 0 or index == total_steps - 1`
+            log_steps = self._log_steps(total_steps, log_every_t)
             img, x_inter, pred = self._device_loop(plan, img, list(reversed([int(t) for t in time_range])),
                                                    self._tables(ddim_use_original_steps), scales, mask, x0, temperature, log_steps)
             intermediates['x_inter'] += list(x_inter)
@@ -384,6 +391,32 @@ class DDIMSampler(_SamplerBase):
 
 
 class PLMSSampler(_SamplerBase):
+    def __init__(self, model, schedule="linear", device_loop=False, **kwargs):
+        super().__init__(model, schedule, **kwargs)
+        self.device_loop = bool(device_loop)
+
+    def _device_loop(self, plan, img, timesteps, tabs, scale, mask, x0, log_steps):
+        """Draw what the per-step route draws, in its order -- per step q_sample's noise if there is a mask, then one noise per
+        _x_prev call (two in the first step, all dropped: sigma is 0) -- then one engine call (fgdm_sample_plms)."""
+        ctx, uctx, flags, control_scales = plan
+        S = len(timesteps)
+        alphas, alphas_prev, s1m = (np.asarray(t)[:S] for t in tabs[:3])
+        qn = []
+        for i in range(S):
+            if mask is not None:
+                qn.append(torch.randn_like(x0))                               # q_sample(x0, ts)
+            for _ in range(2 if i == 0 else 1):
+                _randn(img.shape, img.device)
+        kw = {}
+        if mask is not None:
+            h = self.model._host
+            kw = dict(mask=mask.to(img.dtype).expand_as(img).contiguous(), x0=x0, q_noise=torch.stack(qn),
+                      sqrt_alphas_cumprod_t=[h['sqrt_alphas_cumprod'][int(t)] for t in timesteps],
+                      sqrt_one_minus_alphas_cumprod_t=[h['sqrt_one_minus_alphas_cumprod'][int(t)] for t in timesteps])
+        return self.model.engine.sample_plms(img, ctx, uctx, scale if uctx is not None else 1.0, [int(t) for t in timesteps],
+                                             alphas, alphas_prev, s1m, log_steps=log_steps, control_scales=control_scales,
+                                             flags=flags, **kw)
+
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=True):
         if ddim_eta != 0:
             raise ValueError('ddim_eta must be 0 for PLMS')       # plms.py:25-26
@@ -424,6 +457,17 @@ class PLMSSampler(_SamplerBase):
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         time_range = list(reversed(range(0, timesteps))) if ddim_use_original_steps else np.flip(timesteps)
         total_steps = timesteps if ddim_use_original_steps else timesteps.shape[0]
+        hooks = bool(callback or img_callback or score_corrector is not None or noise_dropout > 0. or quantize_denoised)
+        tabs = self._tables(ddim_use_original_steps)
+        plan = None if total_steps < 1 or np.asarray(tabs[3])[:total_steps].any() else \
+            self._loop_plan(cond, unconditional_conditioning, [unconditional_guidance_scale] * total_steps, mask, x0, img, hooks, {},
+                            entry='sample_plms')
+        if plan is not None:
+            img, x_inter, pred = self._device_loop(plan, img, list(reversed([int(t) for t in time_range])), tabs,
+                                                   unconditional_guidance_scale, mask, x0, self._log_steps(total_steps, log_every_t))
+            intermediates['x_inter'] += list(x_inter)
+            intermediates['pred_x0'] += list(pred)
+            return img, intermediates
         old_eps = []
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
@@ -649,14 +693,64 @@ class _DiscreteVPSchedule:
         return np.float32(lm - np.float32(0.5) * np.log(np.float32(1.) - np.exp(np.float32(2.) * lm)))
 
 
+DPMPP_FIRST, DPMPP_SECOND = 1, 2      # FGDM_DPMPP_FIRST / FGDM_DPMPP_SECOND of include/fgdm.h
+
+
+def dpmpp_tables(ns, steps, order=2):
+    """Every coefficient of a DPM-Solver++ multistep sampling (order 2, time_uniform, lower_order_final), one entry per network
+    evaluation k = 0 .. steps - 1 at t_k, each followed by the update to t_{k+1}; float32 arithmetic, handed out as Python floats.
+    The per-step route and the device loop (fgdm_sample_dpmpp) both read these tables, so they cannot drift apart.
+      t_float                            the model's time input (t_k - 1/N) * 1000                        dpm_solver.py:278-287
+      inv_alpha, neg_sigma_over_alpha    m0 = (x - sigma eps) / alpha as axpby(x, 1/alpha, eps, -sigma/alpha)         :386-399
+      update_kind, c1, cm0, cm1          DPMPP_FIRST:  x = axpby(x, c1, m0, cm0)                                      :504-528
+                                         DPMPP_SECOND: x = axpby(axpby(x, c1, m0, cm0), 1, m1, cm1)                   :755-789"""
+    f32 = np.float32
+    ts = np.linspace(ns.T, 1. / ns.total_N, steps + 1, dtype=np.float32)       # get_time_steps('time_uniform')
+    tab = {k: [] for k in ('t_float', 'inv_alpha', 'neg_sigma_over_alpha', 'update_kind', 'c1', 'cm0', 'cm1')}
+    for k in range(steps):
+        s, t = ts[k], ts[k + 1]
+        tab['t_float'].append(float((f32(s) - f32(1. / ns.total_N)) * f32(1000.)))
+        a, sg = ns.marginal_alpha(s), ns.marginal_std(s)
+        tab['inv_alpha'].append(float(f32(1.) / a))
+        tab['neg_sigma_over_alpha'].append(float(-sg / a))
+        step = k + 1                                                            # the reference's loop variable of this update
+        step_order = 1 if k == 0 else (min(order, steps + 1 - step) if steps < 15 else order)      # init_order = 1; lower_order_final
+        if step_order == 1:                                                     # dpm_solver.py:504-528 (predict_x0 branch)
+            h = ns.marginal_lambda(t) - ns.marginal_lambda(s)
+            c1 = ns.marginal_std(t) / ns.marginal_std(s)
+            c2 = ns.marginal_alpha(t) * f32(np.expm1(-h))
+            kind, cm0, cm1 = DPMPP_FIRST, float(-c2), 0.0
+        else:                                                                   # dpm_solver.py:755-789 ('dpm_solver' type, predict_x0)
+            t1, t0 = ts[k - 1], s
+            l1, l0, lt = ns.marginal_lambda(t1), ns.marginal_lambda(t0), ns.marginal_lambda(t)
+            h0, h = l0 - l1, lt - l0
+            r0 = h0 / h
+            c1 = ns.marginal_std(t) / ns.marginal_std(t0)
+            c2 = ns.marginal_alpha(t) * (f32(np.exp(-h)) - f32(1.))
+            # x_t = c1 x - c2 m0 - 0.5 c2 (m0 - m1) / r0
+            kind, cm0, cm1 = DPMPP_SECOND, float(-c2 - f32(0.5) * c2 / r0), float(f32(0.5) * c2 / r0)
+        tab['update_kind'].append(kind)
+        tab['c1'].append(float(c1))
+        tab['cm0'].append(cm0)
+        tab['cm1'].append(cm1)
+    return tab
+
+
 class DPMSolverSampler:
     """ldm/models/diffusion/dpm_solver/sampler.py:8-82: DPM-Solver++ (data prediction), multistep order 2,
     time_uniform steps from T = 1 to 1/N, lower_order_final, classifier-free guidance as one 2B batch.
-    The model is evaluated at FRACTIONAL timesteps (t - 1/N) * 1000 (dpm_solver.py:278-287)."""
+    The model is evaluated at FRACTIONAL timesteps (t - 1/N) * 1000 (dpm_solver.py:278-287).
+    device_loop=True: the whole sampling is one engine call (fgdm_sample_dpmpp) when nothing asked for needs the host between
+    steps, under the rule of the DDIM sampler's device loop; same tables (dpmpp_tables), same bits."""
 
-    def __init__(self, model, **kwargs):
+    def __init__(self, model, device_loop=False, **kwargs):
         self.model = model
+        self.device_loop = bool(device_loop)
         self.alphas_cumprod = torch.as_tensor(model.alphas_cumprod).clone().detach().to(torch.float32).to(model.device)
+
+    _loop_plan = _SamplerBase._loop_plan
+    _loop_cond = _SamplerBase._loop_cond
+    _cat_cond = staticmethod(_SamplerBase._cat_cond)
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
@@ -676,13 +770,19 @@ class DPMSolverSampler:
         ns = _DiscreteVPSchedule(self.alphas_cumprod.detach().cpu().numpy())
         steps, order = S, 2
         assert steps >= order
-        ts = np.linspace(ns.T, 1. / ns.total_N, steps + 1, dtype=np.float32)       # get_time_steps('time_uniform')
         scale, uc = unconditional_guidance_scale, unconditional_conditioning
+        tab = dpmpp_tables(ns, steps, order)
+        hooks = bool(callback or img_callback or score_corrector is not None or noise_dropout > 0.)
+        plan = self._loop_plan(conditioning, uc, [scale] * steps, None, None, x, hooks, kwargs, entry='sample_dpmpp')
+        if plan is not None:            # (mask / x0 are ignored, as the reference's sampler ignores them)
+            ctx, uctx, flags, control_scales = plan
+            x = self.model.engine.sample_dpmpp(x, ctx, uctx, scale if uctx is not None else 1.0, tab,
+                                               control_scales=control_scales, flags=flags)
+            return x.to(device), None
 
-        def data_prediction(xx, t):
-            # model_wrapper (classifier-free, dpm_solver.py:321-343) + data_prediction_fn (:386-399)
-            t_in = torch.full((xx.shape[0],), float((np.float32(t) - np.float32(1. / ns.total_N)) * np.float32(1000.)),
-                              device=xx.device, dtype=torch.float32)
+        def data_prediction(xx, k):
+            # model_wrapper (classifier-free, dpm_solver.py:321-343) + data_prediction_fn (:386-399) of evaluation k
+            t_in = torch.full((xx.shape[0],), tab['t_float'][k], device=xx.device, dtype=torch.float32)
             if scale == 1. or uc is None:
                 e = self.model.apply_model(xx, t_in, conditioning)
             else:
@@ -690,42 +790,20 @@ class DPMSolverSampler:
                 out = self.model.apply_model(torch.cat([xx] * 2), torch.cat([t_in] * 2), torch.cat([uc, conditioning]), **kw)
                 e_u, e_c = out.chunk(2)
                 e = _k.cfg_combine(e_c.contiguous(), e_u.contiguous(), scale)
-            a, sg = ns.marginal_alpha(t), ns.marginal_std(t)
-            return _k.axpby(xx.contiguous(), float(np.float32(1.) / a), e, float(-sg / a))     # (x - sigma eps) / alpha
+            return _k.axpby(xx.contiguous(), tab['inv_alpha'][k], e, tab['neg_sigma_over_alpha'][k])     # (x - sigma eps) / alpha
 
-        def first_update(xx, s, t, m_s):                         # dpm_solver.py:504-528 (predict_x0 branch)
-            h = ns.marginal_lambda(t) - ns.marginal_lambda(s)
-            c1 = ns.marginal_std(t) / ns.marginal_std(s)
-            c2 = ns.marginal_alpha(t) * np.float32(np.expm1(-h))
-            return _k.axpby(xx, float(c1), m_s, float(-c2))
+        def update(xx, k, m0, m1):       # from t_k to t_{k+1} behind evaluation k: first_update / second_update (dpm_solver.py:504-528, 755-789)
+            y = _k.axpby(xx, tab['c1'][k], m0, tab['cm0'][k])
+            return y if tab['update_kind'][k] == DPMPP_FIRST else _k.axpby(y, 1.0, m1, tab['cm1'][k])
 
-        def second_update(xx, m_prev, t_prev, t):               # dpm_solver.py:755-789 ('dpm_solver' type, predict_x0)
-            (m1, m0), (t1, t0) = m_prev, t_prev
-            l1, l0, lt = ns.marginal_lambda(t1), ns.marginal_lambda(t0), ns.marginal_lambda(t)
-            h0, h = l0 - l1, lt - l0
-            r0 = h0 / h
-            c1 = ns.marginal_std(t) / ns.marginal_std(t0)
-            c2 = ns.marginal_alpha(t) * (np.float32(np.exp(-h)) - np.float32(1.))
-            # x_t = c1 x - c2 m0 - 0.5 c2 (m0 - m1) / r0
-            y = _k.axpby(xx, float(c1), m0, float(-c2 - np.float32(0.5) * c2 / r0))
-            return _k.axpby(y, 1.0, m1, float(np.float32(0.5) * c2 / r0))
-
-        m_prev = [data_prediction(x, ts[0])]
-        t_prev = [ts[0]]
-        x = first_update(x, t_prev[-1], ts[1], m_prev[-1])      # init_order = 1
-        m_prev.append(data_prediction(x, ts[1]))
-        t_prev.append(ts[1])
+        m_prev = [data_prediction(x, 0)]
+        x = update(x, 0, m_prev[-1], None)                      # init_order = 1
+        m_prev.append(data_prediction(x, 1))
         for step in range(order, steps + 1):
-            t = ts[step]
-            step_order = min(order, steps + 1 - step) if steps < 15 else order      # lower_order_final
-            if step_order == 1:
-                x = first_update(x, t_prev[-1], t, m_prev[-1])
-            else:
-                x = second_update(x, m_prev, t_prev, t)
-            t_prev = [t_prev[1], t]
+            x = update(x, step - 1, m_prev[1], m_prev[0])
             m_prev = [m_prev[1], m_prev[1]]
             if step < steps:
-                m_prev[-1] = data_prediction(x, t)
+                m_prev[-1] = data_prediction(x, step)
             if callback:
                 callback(step)
         return x.to(device), None

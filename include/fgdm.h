@@ -347,6 +347,109 @@ typedef struct fgdm_ddim_params {
 } fgdm_ddim_params;
 int fgdm_sample_ddim_ex(fgdm_engine* e, const fgdm_ddim_params* p, void* stream);
 
+/* The whole of PLMSSampler.sample / plms_sampling without host callbacks (ldm/models/diffusion/plms.py:58-236; the sampler
+ * scripts/txt2img_fgdm_inference.py:183 selects with --plms).  eta is 0 (plms.py:25-26): there is no noise term.
+ *
+ * The walk, the table order and the slot conventions are those of fgdm_sample_ddim_ex: host tables of S entries, entry k belonging
+ * to timesteps[k] (ddim_timesteps order; the walk visits k = S-1 ... 0, plms.py:138,150); q_noise and log_steps in WALK order.
+ * Per network evaluation the loop launches ONE elementwise kernel (k_plms_loop_step):
+ *   step 0 (plms.py:219-223) evaluates twice.  Probe: e_t = CFG of the evaluation at timesteps[S-1] is kept as history plane 0 and
+ *     x_prev = step(e_t) goes to the network's input only; the state x is untouched.  The second evaluation runs on that input at
+ *     t_next = timesteps[max(S-2, 0)] (time_range[min(i + 1, len - 1)], plms.py:143: with S == 1 the same timestep again).
+ *     Finish-first: e' = (e_t + e_next) / 2, rounded as the per-step route's axpby with 0.5, 0.5 rounds it.
+ *   step i >= 1 (plms.py:224-232) evaluates once.  Multistep: e_t = CFG is kept as history plane i % 3 and e' is the Adams-Bashforth
+ *     combination of order min(i, 3) over e_t and the planes of steps i-1, i-2, i-3, as fgdm_plms_combine computes it.  The three
+ *     planes are rotated by pointer, nothing is copied: the AB order sequence is 0 (step 0), 1, 2, 3, 3, ...
+ *   Every step but the probe then takes one tail: pred_x0 and x_prev from e' as fgdm_ddim_step with noise = NULL, the stores of a
+ *     logged step, the NEXT step's blend (fgdm_axpby for q_sample, then fgdm_mask_blend, plms.py:145-148) and the stores of x to the
+ *     state and to both halves of the network's input.
+ * The arithmetic is that of fgdm_ddim_step, fgdm_plms_combine, fgdm_axpby and fgdm_mask_blend, rounding for rounding: the loop gives
+ * the bits of the per-step route of fgdm_amd/samplers.py fed the same q_noise.
+ *
+ * CFG is on when uncond is given and cfg_scale != 1, and runs as ONE 2B batch; the loop sets FGDM_FLAG_CFG_PAIRS itself.  Hints come
+ * from fgdm_set_hint; an engine with in_channels > 4 (hybrid c_concat) is refused.
+ * struct_size / reserved0: as for fgdm_ddim_params, from FGDM_PLMS_PARAMS_SIZE_V1 up to the library's own sizeof.
+ * mask [B,4,H,W], x0 [B,4,H,W], q_noise [S, B,4,H,W] (device) and sqrt_alphas_cumprod_t / sqrt_one_minus_alphas_cumprod_t [S] (host):
+ *   as for fgdm_sample_ddim_ex.  log_steps [n_log] (host, strictly ascending walk positions in [0, S)), x_inter_out / pred_x0_out
+ *   [n_log, B,4,H,W] (device, each may be NULL): slot j receives x_prev and pred_x0 of step log_steps[j] (plms.py:170-172).
+ * FGDM_ERR_ARG before any launch (x untouched): a struct_size outside that range, reserved0 != 0; a NULL x / cond / table; S, B, H or
+ * W <= 0; mask without x0, q_noise or the two q_sample tables; n_log < 0, n_log > 0 without log_steps, a log step outside [0, S) or
+ * not above its predecessor; an engine with in_channels > 4. */
+#define FGDM_PLMS_PARAMS_SIZE_V1 168
+typedef struct fgdm_plms_params {
+    int64_t struct_size;
+    float* x;                           /* device [B,4,H,W]: x_T in, the sample out */
+    const float* cond;                  /* device [B,tokens,context_dim] */
+    const float* uncond;                /* device, or NULL */
+    const int64_t* timesteps;
+    const float* alphas;
+    const float* alphas_prev;
+    const float* sqrt_one_minus_alphas;
+    const float* control_scales;        /* host, n_controlnets * 13, or NULL */
+    const float* mask;
+    const float* x0;
+    const float* q_noise;
+    const float* sqrt_alphas_cumprod_t;
+    const float* sqrt_one_minus_alphas_cumprod_t;
+    const int32_t* log_steps;
+    float* x_inter_out;
+    float* pred_x0_out;
+    float cfg_scale;
+    int32_t S;
+    int32_t B;
+    int32_t H;
+    int32_t W;
+    int32_t flags;                      /* FGDM_FLAG_* as for fgdm_apply_model */
+    int32_t n_log;
+    int32_t reserved0;                  /* 0 */
+} fgdm_plms_params;
+int fgdm_sample_plms(fgdm_engine* e, const fgdm_plms_params* p, void* stream);
+
+/* The whole of DPMSolverSampler.sample (ldm/models/diffusion/dpm_solver/sampler.py:22-82): DPM-Solver++ (predict_x0), multistep
+ * order 2, time_uniform steps, lower_order_final (dpm_solver.py:386-399 data prediction, 504-528 first-order update, 755-789
+ * second-order update, 1023-1058 the multistep walk).  The sampler's mask / x0 are ignored by the reference and have no field here.
+ *
+ * The caller hands over one table entry per network evaluation k = 0 ... n_eval - 1 (host; n_eval is the sampler's step count S:
+ * the evaluations at time_uniform t_0 ... t_{S-1}, each followed by the update to t_{k+1}):
+ *   t_float[k]               the model's time input, (t_k - 1/N) * 1000 (dpm_solver.py:278-287): fractional
+ *   inv_alpha[k], neg_sigma_over_alpha[k]     the data prediction m0 = inv_alpha x + neg_sigma_over_alpha eps, i.e. (x - sigma eps) / alpha
+ *   update_kind[k] (int32)   FGDM_DPMPP_FIRST: x = c1 x + cm0 m0;  FGDM_DPMPP_SECOND: x = (c1 x + cm0 m0) + cm1 m1 with m1 the data
+ *                            prediction of evaluation k - 1 (two roundings, the two axpby calls of the per-step route)
+ *   c1[k], cm0[k], cm1[k]    the coefficients of that update as fp32 (cm1 is read for FGDM_DPMPP_SECOND only)
+ * Per evaluation the loop launches ONE elementwise kernel (k_dpmpp_loop_step): CFG combine, m0 (kept in one of two planes that swap
+ * by pointer), the update, and the stores of x to the state and to both halves of the network's input.  Every term is rounded as
+ * fgdm_axpby rounds it: the loop gives the bits of the per-step route of fgdm_amd/samplers.py, which computes the tables with the
+ * same helper (fgdm_amd.samplers.dpmpp_tables).
+ * CFG, flags, hints, struct_size (from FGDM_DPMPP_PARAMS_SIZE_V1) and the reserved fields: as for fgdm_sample_plms.
+ * FGDM_ERR_ARG before any launch (x untouched): a struct_size outside that range, reserved0 or reserved1 != 0; a NULL x / cond / table; n_eval, B,
+ * H or W <= 0; an update_kind that is neither constant, FGDM_DPMPP_SECOND at evaluation 0; an engine with in_channels > 4. */
+#define FGDM_DPMPP_FIRST 1
+#define FGDM_DPMPP_SECOND 2
+#define FGDM_DPMPP_PARAMS_SIZE_V1 128
+typedef struct fgdm_dpmpp_params {
+    int64_t struct_size;
+    float* x;                           /* device [B,4,H,W]: x_T in, the sample out */
+    const float* cond;                  /* device [B,tokens,context_dim] */
+    const float* uncond;                /* device, or NULL */
+    const float* control_scales;        /* host, n_controlnets * 13, or NULL */
+    const float* t_float;
+    const float* inv_alpha;
+    const float* neg_sigma_over_alpha;
+    const int32_t* update_kind;
+    const float* c1;
+    const float* cm0;
+    const float* cm1;
+    float cfg_scale;
+    int32_t n_eval;
+    int32_t B;
+    int32_t H;
+    int32_t W;
+    int32_t flags;                      /* FGDM_FLAG_* as for fgdm_apply_model */
+    int32_t reserved0;                  /* 0 */
+    int32_t reserved1;                  /* 0 */
+} fgdm_dpmpp_params;
+int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* p, void* stream);
+
 /* Built-in kernel timer (no reference counterpart: the reference only prints wall-clock, scripts/txt2img.py:381-396).
  * Between begin and end every stride-th kernel launch is bracketed by HIP events on the launch stream
  * (work / bytes / time totals then refer to the bracketed launches only).
@@ -487,6 +590,34 @@ int fgdm_op_ddim_loop_step(const float* x, const float* e_cond, const float* e_u
                            float sigma_t, float sqrt_one_minus_at, const float* noise, const float* mask, const float* x0,
                            const float* q_noise, float sqrt_ac_next, float sqrt_one_minus_ac_next, float* x_out, float* xin_a,
                            float* xin_b, float* log_x, float* log_pred_x0, int64_t n, void* stream);
+
+/* Diagnostic entries (tests/test_gpu_multistep_loop.py); only the loops of fgdm_sample_plms / fgdm_sample_dpmpp launch these kernels
+ * in the product path.  n fp32 elements; every output may be NULL (nothing is written) and nothing outside n elements is written.
+ *
+ * fgdm_op_plms_loop_step: one launch of k_plms_loop_step.  e = e_uncond + cfg_scale (e_cond - e_uncond) (e_uncond NULL: e_cond)
+ *   -> e_out in every mode (the loop passes NULL in mode 1), then
+ *   mode 0 (probe, plms.py:219-221): x_prev of e, exactly as fgdm_ddim_step with noise NULL -> xin_a, xin_b; x_out, the
+ *     logs and the blend are not touched;
+ *   mode 1 (finish-first, plms.py:222-223): e' = 0.5 e1 + 0.5 e rounded as fgdm_axpby rounds it (e1: the probe's e_t);
+ *   mode 2 (multistep, plms.py:224-232): e' = the combination of fgdm_plms_combine over e, e1, e2, e3 for order 1..3
+ *     (e_out may be e3 itself);
+ *   modes 1 and 2: pred_x0, x_prev from e' as fgdm_ddim_step -> log_pred_x0, log_x; mask given: x = q mask + (1 - mask) x_prev with
+ *     q = sqrt_ac_next x0 + sqrt_one_minus_ac_next q_noise (fgdm_axpby then fgdm_mask_blend), else x = x_prev; x -> x_out, xin_a, xin_b
+ *     (x_out may be x itself).  e_cond NULL: no update, x_prev = x (the launch in front of the first step).
+ *   FGDM_ERR_ARG before any launch: x NULL, n <= 0, e_uncond without e_cond, mask without x0 or q_noise, an unknown mode, mode 1
+ *   without e1, mode 2 with an order outside 1..3 or without the planes of that order.
+ * fgdm_op_dpmpp_loop_step: one launch of k_dpmpp_loop_step.  m0 = inv_alpha x + neg_sigma_over_alpha e -> m0_out; update_kind
+ *   FGDM_DPMPP_FIRST: x = c1 x + cm0 m0; FGDM_DPMPP_SECOND: x = (c1 x + cm0 m0) + cm1 m1; each sum rounded as fgdm_axpby rounds it
+ *   (dpm_solver.py:386-399, 504-528, 755-789); x -> x_out, xin_a, xin_b (x_out may be x itself).
+ *   FGDM_ERR_ARG before any launch: x or e_cond NULL, n <= 0, another update_kind, FGDM_DPMPP_SECOND without m1. */
+int fgdm_op_plms_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, int mode, int order,
+                           const float* e1, const float* e2, const float* e3, float* e_out, float a_t, float a_prev,
+                           float sqrt_one_minus_at, const float* mask, const float* x0, const float* q_noise, float sqrt_ac_next,
+                           float sqrt_one_minus_ac_next, float* x_out, float* xin_a, float* xin_b, float* log_x, float* log_pred_x0,
+                           int64_t n, void* stream);
+int fgdm_op_dpmpp_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float inv_alpha,
+                            float neg_sigma_over_alpha, const float* m1, int update_kind, float c1, float cm0, float cm1,
+                            float* m0_out, float* x_out, float* xin_a, float* xin_b, int64_t n, void* stream);
 
 /* Diagnostic entry (tests/test_gpu_qkv_projection.py); the product path does not call it.
  *
