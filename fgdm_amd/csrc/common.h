@@ -193,33 +193,25 @@ int transpose_pad_keys(const half_t* v, half_t* vt, int B, int Tk, int C, int Tk
 int ddim_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale,
               float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, const float* noise,
               float* x_prev, float* pred_x0, float* e_out, size_t n, hipStream_t s);
-// One step of the device DDIM loop (k_ddim_loop_step): ddim_step's update, then the NEXT step's inpainting blend
-// x = q m + (1 - m) x_prev with q = sa_next x0 + s1m_next qnoise (mask NULL: x = x_prev), stored to x_out and to the two halves
-// of the network's input (each may be NULL); log_x / log_p0 receive x_prev and pred_x0 of a logged step.  ec NULL: no update
-// (x_prev = x): the blend and the input copies in front of the first step.  x_out may alias x; nothing else may overlap.
-struct DdimLoopStep {
-    const float *x, *ec, *eu, *noise, *mask, *x0, *qnoise;
-    float *x_out, *xin_a, *xin_b, *log_x, *log_p0;
-    float cfg, a_t, a_prev, sigma, s1m, sa_next, s1m_next;
-    size_t n;
-};
-int ddim_loop_step(const DdimLoopStep& a, hipStream_t s);
-// One launch per network evaluation of the device PLMS loop (k_plms_loop_step).  mode:
-//   PLMS_PROBE        e_t = CFG(ec, eu) -> e_out; x_prev = step(e_t) -> xin_a / xin_b only (plms.py:219-221)
-//   PLMS_FINISH_FIRST e' = (e1 + CFG(ec, eu)) / 2 as axpby(e1, 0.5, e_next, 0.5): e1 is the probe's e_t (plms.py:222-223)
-//   PLMS_MULTISTEP    e_t = CFG(ec, eu) -> e_out; e' = plms_combine(e_t, e1, e2, e3, order), order 1..3 (plms.py:224-232)
-// and, but for the probe, DdimLoopStep's tail with sigma = 0: pred_x0 / x_prev from e', the logged stores, the NEXT step's blend,
-// x to x_out and the two input halves.  ec NULL: the blend and the stores in front of the first step.  x_out may alias x, and
-// e_out may alias e3 (each element is read before it is written, by the same thread); nothing else may overlap.
-enum { PLMS_PROBE = 0, PLMS_FINISH_FIRST = 1, PLMS_MULTISTEP = 2 };
-struct PlmsLoopStep {
-    const float *x, *ec, *eu, *e1, *e2, *e3, *mask, *x0, *qnoise;
+// One launch per network evaluation of the device DDIM and PLMS loops (k_loop_step).  e_t = CFG(ec, eu) -> e_out, then by mode
+//   LOOP_PLAIN        e' = e_t: a DDIM step (ddim.py:243-268)
+//   LOOP_PROBE        e' = e_t; x_prev = step(e') -> xin_a / xin_b only (plms.py:219-221)
+//   LOOP_FINISH_FIRST e' = (e1 + e_t) / 2 as axpby(e1, 0.5, e_t, 0.5): e1 is the probe's e_t (plms.py:222-223)
+//   LOOP_MULTISTEP    e' = plms_combine(e_t, e1, e2, e3, order), order 1..3 (plms.py:224-232)
+// and, but for the probe: ddim_step's pred_x0 / x_prev from e' (plus sigma * noise, noise not NULL) -> log_x / log_p0 of a logged
+// step, then the NEXT step's inpainting blend x = q m + (1 - m) x_prev with q = sa_next x0 + s1m_next qnoise (mask NULL: x = x_prev),
+// stored to x_out and to the two halves of the network's input (each may be NULL).  ec NULL: no update (x_prev = x): the blend and
+// the input copies in front of the first step.  x_out may alias x, and e_out may alias e3 (each element is read before it is
+// written, by the same thread); nothing else may overlap.  (0..2 are the `mode` values of fgdm_op_plms_loop_step.)
+enum { LOOP_PROBE = 0, LOOP_FINISH_FIRST = 1, LOOP_MULTISTEP = 2, LOOP_PLAIN = 3 };
+struct LoopStep {
+    const float *x, *ec, *eu, *e1, *e2, *e3, *noise, *mask, *x0, *qnoise;
     float *e_out, *x_out, *xin_a, *xin_b, *log_x, *log_p0;
-    float cfg, a_t, a_prev, s1m, sa_next, s1m_next;
+    float cfg, a_t, a_prev, sigma, s1m, sa_next, s1m_next;
     int mode, order;
     size_t n;
 };
-int plms_loop_step(const PlmsLoopStep& a, hipStream_t s);
+int loop_step(const LoopStep& a, hipStream_t s);
 // One launch per network evaluation of the device DPM-Solver++ loop (k_dpmpp_loop_step): the data prediction
 // m0 = axpby(x, inv_alpha, CFG(ec, eu), neg_sigma_over_alpha) -> m0_out, then the update to the next time:
 //   DPMPP_FIRST   x = axpby(x, c1, m0, cm0)                              (dpm_solver.py:504-528)

@@ -224,17 +224,41 @@ int transpose_pad_keys(const half_t* v, half_t* vt, int B, int Tk, int C, int Tk
 // e = e_u + s (e_c - e_u)                                        ldm/models/diffusion/ddim.py:243
 // pred_x0 = (x - sqrt(1-a_t) e) / sqrt(a_t)                      ddim.py:259
 // x_prev  = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev - sigma^2) e + sigma * noise     ddim.py:263-268
+//
+// The loop step kernels further down must give the bits of the per-step kernels they fuse (k_ddim_step, k_plms, k_axpby,
+// k_mask_blend), and this file is compiled with -ffp-contract=fast, under which an expression's source does not say which products
+// are fused into a sum (a `*` behind __fmul_rn included).  So each formula is written ONCE, here, with every rounding explicit --
+// __builtin_fmaf where the product is fused, mul_rn where it is rounded on its own -- and both sets of kernels call it: they agree
+// by construction, under any compiler.  tests/test_gpu_sampler_update_bits.py pins the bits themselves.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+    float p = a * b;
+    asm volatile("" : "+v"(p));     // no instruction: the product is a value in a register, so it cannot become the multiplicand of an FMA
+    return p;
+}
+__device__ __forceinline__ float cfg_combine_rn(float ec, float eu, float s) { return __builtin_fmaf(s, ec - eu, eu); }
+__device__ __forceinline__ float ddim_dir_rn(float a_prev, float sigma) { return sqrtf(__builtin_fmaf(-sigma, sigma, 1.0f - a_prev)); }
+__device__ __forceinline__ float pred_x0_rn(float x, float e, float s1m, float sa) { return __builtin_fmaf(-s1m, e, x) / sa; }
+__device__ __forceinline__ float x_prev_rn(float p0, float e, float sp, float dir) { return mul_rn(dir, e) + mul_rn(sp, p0); }
+__device__ __forceinline__ float add_noise_rn(float xp, float sigma, float noise) { return __builtin_fmaf(sigma, noise, xp); }
+__device__ __forceinline__ float axpby_rn(float ca, float a, float cb, float b) { return __builtin_fmaf(ca, a, mul_rn(cb, b)); }
+__device__ __forceinline__ float mask_blend_rn(float a, float b, float m) { return mul_rn(a, m) + mul_rn(1.0f - m, b); }
+// Adams-Bashforth combinations of plms.py:224-232; order = number of old eps available (1..3); e2 / e3 are read from order 2 / 3 on
+__device__ __forceinline__ float adams_bashforth_rn(int order, float e, const float* e1, const float* e2, const float* e3, size_t i) {
+    if (order == 1) return mul_rn(__builtin_fmaf(3.f, e, -e1[i]), 0.5f);
+    if (order == 2) return (__builtin_fmaf(-16.f, e1[i], mul_rn(23.f, e)) + mul_rn(5.f, e2[i])) / 12.f;
+    return (((mul_rn(55.f, e) - mul_rn(59.f, e1[i])) + mul_rn(37.f, e2[i])) - mul_rn(9.f, e3[i])) / 24.f;
+}
+
 __global__ void k_ddim_step(const float* __restrict__ x, const float* __restrict__ ec, const float* __restrict__ eu,
                             float cfg, float a_t, float a_prev, float sigma, float s1m, const float* __restrict__ noise,
                             float* __restrict__ x_prev, float* __restrict__ pred_x0, float* __restrict__ e_out, size_t n) {
-    const float sa = sqrtf(a_t), sp = sqrtf(a_prev), dir = sqrtf(1.0f - a_prev - sigma * sigma);
+    const float sa = sqrtf(a_t), sp = sqrtf(a_prev), dir = ddim_dir_rn(a_prev, sigma);
     EW_LOOP(i, n) {
         float e = ec[i];
-        if (eu) { const float u = eu[i]; e = u + cfg * (e - u); }
-        const float xi = x[i];
-        const float p0 = (xi - s1m * e) / sa;
-        float xp = sp * p0 + dir * e;
-        if (noise) xp += sigma * noise[i];
+        if (eu) e = cfg_combine_rn(e, eu[i], cfg);
+        const float p0 = pred_x0_rn(x[i], e, s1m, sa);
+        float xp = x_prev_rn(p0, e, sp, dir);
+        if (noise) xp = add_noise_rn(xp, sigma, noise[i]);
         if (x_prev) x_prev[i] = xp;
         if (pred_x0) pred_x0[i] = p0;
         if (e_out) e_out[i] = e;
@@ -248,98 +272,42 @@ int ddim_step(const float* x, const float* e_cond, const float* e_uncond, float 
     return LAUNCH_OK();
 }
 
-// One step of the device DDIM loop (fgdm_sample_ddim_ex), one pass over the n elements:
-//   e = e_u + s (e_c - e_u); pred_x0, x_prev as k_ddim_step (sigma * noise included)                    ddim.py:243,259-268
-//   mask given (there is a next step): x = q m + (1 - m) x_prev, q = sa_next x0 + s1m_next qnoise        ddim.py:151-154
-// and x goes to the state and to both halves of the network's cat([x] * 2) input; a logged step also stores x_prev and pred_x0
-// (the intermediates hold x_prev BEFORE the next step's blend, as the per-step loop appends them).  ec NULL: no update, x_prev = x
-// (the blend and the input copies in front of the first step).  x_out may be x; every other buffer is distinct.
-// The results must be the bits of k_ddim_step, then k_axpby, then k_mask_blend, and this file is compiled with -ffp-contract=fast,
-// under which the backend fuses any product into a following sum (a `*` behind __fmul_rn included).  So every rounding is spelled
-// out as those three kernels perform it: fmaf where they fuse, mul_rn where they round the product on its own.
-// Which of the two each term gets is read off the three kernels' disassembly under the current toolchain (k_ddim_step and
-// k_mask_blend round their two products in one v_pk_mul_f32, k_axpby is v_mul then v_fmac); their source does not pin it.  When
-// tests/test_gpu_ddim_loop.py starts failing after a compiler change, disassemble them again and re-derive the pattern below.
-__device__ __forceinline__ float mul_rn(float a, float b) {
-    float p = a * b;
-    asm volatile("" : "+v"(p));     // no instruction: the product is a value in a register, so it cannot become the multiplicand of an FMA
-    return p;
-}
-__global__ void k_ddim_loop_step(const DdimLoopStep a) {
-    const float sa = sqrtf(a.a_t), sp = sqrtf(a.a_prev), dir = sqrtf(__builtin_fmaf(-a.sigma, a.sigma, 1.0f - a.a_prev));
-    EW_LOOP(i, a.n) {
-        float xp = a.x[i], p0 = 0.f;
-        if (a.ec) {
-            float e = a.ec[i];
-            if (a.eu) { const float u = a.eu[i]; e = __builtin_fmaf(a.cfg, e - u, u); }
-            p0 = __builtin_fmaf(-a.s1m, e, xp) / sa;
-            xp = mul_rn(dir, e) + mul_rn(sp, p0);
-            if (a.noise) xp = __builtin_fmaf(a.sigma, a.noise[i], xp);
-            if (a.log_x) a.log_x[i] = xp;
-            if (a.log_p0) a.log_p0[i] = p0;
-        }
-        float xn = xp;
-        if (a.mask) {
-            const float m = a.mask[i];
-            const float q = __builtin_fmaf(a.sa_next, a.x0[i], mul_rn(a.s1m_next, a.qnoise[i]));     // k_axpby
-            xn = mul_rn(q, m) + mul_rn(1.0f - m, xp);                                                // k_mask_blend
-        }
-        if (a.x_out) a.x_out[i] = xn;
-        if (a.xin_a) a.xin_a[i] = xn;
-        if (a.xin_b) a.xin_b[i] = xn;
-    }
-}
-int ddim_loop_step(const DdimLoopStep& a, hipStream_t s) {
-    if (!a.x || a.n == 0 || (a.mask && (!a.x0 || !a.qnoise)) || (a.eu && !a.ec)) return FGDM_ERR_ARG;
-    FGDM_LAUNCH(k_ddim_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
-    return LAUNCH_OK();
-}
-
-// The tail the two multistep loop kernels share with k_ddim_loop_step: the next step's blend (k_axpby, then k_mask_blend) and the
-// stores of x to the state and to both halves of the network's input.
+// The next step's inpainting blend (k_axpby, then k_mask_blend; ddim.py:151-154) and the stores of x to the state and to both halves
+// of the network's cat([x] * 2) input: the tail of k_loop_step.
 __device__ __forceinline__ void loop_blend_store(float xp, size_t i, const float* mask, const float* x0, const float* qnoise,
                                                  float sa_next, float s1m_next, float* x_out, float* xin_a, float* xin_b) {
     float xn = xp;
-    if (mask) {
-        const float m = mask[i];
-        const float q = __builtin_fmaf(sa_next, x0[i], mul_rn(s1m_next, qnoise[i]));
-        xn = mul_rn(q, m) + mul_rn(1.0f - m, xp);
-    }
+    if (mask) xn = mask_blend_rn(axpby_rn(sa_next, x0[i], s1m_next, qnoise[i]), xp, mask[i]);
     if (x_out) x_out[i] = xn;
     if (xin_a) xin_a[i] = xn;
     if (xin_b) xin_b[i] = xn;
 }
 
-// One launch per network evaluation of the device PLMS loop (fgdm_sample_plms; plms.py:178-236), one pass over the n elements.
-//   probe         e_t = CFG -> e_out;  x_prev = step(e_t) -> the two input halves only              plms.py:219-221
-//   finish-first  e' = (e1 + CFG) / 2 with e1 the probe's e_t, as k_axpby(e1, 0.5, e_next, 0.5)     plms.py:222-223
-//   multistep     e_t = CFG -> e_out;  e' = k_plms(e_t, e1, e2, e3, order)                          plms.py:224-232
-// then (not the probe) pred_x0 / x_prev from e' as k_ddim_step with sigma = 0, the logged stores, the next step's blend and the
-// stores of x, as k_ddim_loop_step.  ec NULL: the blend and the stores in front of the first step.  e_out may be e3: element i
-// of e3 is read before element i of e_out is written, by the same thread.
-// Every rounding is that of the kernel it replaces under the current toolchain (see k_ddim_loop_step): k_ddim_step fuses
-// u + s (e - u) and x - s1m e and rounds sp p0 and dir e on their own; k_axpby is v_mul (cb b) then v_fmac (ca a); k_plms compiles
-// order 1 to fma(3, e, -e1) * 0.5, order 2 to (fma(-16, e1, rn(23 e)) + rn(5 e2)) / 12 and order 3 to four rounded products
-// summed left to right, / 24 (IEEE divisions).  After a compiler change: disassemble k_plms / k_axpby and re-derive.
-__global__ void k_plms_loop_step(const PlmsLoopStep a) {
-    const float sa = sqrtf(a.a_t), sp = sqrtf(a.a_prev), dir = sqrtf(1.0f - a.a_prev);
+// One launch per network evaluation of the device DDIM and PLMS loops (fgdm_sample_ddim_ex, fgdm_sample_plms), one pass over the n
+// elements.  e_t = e_u + s (e_c - e_u) -> e_out, then by mode
+//   plain         e' = e_t                                                                          ddim.py:243
+//   probe         e' = e_t;  x_prev = step(e') -> the two input halves only, nothing else           plms.py:219-221
+//   finish-first  e' = (e1 + e_t) / 2 with e1 the probe's e_t, as k_axpby(e1, 0.5, e_t, 0.5)        plms.py:222-223
+//   multistep     e' = k_plms(e_t, e1, e2, e3, order)                                               plms.py:224-232
+// then pred_x0 / x_prev from e' as k_ddim_step (sigma * noise included; the PLMS loop leaves them 0 / NULL), the logged stores
+// (x_prev BEFORE the next step's blend, as the per-step loop appends it) and loop_blend_store.  ec NULL: no update, x_prev = x (the
+// blend and the input copies in front of the first step).  x_out may be x, and e_out may be e3 (element i is read before it is
+// written, by the same thread); every other buffer is distinct.
+__global__ void k_loop_step(const LoopStep a) {
+    const float sa = sqrtf(a.a_t), sp = sqrtf(a.a_prev), dir = ddim_dir_rn(a.a_prev, a.sigma);
     EW_LOOP(i, a.n) {
         float xp = a.x[i];
         if (a.ec) {
             float e = a.ec[i];
-            if (a.eu) { const float u = a.eu[i]; e = __builtin_fmaf(a.cfg, e - u, u); }
-            float ep = e;      // the probe steps with e_t itself
-            if (a.mode == PLMS_FINISH_FIRST) {
-                ep = __builtin_fmaf(0.5f, a.e1[i], mul_rn(0.5f, e));
-            } else if (a.mode == PLMS_MULTISTEP) {
-                if (a.order == 1) ep = mul_rn(__builtin_fmaf(3.f, e, -a.e1[i]), 0.5f);
-                else if (a.order == 2) ep = (__builtin_fmaf(-16.f, a.e1[i], mul_rn(23.f, e)) + mul_rn(5.f, a.e2[i])) / 12.f;
-                else ep = (((mul_rn(55.f, e) - mul_rn(59.f, a.e1[i])) + mul_rn(37.f, a.e2[i])) - mul_rn(9.f, a.e3[i])) / 24.f;
-            }
+            if (a.eu) e = cfg_combine_rn(e, a.eu[i], a.cfg);
+            float ep = e;
+            if (a.mode == LOOP_FINISH_FIRST) ep = axpby_rn(0.5f, a.e1[i], 0.5f, e);
+            else if (a.mode == LOOP_MULTISTEP) ep = adams_bashforth_rn(a.order, e, a.e1, a.e2, a.e3, i);
             if (a.e_out) a.e_out[i] = e;
-            const float p0 = __builtin_fmaf(-a.s1m, ep, xp) / sa;
-            xp = mul_rn(dir, ep) + mul_rn(sp, p0);
-            if (a.mode == PLMS_PROBE) {
+            const float p0 = pred_x0_rn(xp, ep, a.s1m, sa);
+            xp = x_prev_rn(p0, ep, sp, dir);
+            if (a.noise) xp = add_noise_rn(xp, a.sigma, a.noise[i]);
+            if (a.mode == LOOP_PROBE) {
                 if (a.xin_a) a.xin_a[i] = xp;
                 if (a.xin_b) a.xin_b[i] = xp;
                 continue;
@@ -350,15 +318,15 @@ __global__ void k_plms_loop_step(const PlmsLoopStep a) {
         loop_blend_store(xp, i, a.mask, a.x0, a.qnoise, a.sa_next, a.s1m_next, a.x_out, a.xin_a, a.xin_b);
     }
 }
-int plms_loop_step(const PlmsLoopStep& a, hipStream_t s) {
+int loop_step(const LoopStep& a, hipStream_t s) {
     if (!a.x || a.n == 0 || (a.mask && (!a.x0 || !a.qnoise)) || (a.eu && !a.ec)) return FGDM_ERR_ARG;
     if (a.ec) {
-        if (a.mode != PLMS_PROBE && a.mode != PLMS_FINISH_FIRST && a.mode != PLMS_MULTISTEP) return FGDM_ERR_ARG;
-        if (a.mode == PLMS_FINISH_FIRST && !a.e1) return FGDM_ERR_ARG;
-        if (a.mode == PLMS_MULTISTEP && (a.order < 1 || a.order > 3 || !a.e1 || (a.order >= 2 && !a.e2) || (a.order >= 3 && !a.e3)))
+        if (a.mode != LOOP_PLAIN && a.mode != LOOP_PROBE && a.mode != LOOP_FINISH_FIRST && a.mode != LOOP_MULTISTEP) return FGDM_ERR_ARG;
+        if (a.mode == LOOP_FINISH_FIRST && !a.e1) return FGDM_ERR_ARG;
+        if (a.mode == LOOP_MULTISTEP && (a.order < 1 || a.order > 3 || !a.e1 || (a.order >= 2 && !a.e2) || (a.order >= 3 && !a.e3)))
             return FGDM_ERR_ARG;
     }
-    FGDM_LAUNCH(k_plms_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
+    FGDM_LAUNCH(k_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
     return LAUNCH_OK();
 }
 
@@ -366,16 +334,16 @@ int plms_loop_step(const PlmsLoopStep& a, hipStream_t s) {
 //   m0 = k_axpby(x, inv_alpha, CFG, neg_sigma_over_alpha) -> m0_out
 //   first order   x = k_axpby(x, c1, m0, cm0)
 //   second order  x = k_axpby(k_axpby(x, c1, m0, cm0), 1, m1, cm1)
-// and x to the state and to both halves of the network's input.  Every k_axpby is v_mul (cb b), then v_fmac (ca a).
+// and x to the state and to both halves of the network's input.
 __global__ void k_dpmpp_loop_step(const DpmppLoopStep a) {
     EW_LOOP(i, a.n) {
         const float xi = a.x[i];
         float e = a.ec[i];
-        if (a.eu) { const float u = a.eu[i]; e = __builtin_fmaf(a.cfg, e - u, u); }
-        const float m0 = __builtin_fmaf(a.inv_alpha, xi, mul_rn(a.neg_sigma_over_alpha, e));
+        if (a.eu) e = cfg_combine_rn(e, a.eu[i], a.cfg);
+        const float m0 = axpby_rn(a.inv_alpha, xi, a.neg_sigma_over_alpha, e);
         if (a.m0_out) a.m0_out[i] = m0;
-        float xn = __builtin_fmaf(a.c1, xi, mul_rn(a.cm0, m0));
-        if (a.kind == DPMPP_SECOND) xn = __builtin_fmaf(1.0f, xn, mul_rn(a.cm1, a.m1[i]));
+        float xn = axpby_rn(a.c1, xi, a.cm0, m0);
+        if (a.kind == DPMPP_SECOND) xn = axpby_rn(1.0f, xn, a.cm1, a.m1[i]);
         if (a.x_out) a.x_out[i] = xn;
         if (a.xin_a) a.xin_a[i] = xn;
         if (a.xin_b) a.xin_b[i] = xn;
@@ -388,16 +356,9 @@ int dpmpp_loop_step(const DpmppLoopStep& a, hipStream_t s) {
     return LAUNCH_OK();
 }
 
-// Adams-Bashforth combinations of plms.py:224-232; order = number of old eps available (1..3)
 __global__ void k_plms(const float* __restrict__ e, const float* __restrict__ e1, const float* __restrict__ e2,
                        const float* __restrict__ e3, int order, float* __restrict__ out, size_t n) {
-    EW_LOOP(i, n) {
-        float r;
-        if (order == 1) r = (3.f * e[i] - e1[i]) / 2.f;
-        else if (order == 2) r = (23.f * e[i] - 16.f * e1[i] + 5.f * e2[i]) / 12.f;
-        else r = (55.f * e[i] - 59.f * e1[i] + 37.f * e2[i] - 9.f * e3[i]) / 24.f;
-        out[i] = r;
-    }
+    EW_LOOP(i, n) out[i] = adams_bashforth_rn(order, e[i], e1, e2, e3, i);
 }
 int plms_combine(const float* e_t, const float* e1, const float* e2, const float* e3, int order, float* e_prime,
                  size_t n, hipStream_t s) {
@@ -408,7 +369,7 @@ int plms_combine(const float* e_t, const float* e1, const float* e2, const float
 
 __global__ void k_axpby(const float* __restrict__ a, float ca, const float* __restrict__ b, float cb,
                         float* __restrict__ y, size_t n) {
-    EW_LOOP(i, n) y[i] = ca * a[i] + (b ? cb * b[i] : 0.f);
+    EW_LOOP(i, n) y[i] = b ? axpby_rn(ca, a[i], cb, b[i]) : ca * a[i] + 0.f;
 }
 int axpby(const float* a, float ca, const float* b, float cb, float* y, size_t n, hipStream_t s) {
     FGDM_LAUNCH(k_axpby, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, s, a, ca, b, cb, y, n);
@@ -418,7 +379,7 @@ int axpby(const float* a, float ca, const float* b, float cb, float* y, size_t n
 // inpainting blend img_orig * mask + (1 - mask) * img (ddim.py:151-154, ddpm.py:1419-1421); mask pre-expanded
 __global__ void k_mask_blend(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ m,
                              float* __restrict__ y, size_t n) {
-    EW_LOOP(i, n) y[i] = a[i] * m[i] + (1.0f - m[i]) * b[i];
+    EW_LOOP(i, n) y[i] = mask_blend_rn(a[i], b[i], m[i]);
 }
 int mask_blend(const float* a, const float* b, const float* m, float* y, size_t n, hipStream_t s) {
     FGDM_LAUNCH(k_mask_blend, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, s, a, b, m, y, n);

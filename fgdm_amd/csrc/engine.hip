@@ -1872,115 +1872,9 @@ int fgdm_uint8_to_hint(const uint8_t* src, int B, int H, int W, int C, float* hi
     return u8_to_hint(src, hint, B, H * W, C, as_stream(stream));
 }
 
-// Host-side checks of fgdm_sample_ddim_ex, in front of any launch; nullptr: the parameters are consistent.
-static const char* ddim_params_error(const fgdm_ddim_params* p) {
-    if (p->reserved0 != 0) return "reserved0 must be 0";
-    if (!p->x || !p->cond || !p->timesteps || !p->alphas || !p->alphas_prev || !p->sqrt_one_minus_alphas) return "x, cond or a schedule table is NULL";
-    if (p->S <= 0 || p->B <= 0 || p->H <= 0 || p->W <= 0) return "S, B, H and W must be positive";
-    if (p->mask && (!p->x0 || !p->q_noise || !p->sqrt_alphas_cumprod_t || !p->sqrt_one_minus_alphas_cumprod_t))
-        return "mask needs x0, q_noise and q_sample's two coefficient tables";
-    if (p->sigmas && !p->step_noise)
-        for (int k = 0; k < p->S; ++k)
-            if (p->sigmas[k] != 0.f) return "a sigma is not 0 and step_noise is NULL";
-    if (p->n_log < 0 || (p->n_log > 0 && !p->log_steps)) return "n_log < 0, or log steps without log_steps";
-    for (int j = 0; j < p->n_log; ++j)
-        if (p->log_steps[j] < 0 || p->log_steps[j] >= p->S || (j > 0 && p->log_steps[j] <= p->log_steps[j - 1]))
-            return "log_steps must be strictly ascending walk positions in [0, S)";
-    return nullptr;
-}
-
-int fgdm_sample_ddim_ex(fgdm_engine* e, const fgdm_ddim_params* caller, void* stream) {
-    if (!e || !caller) return FGDM_ERR_ARG;
-    // The caller's struct may be any version this library knows: at least the first one, at most this one; the fields its
-    // version did not have yet read as zero (absent).  A larger size holds fields this library cannot honour.
-    const int64_t size = caller->struct_size;
-    if (size < FGDM_DDIM_PARAMS_SIZE_V1 || size > (int64_t)sizeof(fgdm_ddim_params))
-        return e->fail(FGDM_ERR_ARG, "fgdm_sample_ddim_ex: struct_size is not the sizeof(fgdm_ddim_params) of a known header version");
-    fgdm_ddim_params known{};
-    memcpy(&known, caller, (size_t)size);
-    const fgdm_ddim_params* p = &known;
-    if (const char* why = ddim_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_ddim_ex: ") + why);
-    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
-    hipStream_t s = as_stream(stream);
-    return scoped_call(e, stream, [&]() -> int {
-    const int S = p->S, B = p->B, H = p->H, W = p->W;
-    bool cfg_on = false;      // one decision for the whole walk: the registered context has Bm rows
-    if (p->uncond)
-        for (int i = 0; i < S && !cfg_on; ++i) cfg_on = (p->cfg_scales ? p->cfg_scales[i] : p->cfg_scale) != 1.0f;
-    const int Bm = cfg_on ? 2 * B : B;
-    const size_t n = (size_t)B * 4 * H * W, nctx = (size_t)B * e->ctx_tokens * e->cfg.context_dim;
-    float* x = p->x;
-    float* x2 = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
-    float* eps = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
-    float* c2 = (float*)e->arena.alloc(Bm * (size_t)e->ctx_tokens * e->cfg.context_dim * sizeof(float));
-    int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * Bm * sizeof(int64_t));
-    if (!x2 || !eps || !c2 || !tdev) return e->fail(FGDM_ERR_NOMEM, "workspace");
-    std::vector<int64_t> th((size_t)S * Bm);
-    for (int i = 0; i < S; ++i) for (int b = 0; b < Bm; ++b) th[(size_t)i * Bm + b] = p->timesteps[i];
-    HIP_TRY(hipMemcpyAsync(tdev, th.data(), th.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));   // th is a local: the copy must finish before it goes out of scope
-    if (cfg_on) {   // c_in = cat([uncond, cond])  (ddim.py:226)
-        HIP_TRY(hipMemcpyAsync(c2, p->uncond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c2 + nctx, p->cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
-    } else {
-        HIP_TRY(hipMemcpyAsync(c2, p->cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    int rc = e->set_context(c2, Bm);   // the conditioning is loop-invariant: project it once, pass ctx = NULL below
-    // the blend in front of step `i` (index k = S - 1 - i), done by the kernel of the step before it
-    auto blend = [&](DdimLoopStep& a, int i) {
-        if (!p->mask) return;
-        const int k = S - 1 - i;
-        a.mask = p->mask; a.x0 = p->x0; a.qnoise = p->q_noise + (size_t)i * n;
-        a.sa_next = p->sqrt_alphas_cumprod_t[k]; a.s1m_next = p->sqrt_one_minus_alphas_cumprod_t[k];
-    };
-    if (rc == FGDM_OK) {                // in front of the first step: its blend, and x into the network's input
-        DdimLoopStep a{};
-        a.x = x; a.n = n; a.xin_a = x2; a.xin_b = cfg_on ? x2 + n : nullptr;
-        blend(a, 0);
-        a.x_out = p->mask ? x : nullptr;
-        rc = ddim_loop_step(a, s);
-    }
-    int logged = 0;
-    for (int i = 0; i < S && rc == FGDM_OK; ++i) {
-        const int index = S - 1 - i;   // reversed walk (ddim.py:137,148)
-        rc = e->apply_model(x2, tdev + (size_t)index * Bm, nullptr, nullptr, nullptr, p->control_scales, Bm, H, W, p->flags, eps);
-        if (rc != FGDM_OK) break;
-        DdimLoopStep a{};
-        a.x = x; a.n = n; a.ec = cfg_on ? eps + n : eps; a.eu = cfg_on ? eps : nullptr;
-        a.cfg = p->cfg_scales ? p->cfg_scales[i] : p->cfg_scale;
-        a.a_t = p->alphas[index]; a.a_prev = p->alphas_prev[index]; a.s1m = p->sqrt_one_minus_alphas[index];
-        a.sigma = p->sigmas ? p->sigmas[index] : 0.f;
-        a.noise = a.sigma != 0.f ? p->step_noise + (size_t)i * n : nullptr;
-        a.x_out = x;
-        if (i + 1 < S) { blend(a, i + 1); a.xin_a = x2; a.xin_b = cfg_on ? x2 + n : nullptr; }
-        if (logged < p->n_log && p->log_steps[logged] == i) {
-            a.log_x = p->x_inter_out ? p->x_inter_out + (size_t)logged * n : nullptr;
-            a.log_p0 = p->pred_x0_out ? p->pred_x0_out + (size_t)logged * n : nullptr;
-            ++logged;
-        }
-        rc = ddim_loop_step(a, s);
-    }
-    e->arena.release(x2); e->arena.release(eps); e->arena.release(c2); e->arena.release(tdev);
-    return rc;
-    });
-}
-
-int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* uncond, float cfg_scale, int S,
-                     const int64_t* timesteps, const float* alphas, const float* alphas_prev,
-                     const float* sqrt_one_minus_alphas, const float* control_scales, int B, int H, int W, int flags,
-                     void* stream) {
-    if (!e || !x || !cond || !timesteps || !alphas || !alphas_prev || !sqrt_one_minus_alphas || S <= 0) return FGDM_ERR_ARG;
-    fgdm_ddim_params p{};
-    p.struct_size = sizeof(p);
-    p.x = x; p.cond = cond; p.uncond = uncond; p.cfg_scale = cfg_scale; p.S = S; p.timesteps = timesteps;
-    p.alphas = alphas; p.alphas_prev = alphas_prev; p.sqrt_one_minus_alphas = sqrt_one_minus_alphas;
-    p.control_scales = control_scales; p.B = B; p.H = H; p.W = W; p.flags = flags;
-    return fgdm_sample_ddim_ex(e, &p, stream);
-}
-
-// ---- the two multistep loops (fgdm_sample_plms, fgdm_sample_dpmpp)
-// The caller's struct in the library's layout, as fgdm_sample_ddim_ex reads its own: every size from the first version up to this
-// library's sizeof is accepted and the fields a shorter struct lacks read as zero.  false: a size this library does not know.
+// ---- the device sampler loops (fgdm_sample_ddim_ex, fgdm_sample_plms, fgdm_sample_dpmpp)
+// The caller's struct in the library's layout.  It may be any version this library knows: at least the first one, at most this
+// one; the fields its version did not have yet read as zero (absent).  false: a larger size holds fields this library cannot honour.
 static bool read_params(const void* caller, int64_t size_v1, void* known, size_t size_lib) {
     int64_t size;
     memcpy(&size, caller, sizeof(size));      // struct_size leads every parameter struct
@@ -1990,8 +1884,8 @@ static bool read_params(const void* caller, int64_t size_v1, void* known, size_t
     return true;
 }
 
-// What both loops hold while they run: the network's input (Bm rows), its output, and the loop-invariant context
-// cat([uncond, cond]) (ddim.py:226), registered once so that every evaluation passes ctx = NULL.
+// What every loop holds while it runs: the network's input (Bm rows), its output, and the loop-invariant context
+// cat([uncond, cond]) (ddim.py:226), registered (projected) once so that every evaluation passes ctx = NULL.
 struct LoopWork {
     float *x2 = nullptr, *eps = nullptr, *c2 = nullptr;
     int Bm = 0;
@@ -2016,18 +1910,159 @@ static int loop_begin(fgdm_engine* e, const float* cond, const float* uncond, bo
 static void loop_end(fgdm_engine* e, LoopWork* w) {
     e->arena.release(w->x2); e->arena.release(w->eps); e->arena.release(w->c2);
 }
+// The network's time argument of every evaluation: host entry k, Bm times, at dev[k * Bm].
+extern "C++" template <typename T> static int upload_repeated(const T* host, int count, int Bm, T* dev, hipStream_t s) {
+    std::vector<T> th((size_t)count * Bm);
+    for (int k = 0; k < count; ++k) for (int b = 0; b < Bm; ++b) th[(size_t)k * Bm + b] = host[k];
+    HIP_TRY(hipMemcpyAsync(dev, th.data(), th.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));   // th is a local: the copy must finish before it goes out of scope
+    return FGDM_OK;
+}
 
-static const char* plms_params_error(const fgdm_plms_params* p) {
-    if (p->reserved0 != 0) return "reserved0 must be 0";
-    if (!p->x || !p->cond || !p->timesteps || !p->alphas || !p->alphas_prev || !p->sqrt_one_minus_alphas) return "x, cond or a schedule table is NULL";
-    if (p->S <= 0 || p->B <= 0 || p->H <= 0 || p->W <= 0) return "S, B, H and W must be positive";
-    if (p->mask && (!p->x0 || !p->q_noise || !p->sqrt_alphas_cumprod_t || !p->sqrt_one_minus_alphas_cumprod_t))
+// A walk of the DDIM family, as fgdm_sample_ddim_ex and fgdm_sample_plms fill it from their public structs: the fields the two
+// share by name (walk_from), the DDIM entry's sigmas / step_noise / cfg_scales (NULL: absent), and what the entry has resolved:
+// cfg_on (one decision for the whole walk: the registered context has Bm rows), the flags of every evaluation, and `plms`.
+struct Walk {
+    float* x;
+    const float *cond, *uncond;
+    const int64_t* timesteps;
+    const float *alphas, *alphas_prev, *sqrt_one_minus_alphas, *control_scales;
+    const float *sigmas, *step_noise, *cfg_scales;
+    const float *mask, *x0, *q_noise, *sqrt_alphas_cumprod_t, *sqrt_one_minus_alphas_cumprod_t;
+    const int32_t* log_steps;
+    float *x_inter_out, *pred_x0_out;
+    float cfg_scale;
+    int S, B, H, W, flags, n_log, reserved0;
+    bool cfg_on, plms;
+};
+extern "C++" template <typename P> static Walk walk_from(const P& p) {
+    Walk w{};
+    w.x = p.x; w.cond = p.cond; w.uncond = p.uncond; w.timesteps = p.timesteps;
+    w.alphas = p.alphas; w.alphas_prev = p.alphas_prev; w.sqrt_one_minus_alphas = p.sqrt_one_minus_alphas;
+    w.control_scales = p.control_scales;
+    w.mask = p.mask; w.x0 = p.x0; w.q_noise = p.q_noise;
+    w.sqrt_alphas_cumprod_t = p.sqrt_alphas_cumprod_t; w.sqrt_one_minus_alphas_cumprod_t = p.sqrt_one_minus_alphas_cumprod_t;
+    w.log_steps = p.log_steps; w.x_inter_out = p.x_inter_out; w.pred_x0_out = p.pred_x0_out;
+    w.cfg_scale = p.cfg_scale; w.S = p.S; w.B = p.B; w.H = p.H; w.W = p.W; w.flags = p.flags; w.n_log = p.n_log;
+    w.reserved0 = p.reserved0;
+    return w;
+}
+// Host-side checks of a walk, in front of any launch; nullptr: the parameters are consistent.
+static const char* walk_error(const Walk& p) {
+    if (p.reserved0 != 0) return "reserved0 must be 0";
+    if (!p.x || !p.cond || !p.timesteps || !p.alphas || !p.alphas_prev || !p.sqrt_one_minus_alphas) return "x, cond or a schedule table is NULL";
+    if (p.S <= 0 || p.B <= 0 || p.H <= 0 || p.W <= 0) return "S, B, H and W must be positive";
+    if (p.mask && (!p.x0 || !p.q_noise || !p.sqrt_alphas_cumprod_t || !p.sqrt_one_minus_alphas_cumprod_t))
         return "mask needs x0, q_noise and q_sample's two coefficient tables";
-    if (p->n_log < 0 || (p->n_log > 0 && !p->log_steps)) return "n_log < 0, or log steps without log_steps";
-    for (int j = 0; j < p->n_log; ++j)
-        if (p->log_steps[j] < 0 || p->log_steps[j] >= p->S || (j > 0 && p->log_steps[j] <= p->log_steps[j - 1]))
+    if (p.sigmas && !p.step_noise)
+        for (int k = 0; k < p.S; ++k)
+            if (p.sigmas[k] != 0.f) return "a sigma is not 0 and step_noise is NULL";
+    if (p.n_log < 0 || (p.n_log > 0 && !p.log_steps)) return "n_log < 0, or log steps without log_steps";
+    for (int j = 0; j < p.n_log; ++j)
+        if (p.log_steps[j] < 0 || p.log_steps[j] >= p.S || (j > 0 && p.log_steps[j] <= p.log_steps[j - 1]))
             return "log_steps must be strictly ascending walk positions in [0, S)";
     return nullptr;
+}
+
+// The walk itself (inside the entry's scoped_call): per step one evaluation of the network on cat([x] * 2) (or x, CFG off), then
+// one launch of k_loop_step, which also does the NEXT step's blend and writes x into the network's input.  PLMS (plms.py:178-236)
+// differs in the three history planes, the probe and the second evaluation of the first step, and the mode / order of the launch.
+static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
+    const int S = p.S, H = p.H, W = p.W;
+    const bool cfg_on = p.cfg_on;
+    LoopWork w;
+    int rc = loop_begin(e, p.cond, p.uncond, cfg_on, p.B, H, W, s, &w);
+    const int Bm = w.Bm;
+    const size_t n = w.n;
+    float* x = p.x;
+    float* hist = p.plms ? (float*)e->arena.alloc(3 * n * sizeof(float)) : nullptr;      // e_t of step j lives in plane j % 3
+    int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * Bm * sizeof(int64_t));
+    if (rc == FGDM_OK && (!tdev || (p.plms && !hist))) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
+    if (rc != FGDM_OK) return rc;
+    CHK(upload_repeated(p.timesteps, S, Bm, tdev, s));
+    auto plane = [&](int step) { return hist + (size_t)(step % 3) * n; };
+    // the blend in front of step `i` (index k = S - 1 - i), done by the kernel of the step before it
+    auto blend = [&](LoopStep& a, int i) {
+        if (!p.mask) return;
+        const int k = S - 1 - i;
+        a.mask = p.mask; a.x0 = p.x0; a.qnoise = p.q_noise + (size_t)i * n;
+        a.sa_next = p.sqrt_alphas_cumprod_t[k]; a.s1m_next = p.sqrt_one_minus_alphas_cumprod_t[k];
+    };
+    auto inputs = [&](LoopStep& a) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; };
+    auto eval = [&](int index) {
+        return e->apply_model(w.x2, tdev + (size_t)index * Bm, nullptr, nullptr, nullptr, p.control_scales, Bm, H, W, p.flags, w.eps);
+    };
+    {                                   // in front of the first step: its blend, and x into the network's input
+        LoopStep a{};
+        a.x = x; a.n = n; inputs(a);
+        blend(a, 0);
+        a.x_out = p.mask ? x : nullptr;
+        rc = loop_step(a, s);
+    }
+    int logged = 0;
+    for (int i = 0; i < S && rc == FGDM_OK; ++i) {
+        const int index = S - 1 - i;   // reversed walk (ddim.py:137,148; plms.py:138,150)
+        rc = eval(index);
+        if (rc != FGDM_OK) break;
+        LoopStep a{};
+        a.x = x; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr;
+        a.cfg = p.cfg_scales ? p.cfg_scales[i] : p.cfg_scale;
+        a.a_t = p.alphas[index]; a.a_prev = p.alphas_prev[index]; a.s1m = p.sqrt_one_minus_alphas[index];
+        a.sigma = p.sigmas ? p.sigmas[index] : 0.f;
+        a.noise = a.sigma != 0.f ? p.step_noise + (size_t)i * n : nullptr;
+        if (!p.plms) {
+            a.mode = LOOP_PLAIN;
+        } else if (i == 0) {            // pseudo improved Euler (plms.py:219-223): probe, second evaluation at t_next, finish
+            LoopStep probe = a;
+            probe.mode = LOOP_PROBE; probe.e_out = plane(0); inputs(probe);
+            rc = loop_step(probe, s);
+            if (rc == FGDM_OK) rc = eval(S >= 2 ? S - 2 : 0);
+            if (rc != FGDM_OK) break;
+            a.mode = LOOP_FINISH_FIRST; a.e1 = plane(0);
+        } else {                        // Adams-Bashforth over the last min(i, 3) planes (plms.py:224-232)
+            a.mode = LOOP_MULTISTEP; a.order = i < 3 ? i : 3;
+            a.e_out = plane(i); a.e1 = plane(i - 1);
+            if (i >= 2) a.e2 = plane(i - 2);
+            if (i >= 3) a.e3 = plane(i - 3);      // the plane e_out replaces
+        }
+        a.x_out = x;
+        if (i + 1 < S) { blend(a, i + 1); inputs(a); }
+        if (logged < p.n_log && p.log_steps[logged] == i) {
+            a.log_x = p.x_inter_out ? p.x_inter_out + (size_t)logged * n : nullptr;
+            a.log_p0 = p.pred_x0_out ? p.pred_x0_out + (size_t)logged * n : nullptr;
+            ++logged;
+        }
+        rc = loop_step(a, s);
+    }
+    loop_end(e, &w); e->arena.release(hist); e->arena.release(tdev);
+    return rc;
+}
+
+int fgdm_sample_ddim_ex(fgdm_engine* e, const fgdm_ddim_params* caller, void* stream) {
+    if (!e || !caller) return FGDM_ERR_ARG;
+    fgdm_ddim_params known;
+    if (!read_params(caller, FGDM_DDIM_PARAMS_SIZE_V1, &known, sizeof(known)))
+        return e->fail(FGDM_ERR_ARG, "fgdm_sample_ddim_ex: struct_size is not the sizeof(fgdm_ddim_params) of a known header version");
+    Walk p = walk_from(known);
+    p.sigmas = known.sigmas; p.step_noise = known.step_noise; p.cfg_scales = known.cfg_scales;
+    if (const char* why = walk_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_ddim_ex: ") + why);
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    if (p.uncond)                       // CFG is on when any step's scale is not 1; the flags go to the network as given
+        for (int i = 0; i < p.S && !p.cfg_on; ++i) p.cfg_on = (p.cfg_scales ? p.cfg_scales[i] : p.cfg_scale) != 1.0f;
+    return scoped_call(e, stream, [&] { return run_walk(e, p, as_stream(stream)); });
+}
+
+int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* uncond, float cfg_scale, int S,
+                     const int64_t* timesteps, const float* alphas, const float* alphas_prev,
+                     const float* sqrt_one_minus_alphas, const float* control_scales, int B, int H, int W, int flags,
+                     void* stream) {
+    if (!e || !x || !cond || !timesteps || !alphas || !alphas_prev || !sqrt_one_minus_alphas || S <= 0) return FGDM_ERR_ARG;
+    fgdm_ddim_params p{};
+    p.struct_size = sizeof(p);
+    p.x = x; p.cond = cond; p.uncond = uncond; p.cfg_scale = cfg_scale; p.S = S; p.timesteps = timesteps;
+    p.alphas = alphas; p.alphas_prev = alphas_prev; p.sqrt_one_minus_alphas = sqrt_one_minus_alphas;
+    p.control_scales = control_scales; p.B = B; p.H = H; p.W = W; p.flags = flags;
+    return fgdm_sample_ddim_ex(e, &p, stream);
 }
 
 int fgdm_sample_plms(fgdm_engine* e, const fgdm_plms_params* caller, void* stream) {
@@ -2035,80 +2070,14 @@ int fgdm_sample_plms(fgdm_engine* e, const fgdm_plms_params* caller, void* strea
     fgdm_plms_params known;
     if (!read_params(caller, FGDM_PLMS_PARAMS_SIZE_V1, &known, sizeof(known)))
         return e->fail(FGDM_ERR_ARG, "fgdm_sample_plms: struct_size is not the sizeof(fgdm_plms_params) of a known header version");
-    const fgdm_plms_params* p = &known;
-    if (const char* why = plms_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_plms: ") + why);
+    Walk p = walk_from(known);
+    if (const char* why = walk_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_plms: ") + why);
     if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_sample_plms: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
     if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
-    hipStream_t s = as_stream(stream);
-    return scoped_call(e, stream, [&]() -> int {
-    const int S = p->S, B = p->B, H = p->H, W = p->W;
-    const bool cfg_on = p->uncond && p->cfg_scale != 1.0f;
-    const int flags = cfg_on ? p->flags | FGDM_FLAG_CFG_PAIRS : p->flags & ~FGDM_FLAG_CFG_PAIRS;
-    LoopWork w;
-    int rc = loop_begin(e, p->cond, p->uncond, cfg_on, B, H, W, s, &w);
-    const int Bm = w.Bm;
-    const size_t n = w.n;
-    float* x = p->x;
-    float* hist = (float*)e->arena.alloc(3 * n * sizeof(float));      // e_t of step j lives in plane j % 3
-    int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * Bm * sizeof(int64_t));
-    if (rc == FGDM_OK && (!hist || !tdev)) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
-    if (rc != FGDM_OK) return rc;
-    std::vector<int64_t> th((size_t)S * Bm);
-    for (int i = 0; i < S; ++i) for (int b = 0; b < Bm; ++b) th[(size_t)i * Bm + b] = p->timesteps[i];
-    HIP_TRY(hipMemcpyAsync(tdev, th.data(), th.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));   // th is a local: the copy must finish before it goes out of scope
-    auto plane = [&](int step) { return hist + (size_t)(step % 3) * n; };
-    // the blend in front of step `i` (index k = S - 1 - i), done by the kernel of the step before it
-    auto blend = [&](PlmsLoopStep& a, int i) {
-        if (!p->mask) return;
-        const int k = S - 1 - i;
-        a.mask = p->mask; a.x0 = p->x0; a.qnoise = p->q_noise + (size_t)i * n;
-        a.sa_next = p->sqrt_alphas_cumprod_t[k]; a.s1m_next = p->sqrt_one_minus_alphas_cumprod_t[k];
-    };
-    auto inputs = [&](PlmsLoopStep& a) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; };
-    auto eval = [&](int index) {
-        return e->apply_model(w.x2, tdev + (size_t)index * Bm, nullptr, nullptr, nullptr, p->control_scales, Bm, H, W, flags, w.eps);
-    };
-    {                                   // in front of the first step: its blend, and x into the network's input
-        PlmsLoopStep a{};
-        a.x = x; a.n = n; inputs(a);
-        blend(a, 0);
-        a.x_out = p->mask ? x : nullptr;
-        rc = plms_loop_step(a, s);
-    }
-    int logged = 0;
-    for (int i = 0; i < S && rc == FGDM_OK; ++i) {
-        const int index = S - 1 - i;   // reversed walk (plms.py:138,150)
-        rc = eval(index);
-        if (rc != FGDM_OK) break;
-        PlmsLoopStep a{};
-        a.x = x; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr; a.cfg = p->cfg_scale;
-        a.a_t = p->alphas[index]; a.a_prev = p->alphas_prev[index]; a.s1m = p->sqrt_one_minus_alphas[index];
-        if (i == 0) {                   // pseudo improved Euler (plms.py:219-223): probe, second evaluation at t_next, finish
-            PlmsLoopStep probe = a;
-            probe.mode = PLMS_PROBE; probe.e_out = plane(0); inputs(probe);
-            rc = plms_loop_step(probe, s);
-            if (rc == FGDM_OK) rc = eval(S >= 2 ? S - 2 : 0);
-            if (rc != FGDM_OK) break;
-            a.mode = PLMS_FINISH_FIRST; a.e1 = plane(0);
-        } else {                        // Adams-Bashforth over the last min(i, 3) planes (plms.py:224-232)
-            a.mode = PLMS_MULTISTEP; a.order = i < 3 ? i : 3;
-            a.e_out = plane(i); a.e1 = plane(i - 1);
-            if (i >= 2) a.e2 = plane(i - 2);
-            if (i >= 3) a.e3 = plane(i - 3);      // the plane e_out replaces
-        }
-        a.x_out = x;
-        if (i + 1 < S) { blend(a, i + 1); inputs(a); }
-        if (logged < p->n_log && p->log_steps[logged] == i) {
-            a.log_x = p->x_inter_out ? p->x_inter_out + (size_t)logged * n : nullptr;
-            a.log_p0 = p->pred_x0_out ? p->pred_x0_out + (size_t)logged * n : nullptr;
-            ++logged;
-        }
-        rc = plms_loop_step(a, s);
-    }
-    loop_end(e, &w); e->arena.release(hist); e->arena.release(tdev);
-    return rc;
-    });
+    p.plms = true;
+    p.cfg_on = p.uncond && p.cfg_scale != 1.0f;
+    p.flags = p.cfg_on ? p.flags | FGDM_FLAG_CFG_PAIRS : p.flags & ~FGDM_FLAG_CFG_PAIRS;
+    return scoped_call(e, stream, [&] { return run_walk(e, p, as_stream(stream)); });
 }
 
 static const char* dpmpp_params_error(const fgdm_dpmpp_params* p) {
@@ -2146,10 +2115,7 @@ int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* caller, void* str
     float* tdev = (float*)e->arena.alloc((size_t)K * Bm * sizeof(float));
     if (rc == FGDM_OK && (!m || !tdev)) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
     if (rc != FGDM_OK) return rc;
-    std::vector<float> th((size_t)K * Bm);
-    for (int k = 0; k < K; ++k) for (int b = 0; b < Bm; ++b) th[(size_t)k * Bm + b] = p->t_float[k];
-    HIP_TRY(hipMemcpyAsync(tdev, th.data(), th.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));   // th is a local: the copy must finish before it goes out of scope
+    CHK(upload_repeated(p->t_float, K, Bm, tdev, s));
     HIP_TRY(hipMemcpyAsync(w.x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));      // x_T into the network's input, once
     if (cfg_on) HIP_TRY(hipMemcpyAsync(w.x2 + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     for (int k = 0; k < K && rc == FGDM_OK; ++k) {

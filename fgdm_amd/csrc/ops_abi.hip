@@ -323,12 +323,12 @@ int fgdm_op_ddim_loop_step(const float* x, const float* e_cond, const float* e_u
                            const float* q_noise, float sqrt_ac_next, float sqrt_one_minus_ac_next, float* x_out, float* xin_a,
                            float* xin_b, float* log_x, float* log_pred_x0, int64_t n, void* stream) {
     if (!x || n <= 0 || (e_uncond && !e_cond) || (mask && (!x0 || !q_noise))) return FGDM_ERR_ARG;
-    DdimLoopStep a{};
+    LoopStep a{};
     a.x = x; a.ec = e_cond; a.eu = e_uncond; a.noise = noise; a.mask = mask; a.x0 = x0; a.qnoise = q_noise;
     a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.log_x = log_x; a.log_p0 = log_pred_x0;
     a.cfg = cfg_scale; a.a_t = a_t; a.a_prev = a_prev; a.sigma = sigma_t; a.s1m = sqrt_one_minus_at;
-    a.sa_next = sqrt_ac_next; a.s1m_next = sqrt_one_minus_ac_next; a.n = (size_t)n;
-    return ddim_loop_step(a, as_stream(stream));
+    a.sa_next = sqrt_ac_next; a.s1m_next = sqrt_one_minus_ac_next; a.mode = LOOP_PLAIN; a.n = (size_t)n;
+    return loop_step(a, as_stream(stream));
 }
 
 // Diagnostic entries of tests/test_gpu_multistep_loop.py: one launch of the device PLMS / DPM-Solver++ loop's step kernel on
@@ -338,13 +338,13 @@ int fgdm_op_plms_loop_step(const float* x, const float* e_cond, const float* e_u
                            float sqrt_one_minus_at, const float* mask, const float* x0, const float* q_noise, float sqrt_ac_next,
                            float sqrt_one_minus_ac_next, float* x_out, float* xin_a, float* xin_b, float* log_x, float* log_pred_x0,
                            int64_t n, void* stream) {
-    if (n <= 0) return FGDM_ERR_ARG;
-    PlmsLoopStep a{};
+    if (n <= 0 || (e_cond && mode == LOOP_PLAIN)) return FGDM_ERR_ARG;      // the plain (DDIM) mode is no mode of this entry
+    LoopStep a{};
     a.x = x; a.ec = e_cond; a.eu = e_uncond; a.e1 = e1; a.e2 = e2; a.e3 = e3; a.mask = mask; a.x0 = x0; a.qnoise = q_noise;
     a.e_out = e_out; a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.log_x = log_x; a.log_p0 = log_pred_x0;
     a.cfg = cfg_scale; a.a_t = a_t; a.a_prev = a_prev; a.s1m = sqrt_one_minus_at; a.sa_next = sqrt_ac_next;
     a.s1m_next = sqrt_one_minus_ac_next; a.mode = mode; a.order = order; a.n = (size_t)n;
-    return plms_loop_step(a, as_stream(stream));
+    return loop_step(a, as_stream(stream));
 }
 
 int fgdm_op_dpmpp_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float inv_alpha,

@@ -522,52 +522,12 @@ class Engine:
         sample_ddim's; cfg_scales [S], step_noise / q_noise [S, B,4,H,W] and log_steps in WALK order (slot i: the i-th step that
         runs).  Returns (x, x_inter, pred_x0): the final latent and the two [len(log_steps), B,4,H,W] intermediates (None without
         log steps).  x_T is not modified; out / x_inter_out / pred_x0_out: caller-owned device buffers to use instead of new ones."""
-        dev = lambda v: None if v is None else v.to(self.device, torch.float32).contiguous()
-        x = x_T.to(self.device, torch.float32).clone().contiguous() if out is None else out.copy_(x_T)
-        cond, uncond = dev(cond), dev(uncond)
-        if uncond is not None and tuple(uncond.shape) != tuple(cond.shape):      # one cat([uncond, cond]) batch (ddim.py:222-226)
-            raise ValueError(f'sample_ddim_ex: cond {tuple(cond.shape)} and uncond {tuple(uncond.shape)} must agree')
-        self.set_context_tokens(cond.shape[1])
-        B, _, H, W = x.shape
-        S, n_log = len(timesteps), len(log_steps)
-        step_noise, q_noise, mask, x0 = dev(step_noise), dev(q_noise), dev(mask), dev(x0)
-        for name, v, shape in (('step_noise', step_noise, (S, *x.shape)), ('q_noise', q_noise, (S, *x.shape)),
-                               ('mask', mask, tuple(x.shape)), ('x0', x0, tuple(x.shape))):
-            if v is not None and tuple(v.shape) != tuple(shape):
-                raise ValueError(f'sample_ddim_ex: {name} {tuple(v.shape)} must be {tuple(shape)}')
-        keep = []      # host arrays the struct points into
-
-        def table(a, ctype=C.c_float, conv=float, count=S):
-            if a is None:
-                return None
-            if len(a) != count:
-                raise ValueError(f'sample_ddim_ex: a table of {len(a)} entries where {count} are needed')
-            keep.append((ctype * count)(*[conv(v) for v in a]))
-            return C.cast(keep[-1], C.c_void_p)
-
-        if n_log:
-            x_inter = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if x_inter_out is None else x_inter_out
-            pred_x0 = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if pred_x0_out is None else pred_x0_out
-        else:
-            x_inter = pred_x0 = None
-        p = _lib.FgdmDdimParams()
-        p.struct_size = C.sizeof(p)
-        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
-        p.timesteps = table(timesteps, C.c_int64, int)
-        p.alphas, p.alphas_prev, p.sqrt_one_minus_alphas = table(alphas), table(alphas_prev), table(sqrt_one_minus_alphas)
-        p.sigmas, p.cfg_scales = table(sigmas), table(cfg_scales)
-        p.sqrt_alphas_cumprod_t, p.sqrt_one_minus_alphas_cumprod_t = table(sqrt_alphas_cumprod_t), table(sqrt_one_minus_alphas_cumprod_t)
-        if control_scales is not None:
-            keep.append(np.asarray(control_scales, dtype=np.float32).ravel().copy())
-            p.control_scales = keep[-1].ctypes.data_as(C.c_void_p)
-        p.step_noise, p.mask, p.x0, p.q_noise = _ptr(step_noise), _ptr(mask), _ptr(x0), _ptr(q_noise)
-        p.log_steps = table(log_steps, C.c_int32, int, n_log) if n_log else None
-        p.x_inter_out, p.pred_x0_out = _ptr(x_inter), _ptr(pred_x0)
-        p.cfg_scale, p.S, p.B, p.H, p.W, p.flags, p.n_log = float(cfg_scale), S, B, H, W, int(flags), n_log
-        rc = self.lib.fgdm_sample_ddim_ex(self.h, C.byref(p), _stream())
-        self._ctx_policy = ContextCachePolicy()      # the device-side loop registered its own context
-        self._check(rc, 'fgdm_sample_ddim_ex')
-        return x, x_inter, pred_x0
+        return self._sample_walk('sample_ddim_ex', _lib.FgdmDdimParams(), x_T, cond, uncond, cfg_scale,
+                                 dict(timesteps=timesteps, alphas=alphas, alphas_prev=alphas_prev, sqrt_one_minus_alphas=sqrt_one_minus_alphas,
+                                      sigmas=sigmas, cfg_scales=cfg_scales, sqrt_alphas_cumprod_t=sqrt_alphas_cumprod_t,
+                                      sqrt_one_minus_alphas_cumprod_t=sqrt_one_minus_alphas_cumprod_t),
+                                 dict(step_noise=step_noise, q_noise=q_noise), mask, x0, log_steps, control_scales, flags, out,
+                                 x_inter_out, pred_x0_out)
 
     def _loop_args(self, name, x_T, cond, uncond, out):
         """the state and the conditionings of a device loop on the engine's device, as sample_ddim_ex prepares them"""
@@ -589,43 +549,54 @@ class Engine:
         keep.append((ctype * count)(*[conv(v) for v in a]))
         return C.cast(keep[-1], C.c_void_p)
 
+    def _run_loop(self, name, p, keep, control_scales):
+        """control_scales into the parameter struct `p`, then the native loop fgdm_<name>; `keep` holds host arrays while it runs"""
+        p.struct_size = C.sizeof(p)
+        if control_scales is not None:
+            keep.append(np.asarray(control_scales, dtype=np.float32).ravel().copy())
+            p.control_scales = keep[-1].ctypes.data_as(C.c_void_p)
+        rc = getattr(self.lib, 'fgdm_' + name)(self.h, C.byref(p), _stream())
+        self._ctx_policy = ContextCachePolicy()      # the device-side loop registered its own context
+        self._check(rc, 'fgdm_' + name)
+
+    def _sample_walk(self, name, p, x_T, cond, uncond, cfg_scale, tables, step_tensors, mask, x0, log_steps, control_scales, flags,
+                     out, x_inter_out, pred_x0_out):
+        """sample_ddim_ex / sample_plms: the fields their two structs share by name.  tables: field -> S-entry host table (None:
+        absent), `timesteps` among them; step_tensors: field -> [S, B,4,H,W] tensor or None."""
+        x, cond, uncond = self._loop_args(name, x_T, cond, uncond, out)
+        dev = lambda v: None if v is None else v.to(self.device, torch.float32).contiguous()
+        B, _, H, W = x.shape
+        S, n_log = len(tables['timesteps']), len(log_steps)
+        tensors = {k: (dev(v), (S, *x.shape)) for k, v in step_tensors.items()}
+        tensors.update(mask=(dev(mask), tuple(x.shape)), x0=(dev(x0), tuple(x.shape)))
+        for k, (v, shape) in tensors.items():
+            if v is not None and tuple(v.shape) != tuple(shape):
+                raise ValueError(f'{name}: {k} {tuple(v.shape)} must be {tuple(shape)}')
+            setattr(p, k, _ptr(v))
+        keep = []      # host arrays the struct points into
+        for k, a in tables.items():
+            setattr(p, k, self._table(name, keep, a, S, *((C.c_int64, int) if k == 'timesteps' else ())))
+        if n_log:
+            x_inter = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if x_inter_out is None else x_inter_out
+            pred_x0 = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if pred_x0_out is None else pred_x0_out
+            p.log_steps = self._table(name, keep, log_steps, n_log, C.c_int32, int)
+        else:
+            x_inter = pred_x0 = None
+        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
+        p.x_inter_out, p.pred_x0_out = _ptr(x_inter), _ptr(pred_x0)
+        p.cfg_scale, p.S, p.B, p.H, p.W, p.flags, p.n_log = float(cfg_scale), S, B, H, W, int(flags), n_log
+        self._run_loop(name, p, keep, control_scales)
+        return x, x_inter, pred_x0
+
     def sample_plms(self, x_T, cond, uncond, cfg_scale, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, mask=None, x0=None,
                     q_noise=None, sqrt_alphas_cumprod_t=None, sqrt_one_minus_alphas_cumprod_t=None, log_steps=(),
                     control_scales=None, flags=0, out=None, x_inter_out=None, pred_x0_out=None):
         """The whole PLMS loop on the device (fgdm_sample_plms, include/fgdm.h): the S-entry tables in ddim_timesteps order,
         q_noise [S, B,4,H,W] and log_steps in WALK order, as for sample_ddim_ex.  Returns (x, x_inter, pred_x0)."""
-        x, cond, uncond = self._loop_args('sample_plms', x_T, cond, uncond, out)
-        dev = lambda v: None if v is None else v.to(self.device, torch.float32).contiguous()
-        B, _, H, W = x.shape
-        S, n_log = len(timesteps), len(log_steps)
-        q_noise, mask, x0 = dev(q_noise), dev(mask), dev(x0)
-        for name, v, shape in (('q_noise', q_noise, (S, *x.shape)), ('mask', mask, tuple(x.shape)), ('x0', x0, tuple(x.shape))):
-            if v is not None and tuple(v.shape) != tuple(shape):
-                raise ValueError(f'sample_plms: {name} {tuple(v.shape)} must be {tuple(shape)}')
-        keep = []      # host arrays the struct points into
-        table = lambda a, ctype=C.c_float, conv=float, count=S: self._table('sample_plms', keep, a, count, ctype, conv)
-        if n_log:
-            x_inter = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if x_inter_out is None else x_inter_out
-            pred_x0 = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if pred_x0_out is None else pred_x0_out
-        else:
-            x_inter = pred_x0 = None
-        p = _lib.FgdmPlmsParams()
-        p.struct_size = C.sizeof(p)
-        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
-        p.timesteps = table(timesteps, C.c_int64, int)
-        p.alphas, p.alphas_prev, p.sqrt_one_minus_alphas = table(alphas), table(alphas_prev), table(sqrt_one_minus_alphas)
-        p.sqrt_alphas_cumprod_t, p.sqrt_one_minus_alphas_cumprod_t = table(sqrt_alphas_cumprod_t), table(sqrt_one_minus_alphas_cumprod_t)
-        if control_scales is not None:
-            keep.append(np.asarray(control_scales, dtype=np.float32).ravel().copy())
-            p.control_scales = keep[-1].ctypes.data_as(C.c_void_p)
-        p.mask, p.x0, p.q_noise = _ptr(mask), _ptr(x0), _ptr(q_noise)
-        p.log_steps = table(log_steps, C.c_int32, int, n_log) if n_log else None
-        p.x_inter_out, p.pred_x0_out = _ptr(x_inter), _ptr(pred_x0)
-        p.cfg_scale, p.S, p.B, p.H, p.W, p.flags, p.n_log = float(cfg_scale), S, B, H, W, int(flags), n_log
-        rc = self.lib.fgdm_sample_plms(self.h, C.byref(p), _stream())
-        self._ctx_policy = ContextCachePolicy()      # the device-side loop registered its own context
-        self._check(rc, 'fgdm_sample_plms')
-        return x, x_inter, pred_x0
+        return self._sample_walk('sample_plms', _lib.FgdmPlmsParams(), x_T, cond, uncond, cfg_scale,
+                                 dict(timesteps=timesteps, alphas=alphas, alphas_prev=alphas_prev, sqrt_one_minus_alphas=sqrt_one_minus_alphas,
+                                      sqrt_alphas_cumprod_t=sqrt_alphas_cumprod_t, sqrt_one_minus_alphas_cumprod_t=sqrt_one_minus_alphas_cumprod_t),
+                                 dict(q_noise=q_noise), mask, x0, log_steps, control_scales, flags, out, x_inter_out, pred_x0_out)
 
     def sample_dpmpp(self, x_T, cond, uncond, cfg_scale, tables, control_scales=None, flags=0, out=None):
         """The whole DPM-Solver++ loop on the device (fgdm_sample_dpmpp, include/fgdm.h).  tables: a dict of equally long
@@ -636,18 +607,12 @@ class Engine:
         K = len(tables['t_float'])
         keep = []
         p = _lib.FgdmDpmppParams()
-        p.struct_size = C.sizeof(p)
         p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
         for name in ('t_float', 'inv_alpha', 'neg_sigma_over_alpha', 'c1', 'cm0', 'cm1'):
             setattr(p, name, self._table('sample_dpmpp', keep, tables[name], K))
         p.update_kind = self._table('sample_dpmpp', keep, tables['update_kind'], K, C.c_int32, int)
-        if control_scales is not None:
-            keep.append(np.asarray(control_scales, dtype=np.float32).ravel().copy())
-            p.control_scales = keep[-1].ctypes.data_as(C.c_void_p)
         p.cfg_scale, p.n_eval, p.B, p.H, p.W, p.flags = float(cfg_scale), K, B, H, W, int(flags)
-        rc = self.lib.fgdm_sample_dpmpp(self.h, C.byref(p), _stream())
-        self._ctx_policy = ContextCachePolicy()      # the device-side loop registered its own context
-        self._check(rc, 'fgdm_sample_dpmpp')
+        self._run_loop('sample_dpmpp', p, keep, control_scales)
         return x
 
 

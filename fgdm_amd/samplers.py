@@ -220,6 +220,15 @@ class _SamplerBase:
             return None
         return self._loop_cond(cond, uc, all(on))
 
+    def _mask_kw(self, mask, x0, qn, img, timesteps):
+        """the mask group of a device loop's arguments ({} without a mask); qn: q_sample's noise of every step, already drawn"""
+        if mask is None:
+            return {}
+        h = self.model._host
+        return dict(mask=mask.to(img.dtype).expand_as(img).contiguous(), x0=x0, q_noise=torch.stack(qn),
+                    sqrt_alphas_cumprod_t=[h['sqrt_alphas_cumprod'][int(t)] for t in timesteps],
+                    sqrt_one_minus_alphas_cumprod_t=[h['sqrt_one_minus_alphas_cumprod'][int(t)] for t in timesteps])
+
     @staticmethod
     def _log_steps(total_steps, log_every_t):
         """walk positions whose x_prev / pred_x0 the loops log: `index % log_every_t == 0 or index == total_steps - 1`"""
@@ -246,12 +255,7 @@ class DDIMSampler(_SamplerBase):
                 noise = noise * temperature
             if sigmas.any():
                 sn.append(noise)
-        kw = {}
-        if mask is not None:
-            h = self.model._host
-            kw = dict(mask=mask.to(img.dtype).expand_as(img).contiguous(), x0=x0, q_noise=torch.stack(qn),
-                      sqrt_alphas_cumprod_t=[h['sqrt_alphas_cumprod'][int(t)] for t in timesteps],
-                      sqrt_one_minus_alphas_cumprod_t=[h['sqrt_one_minus_alphas_cumprod'][int(t)] for t in timesteps])
+        kw = self._mask_kw(mask, x0, qn, img, timesteps)
         cfg_on = uctx is not None
         return self.model.engine.sample_ddim_ex(img, ctx, uctx, scales[0] if cfg_on else 1.0, [int(t) for t in timesteps], alphas,
                                                 alphas_prev, s1m, sigmas=sigmas, cfg_scales=scales if cfg_on else None,
@@ -407,12 +411,7 @@ class PLMSSampler(_SamplerBase):
                 qn.append(torch.randn_like(x0))                               # q_sample(x0, ts)
             for _ in range(2 if i == 0 else 1):
                 _randn(img.shape, img.device)
-        kw = {}
-        if mask is not None:
-            h = self.model._host
-            kw = dict(mask=mask.to(img.dtype).expand_as(img).contiguous(), x0=x0, q_noise=torch.stack(qn),
-                      sqrt_alphas_cumprod_t=[h['sqrt_alphas_cumprod'][int(t)] for t in timesteps],
-                      sqrt_one_minus_alphas_cumprod_t=[h['sqrt_one_minus_alphas_cumprod'][int(t)] for t in timesteps])
+        kw = self._mask_kw(mask, x0, qn, img, timesteps)
         return self.model.engine.sample_plms(img, ctx, uctx, scale if uctx is not None else 1.0, [int(t) for t in timesteps],
                                              alphas, alphas_prev, s1m, log_steps=log_steps, control_scales=control_scales,
                                              flags=flags, **kw)

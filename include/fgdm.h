@@ -289,7 +289,7 @@ int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* u
  * x_inter / pred_x0 intermediates (ddim.py:171-173).  decode() from t_start is a call whose tables hold the first t_start entries.
  * fgdm_sample_ddim is this call with every optional pointer NULL.
  *
- * Per step the loop runs the network on cat([x] * 2) (or x, CFG off) and then ONE elementwise kernel (k_ddim_loop_step): CFG
+ * Per step the loop runs the network on cat([x] * 2) (or x, CFG off) and then ONE elementwise kernel (k_loop_step): CFG
  * combine, pred_x0, x_prev (+ sigma * noise), the NEXT step's blend, and the stores of x to the state and to both halves of the
  * network's input.  The arithmetic is that of fgdm_ddim_step, fgdm_axpby (q_sample) and fgdm_mask_blend, rounding for rounding:
  * the loop gives the bits of the per-step route of fgdm_amd/samplers.py fed the same noise.
@@ -352,7 +352,7 @@ int fgdm_sample_ddim_ex(fgdm_engine* e, const fgdm_ddim_params* p, void* stream)
  *
  * The walk, the table order and the slot conventions are those of fgdm_sample_ddim_ex: host tables of S entries, entry k belonging
  * to timesteps[k] (ddim_timesteps order; the walk visits k = S-1 ... 0, plms.py:138,150); q_noise and log_steps in WALK order.
- * Per network evaluation the loop launches ONE elementwise kernel (k_plms_loop_step):
+ * Per network evaluation the loop launches ONE elementwise kernel (k_loop_step):
  *   step 0 (plms.py:219-223) evaluates twice.  Probe: e_t = CFG of the evaluation at timesteps[S-1] is kept as history plane 0 and
  *     x_prev = step(e_t) goes to the network's input only; the state x is untouched.  The second evaluation runs on that input at
  *     t_next = timesteps[max(S-2, 0)] (time_range[min(i + 1, len - 1)], plms.py:143: with S == 1 the same timestep again).
@@ -578,7 +578,7 @@ int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stre
 
 /* Diagnostic entry (tests/test_gpu_ddim_loop.py); only fgdm_sample_ddim_ex's loop launches this kernel in the product path.
  *
- * fgdm_op_ddim_loop_step: one launch of k_ddim_loop_step, the per-step kernel of fgdm_sample_ddim_ex, on n fp32 elements:
+ * fgdm_op_ddim_loop_step: one launch of k_loop_step in its plain mode, the per-step kernel of fgdm_sample_ddim_ex, on n fp32 elements:
  *   e = e_uncond + cfg_scale (e_cond - e_uncond) (e_uncond NULL: e_cond); pred_x0 and x_prev exactly as fgdm_ddim_step (ddim.py:243,
  *   254-268; noise NULL: no sigma term) -> log_pred_x0, log_x (each may be NULL);
  *   mask given: x = q mask + (1 - mask) x_prev with q = sqrt_ac_next x0 + sqrt_one_minus_ac_next q_noise (ddim.py:151-154: the blend
@@ -594,7 +594,7 @@ int fgdm_op_ddim_loop_step(const float* x, const float* e_cond, const float* e_u
 /* Diagnostic entries (tests/test_gpu_multistep_loop.py); only the loops of fgdm_sample_plms / fgdm_sample_dpmpp launch these kernels
  * in the product path.  n fp32 elements; every output may be NULL (nothing is written) and nothing outside n elements is written.
  *
- * fgdm_op_plms_loop_step: one launch of k_plms_loop_step.  e = e_uncond + cfg_scale (e_cond - e_uncond) (e_uncond NULL: e_cond)
+ * fgdm_op_plms_loop_step: one launch of k_loop_step in a PLMS mode.  e = e_uncond + cfg_scale (e_cond - e_uncond) (e_uncond NULL: e_cond)
  *   -> e_out in every mode (the loop passes NULL in mode 1), then
  *   mode 0 (probe, plms.py:219-221): x_prev of e, exactly as fgdm_ddim_step with noise NULL -> xin_a, xin_b; x_out, the
  *     logs and the blend are not touched;

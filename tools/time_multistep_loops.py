@@ -4,7 +4,9 @@ ControlLDM: neither sampler joins the dict conditionings of a ControlLDM into on
 Per case one warm-up of each route, then the routes alternate, `--runs` timed samplings each (host clock around a sampling that
 ends in a device synchronise); prints the median per route, every sample, and whether the two routes gave the same bits.
 
-    python tools/time_multistep_loops.py [--runs 3] [--out profiles/multistep_loop_timing.json]"""
+    python tools/time_multistep_loops.py [--runs 3] [--out profiles/multistep_loop_timing.json] [--samplers ddim,plms,dpmpp]
+
+--samplers adds DDIMSampler (50 steps) or narrows the list; FGDM_LIB selects another build of the library (fgdm_amd/_lib.py)."""
 import argparse
 import json
 import os
@@ -21,6 +23,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--runs', type=int, default=3)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--samplers', default='plms,dpmpp', help='comma-separated: ddim (50 steps), plms (50), dpmpp (20)')
     a = ap.parse_args()
     from fgdm_amd import models, samplers, synth
     from fgdm_amd.engine import SD_V1, Engine
@@ -30,7 +33,8 @@ def main():
     e.finalize()
     m = models.LatentDiffusion(SD_V1, engine=e, use_adapter=False)
     rows = []
-    for name, cls, S in (('plms', samplers.PLMSSampler, 50), ('dpmpp', samplers.DPMSolverSampler, 20)):
+    known = dict(ddim=(samplers.DDIMSampler, 50), plms=(samplers.PLMSSampler, 50), dpmpp=(samplers.DPMSolverSampler, 20))
+    for name, (cls, S) in ((k, known[k]) for k in a.samplers.split(',')):
         for B in (16, 1):
             x_T = torch.from_numpy(synth.latents(B, 64, 64, seed=42)).cuda()
             c = torch.from_numpy(synth.context(B, seed=43)).cuda()
