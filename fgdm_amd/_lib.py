@@ -70,6 +70,22 @@ class FgdmDpmppParams(C.Structure):
             'n_eval', 'B', 'H', 'W', 'flags', 'reserved0', 'reserved1')]
 
 
+class FgdmAncestralParams(C.Structure):
+    """fgdm_ancestral_params of include/fgdm.h (fgdm_sample_ancestral); struct_size must be ctypes.sizeof of this class."""
+    _fields_ = [('struct_size', C.c_int64)] + [(name, C.c_void_p) for name in (
+        'x', 'cond', 'timesteps', 'sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_mean_coef1',
+        'posterior_mean_coef2', 'std', 'step_noise', 'control_scales', 'mask', 'x0', 'q_noise', 'sqrt_alphas_cumprod_t',
+        'sqrt_one_minus_alphas_cumprod_t', 'log_steps', 'x_inter_out')] + [(name, C.c_int32) for name in (
+            'S', 'B', 'H', 'W', 'flags', 'n_log', 'reserved0', 'reserved1')]
+
+
+class FgdmDdimEncodeParams(C.Structure):
+    """fgdm_ddim_encode_params of include/fgdm.h (fgdm_ddim_encode); struct_size must be ctypes.sizeof of this class."""
+    _fields_ = [('struct_size', C.c_int64)] + [(name, C.c_void_p) for name in (
+        'x', 'cond', 'uncond', 'timesteps', 'cx', 'ce', 'control_scales', 'log_steps', 'x_inter_out')] + [
+            ('cfg_scale', C.c_float)] + [(name, C.c_int32) for name in ('S', 'B', 'H', 'W', 'flags', 'n_log', 'reserved0')]
+
+
 DPMPP_FIRST, DPMPP_SECOND = 1, 2      # FGDM_DPMPP_FIRST / FGDM_DPMPP_SECOND
 PLMS_PROBE, PLMS_FINISH_FIRST, PLMS_MULTISTEP = 0, 1, 2      # the modes of fgdm_op_plms_loop_step
 
@@ -122,6 +138,10 @@ SIGNATURES = {
     'fgdm_op_plms_loop_step': (_i, [_p, _p, _p, _f, _i, _i, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p,
                                     _i64, _p]),
     'fgdm_op_dpmpp_loop_step': (_i, [_p, _p, _p, _f, _f, _f, _p, _i, _f, _f, _f, _p, _p, _p, _p, _i64, _p]),
+    'fgdm_sample_ancestral': (_i, [_p, C.POINTER(FgdmAncestralParams), _p]),
+    'fgdm_ddim_encode': (_i, [_p, C.POINTER(FgdmDdimEncodeParams), _p]),
+    'fgdm_op_ancestral_loop_step': (_i, [_p, _p, _f, _f, _f, _f, _f, _p, _p, _p, _p, _f, _f, _p, _p, _p, _i64, _p]),
+    'fgdm_op_invert_loop_step': (_i, [_p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _i64, _p]),
     'fgdm_profile_begin': (_i, [_p, _i]),
     'fgdm_profile_end': (_i, [_p, C.POINTER(C.c_double)]),
     'fgdm_workspace_stats': (_i, [_p, C.POINTER(_i64), C.POINTER(_i64)]),

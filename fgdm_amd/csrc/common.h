@@ -232,6 +232,26 @@ int axpby(const float* a, float ca, const float* b, float cb, float* y, size_t n
 int mask_blend(const float* a, const float* b, const float* m, float* y, size_t n, hipStream_t s);
 int ancestral_step(const float* x, const float* eps, float sqrt_recip, float sqrt_recipm1, float coef1, float coef2,
                    float std, const float* noise, float* out, size_t n, hipStream_t s);
+// One launch per network evaluation of the device ancestral loop (k_ancestral_loop_step): x' = ancestral_step(x, eps, ..., noise)
+// (noise NULL or std == 0: the t == 0 step), then the inpainting blend of the SAME step, x = q m + (1 - m) x' with
+// q = sa_t x0 + s1m_t qnoise (mask NULL: x = x'; ddpm.py:1419-1421) -- k_loop_step blends in front of the NEXT step instead --
+// stored to x_out, the network's input xin and the log plane log_x (each may be NULL).  x_out may alias x; nothing else may overlap.
+struct AncestralLoopStep {
+    const float *x, *eps, *noise, *mask, *x0, *qnoise;
+    float *x_out, *xin, *log_x;
+    float cr, crm1, c1, c2, std, sa_t, s1m_t;
+    size_t n;
+};
+int ancestral_loop_step(const AncestralLoopStep& a, hipStream_t s);
+// One launch per network evaluation of the device DDIM inversion (k_invert_loop_step): x_next = axpby(x, cx, CFG(ec, eu), ce)
+// (eu NULL: e = ec) to x_out, both input halves and the log plane (each may be NULL).  x_out may alias x; nothing else may overlap.
+struct InvertLoopStep {
+    const float *x, *ec, *eu;
+    float *x_out, *xin_a, *xin_b, *log_x;
+    float cfg, cx, ce;
+    size_t n;
+};
+int invert_loop_step(const InvertLoopStep& a, hipStream_t s);
 
 // ---------------------------------------------------------------- patch-wise routes (patches.hip)
 // An NCHW fp32 tensor [B, C, H, W] cut into Ly x Lx crops of [kh, kw] cells every (sh, sw): crop l = ly * Lx + lx starts at

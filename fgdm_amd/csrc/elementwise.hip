@@ -386,20 +386,69 @@ int mask_blend(const float* a, const float* b, const float* m, float* y, size_t 
     return LAUNCH_OK();
 }
 
-// ancestral step (ddpm.py:284-297, 1318-1323): x0 = c_r x - c_rm1 eps; mean = c1 x0 + c2 x; out = mean + std * noise
+// ancestral step (ddpm.py:284-297, 1318-1323): x0 = c_r x - c_rm1 eps; mean = c1 x0 + c2 x; out = mean + std * noise.
+// Written once for k_ancestral and k_ancestral_loop_step, like the helpers above: c_rm1 eps is fused into c_r x, the two products
+// of the mean are rounded on their own, std * noise is fused into the mean (noise NULL: the t == 0 step, no noise term).
+__device__ __forceinline__ float ancestral_rn(float x, float eps, float cr, float crm1, float c1, float c2, float std,
+                                              const float* noise, size_t i) {
+    const float x0 = __builtin_fmaf(-crm1, eps, mul_rn(cr, x));
+    float r = mul_rn(c1, x0) + mul_rn(c2, x);
+    if (noise) r = add_noise_rn(r, std, noise[i]);
+    return r;
+}
 __global__ void k_ancestral(const float* __restrict__ x, const float* __restrict__ eps, float cr, float crm1, float c1,
                             float c2, float std, const float* __restrict__ noise, float* __restrict__ out, size_t n) {
-    EW_LOOP(i, n) {
-        const float x0 = cr * x[i] - crm1 * eps[i];
-        float r = c1 * x0 + c2 * x[i];
-        if (noise) r += std * noise[i];
-        out[i] = r;
-    }
+    EW_LOOP(i, n) out[i] = ancestral_rn(x[i], eps[i], cr, crm1, c1, c2, std, noise, i);
 }
 int ancestral_step(const float* x, const float* eps, float sqrt_recip, float sqrt_recipm1, float coef1, float coef2,
                    float std, const float* noise, float* out, size_t n, hipStream_t s) {
     FGDM_LAUNCH(k_ancestral, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, s, x, eps, sqrt_recip, sqrt_recipm1, coef1,
                        coef2, std, noise, out, n);
+    return LAUNCH_OK();
+}
+
+// One launch per network evaluation of the device ancestral loop (fgdm_sample_ancestral; ddpm.py:1382-1430), one pass over the n
+// elements: x' = k_ancestral(x, eps), then THIS step's inpainting blend x = q m + (1 - m) x' with q = sa_t x0 + s1m_t qnoise
+// (k_axpby, then k_mask_blend; ddpm.py:1419-1421), then the stores to the state, to the network's input and, on a logged step, to
+// the log plane.  p_sample_loop blends AFTER the update, at the timestep of the step that just ran, and logs the blended x; the
+// DDIM-family walks (k_loop_step) blend IN FRONT of the next step, at the next timestep, and log x_prev before that blend.  So a
+// walk cut into several calls carries nothing over but x.  There is no CFG: p_sample has none.
+__global__ void k_ancestral_loop_step(const AncestralLoopStep a) {
+    EW_LOOP(i, a.n) {
+        float xn = ancestral_rn(a.x[i], a.eps[i], a.cr, a.crm1, a.c1, a.c2, a.std, a.noise, i);
+        if (a.mask) xn = mask_blend_rn(axpby_rn(a.sa_t, a.x0[i], a.s1m_t, a.qnoise[i]), xn, a.mask[i]);
+        if (a.x_out) a.x_out[i] = xn;
+        if (a.xin) a.xin[i] = xn;
+        if (a.log_x) a.log_x[i] = xn;
+    }
+}
+int ancestral_loop_step(const AncestralLoopStep& a, hipStream_t s) {
+    if (!a.x || !a.eps || a.n == 0 || (a.mask && (!a.x0 || !a.qnoise))) return FGDM_ERR_ARG;
+    AncestralLoopStep b = a;
+    // std == 0 is the t == 0 step: the per-step route hands k_ancestral no noise there.  (With temperature 0 std is 0 at t > 0 too,
+    // where that route computes fma(0, noise, mean): a difference only in the sign of an exact zero, or on non-finite noise.)
+    if (b.std == 0.f) b.noise = nullptr;
+    FGDM_LAUNCH(k_ancestral_loop_step, dim3(ew_grid(b.n)), dim3(EW_BLOCK), 0, s, b);
+    return LAUNCH_OK();
+}
+
+// One launch per network evaluation of the device DDIM inversion (fgdm_ddim_encode; ddim_hacked.py:234-279):
+// e = CFG(ec, eu) as k_ddim_step's e_out, x_next = k_axpby(x, cx, e, ce), stored to the state, to both halves of the network's
+// input and, on a logged step, to the log plane.
+__global__ void k_invert_loop_step(const InvertLoopStep a) {
+    EW_LOOP(i, a.n) {
+        float e = a.ec[i];
+        if (a.eu) e = cfg_combine_rn(e, a.eu[i], a.cfg);
+        const float xn = axpby_rn(a.cx, a.x[i], a.ce, e);
+        if (a.x_out) a.x_out[i] = xn;
+        if (a.xin_a) a.xin_a[i] = xn;
+        if (a.xin_b) a.xin_b[i] = xn;
+        if (a.log_x) a.log_x[i] = xn;
+    }
+}
+int invert_loop_step(const InvertLoopStep& a, hipStream_t s) {
+    if (!a.x || !a.ec || a.n == 0) return FGDM_ERR_ARG;
+    FGDM_LAUNCH(k_invert_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
     return LAUNCH_OK();
 }
 

@@ -1947,6 +1947,14 @@ extern "C++" template <typename P> static Walk walk_from(const P& p) {
     w.reserved0 = p.reserved0;
     return w;
 }
+// The log_steps of every loop's struct: strictly ascending walk positions in [0, S).
+static const char* log_steps_error(const int32_t* log_steps, int n_log, int S) {
+    if (n_log < 0 || (n_log > 0 && !log_steps)) return "n_log < 0, or log steps without log_steps";
+    for (int j = 0; j < n_log; ++j)
+        if (log_steps[j] < 0 || log_steps[j] >= S || (j > 0 && log_steps[j] <= log_steps[j - 1]))
+            return "log_steps must be strictly ascending walk positions in [0, S)";
+    return nullptr;
+}
 // Host-side checks of a walk, in front of any launch; nullptr: the parameters are consistent.
 static const char* walk_error(const Walk& p) {
     if (p.reserved0 != 0) return "reserved0 must be 0";
@@ -1957,11 +1965,7 @@ static const char* walk_error(const Walk& p) {
     if (p.sigmas && !p.step_noise)
         for (int k = 0; k < p.S; ++k)
             if (p.sigmas[k] != 0.f) return "a sigma is not 0 and step_noise is NULL";
-    if (p.n_log < 0 || (p.n_log > 0 && !p.log_steps)) return "n_log < 0, or log steps without log_steps";
-    for (int j = 0; j < p.n_log; ++j)
-        if (p.log_steps[j] < 0 || p.log_steps[j] >= p.S || (j > 0 && p.log_steps[j] <= p.log_steps[j - 1]))
-            return "log_steps must be strictly ascending walk positions in [0, S)";
-    return nullptr;
+    return log_steps_error(p.log_steps, p.n_log, p.S);
 }
 
 // The walk itself (inside the entry's scoped_call): per step one evaluation of the network on cat([x] * 2) (or x, CFG off), then
@@ -2132,6 +2136,124 @@ int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* caller, void* str
         rc = dpmpp_loop_step(a, s);
     }
     loop_end(e, &w); e->arena.release(m); e->arena.release(tdev);
+    return rc;
+    });
+}
+
+static const char* ancestral_params_error(const fgdm_ancestral_params* p) {
+    if (p->reserved0 != 0 || p->reserved1 != 0) return "reserved0 and reserved1 must be 0";
+    if (!p->x || !p->cond || !p->timesteps || !p->sqrt_recip_alphas_cumprod || !p->sqrt_recipm1_alphas_cumprod ||
+        !p->posterior_mean_coef1 || !p->posterior_mean_coef2 || !p->std)
+        return "x, cond or a table is NULL";
+    if (p->S <= 0 || p->B <= 0 || p->H <= 0 || p->W <= 0) return "S, B, H and W must be positive";
+    if (p->mask && (!p->x0 || !p->q_noise || !p->sqrt_alphas_cumprod_t || !p->sqrt_one_minus_alphas_cumprod_t))
+        return "mask needs x0, q_noise and q_sample's two coefficient tables";
+    if (!p->step_noise)
+        for (int i = 0; i < p->S; ++i)
+            if (p->std[i] != 0.f) return "a std is not 0 and step_noise is NULL";
+    return log_steps_error(p->log_steps, p->n_log, p->S);
+}
+
+// p_sample_loop (ddpm.py:1382-1430): per step one evaluation of the network on x, then one launch of k_ancestral_loop_step, which
+// also does the step's own blend and writes x into the network's input.  Every table is in walk order.
+int fgdm_sample_ancestral(fgdm_engine* e, const fgdm_ancestral_params* caller, void* stream) {
+    if (!e || !caller) return FGDM_ERR_ARG;
+    fgdm_ancestral_params known;
+    if (!read_params(caller, FGDM_ANCESTRAL_PARAMS_SIZE_V1, &known, sizeof(known)))
+        return e->fail(FGDM_ERR_ARG, "fgdm_sample_ancestral: struct_size is not the sizeof(fgdm_ancestral_params) of a known header version");
+    const fgdm_ancestral_params* p = &known;
+    if (const char* why = ancestral_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_ancestral: ") + why);
+    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_sample_ancestral: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    hipStream_t s = as_stream(stream);
+    return scoped_call(e, stream, [&]() -> int {
+    const int S = p->S, B = p->B, H = p->H, W = p->W;
+    const int flags = p->flags & ~FGDM_FLAG_CFG_PAIRS;
+    LoopWork w;
+    int rc = loop_begin(e, p->cond, nullptr, false, B, H, W, s, &w);
+    const size_t n = w.n;
+    float* x = p->x;
+    int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * B * sizeof(int64_t));
+    if (rc == FGDM_OK && !tdev) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
+    if (rc != FGDM_OK) return rc;
+    CHK(upload_repeated(p->timesteps, S, B, tdev, s));
+    HIP_TRY(hipMemcpyAsync(w.x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));      // x_T into the network's input, once
+    int logged = 0;
+    for (int i = 0; i < S && rc == FGDM_OK; ++i) {
+        rc = e->apply_model(w.x2, tdev + (size_t)i * B, nullptr, nullptr, nullptr, p->control_scales, B, H, W, flags, w.eps);
+        if (rc != FGDM_OK) break;
+        AncestralLoopStep a{};
+        a.x = x; a.eps = w.eps; a.n = n;
+        a.cr = p->sqrt_recip_alphas_cumprod[i]; a.crm1 = p->sqrt_recipm1_alphas_cumprod[i];
+        a.c1 = p->posterior_mean_coef1[i]; a.c2 = p->posterior_mean_coef2[i]; a.std = p->std[i];
+        a.noise = a.std != 0.f ? p->step_noise + (size_t)i * n : nullptr;
+        if (p->mask) {
+            a.mask = p->mask; a.x0 = p->x0; a.qnoise = p->q_noise + (size_t)i * n;
+            a.sa_t = p->sqrt_alphas_cumprod_t[i]; a.s1m_t = p->sqrt_one_minus_alphas_cumprod_t[i];
+        }
+        a.x_out = x;
+        if (i + 1 < S) a.xin = w.x2;
+        if (logged < p->n_log && p->log_steps[logged] == i) {
+            a.log_x = p->x_inter_out ? p->x_inter_out + (size_t)logged * n : nullptr;
+            ++logged;
+        }
+        rc = ancestral_loop_step(a, s);
+    }
+    loop_end(e, &w); e->arena.release(tdev);
+    return rc;
+    });
+}
+
+static const char* ddim_encode_params_error(const fgdm_ddim_encode_params* p) {
+    if (p->reserved0 != 0) return "reserved0 must be 0";
+    if (!p->x || !p->cond || !p->timesteps || !p->cx || !p->ce) return "x, cond or a table is NULL";
+    if (p->S <= 0 || p->B <= 0 || p->H <= 0 || p->W <= 0) return "S, B, H and W must be positive";
+    return log_steps_error(p->log_steps, p->n_log, p->S);
+}
+
+// DDIMSampler.encode (ddim_hacked.py:234-279): per step one evaluation of the network on cat([x] * 2) (or x, CFG off), then one
+// launch of k_invert_loop_step.
+int fgdm_ddim_encode(fgdm_engine* e, const fgdm_ddim_encode_params* caller, void* stream) {
+    if (!e || !caller) return FGDM_ERR_ARG;
+    fgdm_ddim_encode_params known;
+    if (!read_params(caller, FGDM_DDIM_ENCODE_PARAMS_SIZE_V1, &known, sizeof(known)))
+        return e->fail(FGDM_ERR_ARG, "fgdm_ddim_encode: struct_size is not the sizeof(fgdm_ddim_encode_params) of a known header version");
+    const fgdm_ddim_encode_params* p = &known;
+    if (const char* why = ddim_encode_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_ddim_encode: ") + why);
+    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_ddim_encode: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    hipStream_t s = as_stream(stream);
+    return scoped_call(e, stream, [&]() -> int {
+    const int S = p->S, B = p->B, H = p->H, W = p->W;
+    const bool cfg_on = p->uncond && p->cfg_scale != 1.0f;
+    const int flags = cfg_on ? p->flags | FGDM_FLAG_CFG_PAIRS : p->flags & ~FGDM_FLAG_CFG_PAIRS;
+    LoopWork w;
+    int rc = loop_begin(e, p->cond, p->uncond, cfg_on, B, H, W, s, &w);
+    const int Bm = w.Bm;
+    const size_t n = w.n;
+    float* x = p->x;
+    int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * Bm * sizeof(int64_t));
+    if (rc == FGDM_OK && !tdev) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
+    if (rc != FGDM_OK) return rc;
+    CHK(upload_repeated(p->timesteps, S, Bm, tdev, s));
+    HIP_TRY(hipMemcpyAsync(w.x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));      // x_0 into the network's input, once
+    if (cfg_on) HIP_TRY(hipMemcpyAsync(w.x2 + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    int logged = 0;
+    for (int i = 0; i < S && rc == FGDM_OK; ++i) {
+        rc = e->apply_model(w.x2, tdev + (size_t)i * Bm, nullptr, nullptr, nullptr, p->control_scales, Bm, H, W, flags, w.eps);
+        if (rc != FGDM_OK) break;
+        InvertLoopStep a{};
+        a.x = x; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr; a.cfg = p->cfg_scale;
+        a.cx = p->cx[i]; a.ce = p->ce[i];
+        a.x_out = x;
+        if (i + 1 < S) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; }
+        if (logged < p->n_log && p->log_steps[logged] == i) {
+            a.log_x = p->x_inter_out ? p->x_inter_out + (size_t)logged * n : nullptr;
+            ++logged;
+        }
+        rc = invert_loop_step(a, s);
+    }
+    loop_end(e, &w); e->arena.release(tdev);
     return rc;
     });
 }

@@ -358,6 +358,30 @@ int fgdm_op_dpmpp_loop_step(const float* x, const float* e_cond, const float* e_
     return dpmpp_loop_step(a, as_stream(stream));
 }
 
+// Diagnostic entries of tests/test_gpu_ancestral_loop.py: one launch of the device ancestral loop's / the device DDIM inversion's
+// step kernel on caller-owned buffers.
+int fgdm_op_ancestral_loop_step(const float* x, const float* eps, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2,
+                                float std, const float* noise, const float* mask, const float* x0, const float* q_noise,
+                                float sqrt_ac_t, float sqrt_one_minus_ac_t, float* x_out, float* xin, float* log_x, int64_t n,
+                                void* stream) {
+    if (n <= 0) return FGDM_ERR_ARG;
+    AncestralLoopStep a{};
+    a.x = x; a.eps = eps; a.noise = noise; a.mask = mask; a.x0 = x0; a.qnoise = q_noise;
+    a.x_out = x_out; a.xin = xin; a.log_x = log_x;
+    a.cr = sqrt_recip_ac; a.crm1 = sqrt_recipm1_ac; a.c1 = coef1; a.c2 = coef2; a.std = std;
+    a.sa_t = sqrt_ac_t; a.s1m_t = sqrt_one_minus_ac_t; a.n = (size_t)n;
+    return ancestral_loop_step(a, as_stream(stream));
+}
+
+int fgdm_op_invert_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float cx, float ce,
+                             float* x_out, float* xin_a, float* xin_b, float* log_x, int64_t n, void* stream) {
+    if (n <= 0) return FGDM_ERR_ARG;
+    InvertLoopStep a{};
+    a.x = x; a.ec = e_cond; a.eu = e_uncond; a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.log_x = log_x;
+    a.cfg = cfg_scale; a.cx = cx; a.ce = ce; a.n = (size_t)n;
+    return invert_loop_step(a, as_stream(stream));
+}
+
 // Host-only entry of tests/test_replay_plan.py: the planner of replay_plan.h on caller-made walks.  Never touches the device.
 int fgdm_replay_plan(int n_walks, const int32_t* lens, const uint64_t* key, const uint32_t* grid_x, const uint64_t* shape, int group_max,
                      int chunk, int32_t* out, int out_cap, int* limits) {

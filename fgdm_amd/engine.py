@@ -615,6 +615,65 @@ class Engine:
         self._run_loop('sample_dpmpp', p, keep, control_scales)
         return x
 
+    def _log_args(self, name, p, keep, x, log_steps, x_inter_out):
+        """log_steps / n_log / x_inter_out of a loop's struct -> the [len(log_steps), B,4,H,W] plane (None without log steps)"""
+        p.n_log = len(log_steps)
+        if not p.n_log:
+            return None
+        x_inter = torch.empty(p.n_log, *x.shape, device=self.device, dtype=torch.float32) if x_inter_out is None else x_inter_out
+        p.log_steps = self._table(name, keep, log_steps, p.n_log, C.c_int32, int)
+        p.x_inter_out = _ptr(x_inter)
+        return x_inter
+
+    def sample_ancestral(self, x_T, cond, timesteps, tables, step_noise=None, mask=None, x0=None, q_noise=None, log_steps=(),
+                         control_scales=None, flags=0, out=None, x_inter_out=None):
+        """The ancestral loop on the device (fgdm_sample_ancestral, include/fgdm.h), S = len(timesteps) steps in WALK order
+        (descending t).  tables: a dict of S-entry lists sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod,
+        posterior_mean_coef1, posterior_mean_coef2, std (temperature folded in, 0 where t == 0) and, with a mask,
+        sqrt_alphas_cumprod_t, sqrt_one_minus_alphas_cumprod_t; step_noise / q_noise [S, B,4,H,W].  Returns (x, x_inter): the
+        final latent and the [len(log_steps), B,4,H,W] logged latents (None without log steps).  x_T is not modified."""
+        name = 'sample_ancestral'
+        x, cond, _ = self._loop_args(name, x_T, cond, None, out)
+        dev = lambda v: None if v is None else v.to(self.device, torch.float32).contiguous()
+        B, _, H, W = x.shape
+        S = len(timesteps)
+        p = _lib.FgdmAncestralParams()
+        tensors = dict(step_noise=(dev(step_noise), (S, *x.shape)), q_noise=(dev(q_noise), (S, *x.shape)),
+                       mask=(dev(mask), tuple(x.shape)), x0=(dev(x0), tuple(x.shape)))
+        for k, (v, shape) in tensors.items():
+            if v is not None and tuple(v.shape) != tuple(shape):
+                raise ValueError(f'{name}: {k} {tuple(v.shape)} must be {tuple(shape)}')
+            setattr(p, k, _ptr(v))
+        keep = []
+        p.timesteps = self._table(name, keep, timesteps, S, C.c_int64, int)
+        for k in ('sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_mean_coef1', 'posterior_mean_coef2', 'std',
+                  'sqrt_alphas_cumprod_t', 'sqrt_one_minus_alphas_cumprod_t'):
+            setattr(p, k, self._table(name, keep, tables.get(k), S))
+        x_inter = self._log_args(name, p, keep, x, log_steps, x_inter_out)
+        p.x, p.cond = _ptr(x), _ptr(cond)
+        p.S, p.B, p.H, p.W, p.flags = S, B, H, W, int(flags)
+        self._run_loop(name, p, keep, control_scales)
+        return x, x_inter
+
+    def ddim_encode(self, x0, cond, uncond, cfg_scale, timesteps, cx, ce, log_steps=(), control_scales=None, flags=0, out=None,
+                    x_inter_out=None):
+        """DDIM inversion on the device (fgdm_ddim_encode, include/fgdm.h): S = len(timesteps) steps over ascending timesteps
+        with the per-step coefficients cx / ce (fgdm_amd.samplers.encode_tables).  Returns (x, x_inter) as sample_ancestral;
+        x0 is not modified."""
+        name = 'ddim_encode'
+        x, cond, uncond = self._loop_args(name, x0, cond, uncond, out)
+        B, _, H, W = x.shape
+        S = len(timesteps)
+        p = _lib.FgdmDdimEncodeParams()
+        keep = []
+        p.timesteps = self._table(name, keep, timesteps, S, C.c_int64, int)
+        p.cx, p.ce = self._table(name, keep, cx, S), self._table(name, keep, ce, S)
+        x_inter = self._log_args(name, p, keep, x, log_steps, x_inter_out)
+        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
+        p.cfg_scale, p.S, p.B, p.H, p.W, p.flags = float(cfg_scale), S, B, H, W, int(flags)
+        self._run_loop(name, p, keep, control_scales)
+        return x, x_inter
+
 
 # ---------------------------------------------------------------------- fused sampler updates
 def ddim_step(x, e_cond, e_uncond, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise=None,

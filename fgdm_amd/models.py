@@ -27,6 +27,14 @@ def _randn(shape, device):
     return torch.randn(shape, device=device)
 
 
+def plan_noise_segments(steps, step_bytes, max_bytes):
+    """The device ancestral loop's walk of `steps` steps, each needing step_bytes of pre-drawn noise, as consecutive segments
+    [(start, stop), ...] of at most max_bytes of noise each: as many whole steps as fit, one step where a single step already
+    exceeds the bound.  The segments cover range(steps) once and in order; a pure function."""
+    per = max(1, int(max_bytes) // max(1, int(step_bytes)))
+    return [(a, min(a + per, steps)) for a in range(0, steps, per)]
+
+
 class _Buffers:
     """schedule tables as float32 torch tensors on the model's device (attribute names of register_schedule)."""
 
@@ -107,7 +115,7 @@ class LatentDiffusion(_Buffers):
                  beta_schedule='linear', linear_start=0.00085, linear_end=0.012, cosine_s=8e-3, given_betas=None,
                  v_posterior=0.0, parameterization='eps', conditioning_key='crossattn', scale_factor=0.18215,
                  channels=4, image_size=32, log_every_t=200, clip_denoised=False, device=0, first_stage_config=None,
-                 cond_stage_config=None, first_stage_encoder=False, **ignored):
+                 cond_stage_config=None, first_stage_encoder=False, device_loop=False, **ignored):
         if parameterization != 'eps':
             raise NotImplementedError(f'parameterization={parameterization!r}: only eps-parameterization is implemented (the shipped '
                                       f'configs, models/config.yaml; {_cfg.SD2_LIMIT}; v-prediction checkpoints are refused)')
@@ -140,6 +148,8 @@ class LatentDiffusion(_Buffers):
                                 linear_end=linear_end, cosine_s=cosine_s, v_posterior=v_posterior,
                                 given_betas=given_betas)
         self._finalized = False
+        self.device_loop = bool(device_loop)                # p_sample_loop / sample as engine calls where nothing needs the host between steps
+        self.max_loop_noise_bytes = 256 << 20               # pre-drawn noise per engine call of that route: a memory bound, not a tuned number
 
     @classmethod
     def engine_args(cls, unet_config=None, use_adapter=None, n_controlnets=0, num_prompts=1, first_stage_config=None,
@@ -483,9 +493,67 @@ class LatentDiffusion(_Buffers):
             return out, self.predict_start_from_noise(x, t, eps)
         return out
 
+    # ---- the device ancestral loop (fgdm_sample_ancestral)
+    def _ancestral_plan(self, cond, img, timesteps, mask, x0, host_hooks, kwargs):
+        """None (per-step route), or (ctx, None, flags, control_scales) for the device loop: the rule the samplers' _loop_plan
+        applies -- nothing asked for runs on the host between steps, and a conditioning the engine's loops take.  Draws no noise."""
+        from . import samplers
+        eng = self.engine
+        if not getattr(self, 'device_loop', False) or host_hooks or timesteps < 1 or not hasattr(eng, 'sample_ancestral'):
+            return None
+        if set(kwargs) - {'repeat_noise', 'temperature'} or self.clip_denoised:
+            return None                 # return_x0, a caller's noise, apply_model's keywords, the refused options: p_sample's business
+        if getattr(self, 'split_input_params', None) is not None or img.dim() != 4 or img.shape[1] != 4:
+            return None
+        if mask is not None and (x0 is None or tuple(x0.shape) != tuple(img.shape)):
+            return None
+        if not isinstance(self, ControlLDM):        # {'c_crossattn': [ctx]} and [ctx] are the tensor ctx (apply_model's _context)
+            if isinstance(cond, dict) and cond.get('c_concat') is None:
+                cond = cond.get('c_crossattn')
+            if isinstance(cond, (list, tuple)) and len(cond) == 1:
+                cond = cond[0]
+        return samplers._SamplerBase._loop_cond_of(self, cond, None, False, None)
+
+    def _device_ancestral(self, plan, img, timesteps, mask, x0, log_every_t, repeat_noise=False, temperature=1.):
+        """The walk t = timesteps - 1 ... 0 as consecutive engine calls of at most max_loop_noise_bytes of pre-drawn noise each.
+        The noise is drawn by the calls of the per-step route in its order -- per step p_sample's, then q_sample's if there is a
+        mask -- so the same generator state gives the same bits.  log_every_t None: nothing is logged.  -> (img, the logged latents)."""
+        ctx, _, flags, control_scales = plan
+        h = self._host
+        ts = list(reversed(range(timesteps)))
+        tab = lambda name: [float(h[name][t]) for t in ts]
+        tables = {k: tab(k) for k in ('sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_mean_coef1',
+                                      'posterior_mean_coef2')}
+        tables['std'] = [0.0 if t == 0 else float(np.exp(0.5 * h['posterior_log_variance_clipped'][t])) * temperature for t in ts]
+        m = None
+        if mask is not None:
+            m = mask.to(img.dtype).expand_as(img).contiguous()
+            tables['sqrt_alphas_cumprod_t'] = tab('sqrt_alphas_cumprod')
+            tables['sqrt_one_minus_alphas_cumprod_t'] = tab('sqrt_one_minus_alphas_cumprod')
+        logs = [j for j, t in enumerate(ts) if log_every_t and (t % log_every_t == 0 or t == timesteps - 1)]
+        inter = []
+        step_bytes = img.numel() * 4 * (1 if mask is None else 2)
+        for a, b in plan_noise_segments(len(ts), step_bytes, getattr(self, 'max_loop_noise_bytes', 256 << 20)):
+            sn = torch.empty(b - a, *img.shape, device=img.device, dtype=torch.float32)
+            qn = None if mask is None else torch.empty_like(sn)
+            for k in range(b - a):
+                sn[k] = _randn((1, *img.shape[1:]) if repeat_noise else img.shape, img.device)      # p_sample (expanded by the copy)
+                if qn is not None:
+                    qn[k] = torch.randn_like(x0)                                                    # q_sample(x0, ts)
+            img, x_inter = self.engine.sample_ancestral(img, ctx, ts[a:b], {k: v[a:b] for k, v in tables.items()}, step_noise=sn,
+                                                        mask=m, x0=None if mask is None else x0, q_noise=qn,
+                                                        log_steps=[j - a for j in logs if a <= j < b],
+                                                        control_scales=control_scales, flags=flags)
+            if x_inter is not None:
+                inter += list(x_inter)
+            del sn, qn          # given back (in stream order) before the next segment's are taken: one bound of noise at a time, not two
+        return img, inter
+
     def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None,
                       timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None,
                       log_every_t=None, **kwargs):
+        """ddpm.py:1382-1430.  A model built with device_loop=True hands the walk to the engine (fgdm_sample_ancestral) when nothing
+        asked for needs the host between steps (_ancestral_plan); everything else, and the default, is the per-step loop below."""
         if quantize_denoised:
             raise NotImplementedError('quantize_denoised needs a VQ first stage')
         log_every_t = log_every_t or self.log_every_t
@@ -497,6 +565,10 @@ class LatentDiffusion(_Buffers):
             timesteps = min(timesteps, start_T)
         if mask is not None:
             assert x0 is not None and x0.shape[2:3] == mask.shape[2:3]
+        plan = self._ancestral_plan(cond, img, timesteps, mask, x0, bool(callback or img_callback), kwargs)
+        if plan is not None:
+            img, logged = self._device_ancestral(plan, img, timesteps, mask, x0, log_every_t if return_intermediates else None, **kwargs)
+            return (img, inter + logged) if return_intermediates else img
         for i in reversed(range(0, timesteps)):
             ts = torch.full((b,), i, device=self.device, dtype=torch.long)
             img = self.p_sample(img, cond, ts, clip_denoised=self.clip_denoised, **kwargs)

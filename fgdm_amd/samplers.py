@@ -16,6 +16,8 @@ loop (fgdm_sample_ddim_ex) when nothing asked for needs the host between steps; 
 the same order, so either route gives the same bits from the same generator state.  Everything else, and the default, is the
 per-step loop below.  PLMSSampler and DPMSolverSampler take the same keyword and the same rule (_loop_plan / _loop_cond) for
 fgdm_sample_plms and fgdm_sample_dpmpp; the DPM-Solver++ coefficients of both routes come from dpmpp_tables.
+ControlDDIMSampler.encode goes to fgdm_ddim_encode under the same rule, with the coefficients of encode_tables on both routes; the
+ancestral loop's switch is the model's (fgdm_amd.models.LatentDiffusion(device_loop=True)).
 """
 import numpy as np
 import torch
@@ -167,19 +169,24 @@ class _SamplerBase:
 
     # ---- the device loops (DDIM, PLMS, DPM-Solver++): what they can take over
     def _loop_cond(self, c, uc, cfg_on):
-        """(ctx, uctx, flags, control_scales) the engine's loop needs for this conditioning, after registering the hints as
-        apply_model would -- or None: a conditioning the loop does not take (the per-step route then treats it as before)."""
+        return _SamplerBase._loop_cond_of(self.model, c, uc, cfg_on, self)      # by class: DPMSolverSampler borrows this method
+
+    @staticmethod
+    def _loop_cond_of(m, c, uc, cfg_on, sampler):
+        """(ctx, uctx, flags, control_scales) the engine's loop needs for this conditioning of model `m`, after registering the
+        hints as apply_model would -- or None: a conditioning the loop does not take (the per-step route then treats it as
+        before).  sampler: the one whose _cat_cond would join the two branches (None, and cfg_on False: the model's own
+        ancestral loop, which has no guidance)."""
         from . import _lib, models
-        m = self.model
         pair = _lib.FLAG_CFG_PAIRS if cfg_on else 0
         if isinstance(m, models.ControlLDM):
             if type(m).apply_model is not models.ControlLDM.apply_model:
                 return None                                                   # a subclass with its own apply_model
-            if cfg_on and not isinstance(self, ControlDDIMSampler):
+            if cfg_on and not isinstance(sampler, ControlDDIMSampler):
                 return None                                                   # only that sampler's _cat_cond joins dict conds
             if not isinstance(c, dict) or len(c.get('c_crossattn') or ()) != 1 or not torch.is_tensor(c['c_crossattn'][0]):
                 return None
-            if cfg_on and (not isinstance(uc, dict) or self._cat_cond(uc, c) is None):
+            if cfg_on and (not isinstance(uc, dict) or sampler._cat_cond(uc, c) is None):
                 return None                                                   # branches that cannot share one batch: two calls per step
             hints = c.get('c_concat')
             flags = pair | (_lib.FLAG_ONLY_MID_CONTROL if m.only_mid_control else 0)
@@ -521,6 +528,19 @@ class PLMSSampler(_SamplerBase):
         return x_prev, pred_x0, e_t
 
 
+def encode_tables(a_next, a_cur):
+    """The coefficients of DDIM inversion's x_next = cx x + ce e_t (ddim_hacked.py:262-266) for every step, from the fp32 alphas of
+    the step's target and source timestep: cx = sqrt(a_next / a_cur) and ce = sqrt(a_next) (sqrt(1 / a_next - 1) - sqrt(1 / a_cur - 1)),
+    evaluated in numpy float32 scalars.  Both routes of ControlDDIMSampler.encode take them from here."""
+    f32 = np.float32
+    a_next, a_cur = np.asarray(a_next, dtype=f32), np.asarray(a_cur, dtype=f32)
+    cx, ce = [], []
+    for i in range(len(a_next)):
+        cx.append(float(np.sqrt(a_next[i] / a_cur[i])))
+        ce.append(float(np.sqrt(a_next[i]) * (np.sqrt(f32(1) / a_next[i] - f32(1)) - np.sqrt(f32(1) / a_cur[i] - f32(1)))))
+    return cx, ce
+
+
 class ControlDDIMSampler(DDIMSampler):
     """controlnet/cldm/ddim_hacked.py: conditionings are dicts {'c_concat': [hint] | None, 'c_crossattn': [ctx]}."""
 
@@ -583,7 +603,8 @@ class ControlDDIMSampler(DDIMSampler):
 
     def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None,
                unconditional_guidance_scale=1.0, unconditional_conditioning=None, callback=None):
-        """DDIM inversion x_0 -> x_{t_enc} (ddim_hacked.py:234-279); requires make_schedule() first."""
+        """DDIM inversion x_0 -> x_{t_enc} (ddim_hacked.py:234-279); requires make_schedule() first.  device_loop=True and no
+        callback: one engine call (fgdm_ddim_encode) under the rule of _loop_plan, with the same bits."""
         timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
         assert t_enc <= timesteps.shape[0]
         if use_original_steps:
@@ -592,28 +613,40 @@ class ControlDDIMSampler(DDIMSampler):
         else:
             a_next = np.asarray(self.ddim_alphas[:t_enc], dtype=np.float32)
             a_cur = np.asarray(self.ddim_alphas_prev[:t_enc], dtype=np.float32)
+        cx, ce = encode_tables(a_next, a_cur)
         x_next = x0
         intermediates, inter_steps = [], []
-        for i in range(t_enc):
-            t = torch.full((x0.shape[0],), int(timesteps[i]), device=self.model.device, dtype=torch.long)
-            if unconditional_guidance_scale == 1.:
-                e = self.model.apply_model(x_next, t, c)
-            else:
-                assert unconditional_conditioning is not None
-                e_c, e_u = self._eval_pair(x_next, t, c, unconditional_conditioning, unconditional_guidance_scale)
-                e = _k.cfg_combine(e_c, e_u, unconditional_guidance_scale) if e_u is not None else e_c
-            f32 = np.float32
-            cx = np.sqrt(a_next[i] / a_cur[i])
-            ce = np.sqrt(a_next[i]) * (np.sqrt(f32(1) / a_next[i] - f32(1)) - np.sqrt(f32(1) / a_cur[i] - f32(1)))
-            x_next = _k.axpby(x_next.contiguous(), float(cx), e, float(ce))
-            if return_intermediates and i % (t_enc // return_intermediates) == 0 and i < t_enc - 1:
-                intermediates.append(x_next)
-                inter_steps.append(i)
-            elif return_intermediates and i >= t_enc - 2:
-                intermediates.append(x_next)
-                inter_steps.append(i)
-            if callback:
-                callback(i)
+        scale, uc = unconditional_guidance_scale, unconditional_conditioning
+        plan = None
+        if t_enc >= 1 and (scale == 1. or uc is not None):
+            plan = self._loop_plan(c, uc if scale != 1. else None, [scale] * t_enc, None, None, x0, bool(callback), {},
+                                   entry='ddim_encode')
+        if plan is not None:
+            ctx, uctx, flags, control_scales = plan
+            inter_steps = [i for i in range(t_enc) if return_intermediates and (
+                (i % (t_enc // return_intermediates) == 0 and i < t_enc - 1) or i >= t_enc - 2)]
+            x_next, x_inter = self.model.engine.ddim_encode(x0, ctx, uctx, scale if uctx is not None else 1.0,
+                                                            [int(t) for t in timesteps[:t_enc]], cx, ce, log_steps=inter_steps,
+                                                            control_scales=control_scales, flags=flags)
+            intermediates = list(x_inter) if inter_steps else []
+        else:
+            for i in range(t_enc):
+                t = torch.full((x0.shape[0],), int(timesteps[i]), device=self.model.device, dtype=torch.long)
+                if unconditional_guidance_scale == 1.:
+                    e = self.model.apply_model(x_next, t, c)
+                else:
+                    assert unconditional_conditioning is not None
+                    e_c, e_u = self._eval_pair(x_next, t, c, unconditional_conditioning, unconditional_guidance_scale)
+                    e = _k.cfg_combine(e_c, e_u, unconditional_guidance_scale) if e_u is not None else e_c
+                x_next = _k.axpby(x_next.contiguous(), cx[i], e, ce[i])
+                if return_intermediates and i % (t_enc // return_intermediates) == 0 and i < t_enc - 1:
+                    intermediates.append(x_next)
+                    inter_steps.append(i)
+                elif return_intermediates and i >= t_enc - 2:
+                    intermediates.append(x_next)
+                    inter_steps.append(i)
+                if callback:
+                    callback(i)
         out = {'x_encoded': x_next, 'intermediate_steps': inter_steps}
         if return_intermediates:
             out.update({'intermediates': intermediates})

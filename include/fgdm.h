@@ -450,6 +450,100 @@ typedef struct fgdm_dpmpp_params {
 } fgdm_dpmpp_params;
 int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* p, void* stream);
 
+/* The ancestral sampler without host callbacks: LatentDiffusion.p_sample_loop / sample (ldm/models/diffusion/ddpm.py:1382-1448;
+ * p_sample :1295-1323, q_posterior :290-297) over S consecutive timesteps.  There is no classifier-free guidance (p_sample has none).
+ *
+ * Every table and every [S, ...] tensor is in WALK order: slot i belongs to the i-th step that runs, timesteps[i] (int64, descending
+ * t; p_sample_loop walks t = T-1 ... 0).  Per step the loop runs the network on x at timesteps[i] and then ONE elementwise kernel
+ * (k_ancestral_loop_step):
+ *   x' = fgdm_ancestral_step(x, eps, sqrt_recip_alphas_cumprod[i], sqrt_recipm1_alphas_cumprod[i], posterior_mean_coef1[i],
+ *        posterior_mean_coef2[i], std[i], step_noise[i]); std[i] = temperature * exp(0.5 * posterior_log_variance_clipped[t]), and
+ *        0 where t == 0 (ddpm.py:1317 nonzero_mask): such a step reads no noise, as fgdm_ancestral_step with noise = NULL.  A std
+ *        of 0 at t > 0 (temperature 0) reads no noise either, while the per-step route still computes fma(0, noise, mean) there:
+ *        the two can differ only in the sign of an exact zero, or where the noise is not finite;
+ *   mask given: x = q mask + (1 - mask) x' with q = sqrt_alphas_cumprod_t[i] x0 + sqrt_one_minus_alphas_cumprod_t[i] q_noise[i]
+ *        (fgdm_axpby, then fgdm_mask_blend).  This is the blend of the SAME step at its own timestep, applied after the update
+ *        (ddpm.py:1419-1421) -- the DDIM-family loops above blend in front of the NEXT step -- so a walk may be cut into several
+ *        calls at any step: the calls share nothing but x;
+ *   x to the state, to the network's input and, on a logged step, to its x_inter_out slot (the x after the blend, ddpm.py:1423-1424).
+ * The arithmetic is that of fgdm_ancestral_step, fgdm_axpby and fgdm_mask_blend, rounding for rounding: the loop gives the bits of
+ * the per-step route of fgdm_amd/models.py fed the same noise.
+ *
+ * The loop clears FGDM_FLAG_CFG_PAIRS; the other flags go to the network as given.  Hints come from fgdm_set_hint; an engine with
+ * in_channels > 4 (hybrid c_concat) is refused.  struct_size / reserved0 / reserved1: as for fgdm_dpmpp_params, from
+ * FGDM_ANCESTRAL_PARAMS_SIZE_V1 up to the library's own sizeof.
+ * step_noise [S, B,4,H,W] (device; NULL requires every std to be 0); mask [B,4,H,W], x0 [B,4,H,W], q_noise [S, B,4,H,W] (device)
+ * and the two q_sample tables [S] (host): read with a mask only, which needs all of them.  log_steps [n_log] (host, strictly ascending walk positions in [0, S)),
+ * x_inter_out [n_log, B,4,H,W] (device, may be NULL).
+ * FGDM_ERR_ARG before any launch (x untouched): a struct_size outside that range, reserved0 or reserved1 != 0; a NULL x / cond /
+ * table; S, B, H or W <= 0; mask without x0, q_noise or the two q_sample tables; a std that is not 0 without step_noise; n_log < 0,
+ * n_log > 0 without log_steps, a log step outside [0, S) or not above its predecessor; an engine with in_channels > 4. */
+#define FGDM_ANCESTRAL_PARAMS_SIZE_V1 176
+typedef struct fgdm_ancestral_params {
+    int64_t struct_size;
+    float* x;                           /* device [B,4,H,W]: x_T (or the latent the walk continues from) in, the sample out */
+    const float* cond;                  /* device [B,tokens,context_dim] */
+    const int64_t* timesteps;
+    const float* sqrt_recip_alphas_cumprod;
+    const float* sqrt_recipm1_alphas_cumprod;
+    const float* posterior_mean_coef1;
+    const float* posterior_mean_coef2;
+    const float* std;
+    const float* step_noise;
+    const float* control_scales;        /* host, n_controlnets * 13, or NULL */
+    const float* mask;
+    const float* x0;
+    const float* q_noise;
+    const float* sqrt_alphas_cumprod_t;
+    const float* sqrt_one_minus_alphas_cumprod_t;
+    const int32_t* log_steps;
+    float* x_inter_out;
+    int32_t S;
+    int32_t B;
+    int32_t H;
+    int32_t W;
+    int32_t flags;                      /* FGDM_FLAG_* as for fgdm_apply_model */
+    int32_t n_log;
+    int32_t reserved0;                  /* 0 */
+    int32_t reserved1;                  /* 0 */
+} fgdm_ancestral_params;
+int fgdm_sample_ancestral(fgdm_engine* e, const fgdm_ancestral_params* p, void* stream);
+
+/* DDIM inversion x_0 -> x_{t_enc} without host callbacks: DDIMSampler.encode (controlnet/cldm/ddim_hacked.py:234-279).  Host tables of S entries in walk order, slot i belonging to timesteps[i] (int64,
+ * ascending t):
+ *   cx[i] = sqrt(a_next / a_cur), ce[i] = sqrt(a_next) (sqrt(1 / a_next - 1) - sqrt(1 / a_cur - 1))     (ddim_hacked.py:262-266)
+ * as fp32 (fgdm_amd.samplers.encode_tables computes them for both routes).  Per step the loop runs the network on cat([x] * 2) (or x,
+ * CFG off) at timesteps[i] and then ONE elementwise kernel (k_invert_loop_step): e = e_uncond + cfg_scale (e_cond - e_uncond) as
+ * fgdm_ddim_step's e_out, x = fgdm_axpby(x, cx[i], e, ce[i]), stored to the state, to both halves of the network's input and, on a
+ * logged step, to its x_inter_out slot.  The loop gives the bits of the per-step route of fgdm_amd/samplers.py.
+ * CFG (on when uncond is given and cfg_scale != 1, ONE 2B batch, FGDM_FLAG_CFG_PAIRS set by the loop), flags, hints, struct_size
+ * (from FGDM_DDIM_ENCODE_PARAMS_SIZE_V1), reserved0, log_steps / x_inter_out: as for fgdm_sample_plms.
+ * FGDM_ERR_ARG before any launch (x untouched): a struct_size outside that range, reserved0 != 0; a NULL x / cond / table; S, B, H or
+ * W <= 0; n_log < 0, n_log > 0 without log_steps, a log step outside [0, S) or not above its predecessor; an engine with
+ * in_channels > 4. */
+#define FGDM_DDIM_ENCODE_PARAMS_SIZE_V1 112
+typedef struct fgdm_ddim_encode_params {
+    int64_t struct_size;
+    float* x;                           /* device [B,4,H,W]: x_0 in, x_{t_enc} out */
+    const float* cond;                  /* device [B,tokens,context_dim] */
+    const float* uncond;                /* device, or NULL */
+    const int64_t* timesteps;
+    const float* cx;
+    const float* ce;
+    const float* control_scales;        /* host, n_controlnets * 13, or NULL */
+    const int32_t* log_steps;
+    float* x_inter_out;
+    float cfg_scale;
+    int32_t S;
+    int32_t B;
+    int32_t H;
+    int32_t W;
+    int32_t flags;                      /* FGDM_FLAG_* as for fgdm_apply_model */
+    int32_t n_log;
+    int32_t reserved0;                  /* 0 */
+} fgdm_ddim_encode_params;
+int fgdm_ddim_encode(fgdm_engine* e, const fgdm_ddim_encode_params* p, void* stream);
+
 /* Built-in kernel timer (no reference counterpart: the reference only prints wall-clock, scripts/txt2img.py:381-396).
  * Between begin and end every stride-th kernel launch is bracketed by HIP events on the launch stream
  * (work / bytes / time totals then refer to the bracketed launches only).
@@ -618,6 +712,23 @@ int fgdm_op_plms_loop_step(const float* x, const float* e_cond, const float* e_u
 int fgdm_op_dpmpp_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float inv_alpha,
                             float neg_sigma_over_alpha, const float* m1, int update_kind, float c1, float cm0, float cm1,
                             float* m0_out, float* x_out, float* xin_a, float* xin_b, int64_t n, void* stream);
+
+/* Diagnostic entries (tests/test_gpu_ancestral_loop.py); only the loops of fgdm_sample_ancestral / fgdm_ddim_encode launch these
+ * kernels in the product path.  n fp32 elements; every output may be NULL and nothing outside n elements is written.
+ *
+ * fgdm_op_ancestral_loop_step: one launch of k_ancestral_loop_step.  x' exactly as fgdm_ancestral_step (noise NULL or std == 0: no
+ *   noise term); mask given: x = q mask + (1 - mask) x' with q = sqrt_ac_t x0 + sqrt_one_minus_ac_t q_noise (fgdm_axpby then
+ *   fgdm_mask_blend: the blend of the SAME step), else x = x'; x -> x_out, xin, log_x (x_out may be x itself).
+ *   FGDM_ERR_ARG before any launch: x or eps NULL, n <= 0, mask without x0 or q_noise.
+ * fgdm_op_invert_loop_step: one launch of k_invert_loop_step.  e = e_uncond + cfg_scale (e_cond - e_uncond) (e_uncond NULL: e_cond),
+ *   x = cx x + ce e rounded as fgdm_axpby rounds it; x -> x_out, xin_a, xin_b, log_x (x_out may be x itself).
+ *   FGDM_ERR_ARG before any launch: x or e_cond NULL, n <= 0. */
+int fgdm_op_ancestral_loop_step(const float* x, const float* eps, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2,
+                                float std, const float* noise, const float* mask, const float* x0, const float* q_noise,
+                                float sqrt_ac_t, float sqrt_one_minus_ac_t, float* x_out, float* xin, float* log_x, int64_t n,
+                                void* stream);
+int fgdm_op_invert_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float cx, float ce,
+                             float* x_out, float* xin_a, float* xin_b, float* log_x, int64_t n, void* stream);
 
 /* Diagnostic entry (tests/test_gpu_qkv_projection.py); the product path does not call it.
  *
