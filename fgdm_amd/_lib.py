@@ -70,6 +70,13 @@ class FgdmDpmppParams(C.Structure):
             'n_eval', 'B', 'H', 'W', 'flags', 'reserved0', 'reserved1')]
 
 
+class FgdmDpmSolverParams(C.Structure):
+    """fgdm_dpm_solver_params of include/fgdm.h (fgdm_sample_dpm_solver); struct_size must be ctypes.sizeof of this class."""
+    _fields_ = [('struct_size', C.c_int64)] + [(name, C.c_void_p) for name in (
+        'x', 'cond', 'uncond', 'control_scales', 't_float', 'conv_x', 'conv_e', 'slot', 'nterms', 'plane', 'coef', 'dest')] + [
+            ('cfg_scale', C.c_float)] + [(name, C.c_int32) for name in ('n_eval', 'B', 'H', 'W', 'flags', 'reserved0', 'reserved1')]
+
+
 class FgdmAncestralParams(C.Structure):
     """fgdm_ancestral_params of include/fgdm.h (fgdm_sample_ancestral); struct_size must be ctypes.sizeof of this class."""
     _fields_ = [('struct_size', C.c_int64)] + [(name, C.c_void_p) for name in (
@@ -87,6 +94,7 @@ class FgdmDdimEncodeParams(C.Structure):
 
 
 DPMPP_FIRST, DPMPP_SECOND = 1, 2      # FGDM_DPMPP_FIRST / FGDM_DPMPP_SECOND
+DPM_PLANE_BASE, DPM_PLANE_HIST0, DPM_PLANE_M, DPM_DEST_STATE, DPM_DEST_EVAL = 0, 1, 4, 1, 2      # FGDM_DPM_PLANE_* / FGDM_DPM_DEST_*
 PLMS_PROBE, PLMS_FINISH_FIRST, PLMS_MULTISTEP = 0, 1, 2      # the modes of fgdm_op_plms_loop_step
 
 _p = C.c_void_p
@@ -138,6 +146,8 @@ SIGNATURES = {
     'fgdm_op_plms_loop_step': (_i, [_p, _p, _p, _f, _i, _i, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p,
                                     _i64, _p]),
     'fgdm_op_dpmpp_loop_step': (_i, [_p, _p, _p, _f, _f, _f, _p, _i, _f, _f, _f, _p, _p, _p, _p, _i64, _p]),
+    'fgdm_sample_dpm_solver': (_i, [_p, C.POINTER(FgdmDpmSolverParams), _p]),
+    'fgdm_op_dpm_program_step': (_i, [_p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
     'fgdm_sample_ancestral': (_i, [_p, C.POINTER(FgdmAncestralParams), _p]),
     'fgdm_ddim_encode': (_i, [_p, C.POINTER(FgdmDdimEncodeParams), _p]),
     'fgdm_op_ancestral_loop_step': (_i, [_p, _p, _f, _f, _f, _f, _f, _p, _p, _p, _p, _f, _f, _p, _p, _p, _i64, _p]),

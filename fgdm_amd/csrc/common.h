@@ -226,6 +226,27 @@ struct DpmppLoopStep {
     size_t n;
 };
 int dpmpp_loop_step(const DpmppLoopStep& a, hipStream_t s);
+// One launch per network evaluation of the device DPM-Solver program loop (k_dpm_program_step; fgdm_sample_dpm_solver), one pass:
+//   e = CFG(ec, eu);  m = conv_x == 0 ? e : axpby(x_eval, conv_x, e, conv_e) -> m_out (the record's history slot)
+//   acc = coef[0] p_0, then acc = fma(coef[j], p_j, acc) for j = 1 .. nterms - 1, p_j = term[j][i], or m where term[j] is NULL
+//   acc -> x_out, xin_a, xin_b (each may be NULL).
+// Every plane is read at element i before anything is written at i, by the same thread: an output may BE an input plane (x_out the
+// base plane, m_out a plane a term reads, xin_a x_eval); planes that overlap in any other way are not allowed.
+enum { DPM_PLANE_BASE = 0, DPM_PLANE_HIST0 = 1, DPM_PLANE_M = 4, DPM_MAX_TERMS = 5 };
+struct DpmProgramStep {
+    const float *x_eval, *ec, *eu;
+    const float* term[DPM_MAX_TERMS];
+    float coef[DPM_MAX_TERMS];
+    float *m_out, *x_out, *xin_a, *xin_b;
+    float cfg, conv_x, conv_e;
+    int nterms;
+    size_t n;
+};
+// term[] / coef[] / nterms / m_out of `a` from a record: planes[0] the base plane, planes[1..3] the history planes (NULL: absent),
+// src[j] in DPM_PLANE_* and slot in -1..2.  FGDM_ERR_ARG: nterms outside 1..5, an unknown plane or slot, a NULL plane a term or the
+// slot names.
+int dpm_program_terms(DpmProgramStep& a, float* const planes[4], int slot, int nterms, const int32_t* src, const float* coef);
+int dpm_program_step(const DpmProgramStep& a, hipStream_t s);
 int plms_combine(const float* e_t, const float* e1, const float* e2, const float* e3, int order,
                  float* e_prime, size_t n, hipStream_t s);
 int axpby(const float* a, float ca, const float* b, float cb, float* y, size_t n, hipStream_t s);

@@ -356,6 +356,57 @@ int dpmpp_loop_step(const DpmppLoopStep& a, hipStream_t s) {
     return LAUNCH_OK();
 }
 
+// The linear combination of a DPM-Solver program record: the first product rounded on its own, every further term fused into the
+// sum, in the record's order.
+__device__ __forceinline__ float lincomb_rn(const float* c, const float* p, int nterms) {
+    float acc = mul_rn(c[0], p[0]);
+#pragma unroll
+    for (int j = 1; j < DPM_MAX_TERMS; ++j)
+        if (j < nterms) acc = __builtin_fmaf(c[j], p[j], acc);
+    return acc;
+}
+// One launch per network evaluation of the device DPM-Solver program loop (fgdm_sample_dpm_solver) and of the per-step route
+// (fgdm_op_dpm_program_step): the model value m of the record (eps, or the data prediction of dpm_solver.py:386-399), kept in its
+// history slot, and the record's update as a linear combination of up to five planes (dpm_solver.py:504-857 expanded on the host).
+// No __restrict__: an output may be one of the input planes, so every load of element i comes before the first store to it.
+__global__ void k_dpm_program_step(const DpmProgramStep a) {
+    EW_LOOP(i, a.n) {
+        float e = a.ec[i];
+        if (a.eu) e = cfg_combine_rn(e, a.eu[i], a.cfg);
+        const float m = a.conv_x == 0.f ? e : axpby_rn(a.conv_x, a.x_eval[i], a.conv_e, e);
+        float p[DPM_MAX_TERMS];
+#pragma unroll
+        for (int j = 0; j < DPM_MAX_TERMS; ++j) p[j] = (j < a.nterms && a.term[j]) ? a.term[j][i] : m;
+        const float acc = lincomb_rn(a.coef, p, a.nterms);
+        if (a.m_out) a.m_out[i] = m;
+        if (a.x_out) a.x_out[i] = acc;
+        if (a.xin_a) a.xin_a[i] = acc;
+        if (a.xin_b) a.xin_b[i] = acc;
+    }
+}
+int dpm_program_terms(DpmProgramStep& a, float* const planes[4], int slot, int nterms, const int32_t* src, const float* coef) {
+    if (nterms < 1 || nterms > DPM_MAX_TERMS || !src || !coef || slot < -1 || slot > 2) return FGDM_ERR_ARG;
+    for (int j = 0; j < DPM_MAX_TERMS; ++j) { a.term[j] = nullptr; a.coef[j] = 0.f; }
+    for (int j = 0; j < nterms; ++j) {
+        if (src[j] < DPM_PLANE_BASE || src[j] > DPM_PLANE_M) return FGDM_ERR_ARG;
+        if (src[j] != DPM_PLANE_M && !planes[src[j]]) return FGDM_ERR_ARG;
+        a.term[j] = src[j] == DPM_PLANE_M ? nullptr : planes[src[j]];
+        a.coef[j] = coef[j];
+    }
+    a.nterms = nterms;
+    a.m_out = nullptr;
+    if (slot >= 0) {
+        if (!planes[DPM_PLANE_HIST0 + slot]) return FGDM_ERR_ARG;
+        a.m_out = planes[DPM_PLANE_HIST0 + slot];
+    }
+    return FGDM_OK;
+}
+int dpm_program_step(const DpmProgramStep& a, hipStream_t s) {
+    if (!a.ec || a.n == 0 || a.nterms < 1 || a.nterms > DPM_MAX_TERMS || (a.conv_x != 0.f && !a.x_eval)) return FGDM_ERR_ARG;
+    FGDM_LAUNCH(k_dpm_program_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
+    return LAUNCH_OK();
+}
+
 __global__ void k_plms(const float* __restrict__ e, const float* __restrict__ e1, const float* __restrict__ e2,
                        const float* __restrict__ e3, int order, float* __restrict__ out, size_t n) {
     EW_LOOP(i, n) out[i] = adams_bashforth_rn(order, e[i], e1, e2, e3, i);

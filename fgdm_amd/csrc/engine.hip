@@ -1872,7 +1872,7 @@ int fgdm_uint8_to_hint(const uint8_t* src, int B, int H, int W, int C, float* hi
     return u8_to_hint(src, hint, B, H * W, C, as_stream(stream));
 }
 
-// ---- the device sampler loops (fgdm_sample_ddim_ex, fgdm_sample_plms, fgdm_sample_dpmpp)
+// ---- the device sampler loops (fgdm_sample_ddim_ex, fgdm_sample_plms, fgdm_sample_dpmpp, fgdm_sample_dpm_solver, ...)
 // The caller's struct in the library's layout.  It may be any version this library knows: at least the first one, at most this
 // one; the fields its version did not have yet read as zero (absent).  false: a larger size holds fields this library cannot honour.
 static bool read_params(const void* caller, int64_t size_v1, void* known, size_t size_lib) {
@@ -2136,6 +2136,79 @@ int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* caller, void* str
         rc = dpmpp_loop_step(a, s);
     }
     loop_end(e, &w); e->arena.release(m); e->arena.release(tdev);
+    return rc;
+    });
+}
+
+// The checks of a DPM-Solver program, in front of any launch; empty: the program is consistent.
+static std::string dpm_program_error(const fgdm_dpm_solver_params* p) {
+    if (p->reserved0 != 0 || p->reserved1 != 0) return "reserved0 and reserved1 must be 0";
+    if (!p->x || !p->cond || !p->t_float || !p->conv_x || !p->conv_e || !p->slot || !p->nterms || !p->plane || !p->coef || !p->dest)
+        return "x, cond or a program array is NULL";
+    if (p->n_eval <= 0 || p->B <= 0 || p->H <= 0 || p->W <= 0) return "n_eval, B, H and W must be positive";
+    bool written[3] = {false, false, false};
+    for (int k = 0; k < p->n_eval; ++k) {
+        const std::string rec = "record " + std::to_string(k) + ": ";
+        const int nt = p->nterms[k];
+        if (nt < 1 || nt > DPM_MAX_TERMS) return rec + "nterms " + std::to_string(nt) + " is outside 1..5";
+        for (int j = 0; j < nt; ++j) {
+            const int src = p->plane[(size_t)k * DPM_MAX_TERMS + j];
+            if (src < FGDM_DPM_PLANE_BASE || src > FGDM_DPM_PLANE_M) return rec + "unknown plane " + std::to_string(src);
+            if (src >= FGDM_DPM_PLANE_HIST0 && src < FGDM_DPM_PLANE_M && !written[src - FGDM_DPM_PLANE_HIST0])
+                return rec + "reads history slot " + std::to_string(src - FGDM_DPM_PLANE_HIST0) + ", which no earlier record wrote";
+        }
+        if (p->slot[k] < -1 || p->slot[k] > 2) return rec + "slot " + std::to_string(p->slot[k]) + " is outside -1..2";
+        if (p->dest[k] != FGDM_DPM_DEST_STATE && p->dest[k] != FGDM_DPM_DEST_EVAL) return rec + "unknown destination " + std::to_string(p->dest[k]);
+        if (p->slot[k] >= 0) written[p->slot[k]] = true;
+    }
+    if (p->dest[p->n_eval - 1] != FGDM_DPM_DEST_STATE) return "the last record does not write the state";
+    return "";
+}
+
+// DPM_Solver.sample (dpm_solver.py:965-1124) as a program: per record one evaluation of the network on the evaluation input, then
+// one launch of k_dpm_program_step.  The evaluation input w.x2 is also the record's x_eval (read and rewritten in place); the state
+// x changes only behind a FGDM_DPM_DEST_STATE record, so the x at s survives the intermediate points of a singlestep update.
+int fgdm_sample_dpm_solver(fgdm_engine* e, const fgdm_dpm_solver_params* caller, void* stream) {
+    if (!e || !caller) return FGDM_ERR_ARG;
+    fgdm_dpm_solver_params known;
+    if (!read_params(caller, FGDM_DPM_SOLVER_PARAMS_SIZE_V1, &known, sizeof(known)))
+        return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpm_solver: struct_size is not the sizeof(fgdm_dpm_solver_params) of a known header version");
+    const fgdm_dpm_solver_params* p = &known;
+    const std::string why = dpm_program_error(p);
+    if (!why.empty()) return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpm_solver: " + why);
+    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpm_solver: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    hipStream_t s = as_stream(stream);
+    return scoped_call(e, stream, [&]() -> int {
+    const int K = p->n_eval, B = p->B, H = p->H, W = p->W;
+    const bool cfg_on = p->uncond && p->cfg_scale != 1.0f;
+    const int flags = cfg_on ? p->flags | FGDM_FLAG_CFG_PAIRS : p->flags & ~FGDM_FLAG_CFG_PAIRS;
+    LoopWork w;
+    int rc = loop_begin(e, p->cond, p->uncond, cfg_on, B, H, W, s, &w);
+    const int Bm = w.Bm;
+    const size_t n = w.n;
+    float* x = p->x;
+    float* hist = (float*)e->arena.alloc(3 * n * sizeof(float));      // the model value of a record lives in plane slot[k]
+    float* tdev = (float*)e->arena.alloc((size_t)K * Bm * sizeof(float));
+    if (rc == FGDM_OK && (!hist || !tdev)) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
+    if (rc != FGDM_OK) return rc;
+    CHK(upload_repeated(p->t_float, K, Bm, tdev, s));
+    HIP_TRY(hipMemcpyAsync(w.x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));      // x_T into the network's input, once
+    if (cfg_on) HIP_TRY(hipMemcpyAsync(w.x2 + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    float* const planes[4] = {x, hist, hist + n, hist + 2 * n};
+    for (int k = 0; k < K && rc == FGDM_OK; ++k) {
+        rc = e->apply_model(w.x2, nullptr, tdev + (size_t)k * Bm, nullptr, nullptr, p->control_scales, Bm, H, W, flags, w.eps);
+        if (rc != FGDM_OK) break;
+        DpmProgramStep a{};
+        rc = dpm_program_terms(a, planes, p->slot[k], p->nterms[k], p->plane + (size_t)k * DPM_MAX_TERMS, p->coef + (size_t)k * DPM_MAX_TERMS);
+        if (rc != FGDM_OK) break;
+        a.x_eval = w.x2; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr; a.cfg = p->cfg_scale;
+        a.conv_x = p->conv_x[k]; a.conv_e = p->conv_e[k];
+        a.x_out = p->dest[k] == FGDM_DPM_DEST_STATE ? x : nullptr;
+        if (k + 1 < K) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; }
+        rc = dpm_program_step(a, s);
+    }
+    loop_end(e, &w); e->arena.release(hist); e->arena.release(tdev);
     return rc;
     });
 }

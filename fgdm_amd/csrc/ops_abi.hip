@@ -358,6 +358,20 @@ int fgdm_op_dpmpp_loop_step(const float* x, const float* e_cond, const float* e_
     return dpmpp_loop_step(a, as_stream(stream));
 }
 
+// One launch of the DPM-Solver program loop's step kernel on caller-owned buffers: the per-step route of fgdm_amd/dpm_solver.py and
+// tests/test_gpu_dpm_solver_loop.py.
+int fgdm_op_dpm_program_step(const float* x_eval, const float* e_cond, const float* e_uncond, float cfg_scale, float conv_x, float conv_e,
+                             float* base, float* hist0, float* hist1, float* hist2, int slot, int nterms, const int32_t* planes,
+                             const float* coefs, float* x_out, float* xin_a, float* xin_b, int64_t n, void* stream) {
+    if (n <= 0) return FGDM_ERR_ARG;
+    DpmProgramStep a{};
+    float* const pl[4] = {base, hist0, hist1, hist2};
+    if (dpm_program_terms(a, pl, slot, nterms, planes, coefs) != FGDM_OK) return FGDM_ERR_ARG;
+    a.x_eval = x_eval; a.ec = e_cond; a.eu = e_uncond; a.cfg = cfg_scale; a.conv_x = conv_x; a.conv_e = conv_e;
+    a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.n = (size_t)n;
+    return dpm_program_step(a, as_stream(stream));
+}
+
 // Diagnostic entries of tests/test_gpu_ancestral_loop.py: one launch of the device ancestral loop's / the device DDIM inversion's
 // step kernel on caller-owned buffers.
 int fgdm_op_ancestral_loop_step(const float* x, const float* eps, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1, float coef2,

@@ -4,6 +4,7 @@
     from ldm.models.diffusion.ddim import DDIMSampler          # scripts/txt2img_fgdm_inference.py:18
     from ldm.models.diffusion.plms import PLMSSampler          # scripts/txt2img_fgdm_inference.py:19
     from ldm.models.diffusion.ddpm import LatentDiffusion
+    from ldm.models.diffusion.dpm_solver.dpm_solver import NoiseScheduleVP, model_wrapper, DPM_Solver
     from controlnet.cldm.ddim_hacked import DDIMSampler        # controlnet/initialize_cn.py:16
     from controlnet.cldm.cldm import ControlLDM
     import controlnet.initialize_cn as initialize_cn           # scripts/txt2img_fgdm_inference.py:25 (process, initialize_controlnet)
@@ -18,17 +19,22 @@ If the real reference packages are already imported, install(replace=True) swaps
 import sys
 import types
 
-from . import config, hack, initialize_cn, models, samplers, seg2image
+from . import config, dpm_solver, hack, initialize_cn, models, samplers, seg2image
 
 _CLDM_MODEL = {'load_state_dict': initialize_cn.load_state_dict, 'get_state_dict': initialize_cn.get_state_dict,
                'create_model': config.create_model}
 _HACK = {'hack_everything': hack.hack_everything, 'disable_verbosity': hack.disable_verbosity,
          'enable_sliced_attention': hack.enable_sliced_attention}      # controlnet/cldm/hack.py:11-28
+_DPM_SOLVER = {'NoiseScheduleVP': dpm_solver.NoiseScheduleVP, 'model_wrapper': dpm_solver.model_wrapper,
+               'DPM_Solver': dpm_solver.DPM_Solver}                       # ldm/models/diffusion/dpm_solver/dpm_solver.py
 _MAP = {
     'ldm.util': {'instantiate_from_config': config.instantiate_from_config},              # scripts/txt2img_fgdm_inference.py:17
     'ldm.models.diffusion.ddim': {'DDIMSampler': samplers.DDIMSampler},
     'ldm.models.diffusion.plms': {'PLMSSampler': samplers.PLMSSampler},
     'ldm.models.diffusion.dpm_solver': {'DPMSolverSampler': samplers.DPMSolverSampler},
+    'ldm.models.diffusion.dpm_solver.dpm_solver': _DPM_SOLVER,
+    'controlnet.ldm.models.diffusion.dpm_solver': {'DPMSolverSampler': samplers.DPMSolverSampler},
+    'controlnet.ldm.models.diffusion.dpm_solver.dpm_solver': _DPM_SOLVER,
     'ldm.models.diffusion.ddpm': {'LatentDiffusion': models.LatentDiffusion, 'DiffusionWrapper': models.DiffusionWrapper},
     'ldm.modules.distributions.distributions': {'DiagonalGaussianDistribution': models.DiagonalGaussianDistribution},
     'controlnet.ldm.util': {'instantiate_from_config': config.instantiate_from_config},

@@ -615,6 +615,30 @@ class Engine:
         self._run_loop('sample_dpmpp', p, keep, control_scales)
         return x
 
+    def sample_dpm_solver(self, x_T, cond, uncond, cfg_scale, program, control_scales=None, flags=0, out=None):
+        """A whole DPM-Solver sampling on the device (fgdm_sample_dpm_solver, include/fgdm.h).  program: the dict of equally long
+        per-evaluation lists of fgdm_amd.dpm_solver.dpm_solver_program (t_float, conv_x, conv_e, slot, nterms, dest, and plane /
+        coef with five entries per record).  Returns the final latent; x_T is not modified."""
+        name = 'sample_dpm_solver'
+        x, cond, uncond = self._loop_args(name, x_T, cond, uncond, out)
+        B, _, H, W = x.shape
+        K = len(program['t_float'])
+        keep = []
+        p = _lib.FgdmDpmSolverParams()
+        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
+        for k in ('t_float', 'conv_x', 'conv_e'):
+            setattr(p, k, self._table(name, keep, program[k], K))
+        for k in ('slot', 'nterms', 'dest'):
+            setattr(p, k, self._table(name, keep, program[k], K, C.c_int32, int))
+        for k, rows in (('plane', program['plane']), ('coef', program['coef'])):
+            if len(rows) != K or any(len(r) != 5 for r in rows):
+                raise ValueError(f'{name}: {k} must hold five entries for each of the {K} records')
+        p.plane = self._table(name, keep, [v for r in program['plane'] for v in r], 5 * K, C.c_int32, int)
+        p.coef = self._table(name, keep, [v for r in program['coef'] for v in r], 5 * K)
+        p.cfg_scale, p.n_eval, p.B, p.H, p.W, p.flags = float(cfg_scale), K, B, H, W, int(flags)
+        self._run_loop(name, p, keep, control_scales)
+        return x
+
     def _log_args(self, name, p, keep, x, log_steps, x_inter_out):
         """log_steps / n_log / x_inter_out of a loop's struct -> the [len(log_steps), B,4,H,W] plane (None without log steps)"""
         p.n_log = len(log_steps)
@@ -790,6 +814,22 @@ def axpby(a, ca, b, cb):
     if rc != 0:
         raise RuntimeError(f'fgdm_axpby failed: {rc}')
     return y
+
+
+def dpm_program_step(x_eval, e_cond, e_uncond, cfg_scale, conv_x, conv_e, base, hist, slot, planes, coefs):
+    """One record of a DPM-Solver program behind its network evaluation (fgdm_op_dpm_program_step, include/fgdm.h): the model value
+    goes to hist[slot] in place (slot -1: nowhere), the update's result is returned.  hist: the three history planes (None: absent)."""
+    lib = _lib.load()
+    n = len(planes)
+    out = torch.empty_like(base)
+    src, cf = (C.c_int32 * n)(*[int(v) for v in planes]), (C.c_float * n)(*[float(v) for v in coefs])
+    rc = lib.fgdm_op_dpm_program_step(_ptr(x_eval), _ptr(e_cond), _ptr(e_uncond), float(cfg_scale), float(conv_x), float(conv_e),
+                                      _ptr(base), _ptr(hist[0]), _ptr(hist[1]), _ptr(hist[2]), int(slot), n,
+                                      C.cast(src, C.c_void_p), C.cast(cf, C.c_void_p), _ptr(out), C.c_void_p(0), C.c_void_p(0),
+                                      base.numel(), _stream())
+    if rc != 0:
+        raise RuntimeError(f'fgdm_op_dpm_program_step failed: {rc}')
+    return out
 
 
 def mask_blend(a, b, mask):

@@ -450,6 +450,58 @@ typedef struct fgdm_dpmpp_params {
 } fgdm_dpmpp_params;
 int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* p, void* stream);
 
+/* The whole of DPM_Solver.sample (ldm/models/diffusion/dpm_solver/dpm_solver.py:965-1124) for the multistep and the singlestep
+ * solvers of order 1..3, noise or data prediction, as a PROGRAM: every update of the family is a linear combination of x and of model
+ * values kept from earlier evaluations, and the caller expands the reference's expressions (:504-857) into those coefficients
+ * (fgdm_amd.dpm_solver.dpm_solver_program).  One record per network evaluation k = 0 ... n_eval - 1 (host arrays):
+ *   t_float[k]             the model's time input, (t - 1/N) * 1000 (:278-287)
+ *   conv_x[k], conv_e[k]   the model value m of the record: conv_x == 0: m = eps; else m = conv_x x_eval + conv_e eps, the data
+ *                          prediction (x - sigma eps) / alpha (:386-399), x_eval being the input the network just ran on
+ *   slot[k] (int32)        the history plane (0..2) m is stored to, or -1: not stored
+ *   nterms[k] (int32), plane[5 k + j] (int32), coef[5 k + j]      the update acc = sum_j coef_j p_j over nterms in 1..5 terms: p_j is
+ *                          FGDM_DPM_PLANE_BASE (the state x), FGDM_DPM_PLANE_HIST0 + s (the history plane s, written by an earlier
+ *                          record) or FGDM_DPM_PLANE_M (this record's m).  Rounding: coef_0 p_0 on its own, then every further term
+ *                          fused into the sum, fma(coef_j, p_j, acc), in order
+ *   dest[k] (int32)        FGDM_DPM_DEST_STATE: acc becomes the state x and the next evaluation input; FGDM_DPM_DEST_EVAL: the next
+ *                          evaluation input only (the intermediate points of the singlestep solvers; x is kept)
+ * Per record the loop runs the network and launches ONE elementwise kernel (k_dpm_program_step, the kernel of
+ * fgdm_op_dpm_program_step): the loop gives the bits of the per-step route of fgdm_amd/dpm_solver.py over the same program.
+ * CFG, flags, hints, struct_size (from FGDM_DPM_SOLVER_PARAMS_SIZE_V1) and the reserved fields: as for fgdm_sample_dpmpp.
+ * FGDM_ERR_ARG before any launch (x untouched), with the offending record named in fgdm_last_error: a struct_size outside that
+ * range, a reserved field != 0; a NULL x / cond / array; n_eval, B, H or W <= 0; nterms outside 1..5; an unknown plane, slot or
+ * destination; a term that reads a history slot no earlier record wrote; a last record that is not FGDM_DPM_DEST_STATE; an engine
+ * with in_channels > 4.  Not part of a program, so not here: method='adaptive', thresholding (both need the data on the host). */
+#define FGDM_DPM_PLANE_BASE 0
+#define FGDM_DPM_PLANE_HIST0 1
+#define FGDM_DPM_PLANE_M 4
+#define FGDM_DPM_DEST_STATE 1
+#define FGDM_DPM_DEST_EVAL 2
+#define FGDM_DPM_SOLVER_PARAMS_SIZE_V1 136
+typedef struct fgdm_dpm_solver_params {
+    int64_t struct_size;
+    float* x;                           /* device [B,4,H,W]: x at t_start in, the sample out */
+    const float* cond;                  /* device [B,tokens,context_dim] */
+    const float* uncond;                /* device, or NULL */
+    const float* control_scales;        /* host, n_controlnets * 13, or NULL */
+    const float* t_float;
+    const float* conv_x;
+    const float* conv_e;
+    const int32_t* slot;
+    const int32_t* nterms;
+    const int32_t* plane;               /* [n_eval * 5] */
+    const float* coef;                  /* [n_eval * 5] */
+    const int32_t* dest;
+    float cfg_scale;
+    int32_t n_eval;
+    int32_t B;
+    int32_t H;
+    int32_t W;
+    int32_t flags;                      /* FGDM_FLAG_* as for fgdm_apply_model */
+    int32_t reserved0;                  /* 0 */
+    int32_t reserved1;                  /* 0 */
+} fgdm_dpm_solver_params;
+int fgdm_sample_dpm_solver(fgdm_engine* e, const fgdm_dpm_solver_params* p, void* stream);
+
 /* The ancestral sampler without host callbacks: LatentDiffusion.p_sample_loop / sample (ldm/models/diffusion/ddpm.py:1382-1448;
  * p_sample :1295-1323, q_posterior :290-297) over S consecutive timesteps.  There is no classifier-free guidance (p_sample has none).
  *
@@ -712,6 +764,20 @@ int fgdm_op_plms_loop_step(const float* x, const float* e_cond, const float* e_u
 int fgdm_op_dpmpp_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float inv_alpha,
                             float neg_sigma_over_alpha, const float* m1, int update_kind, float c1, float cm0, float cm1,
                             float* m0_out, float* x_out, float* xin_a, float* xin_b, int64_t n, void* stream);
+
+/* fgdm_op_dpm_program_step: one launch of k_dpm_program_step on caller-owned buffers of n fp32 elements -- what the per-step route of
+ * fgdm_amd/dpm_solver.py launches behind every network evaluation, and what fgdm_sample_dpm_solver launches per record.
+ *   e = e_uncond + cfg_scale (e_cond - e_uncond) (e_uncond NULL: e_cond);  m = e (conv_x == 0) or conv_x x_eval + conv_e e, rounded as
+ *   fgdm_axpby rounds it;  m -> the history plane `slot` (hist0..2; -1: not stored);  acc = coefs[0] p_0, then fma(coefs[j], p_j, acc)
+ *   for j = 1 .. nterms - 1, p_j by planes[j]: FGDM_DPM_PLANE_BASE `base`, FGDM_DPM_PLANE_HIST0 + s `hist<s>`, FGDM_DPM_PLANE_M the m
+ *   of this launch;  acc -> x_out, xin_a, xin_b (each may be NULL; nothing outside n elements is written).  planes / coefs: host.
+ *   Element i of every plane is read before anything is written at i, by the same thread: x_out may be base, the slot's plane may be
+ *   one a term reads, xin_a may be x_eval.  Planes that overlap in any other way are not allowed.
+ *   FGDM_ERR_ARG before any launch: n <= 0; nterms outside 1..5; planes or coefs NULL; an unknown plane or slot; a NULL plane that a
+ *   term or the slot names; e_cond NULL; x_eval NULL with conv_x != 0. */
+int fgdm_op_dpm_program_step(const float* x_eval, const float* e_cond, const float* e_uncond, float cfg_scale, float conv_x, float conv_e,
+                             float* base, float* hist0, float* hist1, float* hist2, int slot, int nterms, const int32_t* planes,
+                             const float* coefs, float* x_out, float* xin_a, float* xin_b, int64_t n, void* stream);
 
 /* Diagnostic entries (tests/test_gpu_ancestral_loop.py); only the loops of fgdm_sample_ancestral / fgdm_ddim_encode launch these
  * kernels in the product path.  n fp32 elements; every output may be NULL and nothing outside n elements is written.
