@@ -193,6 +193,16 @@ int transpose_pad_keys(const half_t* v, half_t* vt, int B, int Tk, int C, int Tk
 int ddim_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale,
               float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, const float* noise,
               float* x_prev, float* pred_x0, float* e_out, size_t n, hipStream_t s);
+// What every loop step kernel reads and writes besides its own planes: the state x, the network's output as ec / eu (eu NULL: no
+// CFG, e = ec), and where the new x goes: x_out, the two halves of the network's input and, on a logged step, log_x (each may be
+// NULL).  Element i of every input is read before anything is written at i, by the same thread: x_out and xin_a may BE x.  Planes
+// that overlap in any other way are not allowed, but for what a step struct says of its own planes.
+struct StepIO {
+    const float *x, *ec, *eu;
+    float *x_out, *xin_a, *xin_b, *log_x;
+    float cfg;
+    size_t n;
+};
 // One launch per network evaluation of the device DDIM and PLMS loops (k_loop_step).  e_t = CFG(ec, eu) -> e_out, then by mode
 //   LOOP_PLAIN        e' = e_t: a DDIM step (ddim.py:243-268)
 //   LOOP_PROBE        e' = e_t; x_prev = step(e') -> xin_a / xin_b only (plms.py:219-221)
@@ -200,47 +210,45 @@ int ddim_step(const float* x, const float* e_cond, const float* e_uncond, float 
 //   LOOP_MULTISTEP    e' = plms_combine(e_t, e1, e2, e3, order), order 1..3 (plms.py:224-232)
 // and, but for the probe: ddim_step's pred_x0 / x_prev from e' (plus sigma * noise, noise not NULL) -> log_x / log_p0 of a logged
 // step, then the NEXT step's inpainting blend x = q m + (1 - m) x_prev with q = sa_next x0 + s1m_next qnoise (mask NULL: x = x_prev),
-// stored to x_out and to the two halves of the network's input (each may be NULL).  ec NULL: no update (x_prev = x): the blend and
-// the input copies in front of the first step.  x_out may alias x, and e_out may alias e3 (each element is read before it is
-// written, by the same thread); nothing else may overlap.  (0..2 are the `mode` values of fgdm_op_plms_loop_step.)
+// stored as StepIO says.  ec NULL: no update (x_prev = x): the blend and the input copies in front of the first step.  e_out may be
+// e3.  (0..2 are the `mode` values of fgdm_op_plms_loop_step.)
 enum { LOOP_PROBE = 0, LOOP_FINISH_FIRST = 1, LOOP_MULTISTEP = 2, LOOP_PLAIN = 3 };
 struct LoopStep {
-    const float *x, *ec, *eu, *e1, *e2, *e3, *noise, *mask, *x0, *qnoise;
-    float *e_out, *x_out, *xin_a, *xin_b, *log_x, *log_p0;
-    float cfg, a_t, a_prev, sigma, s1m, sa_next, s1m_next;
+    StepIO io;
+    const float *e1, *e2, *e3, *noise, *mask, *x0, *qnoise;
+    float *e_out, *log_p0;
+    float a_t, a_prev, sigma, s1m, sa_next, s1m_next;
     int mode, order;
-    size_t n;
 };
 int loop_step(const LoopStep& a, hipStream_t s);
 // One launch per network evaluation of the device DPM-Solver++ loop (k_dpmpp_loop_step): the data prediction
 // m0 = axpby(x, inv_alpha, CFG(ec, eu), neg_sigma_over_alpha) -> m0_out, then the update to the next time:
 //   DPMPP_FIRST   x = axpby(x, c1, m0, cm0)                              (dpm_solver.py:504-528)
 //   DPMPP_SECOND  x = axpby(axpby(x, c1, m0, cm0), 1, m1, cm1)           (dpm_solver.py:755-789; two roundings, two axpby)
-// and x to x_out and the two input halves (each may be NULL).  x_out may alias x; nothing else may overlap.
+// stored as StepIO says (no log plane).
 enum { DPMPP_FIRST = 1, DPMPP_SECOND = 2 };
 struct DpmppLoopStep {
-    const float *x, *ec, *eu, *m1;
-    float *m0_out, *x_out, *xin_a, *xin_b;
-    float cfg, inv_alpha, neg_sigma_over_alpha, c1, cm0, cm1;
+    StepIO io;
+    const float* m1;
+    float* m0_out;
+    float inv_alpha, neg_sigma_over_alpha, c1, cm0, cm1;
     int kind;
-    size_t n;
 };
 int dpmpp_loop_step(const DpmppLoopStep& a, hipStream_t s);
 // One launch per network evaluation of the device DPM-Solver program loop (k_dpm_program_step; fgdm_sample_dpm_solver), one pass:
-//   e = CFG(ec, eu);  m = conv_x == 0 ? e : axpby(x_eval, conv_x, e, conv_e) -> m_out (the record's history slot)
+//   e = CFG(ec, eu);  m = conv_x == 0 ? e : axpby(io.x, conv_x, e, conv_e) -> m_out (the record's history slot)
 //   acc = coef[0] p_0, then acc = fma(coef[j], p_j, acc) for j = 1 .. nterms - 1, p_j = term[j][i], or m where term[j] is NULL
-//   acc -> x_out, xin_a, xin_b (each may be NULL).
-// Every plane is read at element i before anything is written at i, by the same thread: an output may BE an input plane (x_out the
-// base plane, m_out a plane a term reads, xin_a x_eval); planes that overlap in any other way are not allowed.
+//   acc stored as StepIO says (no log plane).
+// io.x is the input the network just ran on (read only where conv_x != 0), not the state: that is a term plane.  The term planes
+// are read like io.x: x_out may be the base plane, and m_out a plane a term reads.
 enum { DPM_PLANE_BASE = 0, DPM_PLANE_HIST0 = 1, DPM_PLANE_M = 4, DPM_MAX_TERMS = 5 };
 struct DpmProgramStep {
-    const float *x_eval, *ec, *eu;
+    StepIO io;
     const float* term[DPM_MAX_TERMS];
     float coef[DPM_MAX_TERMS];
-    float *m_out, *x_out, *xin_a, *xin_b;
-    float cfg, conv_x, conv_e;
+    float* m_out;
+    float conv_x, conv_e;
     int nterms;
-    size_t n;
 };
 // term[] / coef[] / nterms / m_out of `a` from a record: planes[0] the base plane, planes[1..3] the history planes (NULL: absent),
 // src[j] in DPM_PLANE_* and slot in -1..2.  FGDM_ERR_ARG: nterms outside 1..5, an unknown plane or slot, a NULL plane a term or the
@@ -254,23 +262,20 @@ int mask_blend(const float* a, const float* b, const float* m, float* y, size_t 
 int ancestral_step(const float* x, const float* eps, float sqrt_recip, float sqrt_recipm1, float coef1, float coef2,
                    float std, const float* noise, float* out, size_t n, hipStream_t s);
 // One launch per network evaluation of the device ancestral loop (k_ancestral_loop_step): x' = ancestral_step(x, eps, ..., noise)
-// (noise NULL or std == 0: the t == 0 step), then the inpainting blend of the SAME step, x = q m + (1 - m) x' with
-// q = sa_t x0 + s1m_t qnoise (mask NULL: x = x'; ddpm.py:1419-1421) -- k_loop_step blends in front of the NEXT step instead --
-// stored to x_out, the network's input xin and the log plane log_x (each may be NULL).  x_out may alias x; nothing else may overlap.
+// with eps = io.ec (p_sample has no CFG: io.eu is NULL; noise NULL or std == 0: the t == 0 step), then the inpainting blend of the
+// SAME step, x = q m + (1 - m) x' with q = sa_t x0 + s1m_t qnoise (mask NULL: x = x'; ddpm.py:1419-1421) -- k_loop_step blends in
+// front of the NEXT step instead -- stored as StepIO says, log plane included.
 struct AncestralLoopStep {
-    const float *x, *eps, *noise, *mask, *x0, *qnoise;
-    float *x_out, *xin, *log_x;
+    StepIO io;
+    const float *noise, *mask, *x0, *qnoise;
     float cr, crm1, c1, c2, std, sa_t, s1m_t;
-    size_t n;
 };
 int ancestral_loop_step(const AncestralLoopStep& a, hipStream_t s);
-// One launch per network evaluation of the device DDIM inversion (k_invert_loop_step): x_next = axpby(x, cx, CFG(ec, eu), ce)
-// (eu NULL: e = ec) to x_out, both input halves and the log plane (each may be NULL).  x_out may alias x; nothing else may overlap.
+// One launch per network evaluation of the device DDIM inversion (k_invert_loop_step): x_next = axpby(x, cx, CFG(ec, eu), ce),
+// stored as StepIO says, log plane included.
 struct InvertLoopStep {
-    const float *x, *ec, *eu;
-    float *x_out, *xin_a, *xin_b, *log_x;
-    float cfg, cx, ce;
-    size_t n;
+    StepIO io;
+    float cx, ce;
 };
 int invert_loop_step(const InvertLoopStep& a, hipStream_t s);
 

@@ -272,15 +272,28 @@ int ddim_step(const float* x, const float* e_cond, const float* e_uncond, float 
     return LAUNCH_OK();
 }
 
-// The next step's inpainting blend (k_axpby, then k_mask_blend; ddim.py:151-154) and the stores of x to the state and to both halves
-// of the network's cat([x] * 2) input: the tail of k_loop_step.
-__device__ __forceinline__ void loop_blend_store(float xp, size_t i, const float* mask, const float* x0, const float* qnoise,
-                                                 float sa_next, float s1m_next, float* x_out, float* xin_a, float* xin_b) {
+// The two ends every loop step kernel shares (StepIO, common.h): the network's e at element i (ec, or the CFG combine of k_ddim_step
+// where eu is given), and the stores of the new x to the state and to both halves of the network's cat([x] * 2) input.  The log store
+// stays with each kernel: they log different values.
+__device__ __forceinline__ float step_eps(const StepIO& io, size_t i) {
+    float e = io.ec[i];
+    if (io.eu) e = cfg_combine_rn(e, io.eu[i], io.cfg);
+    return e;
+}
+__device__ __forceinline__ void step_store(const StepIO& io, size_t i, float xn) {
+    if (io.x_out) io.x_out[i] = xn;
+    if (io.xin_a) io.xin_a[i] = xn;
+    if (io.xin_b) io.xin_b[i] = xn;
+}
+// ... and the host check of the I/O in front of every launch; need_ec: the kernel has no mode without an update
+static bool step_io_ok(const StepIO& io, bool need_ec = true, bool need_x = true) {
+    return (io.x || !need_x) && io.n != 0 && (io.ec || (!need_ec && !io.eu));
+}
+// The next step's inpainting blend (k_axpby, then k_mask_blend; ddim.py:151-154), then the shared store: the tail of k_loop_step.
+__device__ __forceinline__ void loop_blend_store(const LoopStep& a, size_t i, float xp) {
     float xn = xp;
-    if (mask) xn = mask_blend_rn(axpby_rn(sa_next, x0[i], s1m_next, qnoise[i]), xp, mask[i]);
-    if (x_out) x_out[i] = xn;
-    if (xin_a) xin_a[i] = xn;
-    if (xin_b) xin_b[i] = xn;
+    if (a.mask) xn = mask_blend_rn(axpby_rn(a.sa_next, a.x0[i], a.s1m_next, a.qnoise[i]), xp, a.mask[i]);
+    step_store(a.io, i, xn);
 }
 
 // One launch per network evaluation of the device DDIM and PLMS loops (fgdm_sample_ddim_ex, fgdm_sample_plms), one pass over the n
@@ -291,15 +304,13 @@ __device__ __forceinline__ void loop_blend_store(float xp, size_t i, const float
 //   multistep     e' = k_plms(e_t, e1, e2, e3, order)                                               plms.py:224-232
 // then pred_x0 / x_prev from e' as k_ddim_step (sigma * noise included; the PLMS loop leaves them 0 / NULL), the logged stores
 // (x_prev BEFORE the next step's blend, as the per-step loop appends it) and loop_blend_store.  ec NULL: no update, x_prev = x (the
-// blend and the input copies in front of the first step).  x_out may be x, and e_out may be e3 (element i is read before it is
-// written, by the same thread); every other buffer is distinct.
+// blend and the input copies in front of the first step).  e_out may be e3 (read before it is written, as StepIO says of x).
 __global__ void k_loop_step(const LoopStep a) {
     const float sa = sqrtf(a.a_t), sp = sqrtf(a.a_prev), dir = ddim_dir_rn(a.a_prev, a.sigma);
-    EW_LOOP(i, a.n) {
-        float xp = a.x[i];
-        if (a.ec) {
-            float e = a.ec[i];
-            if (a.eu) e = cfg_combine_rn(e, a.eu[i], a.cfg);
+    EW_LOOP(i, a.io.n) {
+        float xp = a.io.x[i];
+        if (a.io.ec) {
+            const float e = step_eps(a.io, i);
             float ep = e;
             if (a.mode == LOOP_FINISH_FIRST) ep = axpby_rn(0.5f, a.e1[i], 0.5f, e);
             else if (a.mode == LOOP_MULTISTEP) ep = adams_bashforth_rn(a.order, e, a.e1, a.e2, a.e3, i);
@@ -308,25 +319,25 @@ __global__ void k_loop_step(const LoopStep a) {
             xp = x_prev_rn(p0, ep, sp, dir);
             if (a.noise) xp = add_noise_rn(xp, a.sigma, a.noise[i]);
             if (a.mode == LOOP_PROBE) {
-                if (a.xin_a) a.xin_a[i] = xp;
-                if (a.xin_b) a.xin_b[i] = xp;
+                if (a.io.xin_a) a.io.xin_a[i] = xp;
+                if (a.io.xin_b) a.io.xin_b[i] = xp;
                 continue;
             }
-            if (a.log_x) a.log_x[i] = xp;
+            if (a.io.log_x) a.io.log_x[i] = xp;
             if (a.log_p0) a.log_p0[i] = p0;
         }
-        loop_blend_store(xp, i, a.mask, a.x0, a.qnoise, a.sa_next, a.s1m_next, a.x_out, a.xin_a, a.xin_b);
+        loop_blend_store(a, i, xp);
     }
 }
 int loop_step(const LoopStep& a, hipStream_t s) {
-    if (!a.x || a.n == 0 || (a.mask && (!a.x0 || !a.qnoise)) || (a.eu && !a.ec)) return FGDM_ERR_ARG;
-    if (a.ec) {
+    if (!step_io_ok(a.io, false) || (a.mask && (!a.x0 || !a.qnoise))) return FGDM_ERR_ARG;
+    if (a.io.ec) {
         if (a.mode != LOOP_PLAIN && a.mode != LOOP_PROBE && a.mode != LOOP_FINISH_FIRST && a.mode != LOOP_MULTISTEP) return FGDM_ERR_ARG;
         if (a.mode == LOOP_FINISH_FIRST && !a.e1) return FGDM_ERR_ARG;
         if (a.mode == LOOP_MULTISTEP && (a.order < 1 || a.order > 3 || !a.e1 || (a.order >= 2 && !a.e2) || (a.order >= 3 && !a.e3)))
             return FGDM_ERR_ARG;
     }
-    FGDM_LAUNCH(k_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
+    FGDM_LAUNCH(k_loop_step, dim3(ew_grid(a.io.n)), dim3(EW_BLOCK), 0, s, a);
     return LAUNCH_OK();
 }
 
@@ -336,23 +347,19 @@ int loop_step(const LoopStep& a, hipStream_t s) {
 //   second order  x = k_axpby(k_axpby(x, c1, m0, cm0), 1, m1, cm1)
 // and x to the state and to both halves of the network's input.
 __global__ void k_dpmpp_loop_step(const DpmppLoopStep a) {
-    EW_LOOP(i, a.n) {
-        const float xi = a.x[i];
-        float e = a.ec[i];
-        if (a.eu) e = cfg_combine_rn(e, a.eu[i], a.cfg);
+    EW_LOOP(i, a.io.n) {
+        const float xi = a.io.x[i];
+        const float e = step_eps(a.io, i);
         const float m0 = axpby_rn(a.inv_alpha, xi, a.neg_sigma_over_alpha, e);
         if (a.m0_out) a.m0_out[i] = m0;
         float xn = axpby_rn(a.c1, xi, a.cm0, m0);
         if (a.kind == DPMPP_SECOND) xn = axpby_rn(1.0f, xn, a.cm1, a.m1[i]);
-        if (a.x_out) a.x_out[i] = xn;
-        if (a.xin_a) a.xin_a[i] = xn;
-        if (a.xin_b) a.xin_b[i] = xn;
+        step_store(a.io, i, xn);
     }
 }
 int dpmpp_loop_step(const DpmppLoopStep& a, hipStream_t s) {
-    if (!a.x || !a.ec || a.n == 0 || (a.kind != DPMPP_FIRST && a.kind != DPMPP_SECOND) || (a.kind == DPMPP_SECOND && !a.m1))
-        return FGDM_ERR_ARG;
-    FGDM_LAUNCH(k_dpmpp_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
+    if (!step_io_ok(a.io) || (a.kind != DPMPP_FIRST && a.kind != DPMPP_SECOND) || (a.kind == DPMPP_SECOND && !a.m1)) return FGDM_ERR_ARG;
+    FGDM_LAUNCH(k_dpmpp_loop_step, dim3(ew_grid(a.io.n)), dim3(EW_BLOCK), 0, s, a);
     return LAUNCH_OK();
 }
 
@@ -370,18 +377,15 @@ __device__ __forceinline__ float lincomb_rn(const float* c, const float* p, int 
 // history slot, and the record's update as a linear combination of up to five planes (dpm_solver.py:504-857 expanded on the host).
 // No __restrict__: an output may be one of the input planes, so every load of element i comes before the first store to it.
 __global__ void k_dpm_program_step(const DpmProgramStep a) {
-    EW_LOOP(i, a.n) {
-        float e = a.ec[i];
-        if (a.eu) e = cfg_combine_rn(e, a.eu[i], a.cfg);
-        const float m = a.conv_x == 0.f ? e : axpby_rn(a.conv_x, a.x_eval[i], a.conv_e, e);
+    EW_LOOP(i, a.io.n) {
+        const float e = step_eps(a.io, i);
+        const float m = a.conv_x == 0.f ? e : axpby_rn(a.conv_x, a.io.x[i], a.conv_e, e);
         float p[DPM_MAX_TERMS];
 #pragma unroll
         for (int j = 0; j < DPM_MAX_TERMS; ++j) p[j] = (j < a.nterms && a.term[j]) ? a.term[j][i] : m;
         const float acc = lincomb_rn(a.coef, p, a.nterms);
         if (a.m_out) a.m_out[i] = m;
-        if (a.x_out) a.x_out[i] = acc;
-        if (a.xin_a) a.xin_a[i] = acc;
-        if (a.xin_b) a.xin_b[i] = acc;
+        step_store(a.io, i, acc);
     }
 }
 int dpm_program_terms(DpmProgramStep& a, float* const planes[4], int slot, int nterms, const int32_t* src, const float* coef) {
@@ -402,8 +406,8 @@ int dpm_program_terms(DpmProgramStep& a, float* const planes[4], int slot, int n
     return FGDM_OK;
 }
 int dpm_program_step(const DpmProgramStep& a, hipStream_t s) {
-    if (!a.ec || a.n == 0 || a.nterms < 1 || a.nterms > DPM_MAX_TERMS || (a.conv_x != 0.f && !a.x_eval)) return FGDM_ERR_ARG;
-    FGDM_LAUNCH(k_dpm_program_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
+    if (!step_io_ok(a.io, true, a.conv_x != 0.f) || a.nterms < 1 || a.nterms > DPM_MAX_TERMS) return FGDM_ERR_ARG;
+    FGDM_LAUNCH(k_dpm_program_step, dim3(ew_grid(a.io.n)), dim3(EW_BLOCK), 0, s, a);
     return LAUNCH_OK();
 }
 
@@ -465,21 +469,20 @@ int ancestral_step(const float* x, const float* eps, float sqrt_recip, float sqr
 // DDIM-family walks (k_loop_step) blend IN FRONT of the next step, at the next timestep, and log x_prev before that blend.  So a
 // walk cut into several calls carries nothing over but x.  There is no CFG: p_sample has none.
 __global__ void k_ancestral_loop_step(const AncestralLoopStep a) {
-    EW_LOOP(i, a.n) {
-        float xn = ancestral_rn(a.x[i], a.eps[i], a.cr, a.crm1, a.c1, a.c2, a.std, a.noise, i);
+    EW_LOOP(i, a.io.n) {
+        float xn = ancestral_rn(a.io.x[i], step_eps(a.io, i), a.cr, a.crm1, a.c1, a.c2, a.std, a.noise, i);
         if (a.mask) xn = mask_blend_rn(axpby_rn(a.sa_t, a.x0[i], a.s1m_t, a.qnoise[i]), xn, a.mask[i]);
-        if (a.x_out) a.x_out[i] = xn;
-        if (a.xin) a.xin[i] = xn;
-        if (a.log_x) a.log_x[i] = xn;
+        step_store(a.io, i, xn);
+        if (a.io.log_x) a.io.log_x[i] = xn;
     }
 }
 int ancestral_loop_step(const AncestralLoopStep& a, hipStream_t s) {
-    if (!a.x || !a.eps || a.n == 0 || (a.mask && (!a.x0 || !a.qnoise))) return FGDM_ERR_ARG;
+    if (!step_io_ok(a.io) || (a.mask && (!a.x0 || !a.qnoise))) return FGDM_ERR_ARG;
     AncestralLoopStep b = a;
     // std == 0 is the t == 0 step: the per-step route hands k_ancestral no noise there.  (With temperature 0 std is 0 at t > 0 too,
     // where that route computes fma(0, noise, mean): a difference only in the sign of an exact zero, or on non-finite noise.)
     if (b.std == 0.f) b.noise = nullptr;
-    FGDM_LAUNCH(k_ancestral_loop_step, dim3(ew_grid(b.n)), dim3(EW_BLOCK), 0, s, b);
+    FGDM_LAUNCH(k_ancestral_loop_step, dim3(ew_grid(b.io.n)), dim3(EW_BLOCK), 0, s, b);
     return LAUNCH_OK();
 }
 
@@ -487,19 +490,15 @@ int ancestral_loop_step(const AncestralLoopStep& a, hipStream_t s) {
 // e = CFG(ec, eu) as k_ddim_step's e_out, x_next = k_axpby(x, cx, e, ce), stored to the state, to both halves of the network's
 // input and, on a logged step, to the log plane.
 __global__ void k_invert_loop_step(const InvertLoopStep a) {
-    EW_LOOP(i, a.n) {
-        float e = a.ec[i];
-        if (a.eu) e = cfg_combine_rn(e, a.eu[i], a.cfg);
-        const float xn = axpby_rn(a.cx, a.x[i], a.ce, e);
-        if (a.x_out) a.x_out[i] = xn;
-        if (a.xin_a) a.xin_a[i] = xn;
-        if (a.xin_b) a.xin_b[i] = xn;
-        if (a.log_x) a.log_x[i] = xn;
+    EW_LOOP(i, a.io.n) {
+        const float xn = axpby_rn(a.cx, a.io.x[i], a.ce, step_eps(a.io, i));
+        step_store(a.io, i, xn);
+        if (a.io.log_x) a.io.log_x[i] = xn;
     }
 }
 int invert_loop_step(const InvertLoopStep& a, hipStream_t s) {
-    if (!a.x || !a.ec || a.n == 0) return FGDM_ERR_ARG;
-    FGDM_LAUNCH(k_invert_loop_step, dim3(ew_grid(a.n)), dim3(EW_BLOCK), 0, s, a);
+    if (!step_io_ok(a.io)) return FGDM_ERR_ARG;
+    FGDM_LAUNCH(k_invert_loop_step, dim3(ew_grid(a.io.n)), dim3(EW_BLOCK), 0, s, a);
     return LAUNCH_OK();
 }
 

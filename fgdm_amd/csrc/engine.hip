@@ -1486,6 +1486,126 @@ template <typename F> static int scoped_call(fgdm_engine* e, void* stream, F f) 
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------------ device sampler loops: the driver
+// The caller's struct in the library's layout.  It may be any version this library knows: at least the first one, at most this
+// one; the fields its version did not have yet read as zero (absent).  false: a larger size holds fields this library cannot honour.
+static bool read_params(const void* caller, int64_t size_v1, void* known, size_t size_lib) {
+    int64_t size;
+    memcpy(&size, caller, sizeof(size));      // struct_size leads every parameter struct
+    if (size < size_v1 || size > (int64_t)size_lib) return false;
+    memset(known, 0, size_lib);
+    memcpy(known, caller, (size_t)size);
+    return true;
+}
+
+// The network's time argument of every evaluation: host entry k, Bm times, at dev[k * Bm].
+template <typename T> static int upload_repeated(const T* host, int count, int Bm, T* dev, hipStream_t s) {
+    std::vector<T> th((size_t)count * Bm);
+    for (int k = 0; k < count; ++k) for (int b = 0; b < Bm; ++b) th[(size_t)k * Bm + b] = host[k];
+    HIP_TRY(hipMemcpyAsync(dev, th.data(), th.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));   // th is a local: the copy must finish before it goes out of scope
+    return FGDM_OK;
+}
+
+// CFG of a loop: on when uncond is given and the scale is not 1, and then the loop owns FGDM_FLAG_CFG_PAIRS
+static bool loop_cfg_on(const float* uncond, float cfg_scale) { return uncond && cfg_scale != 1.0f; }
+static int loop_flags(int flags, bool cfg_on) { return cfg_on ? flags | FGDM_FLAG_CFG_PAIRS : flags & ~FGDM_FLAG_CFG_PAIRS; }
+
+// The driver of the six device loops (inside the entry's scoped_call).  It owns what every loop holds while it runs -- the
+// network's input x2 (Bm rows: cat([x] * 2), or x with CFG off), its output eps, the loop-invariant context cat([uncond, cond])
+// (ddim.py:226), registered (projected) once so that every evaluation passes ctx = NULL, the history planes an entry asks for and
+// the device time table (int64 timesteps or fractional times, whichever the entry has) -- and does every allocation, copy and
+// network evaluation of a loop.  An entry keeps its coefficients, its history rotation and its step kernel.
+struct Loop {
+    fgdm_engine* e;
+    hipStream_t s;
+    float* x;                       // the caller's state
+    const float* control_scales;
+    int B, H, W, K, flags;          // K evaluations' times; the flags as the entry resolved them
+    bool cfg_on;
+    const int32_t* log_steps;
+    int n_log;
+    float *x2 = nullptr, *eps = nullptr, *c2 = nullptr, *hist = nullptr;
+    int64_t* t_int = nullptr;
+    float* t_float = nullptr;
+    int Bm = 0, logged = 0;
+    size_t n = 0;
+
+    // P: a public parameter struct, or a Walk
+    template <typename P> Loop(fgdm_engine* e_, hipStream_t s_, const P& p, int K_, bool cfg_on_, int flags_, const int32_t* log_steps_ = nullptr, int n_log_ = 0)
+        : e(e_), s(s_), x(p.x), control_scales(p.control_scales), B(p.B), H(p.H), W(p.W), K(K_), flags(flags_), cfg_on(cfg_on_),
+          log_steps(log_steps_), n_log(n_log_) {}
+
+    int begin(const float* cond, const float* uncond, const int64_t* times_int, const float* times_float, int hist_planes) {
+        Bm = cfg_on ? 2 * B : B;
+        n = (size_t)B * 4 * H * W;
+        const size_t nctx = (size_t)B * e->ctx_tokens * e->cfg.context_dim;
+        x2 = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
+        eps = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
+        c2 = (float*)e->arena.alloc(Bm * (size_t)e->ctx_tokens * e->cfg.context_dim * sizeof(float));
+        if (!x2 || !eps || !c2) return e->fail(FGDM_ERR_NOMEM, "workspace");
+        if (cfg_on) {
+            HIP_TRY(hipMemcpyAsync(c2, uncond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(c2 + nctx, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+        } else {
+            HIP_TRY(hipMemcpyAsync(c2, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        CHK(e->set_context(c2, Bm));
+        if (hist_planes) hist = (float*)e->arena.alloc(hist_planes * n * sizeof(float));
+        void* tdev = e->arena.alloc((size_t)K * Bm * (times_int ? sizeof(int64_t) : sizeof(float)));
+        if (!tdev || (hist_planes && !hist)) return e->fail(FGDM_ERR_NOMEM, "workspace");
+        if (times_int) return upload_repeated(times_int, K, Bm, t_int = (int64_t*)tdev, s);
+        return upload_repeated(times_float, K, Bm, t_float = (float*)tdev, s);
+    }
+    float* plane(int j) const { return hist + (size_t)j * n; }
+    // x into the network's input, once, for the loops whose first launch is not a blend
+    int seed() {
+        HIP_TRY(hipMemcpyAsync(x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (cfg_on) HIP_TRY(hipMemcpyAsync(x2 + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return FGDM_OK;
+    }
+    // the network on x2 at time table entry k
+    int eval(int k) {
+        return e->apply_model(x2, t_int ? t_int + (size_t)k * Bm : nullptr, t_float ? t_float + (size_t)k * Bm : nullptr, nullptr, nullptr,
+                              control_scales, Bm, H, W, flags, eps);
+    }
+    void feed(StepIO& io) const { io.xin_a = x2; io.xin_b = cfg_on ? x2 + n : nullptr; }
+    // the I/O of step i of K behind its evaluation: the input halves only when another evaluation follows
+    StepIO step_io(int i, float cfg) const {
+        StepIO io{};
+        io.x = x; io.n = n; io.ec = cfg_on ? eps + n : eps; io.eu = cfg_on ? eps : nullptr; io.cfg = cfg; io.x_out = x;
+        if (i + 1 < K) feed(io);
+        return io;
+    }
+    // step i's slot in the log tensors, or -1: not logged
+    int log_slot(int i) { return logged < n_log && log_steps[logged] == i ? logged++ : -1; }
+    float* log_plane(float* out, int slot) const { return out && slot >= 0 ? out + (size_t)slot * n : nullptr; }
+    int end(int rc) {
+        e->arena.release(x2); e->arena.release(eps); e->arena.release(c2); e->arena.release(hist);
+        e->arena.release(t_int); e->arena.release(t_float);
+        return rc;
+    }
+};
+
+// What the six entries do in front of their loop, in this order: NULL engine or struct; the struct's size; the entry's own checks
+// (`check`: nullptr / empty = consistent); hybrid networks; unfinalized weights; then `body(e, known, stream)` in a scoped_call.
+static std::string why_text(const char* why) { return why ? why : ""; }
+static std::string why_text(const std::string& why) { return why; }
+template <typename P, typename Check, typename Body>
+static int loop_entry(fgdm_engine* e, const P* caller, void* stream, int64_t size_v1, const char* entry, const char* struct_name,
+                      bool refuse_hybrid, Check check, Body body) {
+    if (!e || !caller) return FGDM_ERR_ARG;
+    const std::string name = entry;
+    P known;
+    if (!read_params(caller, size_v1, &known, sizeof(known)))
+        return e->fail(FGDM_ERR_ARG, name + ": struct_size is not the sizeof(" + struct_name + ") of a known header version");
+    const std::string why = why_text(check(known));
+    if (!why.empty()) return e->fail(FGDM_ERR_ARG, name + ": " + why);
+    if (refuse_hybrid && e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, name + ": in_channels > 4 (hybrid c_concat) is not taken by the device loops");
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    return scoped_call(e, stream, [&] { return body(e, known, as_stream(stream)); });
+}
+
 extern "C" {
 
 int fgdm_create(const fgdm_config* cfg, int device, fgdm_engine** out) {
@@ -1873,52 +1993,6 @@ int fgdm_uint8_to_hint(const uint8_t* src, int B, int H, int W, int C, float* hi
 }
 
 // ---- the device sampler loops (fgdm_sample_ddim_ex, fgdm_sample_plms, fgdm_sample_dpmpp, fgdm_sample_dpm_solver, ...)
-// The caller's struct in the library's layout.  It may be any version this library knows: at least the first one, at most this
-// one; the fields its version did not have yet read as zero (absent).  false: a larger size holds fields this library cannot honour.
-static bool read_params(const void* caller, int64_t size_v1, void* known, size_t size_lib) {
-    int64_t size;
-    memcpy(&size, caller, sizeof(size));      // struct_size leads every parameter struct
-    if (size < size_v1 || size > (int64_t)size_lib) return false;
-    memset(known, 0, size_lib);
-    memcpy(known, caller, (size_t)size);
-    return true;
-}
-
-// What every loop holds while it runs: the network's input (Bm rows), its output, and the loop-invariant context
-// cat([uncond, cond]) (ddim.py:226), registered (projected) once so that every evaluation passes ctx = NULL.
-struct LoopWork {
-    float *x2 = nullptr, *eps = nullptr, *c2 = nullptr;
-    int Bm = 0;
-    size_t n = 0;
-};
-static int loop_begin(fgdm_engine* e, const float* cond, const float* uncond, bool cfg_on, int B, int H, int W, hipStream_t s, LoopWork* w) {
-    w->Bm = cfg_on ? 2 * B : B;
-    w->n = (size_t)B * 4 * H * W;
-    const size_t nctx = (size_t)B * e->ctx_tokens * e->cfg.context_dim;
-    w->x2 = (float*)e->arena.alloc(w->Bm * 4 * (size_t)H * W * sizeof(float));
-    w->eps = (float*)e->arena.alloc(w->Bm * 4 * (size_t)H * W * sizeof(float));
-    w->c2 = (float*)e->arena.alloc(w->Bm * (size_t)e->ctx_tokens * e->cfg.context_dim * sizeof(float));
-    if (!w->x2 || !w->eps || !w->c2) return e->fail(FGDM_ERR_NOMEM, "workspace");
-    if (cfg_on) {
-        HIP_TRY(hipMemcpyAsync(w->c2, uncond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(w->c2 + nctx, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
-    } else {
-        HIP_TRY(hipMemcpyAsync(w->c2, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    return e->set_context(w->c2, w->Bm);
-}
-static void loop_end(fgdm_engine* e, LoopWork* w) {
-    e->arena.release(w->x2); e->arena.release(w->eps); e->arena.release(w->c2);
-}
-// The network's time argument of every evaluation: host entry k, Bm times, at dev[k * Bm].
-extern "C++" template <typename T> static int upload_repeated(const T* host, int count, int Bm, T* dev, hipStream_t s) {
-    std::vector<T> th((size_t)count * Bm);
-    for (int k = 0; k < count; ++k) for (int b = 0; b < Bm; ++b) th[(size_t)k * Bm + b] = host[k];
-    HIP_TRY(hipMemcpyAsync(dev, th.data(), th.size() * sizeof(T), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));   // th is a local: the copy must finish before it goes out of scope
-    return FGDM_OK;
-}
-
 // A walk of the DDIM family, as fgdm_sample_ddim_ex and fgdm_sample_plms fill it from their public structs: the fields the two
 // share by name (walk_from), the DDIM entry's sigmas / step_noise / cfg_scales (NULL: absent), and what the entry has resolved:
 // cfg_on (one decision for the whole walk: the registered context has Bm rows), the flags of every evaluation, and `plms`.
@@ -1972,19 +2046,11 @@ static const char* walk_error(const Walk& p) {
 // one launch of k_loop_step, which also does the NEXT step's blend and writes x into the network's input.  PLMS (plms.py:178-236)
 // differs in the three history planes, the probe and the second evaluation of the first step, and the mode / order of the launch.
 static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
-    const int S = p.S, H = p.H, W = p.W;
-    const bool cfg_on = p.cfg_on;
-    LoopWork w;
-    int rc = loop_begin(e, p.cond, p.uncond, cfg_on, p.B, H, W, s, &w);
-    const int Bm = w.Bm;
-    const size_t n = w.n;
-    float* x = p.x;
-    float* hist = p.plms ? (float*)e->arena.alloc(3 * n * sizeof(float)) : nullptr;      // e_t of step j lives in plane j % 3
-    int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * Bm * sizeof(int64_t));
-    if (rc == FGDM_OK && (!tdev || (p.plms && !hist))) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
-    if (rc != FGDM_OK) return rc;
-    CHK(upload_repeated(p.timesteps, S, Bm, tdev, s));
-    auto plane = [&](int step) { return hist + (size_t)(step % 3) * n; };
+    const int S = p.S;
+    Loop L(e, s, p, S, p.cfg_on, p.flags, p.log_steps, p.n_log);
+    CHK(L.begin(p.cond, p.uncond, p.timesteps, nullptr, p.plms ? 3 : 0));      // PLMS: e_t of step j lives in plane j % 3
+    const size_t n = L.n;
+    auto plane = [&](int step) { return L.plane(step % 3); };
     // the blend in front of step `i` (index k = S - 1 - i), done by the kernel of the step before it
     auto blend = [&](LoopStep& a, int i) {
         if (!p.mask) return;
@@ -1992,25 +2058,20 @@ static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
         a.mask = p.mask; a.x0 = p.x0; a.qnoise = p.q_noise + (size_t)i * n;
         a.sa_next = p.sqrt_alphas_cumprod_t[k]; a.s1m_next = p.sqrt_one_minus_alphas_cumprod_t[k];
     };
-    auto inputs = [&](LoopStep& a) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; };
-    auto eval = [&](int index) {
-        return e->apply_model(w.x2, tdev + (size_t)index * Bm, nullptr, nullptr, nullptr, p.control_scales, Bm, H, W, p.flags, w.eps);
-    };
+    int rc;
     {                                   // in front of the first step: its blend, and x into the network's input
         LoopStep a{};
-        a.x = x; a.n = n; inputs(a);
+        a.io.x = L.x; a.io.n = n; L.feed(a.io);
         blend(a, 0);
-        a.x_out = p.mask ? x : nullptr;
+        a.io.x_out = p.mask ? L.x : nullptr;
         rc = loop_step(a, s);
     }
-    int logged = 0;
     for (int i = 0; i < S && rc == FGDM_OK; ++i) {
         const int index = S - 1 - i;   // reversed walk (ddim.py:137,148; plms.py:138,150)
-        rc = eval(index);
+        rc = L.eval(index);
         if (rc != FGDM_OK) break;
         LoopStep a{};
-        a.x = x; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr;
-        a.cfg = p.cfg_scales ? p.cfg_scales[i] : p.cfg_scale;
+        a.io = L.step_io(i, p.cfg_scales ? p.cfg_scales[i] : p.cfg_scale);
         a.a_t = p.alphas[index]; a.a_prev = p.alphas_prev[index]; a.s1m = p.sqrt_one_minus_alphas[index];
         a.sigma = p.sigmas ? p.sigmas[index] : 0.f;
         a.noise = a.sigma != 0.f ? p.step_noise + (size_t)i * n : nullptr;
@@ -2018,9 +2079,9 @@ static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
             a.mode = LOOP_PLAIN;
         } else if (i == 0) {            // pseudo improved Euler (plms.py:219-223): probe, second evaluation at t_next, finish
             LoopStep probe = a;
-            probe.mode = LOOP_PROBE; probe.e_out = plane(0); inputs(probe);
+            probe.mode = LOOP_PROBE; probe.e_out = plane(0); L.feed(probe.io);
             rc = loop_step(probe, s);
-            if (rc == FGDM_OK) rc = eval(S >= 2 ? S - 2 : 0);
+            if (rc == FGDM_OK) rc = L.eval(S >= 2 ? S - 2 : 0);
             if (rc != FGDM_OK) break;
             a.mode = LOOP_FINISH_FIRST; a.e1 = plane(0);
         } else {                        // Adams-Bashforth over the last min(i, 3) planes (plms.py:224-232)
@@ -2029,31 +2090,29 @@ static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
             if (i >= 2) a.e2 = plane(i - 2);
             if (i >= 3) a.e3 = plane(i - 3);      // the plane e_out replaces
         }
-        a.x_out = x;
-        if (i + 1 < S) { blend(a, i + 1); inputs(a); }
-        if (logged < p.n_log && p.log_steps[logged] == i) {
-            a.log_x = p.x_inter_out ? p.x_inter_out + (size_t)logged * n : nullptr;
-            a.log_p0 = p.pred_x0_out ? p.pred_x0_out + (size_t)logged * n : nullptr;
-            ++logged;
-        }
+        if (i + 1 < S) blend(a, i + 1);
+        const int slot = L.log_slot(i);
+        a.io.log_x = L.log_plane(p.x_inter_out, slot); a.log_p0 = L.log_plane(p.pred_x0_out, slot);
         rc = loop_step(a, s);
     }
-    loop_end(e, &w); e->arena.release(hist); e->arena.release(tdev);
-    return rc;
+    return L.end(rc);
 }
 
-int fgdm_sample_ddim_ex(fgdm_engine* e, const fgdm_ddim_params* caller, void* stream) {
-    if (!e || !caller) return FGDM_ERR_ARG;
-    fgdm_ddim_params known;
-    if (!read_params(caller, FGDM_DDIM_PARAMS_SIZE_V1, &known, sizeof(known)))
-        return e->fail(FGDM_ERR_ARG, "fgdm_sample_ddim_ex: struct_size is not the sizeof(fgdm_ddim_params) of a known header version");
+static Walk ddim_walk(const fgdm_ddim_params& known) {
     Walk p = walk_from(known);
     p.sigmas = known.sigmas; p.step_noise = known.step_noise; p.cfg_scales = known.cfg_scales;
-    if (const char* why = walk_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_ddim_ex: ") + why);
-    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
-    if (p.uncond)                       // CFG is on when any step's scale is not 1; the flags go to the network as given
-        for (int i = 0; i < p.S && !p.cfg_on; ++i) p.cfg_on = (p.cfg_scales ? p.cfg_scales[i] : p.cfg_scale) != 1.0f;
-    return scoped_call(e, stream, [&] { return run_walk(e, p, as_stream(stream)); });
+    return p;
+}
+// This entry takes hybrid networks, and the flags go to the network as given; CFG is on when any step's scale is not 1
+int fgdm_sample_ddim_ex(fgdm_engine* e, const fgdm_ddim_params* caller, void* stream) {
+    return loop_entry(e, caller, stream, FGDM_DDIM_PARAMS_SIZE_V1, "fgdm_sample_ddim_ex", "fgdm_ddim_params", false,
+                      [](const fgdm_ddim_params& known) { return walk_error(ddim_walk(known)); },
+                      [](fgdm_engine* e, const fgdm_ddim_params& known, hipStream_t s) {
+                          Walk p = ddim_walk(known);
+                          if (p.uncond)
+                              for (int i = 0; i < p.S && !p.cfg_on; ++i) p.cfg_on = (p.cfg_scales ? p.cfg_scales[i] : p.cfg_scale) != 1.0f;
+                          return run_walk(e, p, s);
+                      });
 }
 
 int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* uncond, float cfg_scale, int S,
@@ -2070,18 +2129,15 @@ int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* u
 }
 
 int fgdm_sample_plms(fgdm_engine* e, const fgdm_plms_params* caller, void* stream) {
-    if (!e || !caller) return FGDM_ERR_ARG;
-    fgdm_plms_params known;
-    if (!read_params(caller, FGDM_PLMS_PARAMS_SIZE_V1, &known, sizeof(known)))
-        return e->fail(FGDM_ERR_ARG, "fgdm_sample_plms: struct_size is not the sizeof(fgdm_plms_params) of a known header version");
-    Walk p = walk_from(known);
-    if (const char* why = walk_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_plms: ") + why);
-    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_sample_plms: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
-    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
-    p.plms = true;
-    p.cfg_on = p.uncond && p.cfg_scale != 1.0f;
-    p.flags = p.cfg_on ? p.flags | FGDM_FLAG_CFG_PAIRS : p.flags & ~FGDM_FLAG_CFG_PAIRS;
-    return scoped_call(e, stream, [&] { return run_walk(e, p, as_stream(stream)); });
+    return loop_entry(e, caller, stream, FGDM_PLMS_PARAMS_SIZE_V1, "fgdm_sample_plms", "fgdm_plms_params", true,
+                      [](const fgdm_plms_params& known) { return walk_error(walk_from(known)); },
+                      [](fgdm_engine* e, const fgdm_plms_params& known, hipStream_t s) {
+                          Walk p = walk_from(known);
+                          p.plms = true;
+                          p.cfg_on = loop_cfg_on(p.uncond, p.cfg_scale);
+                          p.flags = loop_flags(p.flags, p.cfg_on);
+                          return run_walk(e, p, s);
+                      });
 }
 
 static const char* dpmpp_params_error(const fgdm_dpmpp_params* p) {
@@ -2096,48 +2152,29 @@ static const char* dpmpp_params_error(const fgdm_dpmpp_params* p) {
     return nullptr;
 }
 
-int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* caller, void* stream) {
-    if (!e || !caller) return FGDM_ERR_ARG;
-    fgdm_dpmpp_params known;
-    if (!read_params(caller, FGDM_DPMPP_PARAMS_SIZE_V1, &known, sizeof(known)))
-        return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpmpp: struct_size is not the sizeof(fgdm_dpmpp_params) of a known header version");
-    const fgdm_dpmpp_params* p = &known;
-    if (const char* why = dpmpp_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_dpmpp: ") + why);
-    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpmpp: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
-    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
-    hipStream_t s = as_stream(stream);
-    return scoped_call(e, stream, [&]() -> int {
-    const int K = p->n_eval, B = p->B, H = p->H, W = p->W;
-    const bool cfg_on = p->uncond && p->cfg_scale != 1.0f;
-    const int flags = cfg_on ? p->flags | FGDM_FLAG_CFG_PAIRS : p->flags & ~FGDM_FLAG_CFG_PAIRS;
-    LoopWork w;
-    int rc = loop_begin(e, p->cond, p->uncond, cfg_on, B, H, W, s, &w);
-    const int Bm = w.Bm;
-    const size_t n = w.n;
-    float* x = p->x;
-    float* m = (float*)e->arena.alloc(2 * n * sizeof(float));         // the data prediction of evaluation k lives in plane k % 2
-    float* tdev = (float*)e->arena.alloc((size_t)K * Bm * sizeof(float));
-    if (rc == FGDM_OK && (!m || !tdev)) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
-    if (rc != FGDM_OK) return rc;
-    CHK(upload_repeated(p->t_float, K, Bm, tdev, s));
-    HIP_TRY(hipMemcpyAsync(w.x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));      // x_T into the network's input, once
-    if (cfg_on) HIP_TRY(hipMemcpyAsync(w.x2 + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+static int run_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params& p, hipStream_t s) {
+    const int K = p.n_eval;
+    const bool cfg_on = loop_cfg_on(p.uncond, p.cfg_scale);
+    Loop L(e, s, p, K, cfg_on, loop_flags(p.flags, cfg_on));
+    CHK(L.begin(p.cond, p.uncond, nullptr, p.t_float, 2));      // the data prediction of evaluation k lives in plane k % 2
+    CHK(L.seed());
+    int rc = FGDM_OK;
     for (int k = 0; k < K && rc == FGDM_OK; ++k) {
-        rc = e->apply_model(w.x2, nullptr, tdev + (size_t)k * Bm, nullptr, nullptr, p->control_scales, Bm, H, W, flags, w.eps);
+        rc = L.eval(k);
         if (rc != FGDM_OK) break;
         DpmppLoopStep a{};
-        a.x = x; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr; a.cfg = p->cfg_scale;
-        a.inv_alpha = p->inv_alpha[k]; a.neg_sigma_over_alpha = p->neg_sigma_over_alpha[k];
-        a.kind = p->update_kind[k]; a.c1 = p->c1[k]; a.cm0 = p->cm0[k]; a.cm1 = p->cm1[k];
-        a.m0_out = m + (size_t)(k % 2) * n;
-        a.m1 = k > 0 ? m + (size_t)((k - 1) % 2) * n : nullptr;
-        a.x_out = x;
-        if (k + 1 < K) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; }
+        a.io = L.step_io(k, p.cfg_scale);
+        a.inv_alpha = p.inv_alpha[k]; a.neg_sigma_over_alpha = p.neg_sigma_over_alpha[k];
+        a.kind = p.update_kind[k]; a.c1 = p.c1[k]; a.cm0 = p.cm0[k]; a.cm1 = p.cm1[k];
+        a.m0_out = L.plane(k % 2);
+        a.m1 = k > 0 ? L.plane((k - 1) % 2) : nullptr;
         rc = dpmpp_loop_step(a, s);
     }
-    loop_end(e, &w); e->arena.release(m); e->arena.release(tdev);
-    return rc;
-    });
+    return L.end(rc);
+}
+int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* caller, void* stream) {
+    return loop_entry(e, caller, stream, FGDM_DPMPP_PARAMS_SIZE_V1, "fgdm_sample_dpmpp", "fgdm_dpmpp_params", true,
+                      [](const fgdm_dpmpp_params& known) { return dpmpp_params_error(&known); }, run_dpmpp);
 }
 
 // The checks of a DPM-Solver program, in front of any launch; empty: the program is consistent.
@@ -2166,51 +2203,33 @@ static std::string dpm_program_error(const fgdm_dpm_solver_params* p) {
 }
 
 // DPM_Solver.sample (dpm_solver.py:965-1124) as a program: per record one evaluation of the network on the evaluation input, then
-// one launch of k_dpm_program_step.  The evaluation input w.x2 is also the record's x_eval (read and rewritten in place); the state
+// one launch of k_dpm_program_step.  The evaluation input L.x2 is also the record's x_eval (io.x) (read and rewritten in place); the state
 // x changes only behind a FGDM_DPM_DEST_STATE record, so the x at s survives the intermediate points of a singlestep update.
-int fgdm_sample_dpm_solver(fgdm_engine* e, const fgdm_dpm_solver_params* caller, void* stream) {
-    if (!e || !caller) return FGDM_ERR_ARG;
-    fgdm_dpm_solver_params known;
-    if (!read_params(caller, FGDM_DPM_SOLVER_PARAMS_SIZE_V1, &known, sizeof(known)))
-        return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpm_solver: struct_size is not the sizeof(fgdm_dpm_solver_params) of a known header version");
-    const fgdm_dpm_solver_params* p = &known;
-    const std::string why = dpm_program_error(p);
-    if (!why.empty()) return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpm_solver: " + why);
-    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_sample_dpm_solver: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
-    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
-    hipStream_t s = as_stream(stream);
-    return scoped_call(e, stream, [&]() -> int {
-    const int K = p->n_eval, B = p->B, H = p->H, W = p->W;
-    const bool cfg_on = p->uncond && p->cfg_scale != 1.0f;
-    const int flags = cfg_on ? p->flags | FGDM_FLAG_CFG_PAIRS : p->flags & ~FGDM_FLAG_CFG_PAIRS;
-    LoopWork w;
-    int rc = loop_begin(e, p->cond, p->uncond, cfg_on, B, H, W, s, &w);
-    const int Bm = w.Bm;
-    const size_t n = w.n;
-    float* x = p->x;
-    float* hist = (float*)e->arena.alloc(3 * n * sizeof(float));      // the model value of a record lives in plane slot[k]
-    float* tdev = (float*)e->arena.alloc((size_t)K * Bm * sizeof(float));
-    if (rc == FGDM_OK && (!hist || !tdev)) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
-    if (rc != FGDM_OK) return rc;
-    CHK(upload_repeated(p->t_float, K, Bm, tdev, s));
-    HIP_TRY(hipMemcpyAsync(w.x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));      // x_T into the network's input, once
-    if (cfg_on) HIP_TRY(hipMemcpyAsync(w.x2 + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    float* const planes[4] = {x, hist, hist + n, hist + 2 * n};
+static int run_dpm_program(fgdm_engine* e, const fgdm_dpm_solver_params& p, hipStream_t s) {
+    const int K = p.n_eval;
+    const bool cfg_on = loop_cfg_on(p.uncond, p.cfg_scale);
+    Loop L(e, s, p, K, cfg_on, loop_flags(p.flags, cfg_on));
+    CHK(L.begin(p.cond, p.uncond, nullptr, p.t_float, 3));      // the model value of a record lives in plane slot[k]
+    CHK(L.seed());
+    float* const planes[4] = {L.x, L.plane(0), L.plane(1), L.plane(2)};
+    int rc = FGDM_OK;
     for (int k = 0; k < K && rc == FGDM_OK; ++k) {
-        rc = e->apply_model(w.x2, nullptr, tdev + (size_t)k * Bm, nullptr, nullptr, p->control_scales, Bm, H, W, flags, w.eps);
+        rc = L.eval(k);
         if (rc != FGDM_OK) break;
         DpmProgramStep a{};
-        rc = dpm_program_terms(a, planes, p->slot[k], p->nterms[k], p->plane + (size_t)k * DPM_MAX_TERMS, p->coef + (size_t)k * DPM_MAX_TERMS);
+        rc = dpm_program_terms(a, planes, p.slot[k], p.nterms[k], p.plane + (size_t)k * DPM_MAX_TERMS, p.coef + (size_t)k * DPM_MAX_TERMS);
         if (rc != FGDM_OK) break;
-        a.x_eval = w.x2; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr; a.cfg = p->cfg_scale;
-        a.conv_x = p->conv_x[k]; a.conv_e = p->conv_e[k];
-        a.x_out = p->dest[k] == FGDM_DPM_DEST_STATE ? x : nullptr;
-        if (k + 1 < K) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; }
+        a.io = L.step_io(k, p.cfg_scale);
+        a.io.x = L.x2;                  // x_eval; the state is the base plane
+        if (p.dest[k] != FGDM_DPM_DEST_STATE) a.io.x_out = nullptr;
+        a.conv_x = p.conv_x[k]; a.conv_e = p.conv_e[k];
         rc = dpm_program_step(a, s);
     }
-    loop_end(e, &w); e->arena.release(hist); e->arena.release(tdev);
-    return rc;
-    });
+    return L.end(rc);
+}
+int fgdm_sample_dpm_solver(fgdm_engine* e, const fgdm_dpm_solver_params* caller, void* stream) {
+    return loop_entry(e, caller, stream, FGDM_DPM_SOLVER_PARAMS_SIZE_V1, "fgdm_sample_dpm_solver", "fgdm_dpm_solver_params", true,
+                      [](const fgdm_dpm_solver_params& known) { return dpm_program_error(&known); }, run_dpm_program);
 }
 
 static const char* ancestral_params_error(const fgdm_ancestral_params* p) {
@@ -2229,52 +2248,33 @@ static const char* ancestral_params_error(const fgdm_ancestral_params* p) {
 
 // p_sample_loop (ddpm.py:1382-1430): per step one evaluation of the network on x, then one launch of k_ancestral_loop_step, which
 // also does the step's own blend and writes x into the network's input.  Every table is in walk order.
-int fgdm_sample_ancestral(fgdm_engine* e, const fgdm_ancestral_params* caller, void* stream) {
-    if (!e || !caller) return FGDM_ERR_ARG;
-    fgdm_ancestral_params known;
-    if (!read_params(caller, FGDM_ANCESTRAL_PARAMS_SIZE_V1, &known, sizeof(known)))
-        return e->fail(FGDM_ERR_ARG, "fgdm_sample_ancestral: struct_size is not the sizeof(fgdm_ancestral_params) of a known header version");
-    const fgdm_ancestral_params* p = &known;
-    if (const char* why = ancestral_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_sample_ancestral: ") + why);
-    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_sample_ancestral: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
-    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
-    hipStream_t s = as_stream(stream);
-    return scoped_call(e, stream, [&]() -> int {
-    const int S = p->S, B = p->B, H = p->H, W = p->W;
-    const int flags = p->flags & ~FGDM_FLAG_CFG_PAIRS;
-    LoopWork w;
-    int rc = loop_begin(e, p->cond, nullptr, false, B, H, W, s, &w);
-    const size_t n = w.n;
-    float* x = p->x;
-    int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * B * sizeof(int64_t));
-    if (rc == FGDM_OK && !tdev) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
-    if (rc != FGDM_OK) return rc;
-    CHK(upload_repeated(p->timesteps, S, B, tdev, s));
-    HIP_TRY(hipMemcpyAsync(w.x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));      // x_T into the network's input, once
-    int logged = 0;
+static int run_ancestral(fgdm_engine* e, const fgdm_ancestral_params& p, hipStream_t s) {
+    const int S = p.S;
+    Loop L(e, s, p, S, false, loop_flags(p.flags, false), p.log_steps, p.n_log);
+    CHK(L.begin(p.cond, nullptr, p.timesteps, nullptr, 0));
+    CHK(L.seed());
+    const size_t n = L.n;
+    int rc = FGDM_OK;
     for (int i = 0; i < S && rc == FGDM_OK; ++i) {
-        rc = e->apply_model(w.x2, tdev + (size_t)i * B, nullptr, nullptr, nullptr, p->control_scales, B, H, W, flags, w.eps);
+        rc = L.eval(i);
         if (rc != FGDM_OK) break;
         AncestralLoopStep a{};
-        a.x = x; a.eps = w.eps; a.n = n;
-        a.cr = p->sqrt_recip_alphas_cumprod[i]; a.crm1 = p->sqrt_recipm1_alphas_cumprod[i];
-        a.c1 = p->posterior_mean_coef1[i]; a.c2 = p->posterior_mean_coef2[i]; a.std = p->std[i];
-        a.noise = a.std != 0.f ? p->step_noise + (size_t)i * n : nullptr;
-        if (p->mask) {
-            a.mask = p->mask; a.x0 = p->x0; a.qnoise = p->q_noise + (size_t)i * n;
-            a.sa_t = p->sqrt_alphas_cumprod_t[i]; a.s1m_t = p->sqrt_one_minus_alphas_cumprod_t[i];
+        a.io = L.step_io(i, 0.f);
+        a.cr = p.sqrt_recip_alphas_cumprod[i]; a.crm1 = p.sqrt_recipm1_alphas_cumprod[i];
+        a.c1 = p.posterior_mean_coef1[i]; a.c2 = p.posterior_mean_coef2[i]; a.std = p.std[i];
+        a.noise = a.std != 0.f ? p.step_noise + (size_t)i * n : nullptr;
+        if (p.mask) {
+            a.mask = p.mask; a.x0 = p.x0; a.qnoise = p.q_noise + (size_t)i * n;
+            a.sa_t = p.sqrt_alphas_cumprod_t[i]; a.s1m_t = p.sqrt_one_minus_alphas_cumprod_t[i];
         }
-        a.x_out = x;
-        if (i + 1 < S) a.xin = w.x2;
-        if (logged < p->n_log && p->log_steps[logged] == i) {
-            a.log_x = p->x_inter_out ? p->x_inter_out + (size_t)logged * n : nullptr;
-            ++logged;
-        }
+        a.io.log_x = L.log_plane(p.x_inter_out, L.log_slot(i));
         rc = ancestral_loop_step(a, s);
     }
-    loop_end(e, &w); e->arena.release(tdev);
-    return rc;
-    });
+    return L.end(rc);
+}
+int fgdm_sample_ancestral(fgdm_engine* e, const fgdm_ancestral_params* caller, void* stream) {
+    return loop_entry(e, caller, stream, FGDM_ANCESTRAL_PARAMS_SIZE_V1, "fgdm_sample_ancestral", "fgdm_ancestral_params", true,
+                      [](const fgdm_ancestral_params& known) { return ancestral_params_error(&known); }, run_ancestral);
 }
 
 static const char* ddim_encode_params_error(const fgdm_ddim_encode_params* p) {
@@ -2286,49 +2286,27 @@ static const char* ddim_encode_params_error(const fgdm_ddim_encode_params* p) {
 
 // DDIMSampler.encode (ddim_hacked.py:234-279): per step one evaluation of the network on cat([x] * 2) (or x, CFG off), then one
 // launch of k_invert_loop_step.
-int fgdm_ddim_encode(fgdm_engine* e, const fgdm_ddim_encode_params* caller, void* stream) {
-    if (!e || !caller) return FGDM_ERR_ARG;
-    fgdm_ddim_encode_params known;
-    if (!read_params(caller, FGDM_DDIM_ENCODE_PARAMS_SIZE_V1, &known, sizeof(known)))
-        return e->fail(FGDM_ERR_ARG, "fgdm_ddim_encode: struct_size is not the sizeof(fgdm_ddim_encode_params) of a known header version");
-    const fgdm_ddim_encode_params* p = &known;
-    if (const char* why = ddim_encode_params_error(p)) return e->fail(FGDM_ERR_ARG, std::string("fgdm_ddim_encode: ") + why);
-    if (e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, "fgdm_ddim_encode: in_channels > 4 (hybrid c_concat) is not taken by the device loops");
-    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
-    hipStream_t s = as_stream(stream);
-    return scoped_call(e, stream, [&]() -> int {
-    const int S = p->S, B = p->B, H = p->H, W = p->W;
-    const bool cfg_on = p->uncond && p->cfg_scale != 1.0f;
-    const int flags = cfg_on ? p->flags | FGDM_FLAG_CFG_PAIRS : p->flags & ~FGDM_FLAG_CFG_PAIRS;
-    LoopWork w;
-    int rc = loop_begin(e, p->cond, p->uncond, cfg_on, B, H, W, s, &w);
-    const int Bm = w.Bm;
-    const size_t n = w.n;
-    float* x = p->x;
-    int64_t* tdev = (int64_t*)e->arena.alloc((size_t)S * Bm * sizeof(int64_t));
-    if (rc == FGDM_OK && !tdev) rc = e->fail(FGDM_ERR_NOMEM, "workspace");
-    if (rc != FGDM_OK) return rc;
-    CHK(upload_repeated(p->timesteps, S, Bm, tdev, s));
-    HIP_TRY(hipMemcpyAsync(w.x2, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));      // x_0 into the network's input, once
-    if (cfg_on) HIP_TRY(hipMemcpyAsync(w.x2 + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    int logged = 0;
+static int run_ddim_encode(fgdm_engine* e, const fgdm_ddim_encode_params& p, hipStream_t s) {
+    const int S = p.S;
+    const bool cfg_on = loop_cfg_on(p.uncond, p.cfg_scale);
+    Loop L(e, s, p, S, cfg_on, loop_flags(p.flags, cfg_on), p.log_steps, p.n_log);
+    CHK(L.begin(p.cond, p.uncond, p.timesteps, nullptr, 0));
+    CHK(L.seed());
+    int rc = FGDM_OK;
     for (int i = 0; i < S && rc == FGDM_OK; ++i) {
-        rc = e->apply_model(w.x2, tdev + (size_t)i * Bm, nullptr, nullptr, nullptr, p->control_scales, Bm, H, W, flags, w.eps);
+        rc = L.eval(i);
         if (rc != FGDM_OK) break;
         InvertLoopStep a{};
-        a.x = x; a.n = n; a.ec = cfg_on ? w.eps + n : w.eps; a.eu = cfg_on ? w.eps : nullptr; a.cfg = p->cfg_scale;
-        a.cx = p->cx[i]; a.ce = p->ce[i];
-        a.x_out = x;
-        if (i + 1 < S) { a.xin_a = w.x2; a.xin_b = cfg_on ? w.x2 + n : nullptr; }
-        if (logged < p->n_log && p->log_steps[logged] == i) {
-            a.log_x = p->x_inter_out ? p->x_inter_out + (size_t)logged * n : nullptr;
-            ++logged;
-        }
+        a.io = L.step_io(i, p.cfg_scale);
+        a.cx = p.cx[i]; a.ce = p.ce[i];
+        a.io.log_x = L.log_plane(p.x_inter_out, L.log_slot(i));
         rc = invert_loop_step(a, s);
     }
-    loop_end(e, &w); e->arena.release(tdev);
-    return rc;
-    });
+    return L.end(rc);
+}
+int fgdm_ddim_encode(fgdm_engine* e, const fgdm_ddim_encode_params* caller, void* stream) {
+    return loop_entry(e, caller, stream, FGDM_DDIM_ENCODE_PARAMS_SIZE_V1, "fgdm_ddim_encode", "fgdm_ddim_encode_params", true,
+                      [](const fgdm_ddim_encode_params& known) { return ddim_encode_params_error(&known); }, run_ddim_encode);
 }
 
 }  // extern "C"

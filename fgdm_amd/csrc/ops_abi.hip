@@ -324,10 +324,10 @@ int fgdm_op_ddim_loop_step(const float* x, const float* e_cond, const float* e_u
                            float* xin_b, float* log_x, float* log_pred_x0, int64_t n, void* stream) {
     if (!x || n <= 0 || (e_uncond && !e_cond) || (mask && (!x0 || !q_noise))) return FGDM_ERR_ARG;
     LoopStep a{};
-    a.x = x; a.ec = e_cond; a.eu = e_uncond; a.noise = noise; a.mask = mask; a.x0 = x0; a.qnoise = q_noise;
-    a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.log_x = log_x; a.log_p0 = log_pred_x0;
-    a.cfg = cfg_scale; a.a_t = a_t; a.a_prev = a_prev; a.sigma = sigma_t; a.s1m = sqrt_one_minus_at;
-    a.sa_next = sqrt_ac_next; a.s1m_next = sqrt_one_minus_ac_next; a.mode = LOOP_PLAIN; a.n = (size_t)n;
+    a.io = StepIO{x, e_cond, e_uncond, x_out, xin_a, xin_b, log_x, cfg_scale, (size_t)n};
+    a.noise = noise; a.mask = mask; a.x0 = x0; a.qnoise = q_noise; a.log_p0 = log_pred_x0;
+    a.a_t = a_t; a.a_prev = a_prev; a.sigma = sigma_t; a.s1m = sqrt_one_minus_at;
+    a.sa_next = sqrt_ac_next; a.s1m_next = sqrt_one_minus_ac_next; a.mode = LOOP_PLAIN;
     return loop_step(a, as_stream(stream));
 }
 
@@ -340,10 +340,10 @@ int fgdm_op_plms_loop_step(const float* x, const float* e_cond, const float* e_u
                            int64_t n, void* stream) {
     if (n <= 0 || (e_cond && mode == LOOP_PLAIN)) return FGDM_ERR_ARG;      // the plain (DDIM) mode is no mode of this entry
     LoopStep a{};
-    a.x = x; a.ec = e_cond; a.eu = e_uncond; a.e1 = e1; a.e2 = e2; a.e3 = e3; a.mask = mask; a.x0 = x0; a.qnoise = q_noise;
-    a.e_out = e_out; a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.log_x = log_x; a.log_p0 = log_pred_x0;
-    a.cfg = cfg_scale; a.a_t = a_t; a.a_prev = a_prev; a.s1m = sqrt_one_minus_at; a.sa_next = sqrt_ac_next;
-    a.s1m_next = sqrt_one_minus_ac_next; a.mode = mode; a.order = order; a.n = (size_t)n;
+    a.io = StepIO{x, e_cond, e_uncond, x_out, xin_a, xin_b, log_x, cfg_scale, (size_t)n};
+    a.e1 = e1; a.e2 = e2; a.e3 = e3; a.mask = mask; a.x0 = x0; a.qnoise = q_noise; a.e_out = e_out; a.log_p0 = log_pred_x0;
+    a.a_t = a_t; a.a_prev = a_prev; a.s1m = sqrt_one_minus_at; a.sa_next = sqrt_ac_next;
+    a.s1m_next = sqrt_one_minus_ac_next; a.mode = mode; a.order = order;
     return loop_step(a, as_stream(stream));
 }
 
@@ -352,9 +352,9 @@ int fgdm_op_dpmpp_loop_step(const float* x, const float* e_cond, const float* e_
                             float* m0_out, float* x_out, float* xin_a, float* xin_b, int64_t n, void* stream) {
     if (n <= 0) return FGDM_ERR_ARG;
     DpmppLoopStep a{};
-    a.x = x; a.ec = e_cond; a.eu = e_uncond; a.m1 = m1; a.m0_out = m0_out; a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b;
-    a.cfg = cfg_scale; a.inv_alpha = inv_alpha; a.neg_sigma_over_alpha = neg_sigma_over_alpha; a.c1 = c1; a.cm0 = cm0; a.cm1 = cm1;
-    a.kind = update_kind; a.n = (size_t)n;
+    a.io = StepIO{x, e_cond, e_uncond, x_out, xin_a, xin_b, nullptr, cfg_scale, (size_t)n};
+    a.m1 = m1; a.m0_out = m0_out; a.inv_alpha = inv_alpha; a.neg_sigma_over_alpha = neg_sigma_over_alpha; a.c1 = c1; a.cm0 = cm0; a.cm1 = cm1;
+    a.kind = update_kind;
     return dpmpp_loop_step(a, as_stream(stream));
 }
 
@@ -367,8 +367,8 @@ int fgdm_op_dpm_program_step(const float* x_eval, const float* e_cond, const flo
     DpmProgramStep a{};
     float* const pl[4] = {base, hist0, hist1, hist2};
     if (dpm_program_terms(a, pl, slot, nterms, planes, coefs) != FGDM_OK) return FGDM_ERR_ARG;
-    a.x_eval = x_eval; a.ec = e_cond; a.eu = e_uncond; a.cfg = cfg_scale; a.conv_x = conv_x; a.conv_e = conv_e;
-    a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.n = (size_t)n;
+    a.io = StepIO{x_eval, e_cond, e_uncond, x_out, xin_a, xin_b, nullptr, cfg_scale, (size_t)n};
+    a.conv_x = conv_x; a.conv_e = conv_e;
     return dpm_program_step(a, as_stream(stream));
 }
 
@@ -380,10 +380,10 @@ int fgdm_op_ancestral_loop_step(const float* x, const float* eps, float sqrt_rec
                                 void* stream) {
     if (n <= 0) return FGDM_ERR_ARG;
     AncestralLoopStep a{};
-    a.x = x; a.eps = eps; a.noise = noise; a.mask = mask; a.x0 = x0; a.qnoise = q_noise;
-    a.x_out = x_out; a.xin = xin; a.log_x = log_x;
+    a.io = StepIO{x, eps, nullptr, x_out, xin, nullptr, log_x, 0.f, (size_t)n};
+    a.noise = noise; a.mask = mask; a.x0 = x0; a.qnoise = q_noise;
     a.cr = sqrt_recip_ac; a.crm1 = sqrt_recipm1_ac; a.c1 = coef1; a.c2 = coef2; a.std = std;
-    a.sa_t = sqrt_ac_t; a.s1m_t = sqrt_one_minus_ac_t; a.n = (size_t)n;
+    a.sa_t = sqrt_ac_t; a.s1m_t = sqrt_one_minus_ac_t;
     return ancestral_loop_step(a, as_stream(stream));
 }
 
@@ -391,8 +391,8 @@ int fgdm_op_invert_loop_step(const float* x, const float* e_cond, const float* e
                              float* x_out, float* xin_a, float* xin_b, float* log_x, int64_t n, void* stream) {
     if (n <= 0) return FGDM_ERR_ARG;
     InvertLoopStep a{};
-    a.x = x; a.ec = e_cond; a.eu = e_uncond; a.x_out = x_out; a.xin_a = xin_a; a.xin_b = xin_b; a.log_x = log_x;
-    a.cfg = cfg_scale; a.cx = cx; a.ce = ce; a.n = (size_t)n;
+    a.io = StepIO{x, e_cond, e_uncond, x_out, xin_a, xin_b, log_x, cfg_scale, (size_t)n};
+    a.cx = cx; a.ce = ce;
     return invert_loop_step(a, as_stream(stream));
 }
 

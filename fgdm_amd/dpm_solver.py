@@ -10,7 +10,7 @@ Every update of the family is a linear combination of x and of model values kept
 compiles into a flat PROGRAM with one record per network evaluation (dpm_solver_program).  Both routes read that program and nothing
 else: the per-step route below (any callable model_fn; one launch of k_dpm_program_step per record through engine.dpm_program_step)
 and the device loop (DPM_Solver(..., device_loop=True) -> Engine.sample_dpm_solver / fgdm_sample_dpm_solver: the whole sampling in
-one engine call, when model_fn is the object model_wrapper returns and _SamplerBase._loop_plan takes its conditionings).
+one engine call, when model_fn is the object model_wrapper returns and samplers._loop_plan takes its conditionings).
 Not carried over, and refused by name: the continuous schedules, classifier guidance, the 'x_start' / 'v' / 'score' model types,
 dynamic thresholding, method='adaptive' (a data-dependent step control: it needs the host between evaluations).
 """
@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import engine as _k
-from .samplers import _DiscreteVPSchedule, _SamplerBase
+from .samplers import _DiscreteVPSchedule, _loop_plan
 
 # the planes a term of a record's update can name (FGDM_DPM_PLANE_* of include/fgdm.h)
 PLANE_BASE, PLANE_HIST0, PLANE_HIST1, PLANE_HIST2, PLANE_M = 0, 1, 2, 3, 4
@@ -402,20 +402,10 @@ def program_error(prog):
     return None
 
 
-class _LoopRule:
-    """what _SamplerBase._loop_plan reads of a sampler, for a DPM_Solver"""
-    _loop_plan = _SamplerBase._loop_plan
-    _loop_cond = _SamplerBase._loop_cond
-    _cat_cond = staticmethod(_SamplerBase._cat_cond)
-
-    def __init__(self, model, device_loop):
-        self.model, self.device_loop = model, device_loop
-
-
 class DPM_Solver:
     """dpm_solver.py:351-1124.  model_fn: the object model_wrapper returns, or any callable (x, t_continuous) -> eps.
     device_loop=True (an added keyword, off by default): sample() hands the whole sampling to the engine (fgdm_sample_dpm_solver)
-    when model_fn is the wrapper's object over a LatentDiffusion / ControlLDM mirror and _SamplerBase._loop_plan takes its
+    when model_fn is the wrapper's object over a LatentDiffusion / ControlLDM mirror and samplers._loop_plan takes its
     conditionings -- the rule of the other device loops; same program, same bits as the per-step route."""
 
     def __init__(self, model_fn, noise_schedule, predict_x0=False, thresholding=False, max_val=1., device_loop=False):
@@ -434,10 +424,8 @@ class DPM_Solver:
         w = self.model
         if not self.device_loop or not isinstance(w, _WrappedModel) or w.ldm is None or w.guidance_type != 'classifier-free':
             return None
-        rule = _LoopRule(w.ldm, True)
-        scale = w.guidance_scale
-        plan = rule._loop_plan(w.condition, w.unconditional_condition, [scale] * len(prog['t_float']), None, None, x, False,
-                               w.model_kwargs, entry='sample_dpm_solver')
+        plan = _loop_plan(w.ldm, None, w.condition, w.unconditional_condition, [w.guidance_scale] * len(prog['t_float']), None, None, x,
+                          False, w.model_kwargs, entry='sample_dpm_solver')
         return None if plan is None else (w.ldm.engine, *plan)
 
     def sample(self, x, steps=20, t_start=None, t_end=None, order=3, skip_type='time_uniform', method='singlestep',

@@ -491,27 +491,16 @@ class Engine:
     def sample_ddim(self, x_T, cond, uncond, cfg_scale, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas,
                     control_scales=None, flags=0):
         """Whole eta=0 DDIM loop on the device; returns the final latent (x_T is not modified)."""
-        x = x_T.to(self.device, torch.float32).clone().contiguous()
-        cond = cond.to(self.device, torch.float32).contiguous()
-        if uncond is not None:
-            uncond = uncond.to(self.device, torch.float32).contiguous()
-            if tuple(uncond.shape) != tuple(cond.shape):      # the loop runs cat([uncond, cond]) as one batch (ddim.py:222-226)
-                raise ValueError(f'sample_ddim: cond {tuple(cond.shape)} and uncond {tuple(uncond.shape)} must agree')
-        self.set_context_tokens(cond.shape[1])
-        B, _, H, W = x.shape
+        def legacy(p):      # the positional entry of the first ABI version: kept exercised
+            f32, i64 = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+            return self.lib.fgdm_sample_ddim(self.h, p.x, p.cond, p.uncond, p.cfg_scale, p.S, C.cast(p.timesteps, i64), C.cast(p.alphas, f32),
+                                             C.cast(p.alphas_prev, f32), C.cast(p.sqrt_one_minus_alphas, f32), p.control_scales, p.B, p.H,
+                                             p.W, p.flags, _stream())
         S = len(timesteps)
-        ts = (C.c_int64 * S)(*[int(v) for v in timesteps])
-        fa = lambda a: (C.c_float * S)(*[float(v) for v in a])
-        if control_scales is not None:
-            sc_host = np.asarray(control_scales, dtype=np.float32).ravel().copy()
-            sc_ptr = sc_host.ctypes.data_as(C.c_void_p)
-        else:
-            sc_ptr = C.c_void_p(0)
-        rc = self.lib.fgdm_sample_ddim(self.h, _ptr(x), _ptr(cond), _ptr(uncond), float(cfg_scale), S, ts, fa(alphas),
-                                       fa(alphas_prev), fa(sqrt_one_minus_alphas), sc_ptr, B, H, W, flags, _stream())
-        self._ctx_policy = ContextCachePolicy()      # the device-side loop registered its own context
-        self._check(rc, 'fgdm_sample_ddim')
-        return x
+        return self._device_loop('sample_ddim', _lib.FgdmDdimParams(), x_T, cond, uncond, None, 'S', S,
+                                 dict(timesteps=(timesteps, C.c_int64, S), alphas=alphas, alphas_prev=alphas_prev,
+                                      sqrt_one_minus_alphas=sqrt_one_minus_alphas), control_scales=control_scales, call=legacy,
+                                 cfg_scale=float(cfg_scale), flags=int(flags))[0]
 
     def sample_ddim_ex(self, x_T, cond, uncond, cfg_scale, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, sigmas=None,
                        cfg_scales=None, step_noise=None, mask=None, x0=None, q_noise=None, sqrt_alphas_cumprod_t=None,
@@ -522,12 +511,14 @@ class Engine:
         sample_ddim's; cfg_scales [S], step_noise / q_noise [S, B,4,H,W] and log_steps in WALK order (slot i: the i-th step that
         runs).  Returns (x, x_inter, pred_x0): the final latent and the two [len(log_steps), B,4,H,W] intermediates (None without
         log steps).  x_T is not modified; out / x_inter_out / pred_x0_out: caller-owned device buffers to use instead of new ones."""
-        return self._sample_walk('sample_ddim_ex', _lib.FgdmDdimParams(), x_T, cond, uncond, cfg_scale,
-                                 dict(timesteps=timesteps, alphas=alphas, alphas_prev=alphas_prev, sqrt_one_minus_alphas=sqrt_one_minus_alphas,
-                                      sigmas=sigmas, cfg_scales=cfg_scales, sqrt_alphas_cumprod_t=sqrt_alphas_cumprod_t,
-                                      sqrt_one_minus_alphas_cumprod_t=sqrt_one_minus_alphas_cumprod_t),
-                                 dict(step_noise=step_noise, q_noise=q_noise), mask, x0, log_steps, control_scales, flags, out,
-                                 x_inter_out, pred_x0_out)
+        S = len(timesteps)
+        return self._device_loop('sample_ddim_ex', _lib.FgdmDdimParams(), x_T, cond, uncond, out, 'S', S,
+                                 dict(timesteps=(timesteps, C.c_int64, S), alphas=alphas, alphas_prev=alphas_prev,
+                                      sqrt_one_minus_alphas=sqrt_one_minus_alphas, sigmas=sigmas, cfg_scales=cfg_scales,
+                                      sqrt_alphas_cumprod_t=sqrt_alphas_cumprod_t, sqrt_one_minus_alphas_cumprod_t=sqrt_one_minus_alphas_cumprod_t),
+                                 dict(step_noise=(step_noise, (S,)), q_noise=(q_noise, (S,)), mask=(mask, ()), x0=(x0, ())),
+                                 (log_steps, dict(x_inter_out=x_inter_out, pred_x0_out=pred_x0_out)), control_scales,
+                                 cfg_scale=float(cfg_scale), flags=int(flags))
 
     def _loop_args(self, name, x_T, cond, uncond, out):
         """the state and the conditionings of a device loop on the engine's device, as sample_ddim_ex prepares them"""
@@ -549,105 +540,99 @@ class Engine:
         keep.append((ctype * count)(*[conv(v) for v in a]))
         return C.cast(keep[-1], C.c_void_p)
 
-    def _run_loop(self, name, p, keep, control_scales):
-        """control_scales into the parameter struct `p`, then the native loop fgdm_<name>; `keep` holds host arrays while it runs"""
+    def _run_loop(self, name, p, keep, control_scales, call=None):
+        """control_scales into the parameter struct `p`, then the native loop fgdm_<name> (or `call(p)`: the legacy entry); `keep`
+        holds host arrays while it runs"""
         p.struct_size = C.sizeof(p)
         if control_scales is not None:
             keep.append(np.asarray(control_scales, dtype=np.float32).ravel().copy())
             p.control_scales = keep[-1].ctypes.data_as(C.c_void_p)
-        rc = getattr(self.lib, 'fgdm_' + name)(self.h, C.byref(p), _stream())
+        rc = call(p) if call else getattr(self.lib, 'fgdm_' + name)(self.h, C.byref(p), _stream())
         self._ctx_policy = ContextCachePolicy()      # the device-side loop registered its own context
         self._check(rc, 'fgdm_' + name)
 
-    def _sample_walk(self, name, p, x_T, cond, uncond, cfg_scale, tables, step_tensors, mask, x0, log_steps, control_scales, flags,
-                     out, x_inter_out, pred_x0_out):
-        """sample_ddim_ex / sample_plms: the fields their two structs share by name.  tables: field -> S-entry host table (None:
-        absent), `timesteps` among them; step_tensors: field -> [S, B,4,H,W] tensor or None."""
-        x, cond, uncond = self._loop_args(name, x_T, cond, uncond, out)
-        dev = lambda v: None if v is None else v.to(self.device, torch.float32).contiguous()
-        B, _, H, W = x.shape
-        S, n_log = len(tables['timesteps']), len(log_steps)
-        tensors = {k: (dev(v), (S, *x.shape)) for k, v in step_tensors.items()}
-        tensors.update(mask=(dev(mask), tuple(x.shape)), x0=(dev(x0), tuple(x.shape)))
-        for k, (v, shape) in tensors.items():
-            if v is not None and tuple(v.shape) != tuple(shape):
-                raise ValueError(f'{name}: {k} {tuple(v.shape)} must be {tuple(shape)}')
+    def _log_args(self, name, p, keep, x, log_steps, outs):
+        """log_steps / n_log / the log planes of a loop's struct.  outs: field -> caller-owned buffer or None.  Returns the
+        [len(log_steps), B,4,H,W] plane of every field (None without log steps)."""
+        p.n_log = len(log_steps)
+        if not p.n_log:
+            return [None] * len(outs)
+        planes = [torch.empty(p.n_log, *x.shape, device=self.device, dtype=torch.float32) if v is None else v for v in outs.values()]
+        p.log_steps = self._table(name, keep, log_steps, p.n_log, C.c_int32, int)
+        for k, v in zip(outs, planes):
             setattr(p, k, _ptr(v))
-        keep = []      # host arrays the struct points into
-        for k, a in tables.items():
-            setattr(p, k, self._table(name, keep, a, S, *((C.c_int64, int) if k == 'timesteps' else ())))
-        if n_log:
-            x_inter = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if x_inter_out is None else x_inter_out
-            pred_x0 = torch.empty(n_log, *x.shape, device=self.device, dtype=torch.float32) if pred_x0_out is None else pred_x0_out
-            p.log_steps = self._table(name, keep, log_steps, n_log, C.c_int32, int)
-        else:
-            x_inter = pred_x0 = None
-        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
-        p.x_inter_out, p.pred_x0_out = _ptr(x_inter), _ptr(pred_x0)
-        p.cfg_scale, p.S, p.B, p.H, p.W, p.flags, p.n_log = float(cfg_scale), S, B, H, W, int(flags), n_log
-        self._run_loop(name, p, keep, control_scales)
-        return x, x_inter, pred_x0
+        return planes
+
+    def _device_loop(self, name, p, x_T, cond, uncond, out, count_field, count, tables, tensors=None, logs=None, control_scales=None,
+                     call=None, **scalars):
+        """What every device loop does around its native entry fgdm_<name>: the state and the conditionings (_loop_args), then into
+        the parameter struct `p` the device tensors (field -> (tensor or None, leading dims in front of x's shape)), the host tables
+        in the caller's order (field -> `count` floats or None, or (values, ctype, entries) for another type or length; values may
+        be a function that is called at its turn), the log group (log_steps, {field: caller-owned plane or None}) of the loops that
+        have one, the sizes and the scalar fields; then the call.  Returns (x, *log planes)."""
+        x, cond, uncond = self._loop_args(name, x_T, cond, uncond, out)
+        keep = []      # what the struct points into: converted tensors and host arrays, held until the call has returned
+        for k, (v, lead) in (tensors or {}).items():
+            v = None if v is None else v.to(self.device, torch.float32).contiguous()
+            if v is not None and tuple(v.shape) != (*lead, *x.shape):
+                raise ValueError(f'{name}: {k} {tuple(v.shape)} must be {(*lead, *x.shape)}')
+            keep.append(v)
+            setattr(p, k, _ptr(v))
+        for k, spec in tables.items():
+            a, ctype, n = spec if isinstance(spec, tuple) else (spec, C.c_float, count)
+            setattr(p, k, self._table(name, keep, a() if callable(a) else a, n, ctype, float if ctype is C.c_float else int))
+        planes = self._log_args(name, p, keep, x, *logs) if logs else []
+        p.x, p.cond = _ptr(x), _ptr(cond)
+        if uncond is not None:
+            p.uncond = _ptr(uncond)
+        _, _, H, W = x.shape
+        for k, v in dict(scalars, B=x.shape[0], H=H, W=W, **{count_field: count}).items():
+            setattr(p, k, v)
+        self._run_loop(name, p, keep, control_scales, call)
+        return (x, *planes)
 
     def sample_plms(self, x_T, cond, uncond, cfg_scale, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, mask=None, x0=None,
                     q_noise=None, sqrt_alphas_cumprod_t=None, sqrt_one_minus_alphas_cumprod_t=None, log_steps=(),
                     control_scales=None, flags=0, out=None, x_inter_out=None, pred_x0_out=None):
         """The whole PLMS loop on the device (fgdm_sample_plms, include/fgdm.h): the S-entry tables in ddim_timesteps order,
         q_noise [S, B,4,H,W] and log_steps in WALK order, as for sample_ddim_ex.  Returns (x, x_inter, pred_x0)."""
-        return self._sample_walk('sample_plms', _lib.FgdmPlmsParams(), x_T, cond, uncond, cfg_scale,
-                                 dict(timesteps=timesteps, alphas=alphas, alphas_prev=alphas_prev, sqrt_one_minus_alphas=sqrt_one_minus_alphas,
-                                      sqrt_alphas_cumprod_t=sqrt_alphas_cumprod_t, sqrt_one_minus_alphas_cumprod_t=sqrt_one_minus_alphas_cumprod_t),
-                                 dict(q_noise=q_noise), mask, x0, log_steps, control_scales, flags, out, x_inter_out, pred_x0_out)
+        S = len(timesteps)
+        return self._device_loop('sample_plms', _lib.FgdmPlmsParams(), x_T, cond, uncond, out, 'S', S,
+                                 dict(timesteps=(timesteps, C.c_int64, S), alphas=alphas, alphas_prev=alphas_prev,
+                                      sqrt_one_minus_alphas=sqrt_one_minus_alphas, sqrt_alphas_cumprod_t=sqrt_alphas_cumprod_t,
+                                      sqrt_one_minus_alphas_cumprod_t=sqrt_one_minus_alphas_cumprod_t),
+                                 dict(q_noise=(q_noise, (S,)), mask=(mask, ()), x0=(x0, ())),
+                                 (log_steps, dict(x_inter_out=x_inter_out, pred_x0_out=pred_x0_out)), control_scales,
+                                 cfg_scale=float(cfg_scale), flags=int(flags))
 
     def sample_dpmpp(self, x_T, cond, uncond, cfg_scale, tables, control_scales=None, flags=0, out=None):
         """The whole DPM-Solver++ loop on the device (fgdm_sample_dpmpp, include/fgdm.h).  tables: a dict of equally long
         per-evaluation lists t_float, inv_alpha, neg_sigma_over_alpha, update_kind, c1, cm0, cm1 (fgdm_amd.samplers.dpmpp_tables).
         Returns the final latent; x_T is not modified."""
-        x, cond, uncond = self._loop_args('sample_dpmpp', x_T, cond, uncond, out)
-        B, _, H, W = x.shape
         K = len(tables['t_float'])
-        keep = []
-        p = _lib.FgdmDpmppParams()
-        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
-        for name in ('t_float', 'inv_alpha', 'neg_sigma_over_alpha', 'c1', 'cm0', 'cm1'):
-            setattr(p, name, self._table('sample_dpmpp', keep, tables[name], K))
-        p.update_kind = self._table('sample_dpmpp', keep, tables['update_kind'], K, C.c_int32, int)
-        p.cfg_scale, p.n_eval, p.B, p.H, p.W, p.flags = float(cfg_scale), K, B, H, W, int(flags)
-        self._run_loop('sample_dpmpp', p, keep, control_scales)
-        return x
+        return self._device_loop('sample_dpmpp', _lib.FgdmDpmppParams(), x_T, cond, uncond, out, 'n_eval', K,
+                                 dict({k: tables[k] for k in ('t_float', 'inv_alpha', 'neg_sigma_over_alpha', 'c1', 'cm0', 'cm1')},
+                                      update_kind=(tables['update_kind'], C.c_int32, K)), control_scales=control_scales,
+                                 cfg_scale=float(cfg_scale), flags=int(flags))[0]
 
     def sample_dpm_solver(self, x_T, cond, uncond, cfg_scale, program, control_scales=None, flags=0, out=None):
         """A whole DPM-Solver sampling on the device (fgdm_sample_dpm_solver, include/fgdm.h).  program: the dict of equally long
         per-evaluation lists of fgdm_amd.dpm_solver.dpm_solver_program (t_float, conv_x, conv_e, slot, nterms, dest, and plane /
         coef with five entries per record).  Returns the final latent; x_T is not modified."""
-        name = 'sample_dpm_solver'
-        x, cond, uncond = self._loop_args(name, x_T, cond, uncond, out)
-        B, _, H, W = x.shape
         K = len(program['t_float'])
-        keep = []
-        p = _lib.FgdmDpmSolverParams()
-        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
-        for k in ('t_float', 'conv_x', 'conv_e'):
-            setattr(p, k, self._table(name, keep, program[k], K))
-        for k in ('slot', 'nterms', 'dest'):
-            setattr(p, k, self._table(name, keep, program[k], K, C.c_int32, int))
-        for k, rows in (('plane', program['plane']), ('coef', program['coef'])):
-            if len(rows) != K or any(len(r) != 5 for r in rows):
-                raise ValueError(f'{name}: {k} must hold five entries for each of the {K} records')
-        p.plane = self._table(name, keep, [v for r in program['plane'] for v in r], 5 * K, C.c_int32, int)
-        p.coef = self._table(name, keep, [v for r in program['coef'] for v in r], 5 * K)
-        p.cfg_scale, p.n_eval, p.B, p.H, p.W, p.flags = float(cfg_scale), K, B, H, W, int(flags)
-        self._run_loop(name, p, keep, control_scales)
-        return x
 
-    def _log_args(self, name, p, keep, x, log_steps, x_inter_out):
-        """log_steps / n_log / x_inter_out of a loop's struct -> the [len(log_steps), B,4,H,W] plane (None without log steps)"""
-        p.n_log = len(log_steps)
-        if not p.n_log:
-            return None
-        x_inter = torch.empty(p.n_log, *x.shape, device=self.device, dtype=torch.float32) if x_inter_out is None else x_inter_out
-        p.log_steps = self._table(name, keep, log_steps, p.n_log, C.c_int32, int)
-        p.x_inter_out = _ptr(x_inter)
-        return x_inter
+        def rows(k, check):      # program[k] as one table; at its turn, so that the row check comes behind the one-entry tables
+            def flat():
+                for j in check:
+                    if len(program[j]) != K or any(len(r) != 5 for r in program[j]):
+                        raise ValueError(f'sample_dpm_solver: {j} must hold five entries for each of the {K} records')
+                return [v for r in program[k] for v in r]
+            return flat
+        return self._device_loop('sample_dpm_solver', _lib.FgdmDpmSolverParams(), x_T, cond, uncond, out, 'n_eval', K,
+                                 dict({k: program[k] for k in ('t_float', 'conv_x', 'conv_e')},
+                                      **{k: (program[k], C.c_int32, K) for k in ('slot', 'nterms', 'dest')},
+                                      plane=(rows('plane', ('plane', 'coef')), C.c_int32, 5 * K), coef=(rows('coef', ()), C.c_float, 5 * K)),
+                                 control_scales=control_scales, cfg_scale=float(cfg_scale), flags=int(flags))[0]
 
     def sample_ancestral(self, x_T, cond, timesteps, tables, step_noise=None, mask=None, x0=None, q_noise=None, log_steps=(),
                          control_scales=None, flags=0, out=None, x_inter_out=None):
@@ -656,47 +641,24 @@ class Engine:
         posterior_mean_coef1, posterior_mean_coef2, std (temperature folded in, 0 where t == 0) and, with a mask,
         sqrt_alphas_cumprod_t, sqrt_one_minus_alphas_cumprod_t; step_noise / q_noise [S, B,4,H,W].  Returns (x, x_inter): the
         final latent and the [len(log_steps), B,4,H,W] logged latents (None without log steps).  x_T is not modified."""
-        name = 'sample_ancestral'
-        x, cond, _ = self._loop_args(name, x_T, cond, None, out)
-        dev = lambda v: None if v is None else v.to(self.device, torch.float32).contiguous()
-        B, _, H, W = x.shape
         S = len(timesteps)
-        p = _lib.FgdmAncestralParams()
-        tensors = dict(step_noise=(dev(step_noise), (S, *x.shape)), q_noise=(dev(q_noise), (S, *x.shape)),
-                       mask=(dev(mask), tuple(x.shape)), x0=(dev(x0), tuple(x.shape)))
-        for k, (v, shape) in tensors.items():
-            if v is not None and tuple(v.shape) != tuple(shape):
-                raise ValueError(f'{name}: {k} {tuple(v.shape)} must be {tuple(shape)}')
-            setattr(p, k, _ptr(v))
-        keep = []
-        p.timesteps = self._table(name, keep, timesteps, S, C.c_int64, int)
-        for k in ('sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_mean_coef1', 'posterior_mean_coef2', 'std',
-                  'sqrt_alphas_cumprod_t', 'sqrt_one_minus_alphas_cumprod_t'):
-            setattr(p, k, self._table(name, keep, tables.get(k), S))
-        x_inter = self._log_args(name, p, keep, x, log_steps, x_inter_out)
-        p.x, p.cond = _ptr(x), _ptr(cond)
-        p.S, p.B, p.H, p.W, p.flags = S, B, H, W, int(flags)
-        self._run_loop(name, p, keep, control_scales)
-        return x, x_inter
+        return self._device_loop('sample_ancestral', _lib.FgdmAncestralParams(), x_T, cond, None, out, 'S', S,
+                                 dict({'timesteps': (timesteps, C.c_int64, S)},
+                                      **{k: tables.get(k) for k in ('sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod',
+                                                                    'posterior_mean_coef1', 'posterior_mean_coef2', 'std',
+                                                                    'sqrt_alphas_cumprod_t', 'sqrt_one_minus_alphas_cumprod_t')}),
+                                 dict(step_noise=(step_noise, (S,)), q_noise=(q_noise, (S,)), mask=(mask, ()), x0=(x0, ())),
+                                 (log_steps, dict(x_inter_out=x_inter_out)), control_scales, flags=int(flags))
 
     def ddim_encode(self, x0, cond, uncond, cfg_scale, timesteps, cx, ce, log_steps=(), control_scales=None, flags=0, out=None,
                     x_inter_out=None):
         """DDIM inversion on the device (fgdm_ddim_encode, include/fgdm.h): S = len(timesteps) steps over ascending timesteps
         with the per-step coefficients cx / ce (fgdm_amd.samplers.encode_tables).  Returns (x, x_inter) as sample_ancestral;
         x0 is not modified."""
-        name = 'ddim_encode'
-        x, cond, uncond = self._loop_args(name, x0, cond, uncond, out)
-        B, _, H, W = x.shape
         S = len(timesteps)
-        p = _lib.FgdmDdimEncodeParams()
-        keep = []
-        p.timesteps = self._table(name, keep, timesteps, S, C.c_int64, int)
-        p.cx, p.ce = self._table(name, keep, cx, S), self._table(name, keep, ce, S)
-        x_inter = self._log_args(name, p, keep, x, log_steps, x_inter_out)
-        p.x, p.cond, p.uncond = _ptr(x), _ptr(cond), _ptr(uncond)
-        p.cfg_scale, p.S, p.B, p.H, p.W, p.flags = float(cfg_scale), S, B, H, W, int(flags)
-        self._run_loop(name, p, keep, control_scales)
-        return x, x_inter
+        return self._device_loop('ddim_encode', _lib.FgdmDdimEncodeParams(), x0, cond, uncond, out, 'S', S,
+                                 dict(timesteps=(timesteps, C.c_int64, S), cx=cx, ce=ce), logs=(log_steps, dict(x_inter_out=x_inter_out)),
+                                 control_scales=control_scales, cfg_scale=float(cfg_scale), flags=int(flags))
 
 
 # ---------------------------------------------------------------------- fused sampler updates

@@ -512,7 +512,7 @@ class LatentDiffusion(_Buffers):
                 cond = cond.get('c_crossattn')
             if isinstance(cond, (list, tuple)) and len(cond) == 1:
                 cond = cond[0]
-        return samplers._SamplerBase._loop_cond_of(self, cond, None, False, None)
+        return samplers._loop_cond(self, cond, None, False)
 
     def _device_ancestral(self, plan, img, timesteps, mask, x0, log_every_t, repeat_noise=False, temperature=1.):
         """The walk t = timesteps - 1 ... 0 as consecutive engine calls of at most max_loop_noise_bytes of pre-drawn noise each.

@@ -14,7 +14,7 @@ Not carried over (dead or unreachable in the reference): infer
 DDIMSampler / ControlDDIMSampler(model, device_loop=True) hand a whole sample() / ddim_sampling() / decode() to the engine's device
 loop (fgdm_sample_ddim_ex) when nothing asked for needs the host between steps; the noise is drawn beforehand by the same calls in
 the same order, so either route gives the same bits from the same generator state.  Everything else, and the default, is the
-per-step loop below.  PLMSSampler and DPMSolverSampler take the same keyword and the same rule (_loop_plan / _loop_cond) for
+per-step loop below.  PLMSSampler and DPMSolverSampler take the same keyword and the same rule (_loop_plan / _loop_cond below) for
 fgdm_sample_plms and fgdm_sample_dpmpp; the DPM-Solver++ coefficients of both routes come from dpmpp_tables.
 ControlDDIMSampler.encode goes to fgdm_ddim_encode under the same rule, with the coefficients of encode_tables on both routes; the
 ancestral loop's switch is the model's (fgdm_amd.models.LatentDiffusion(device_loop=True)).
@@ -28,6 +28,63 @@ from . import schedule
 
 def _randn(shape, device):
     return torch.randn(shape, device=device)
+
+
+# ---- the device loops (DDIM, PLMS, DPM-Solver++, the DPM-Solver program, ancestral, DDIM inversion): what they can take over
+def _loop_cond(m, c, uc, cfg_on, sampler=None):
+    """(ctx, uctx, flags, control_scales) the engine's loop needs for this conditioning of model `m`, after registering the
+    hints as apply_model would -- or None: a conditioning the loop does not take (the per-step route then treats it as
+    before).  sampler: the one whose _cat_cond would join the two branches of a ControlLDM (None: no sampler joins them)."""
+    from . import _lib, models
+    pair = _lib.FLAG_CFG_PAIRS if cfg_on else 0
+    if isinstance(m, models.ControlLDM):
+        if type(m).apply_model is not models.ControlLDM.apply_model:
+            return None                                                   # a subclass with its own apply_model
+        if cfg_on and not isinstance(sampler, ControlDDIMSampler):
+            return None                                                   # only that sampler's _cat_cond joins dict conds
+        if not isinstance(c, dict) or len(c.get('c_crossattn') or ()) != 1 or not torch.is_tensor(c['c_crossattn'][0]):
+            return None
+        if cfg_on and (not isinstance(uc, dict) or sampler._cat_cond(uc, c) is None):
+            return None                                                   # branches that cannot share one batch: two calls per step
+        hints = c.get('c_concat')
+        flags = pair | (_lib.FLAG_ONLY_MID_CONTROL if m.only_mid_control else 0)
+        ctx, uctx = c['c_crossattn'][0], uc['c_crossattn'][0] if cfg_on else None
+        if hints is None:
+            return ctx, uctx, flags | _lib.FLAG_NO_CONTROL, None
+        if m.n_controlnets == 1:
+            hints = [hints[0] if len(hints) == 1 else torch.cat(hints, 1)]
+        if len(hints) != m.n_controlnets:
+            return None
+        for k, h in enumerate(hints):
+            m.engine.set_hint(k, h)
+        return ctx, uctx, flags, m._scales()
+    if type(m).apply_model is not models.LatentDiffusion.apply_model or m.model.conditioning_key != 'crossattn':
+        return None                                                       # hybrid c_concat, or a model with its own apply_model
+    if not torch.is_tensor(c) or getattr(m.engine, '_conds_key', None) is not None:
+        return None
+    if cfg_on and (not torch.is_tensor(uc) or tuple(uc.shape) != tuple(c.shape)):
+        return None
+    return c, uc if cfg_on else None, _lib.FLAG_NO_CONTROL | pair, None
+
+
+def _loop_plan(m, sampler, cond, uc, scales, mask, x0, img, host_hooks, kwargs, entry='sample_ddim_ex'):
+    """None (per-step route), or the conditioning part of the device loop's arguments for model `m`.  sampler: the one that asks
+    (its device_loop switch and dynamic threshold are honoured), or None: the caller has its own switch.  `scales`: the guidance
+    scale of every step of the walk; host_hooks: whether anything asked for runs on the host between steps; entry: the engine
+    method that runs the loop.  Draws no noise."""
+    eng = getattr(m, 'engine', None)
+    if (sampler is not None and not getattr(sampler, 'device_loop', False)) or eng is None or not hasattr(eng, entry) or host_hooks or kwargs:
+        return None
+    if getattr(m, 'split_input_params', None) is not None or getattr(sampler, '_dyn', None) is not None:
+        return None
+    if getattr(m, 'parameterization', 'eps') != 'eps' or not hasattr(m, '_host') or img.dim() != 4 or img.shape[1] != 4:
+        return None
+    on = [uc is not None and s != 1. for s in scales]
+    if any(on) != all(on):
+        return None                 # a ucg_schedule that is 1 at some steps: those steps run without the unconditional half
+    if mask is not None and (x0 is None or tuple(x0.shape) != tuple(img.shape)):
+        return None
+    return _loop_cond(m, cond, uc, all(on), sampler)
 
 
 class _SamplerBase:
@@ -167,66 +224,6 @@ class _SamplerBase:
         return _k.axpby(x0.contiguous(), float(sa[ti.flat[0]]), noise.contiguous(), float(s1m[ti.flat[0]]))
 
 
-    # ---- the device loops (DDIM, PLMS, DPM-Solver++): what they can take over
-    def _loop_cond(self, c, uc, cfg_on):
-        return _SamplerBase._loop_cond_of(self.model, c, uc, cfg_on, self)      # by class: DPMSolverSampler borrows this method
-
-    @staticmethod
-    def _loop_cond_of(m, c, uc, cfg_on, sampler):
-        """(ctx, uctx, flags, control_scales) the engine's loop needs for this conditioning of model `m`, after registering the
-        hints as apply_model would -- or None: a conditioning the loop does not take (the per-step route then treats it as
-        before).  sampler: the one whose _cat_cond would join the two branches (None, and cfg_on False: the model's own
-        ancestral loop, which has no guidance)."""
-        from . import _lib, models
-        pair = _lib.FLAG_CFG_PAIRS if cfg_on else 0
-        if isinstance(m, models.ControlLDM):
-            if type(m).apply_model is not models.ControlLDM.apply_model:
-                return None                                                   # a subclass with its own apply_model
-            if cfg_on and not isinstance(sampler, ControlDDIMSampler):
-                return None                                                   # only that sampler's _cat_cond joins dict conds
-            if not isinstance(c, dict) or len(c.get('c_crossattn') or ()) != 1 or not torch.is_tensor(c['c_crossattn'][0]):
-                return None
-            if cfg_on and (not isinstance(uc, dict) or sampler._cat_cond(uc, c) is None):
-                return None                                                   # branches that cannot share one batch: two calls per step
-            hints = c.get('c_concat')
-            flags = pair | (_lib.FLAG_ONLY_MID_CONTROL if m.only_mid_control else 0)
-            ctx, uctx = c['c_crossattn'][0], uc['c_crossattn'][0] if cfg_on else None
-            if hints is None:
-                return ctx, uctx, flags | _lib.FLAG_NO_CONTROL, None
-            if m.n_controlnets == 1:
-                hints = [hints[0] if len(hints) == 1 else torch.cat(hints, 1)]
-            if len(hints) != m.n_controlnets:
-                return None
-            for k, h in enumerate(hints):
-                m.engine.set_hint(k, h)
-            return ctx, uctx, flags, m._scales()
-        if type(m).apply_model is not models.LatentDiffusion.apply_model or m.model.conditioning_key != 'crossattn':
-            return None                                                       # hybrid c_concat, or a model with its own apply_model
-        if not torch.is_tensor(c) or getattr(m.engine, '_conds_key', None) is not None:
-            return None
-        if cfg_on and (not torch.is_tensor(uc) or tuple(uc.shape) != tuple(c.shape)):
-            return None
-        return c, uc if cfg_on else None, _lib.FLAG_NO_CONTROL | pair, None
-
-    def _loop_plan(self, cond, uc, scales, mask, x0, img, host_hooks, kwargs, entry='sample_ddim_ex'):
-        """None (per-step route), or the conditioning part of the device loop's arguments.  `scales`: the guidance scale of
-        every step of the walk; host_hooks: whether anything asked for runs on the host between steps; entry: the engine
-        method that runs the loop.  Draws no noise."""
-        m = self.model
-        eng = getattr(m, 'engine', None)
-        if not getattr(self, 'device_loop', False) or eng is None or not hasattr(eng, entry) or host_hooks or kwargs:
-            return None
-        if getattr(m, 'split_input_params', None) is not None or getattr(self, '_dyn', None) is not None:
-            return None
-        if getattr(m, 'parameterization', 'eps') != 'eps' or not hasattr(m, '_host') or img.dim() != 4 or img.shape[1] != 4:
-            return None
-        on = [uc is not None and s != 1. for s in scales]
-        if any(on) != all(on):
-            return None                 # a ucg_schedule that is 1 at some steps: those steps run without the unconditional half
-        if mask is not None and (x0 is None or tuple(x0.shape) != tuple(img.shape)):
-            return None
-        return self._loop_cond(cond, uc, all(on))
-
     def _mask_kw(self, mask, x0, qn, img, timesteps):
         """the mask group of a device loop's arguments ({} without a mask); qn: q_sample's noise of every step, already drawn"""
         if mask is None:
@@ -312,7 +309,7 @@ class DDIMSampler(_SamplerBase):
         hooks = bool(callback or img_callback or score_corrector is not None or noise_dropout > 0. or quantize_denoised
                      or inference_loss)
         plan = None if scales is None or total_steps < 1 else \
-            self._loop_plan(cond, unconditional_conditioning, scales, mask, x0, img, hooks, kwargs)
+            _loop_plan(self.model, self, cond, unconditional_conditioning, scales, mask, x0, img, hooks, kwargs)
         if plan is not None:
             log_steps = self._log_steps(total_steps, log_every_t)
             img, x_inter, pred = self._device_loop(plan, img, list(reversed([int(t) for t in time_range])),
@@ -385,7 +382,7 @@ class DDIMSampler(_SamplerBase):
         x_dec = x_latent
         # (ControlDDIMSampler.p_sample_ddim reads a ucg_schedule left by an earlier ddim_sampling at i = 0: per-step route)
         plan = None if total_steps < 1 or getattr(self, '_ucg', None) is not None else \
-            self._loop_plan(cond, unconditional_conditioning, [unconditional_guidance_scale] * total_steps, None, None, x_latent,
+            _loop_plan(self.model, self, cond, unconditional_conditioning, [unconditional_guidance_scale] * total_steps, None, None, x_latent,
                             bool(callback), {})
         if plan is not None:
             return self._device_loop(plan, x_latent, [int(t) for t in timesteps], self._tables(use_original_steps),
@@ -466,7 +463,7 @@ class PLMSSampler(_SamplerBase):
         hooks = bool(callback or img_callback or score_corrector is not None or noise_dropout > 0. or quantize_denoised)
         tabs = self._tables(ddim_use_original_steps)
         plan = None if total_steps < 1 or np.asarray(tabs[3])[:total_steps].any() else \
-            self._loop_plan(cond, unconditional_conditioning, [unconditional_guidance_scale] * total_steps, mask, x0, img, hooks, {},
+            _loop_plan(self.model, self, cond, unconditional_conditioning, [unconditional_guidance_scale] * total_steps, mask, x0, img, hooks, {},
                             entry='sample_plms')
         if plan is not None:
             img, x_inter, pred = self._device_loop(plan, img, list(reversed([int(t) for t in time_range])), tabs,
@@ -619,7 +616,7 @@ class ControlDDIMSampler(DDIMSampler):
         scale, uc = unconditional_guidance_scale, unconditional_conditioning
         plan = None
         if t_enc >= 1 and (scale == 1. or uc is not None):
-            plan = self._loop_plan(c, uc if scale != 1. else None, [scale] * t_enc, None, None, x0, bool(callback), {},
+            plan = _loop_plan(self.model, self, c, uc if scale != 1. else None, [scale] * t_enc, None, None, x0, bool(callback), {},
                                    entry='ddim_encode')
         if plan is not None:
             ctx, uctx, flags, control_scales = plan
@@ -780,10 +777,6 @@ class DPMSolverSampler:
         self.device_loop = bool(device_loop)
         self.alphas_cumprod = torch.as_tensor(model.alphas_cumprod).clone().detach().to(torch.float32).to(model.device)
 
-    _loop_plan = _SamplerBase._loop_plan
-    _loop_cond = _SamplerBase._loop_cond
-    _cat_cond = staticmethod(_SamplerBase._cat_cond)
-
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
 
@@ -805,7 +798,7 @@ class DPMSolverSampler:
         scale, uc = unconditional_guidance_scale, unconditional_conditioning
         tab = dpmpp_tables(ns, steps, order)
         hooks = bool(callback or img_callback or score_corrector is not None or noise_dropout > 0.)
-        plan = self._loop_plan(conditioning, uc, [scale] * steps, None, None, x, hooks, kwargs, entry='sample_dpmpp')
+        plan = _loop_plan(self.model, self, conditioning, uc, [scale] * steps, None, None, x, hooks, kwargs, entry='sample_dpmpp')
         if plan is not None:            # (mask / x0 are ignored, as the reference's sampler ignores them)
             ctx, uctx, flags, control_scales = plan
             x = self.model.engine.sample_dpmpp(x, ctx, uctx, scale if uctx is not None else 1.0, tab,

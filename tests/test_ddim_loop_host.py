@@ -340,3 +340,41 @@ def test_entries_refuse_null_arguments_without_a_device():
         x, ec, eu, 1.0, 0.5, 0.6, 0.0, 0.7, null, mask, x0, qn, 0.5, 0.5, q, null, null, null, null, n, null)
     assert step(x=null) == -1 and step(n=0) == -1 and step(ec=null, eu=q) == -1
     assert step(mask=q) == -1 and step(mask=q, x0=q) == -1 and step(mask=q, qn=q) == -1
+
+
+def test_converted_tensors_live_until_the_native_call_returns():
+    """a step tensor that is not fp32, contiguous and on the engine's device is copied; the struct must point into a copy that is
+    still alive while the native loop runs, and a log plane allocated afterwards must not land in a freed copy"""
+    from fgdm_amd import engine as E
+
+    class HostEngine(E.Engine):
+        def __init__(self):
+            self.device, self.seen = torch.device('cpu'), None
+
+        def set_context_tokens(self, n):
+            pass
+
+        def _run_loop(self, name, p, keep, control_scales, call=None):
+            self.seen = (p, {t.data_ptr() for t in keep if torch.is_tensor(t)})
+
+    e, S = HostEngine(), 3
+    x, c = torch.randn(1, 4, 8, 8), torch.randn(1, 77, 8)
+    noise = torch.randn(S, 1, 4, 8, 8, dtype=torch.float64)                       # another dtype
+    mask = torch.ones(1, 4, 8, 8).transpose(2, 3)                                  # not contiguous
+    tab = [0.5] * S
+    for call in (lambda: e.sample_ddim_ex(x, c, None, 1.0, [1, 2, 3], tab, tab, tab, sigmas=tab, step_noise=noise, mask=mask, x0=x.double(),
+                                          q_noise=noise, sqrt_alphas_cumprod_t=tab, sqrt_one_minus_alphas_cumprod_t=tab, log_steps=(1,)),
+                 lambda: e.sample_plms(x, c, None, 1.0, [1, 2, 3], tab, tab, tab, mask=mask, x0=x.double(), q_noise=noise,
+                                       sqrt_alphas_cumprod_t=tab, sqrt_one_minus_alphas_cumprod_t=tab, log_steps=(1,)),
+                 lambda: e.sample_ancestral(x, c, [3, 2, 1], dict(sqrt_recip_alphas_cumprod=tab, sqrt_recipm1_alphas_cumprod=tab,
+                                                                  posterior_mean_coef1=tab, posterior_mean_coef2=tab, std=tab,
+                                                                  sqrt_alphas_cumprod_t=tab, sqrt_one_minus_alphas_cumprod_t=tab),
+                                            step_noise=noise, mask=mask, x0=x.double(), q_noise=noise, log_steps=(1,))):
+        call()
+        p, alive = e.seen
+        fields = [k for k in ('step_noise', 'q_noise', 'mask', 'x0') if hasattr(p, k)]
+        assert len(fields) >= 3
+        for k in fields:
+            assert getattr(p, k) in alive, k
+        assert p.mask != mask.data_ptr() and p.q_noise != noise.data_ptr()
+        assert p.x_inter_out and p.x_inter_out not in alive
