@@ -93,6 +93,15 @@ class FgdmDdimEncodeParams(C.Structure):
             ('cfg_scale', C.c_float)] + [(name, C.c_int32) for name in ('S', 'B', 'H', 'W', 'flags', 'n_log', 'reserved0')]
 
 
+class FgdmAttentionCapture(C.Structure):
+    """fgdm_attention_capture of include/fgdm.h (fgdm_attention_capture_set); struct_size must be ctypes.sizeof of this class."""
+    _fields_ = [('struct_size', C.c_int64), ('tokens', C.POINTER(C.c_int32)), ('block_mask', C.c_uint32)] + [
+        (name, C.c_int32) for name in ('n_tokens', 'rows', 'mode', 'batch', 'latent_h', 'latent_w', 'reserved0')]
+
+
+ATTENTION_CAPTURE_MAX_KEYS = 256                                        # FGDM_ATTENTION_CAPTURE_MAX_KEYS
+CAPTURE_ROWS = {'all': 0, 'cond': 1, 'uncond': 2}                       # FGDM_CAPTURE_ROWS_*
+CAPTURE_MODES = {'sum': 0, 'last': 1}                                   # FGDM_CAPTURE_SUM / FGDM_CAPTURE_LAST
 DPMPP_FIRST, DPMPP_SECOND = 1, 2      # FGDM_DPMPP_FIRST / FGDM_DPMPP_SECOND
 DPM_PLANE_BASE, DPM_PLANE_HIST0, DPM_PLANE_M, DPM_DEST_STATE, DPM_DEST_EVAL = 0, 1, 4, 1, 2      # FGDM_DPM_PLANE_* / FGDM_DPM_DEST_*
 PLMS_PROBE, PLMS_FINISH_FIRST, PLMS_MULTISTEP = 0, 1, 2      # the modes of fgdm_op_plms_loop_step
@@ -120,6 +129,11 @@ SIGNATURES = {
     'fgdm_clip_encode_skip': (_i, [_p, _p, _i, _i, _i, _p, _p]),
     'fgdm_set_context_tokens': (_i, [_p, _i]),
     'fgdm_get_context_tokens': (_i, [_p]),
+    'fgdm_attention_capture_set': (_i, [_p, C.POINTER(FgdmAttentionCapture)]),
+    'fgdm_attention_capture_reset': (_i, [_p, _p]),
+    'fgdm_attention_capture_info': (_i, [_p, _i, C.POINTER(_i64), C.POINTER(C.c_int32)]),
+    'fgdm_attention_capture_block_size': (_i, [_p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'fgdm_attention_capture_read': (_i, [_p, _i, _p, _p]),
     'fgdm_run_block': (_i, [_p, C.c_char_p, _p, _i, _p, _i, _p, _p, _i, _i, _i, _p, _i64, C.POINTER(_i64), _p]),
     'fgdm_vae_decode': (_i, [_p, _p, _i, _i, _i, _f, _p, _p]),
     'fgdm_vae_encode': (_i, [_p, _p, _i, _i, _i, _p, _p]),
@@ -164,12 +178,14 @@ SIGNATURES = {
     'fgdm_op_linear_ln_linear': (_i, [_p] * 8 + [_i] * 5 + [_p, _p, C.POINTER(_i), _p]),
     'fgdm_bench_norm': (_i, [_i] * 7 + [C.POINTER(_f)]),
     'fgdm_bench_attention': (_i, [_i] * 6 + [C.POINTER(_f)]),
+    'fgdm_bench_attention_maps': (_i, [_i] * 7 + [C.POINTER(_f)]),
     'fgdm_bench_ff': (_i, [_i] * 4 + [C.POINTER(_f)]),
     'fgdm_op_groupnorm': (_i, [_p, _i, _p, _i, _i, _i, _p, _p, _f, _i, _p, _p]),
     'fgdm_op_layernorm': (_i, [_p, _i, _i, _p, _p, _f, _p, _p]),
     'fgdm_op_attention': (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     'fgdm_op_attention_ex': (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     'fgdm_debug_last_attention_kernel': (_i, []),
+    'fgdm_op_cross_attention_maps': (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     'fgdm_op_small_attention': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     'fgdm_op_vae_attention': (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     'fgdm_op_softmax_rows': (_i, [_p, _p, _i, _i, _p]),

@@ -47,12 +47,23 @@ __device__ __forceinline__ float att_max_cross(float mx) {
     return fmaxf(lo, hi);
 }
 
-template <int D>
+// Capturing instantiations (cross-attention maps, DESIGN.md "Cross-attention maps"): the two kernels that take text contexts carry a
+// parameter pack Cap, empty in the instantiations of the product path -- whose signature, registers and instructions are what they
+// were -- and one float* in the capturing ones: the per-head probability planes P [B, H, T, Tk] fp32 (row stride exactly Tk: pad
+// keys have no slot to be stored in).  P[b, h, t, k] = softmax_k(q k^T d^-1/2), from the fp32 exponentials BEFORE they are rounded to
+// fp16 for V^T P^T, divided by their own fp32 sum (not by the fp16 sum that normalises O).  attn_maps_reduce_kernel below averages
+// the planes over heads in head order.  Plain per-lane stores; nothing else in the kernel reads them, O keeps its bits.
+__device__ __forceinline__ float* att_cap_plane() { return nullptr; }
+__device__ __forceinline__ float* att_cap_plane(float* p) { return p; }
+#define ATT_CAP_MAX_KEYS 256      // the capturing kernels' key limit (fgdm.h: FGDM_ATTENTION_CAPTURE_MAX_KEYS)
+
+template <int D, class... Cap>
 __global__ __launch_bounds__(256) void attn_kernel(const half_t* __restrict__ Q, int ldq,
                                                    const half_t* __restrict__ K, int ldk,
                                                    const half_t* __restrict__ Vt, int ldvt,
                                                    half_t* __restrict__ O, int ldo,
-                                                   int H, int T, int Tk, float sl2e) {
+                                                   int H, int T, int Tk, float sl2e, Cap... cap) {
+    constexpr bool CAP = sizeof...(Cap) > 0;
     constexpr int DP = (D + 15) / 16 * 16;   // QK^T contraction length, padded to MFMA K
     constexpr int NKS = DP / 16;
     constexpr int DT = (D + 31) / 32;         // 32-row tiles of O^T
@@ -124,6 +135,16 @@ __global__ __launch_bounds__(256) void attn_kernel(const half_t* __restrict__ Q,
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
     float m_run = FOLD ? 0.f : -INFINITY, l_run = 0.f;   // l_run only used when there is no spare row (D = 160)
+    // CAP (Tk <= ATT_CAP_MAX_KEYS = four tiles): the softmax is online, so a tile's probabilities are stored as they are -- relative to
+    // the running maximum of their tile, cap_m[tile] -- and put right behind the loop, when the final maximum and the fp32 sum cap_l
+    // (rescaled with O) are known: each lane multiplies what it stored itself by exp2(cap_m[tile] - m_run) / cap_l
+    float cap_l = 0.f, cap_m[CAP ? ATT_CAP_MAX_KEYS / 64 : 1];
+    float* cap_row = nullptr;
+    if constexpr (CAP) {
+#pragma unroll
+        for (int j = 0; j < ATT_CAP_MAX_KEYS / 64; ++j) cap_m[j] = 0.f;
+        cap_row = att_cap_plane(cap...) + (((size_t)b * H + head) * T + min(q, T - 1)) * Tk;
+    }
 
     const half_t* Kb = K + (size_t)b * Tk * ldk + head * D;
     const half_t* Vb = Vt + ((size_t)b * H + head) * D * ldvt;
@@ -253,6 +274,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const half_t* __restrict__ Q,
                 const float delta = m_run - m_hat;
                 const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(delta);
                 m_run = m_hat;
+                if constexpr (CAP) cap_l *= alpha;
 #pragma unroll
                 for (int t = 0; t < DT; ++t)
 #pragma unroll
@@ -282,6 +304,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const half_t* __restrict__ Q,
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
             m_run = m_new;
             l_run *= alpha;
+            if constexpr (CAP) cap_l *= alpha;
 #pragma unroll
             for (int t = 0; t < DT; ++t)
 #pragma unroll
@@ -297,6 +320,21 @@ __global__ __launch_bounds__(256) void attn_kernel(const half_t* __restrict__ Q,
             }
         }
         if constexpr (!ONES) l_run += psum;
+        if constexpr (CAP) {      // the fp32 probabilities of this tile, against m_run as it stands now (keys >= Tk: no slot, not stored)
+#pragma unroll
+            for (int j = 0; j < ATT_CAP_MAX_KEYS / 64; ++j)
+                cap_m[j] = (j == (k0 >> 6)) ? m_run : cap_m[j];
+            float cs = 0.f;
+#pragma unroll
+            for (int sub = 0; sub < NSUB; ++sub)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    cs += sacc[sub][r];
+                    const int key = k0 + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    if (q < T && key < Tk) cap_row[key] = sacc[sub][r];
+                }
+            cap_l += cs;
+        }
 
         // ---- O^T += Vt P^T   (with ONES: row D of O^T accumulates sum_k p)
 #pragma unroll
@@ -327,6 +365,20 @@ __global__ __launch_bounds__(256) void attn_kernel(const half_t* __restrict__ Q,
         }
     }
 
+    if constexpr (CAP) {
+        __syncthreads();      // every lane re-reads only what it stored itself; the barrier drains those stores first
+        const float cinv = 1.0f / (cap_l + __shfl_xor(cap_l, 32));
+#pragma unroll
+        for (int j = 0; j < ATT_CAP_MAX_KEYS / 64; ++j)
+            if (j * 64 < Tk) {
+                const float f = __builtin_amdgcn_exp2f(cap_m[j] - m_run) * cinv;
+#pragma unroll
+                for (int r = 0; r < 32; ++r) {
+                    const int key = j * 64 + (r >> 4) * 32 + (r & 3) + 8 * ((r & 15) >> 2) + 4 * lh;
+                    if (q < T && key < Tk) cap_row[key] *= f;
+                }
+            }
+    }
     float l_tot;
     if constexpr (ONES) {
         // row D of O^T lives in tile D/32, register (D%32 -> (r&3)+8(r>>2)+4h): fetch it from the lane half that owns it
@@ -374,12 +426,13 @@ constexpr int attn_cross_lds(int D, int NS) {
     const int DP = (D + 15) / 16 * 16, DT = (D + 31) / 32, KEYS = NS * 32;
     return KEYS * (DP * 2 + 16) + DT * 32 * (KEYS * 2 + 72) + (D <= 80 ? 4 * 32 * (D * 2 + 8) : 0);
 }
-template <int D, int NS>
+template <int D, int NS, class... Cap>
 __global__ __launch_bounds__(256) void attn_cross_kernel(const half_t* __restrict__ Q, int ldq,
                                                          const half_t* __restrict__ K, int ldk,
                                                          const half_t* __restrict__ Vt, int ldvt,
                                                          half_t* __restrict__ O, int ldo,
-                                                         int H, int T, int Tk, float sl2e, int cpw) {
+                                                         int H, int T, int Tk, float sl2e, int cpw, Cap... cap) {
+    constexpr bool CAP = sizeof...(Cap) > 0;      // the capturing instantiation (see att_cap_plane above)
     constexpr int KEYS = NS * 32;
     constexpr int DP = (D + 15) / 16 * 16, NKS = DP / 16, DT = (D + 31) / 32;
     constexpr bool ONES = (DT * 32 > D);
@@ -551,6 +604,24 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(const half_t* __restric
                 sacc[sub][r] = pv;
                 if constexpr (!ONES) psum += pv;
             }
+        if constexpr (CAP) {      // all keys are here: the row's maximum and its fp32 sum are final before V^T P^T
+            float cs = 0.f;
+#pragma unroll
+            for (int sub = 0; sub < NS; ++sub)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) cs += sacc[sub][r];      // masked keys: exp2(-inf) = 0
+            const float cinv = 1.0f / (cs + __shfl_xor(cs, 32));
+            if (q < T) {
+                float* cap_row = att_cap_plane(cap...) + (((size_t)b * H + head) * T + q) * Tk;
+#pragma unroll
+                for (int sub = 0; sub < NS; ++sub)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int key = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        if (key < Tk) cap_row[key] = sacc[sub][r] * cinv;
+                    }
+            }
+        }
         // ---- O^T = V^T P^T (row D of O^T: the sum of the fp16 probabilities)
         f32x16 oacc[DT];
 #pragma unroll
@@ -1537,7 +1608,9 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
 // Which kernel attention_launch chose on its last successful call in this process (fgdm_debug_last_attention_kernel: the parity
 // tests assert that a case reaches the kernel it was written for).  Host side only: one store of a plain int per launch.
 enum AttnKernelId { ATT_KID_NONE = 0, ATT_KID_GENERAL = 1, ATT_KID_CROSS = 2, ATT_KID_CROSS_LONG = 3, ATT_KID_PP = 4, ATT_KID_DQ16 = 5,
-                    ATT_KID_DQ32 = 6 };
+                    ATT_KID_DQ32 = 6,
+                    // the capturing instantiations (attention_capture_launch)
+                    ATT_KID_GENERAL_CAP = 7, ATT_KID_CROSS_CAP = 8, ATT_KID_CROSS_LONG_CAP = 9 };
 static int g_last_attn_kernel = ATT_KID_NONE;
 int attention_last_kernel() { return g_last_attn_kernel; }
 static int att_launched(int kid) {
@@ -1555,6 +1628,7 @@ struct AttnCall {
     int B, H, T, Tk;
     float sl2e;
     hipStream_t s;
+    float* cap = nullptr;      // the per-head planes of a capturing call, else NULL
 };
 template <auto Kernel, class... Extra>
 static int att_launch(const AttnCall& c, dim3 grid, int threads, int lds, int kid, Extra... extra) {
@@ -1576,7 +1650,9 @@ static int by_head_width(int d, F&& f) {
 
 template <int D>
 static int launch_general(const AttnCall& c) {
-    return att_launch<attn_kernel<D>>(c, dim3(((c.T + 127) / 128) * c.H * c.B), 256, 0, ATT_KID_GENERAL);
+    const dim3 grid(((c.T + 127) / 128) * c.H * c.B);
+    if (c.cap) return att_launch<attn_kernel<D, float*>>(c, grid, 256, 0, ATT_KID_GENERAL_CAP, c.cap);
+    return att_launch<attn_kernel<D>>(c, grid, 256, 0, ATT_KID_GENERAL);
 }
 template <int D>
 static int launch_pp(const AttnCall& c) {
@@ -1622,9 +1698,14 @@ static int launch_cross(const AttnCall& c, int cpw) {
         return FGDM_ERR_ARG;
     } else {
         if ((c.Tk + 31) / 32 != NS || c.ldvt < NS * 32) return FGDM_ERR_ARG;      // the kernel's contract: it masks sub-tile NS - 1 only
+        const dim3 grid(((c.T + 128 * cpw - 1) / (128 * cpw)) * c.H * c.B);
+        if (c.cap) {
+            constexpr auto kc = attn_cross_kernel<D, NS, float*>;
+            if (dyn && fgdm_dyn_lds<kc>(dyn) != FGDM_OK) return FGDM_ERR_HIP;
+            return att_launch<kc>(c, grid, 256, dyn, NS == 3 ? ATT_KID_CROSS_CAP : ATT_KID_CROSS_LONG_CAP, cpw, c.cap);
+        }
         constexpr auto k = attn_cross_kernel<D, NS>;
         if (dyn && fgdm_dyn_lds<k>(dyn) != FGDM_OK) return FGDM_ERR_HIP;
-        const dim3 grid(((c.T + 128 * cpw - 1) / (128 * cpw)) * c.H * c.B);
         return att_launch<k>(c, grid, 256, dyn, NS == 3 ? ATT_KID_CROSS : ATT_KID_CROSS_LONG, cpw);
     }
 }
@@ -1643,25 +1724,30 @@ static int launch_cross_ns(const AttnCall& c, int ns, int cpw) {
 
 // The first condition that holds decides (tests/attention_dispatch.py states the same rules a second time); the knobs are read in
 // this order, each when its condition is reached.
-int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
-                     int ldo, int B, int H, int T, int Tk, int d, int q_prescaled, hipStream_t s) {
+// cap: NULL, or the per-head planes of a capturing call (attention_capture_launch).  The rules are the same either way; a capturing
+// call that they send to a kernel without a capturing instantiation (the long self-attention kernels) is FGDM_ERR_ARG.
+static int attention_dispatch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
+                              int ldo, int B, int H, int T, int Tk, int d, int q_prescaled, float* cap, hipStream_t s) {
     if (B <= 0 || H <= 0 || T <= 0 || Tk <= 0) return FGDM_ERR_ARG;
     if (ldvt < (Tk + 63) / 64 * 64 || (ldvt & 7) || (ldq & 7) || (ldk & 7) || (ldo & 3)) return FGDM_ERR_ARG;
     // q_prescaled: the to_q weights were packed with log2(e) d^-1/2 folded in (fgdm_finalize_weights), so Q arrives in the
     // log2 domain with ONE fp16 rounding; the kernels then multiply by exactly 1
     const float sl2e = q_prescaled ? 1.0f : 1.4426950408889634f / sqrtf((float)d);
-    const AttnCall c{Q, ldq, K, ldk, Vt, ldvt, O, ldo, B, H, T, Tk, sl2e, s};
+    const AttnCall c{Q, ldq, K, ldk, Vt, ldvt, O, ldo, B, H, T, Tk, sl2e, s, cap};
     const bool pp_on = knob_once(KNOB_ATTN_PP) != 0;
     // long self-attention, d = 40: the two-strand kernels.  FGDM_ATTN_DQ: 0 = off, 1 = 16-wide V^T P^T (the faster one on random
     // operands), anything else = 32-wide (default 3: the faster one inside the network).  Under FGDM_ATTN_ABL the
     // ablated 32-wide kernel is taken at FGDM_ATTN_DQ=3 only, the ablated 16-wide one otherwise
     const int dq = knob_once(KNOB_ATTN_DQ);
     if (dq > 0 && d == 40 && two_strand_ok(c, d)) {
+        if (cap) return FGDM_ERR_ARG;
         if (const int abl = knob_once(KNOB_ATTN_ABL)) return launch_ablation_bits(c, abl, dq == 3);
         return dq == 1 ? launch_two_strand<attn_dq_kernel<40, 4>>(c, ATT_KID_DQ16) : launch_two_strand<attn_dq32_kernel<40, 4>>(c, ATT_KID_DQ32);
     }
     // d = 80: the 32-wide kernel at one wave per SIMD (its two strands need ~280 registers); FGDM_ATTN_DQ80=0 switches it off (A/B)
     const int dq80 = knob_once(KNOB_ATTN_DQ80);
+    if (cap && ((dq80 > 0 && (d == 80 || d == 64) && two_strand_ok(c, d)) || (pp_on && T >= 256 && Tk >= 256 && (d == 40 || d == 64 || d == 80))))
+        return FGDM_ERR_ARG;
     if (dq80 > 0 && d == 80 && two_strand_ok(c, d)) return launch_two_strand<attn_dq32_kernel<80, 4>>(c, ATT_KID_DQ32);
     // d = 64 (SD-2.x: a fixed head width): the 32-wide kernel as well, one wave per SIMD like d = 80 and behind the same switch --
     // FGDM_ATTN_DQ80=0 sends both to the ping-pong kernel (A/B; the measurement behind the default: profiles/attention_d64.txt)
@@ -1681,4 +1767,41 @@ int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const h
         return by_head_width(d, [&](auto dc) { return launch_cross_ns<decltype(dc)::value>(c, ns, std::min(cross_long, T / 128)); });
     // everything else: the general kernel
     return by_head_width(d, [&](auto dc) { return launch_general<decltype(dc)::value>(c); });
+}
+int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O,
+                     int ldo, int B, int H, int T, int Tk, int d, int q_prescaled, hipStream_t s) {
+    return attention_dispatch(Q, ldq, K, ldk, Vt, ldvt, O, ldo, B, H, T, Tk, d, q_prescaled, nullptr, s);
+}
+
+// =====================================================================================================================
+// Cross-attention maps.  The head reduction is a second, small kernel: the capturing instantiations above write one probability
+// plane per head, and this kernel sums a (row, query, token) element over the planes h = 0 .. H - 1 IN THAT ORDER, one thread per
+// element -- no atomics, no order that depends on scheduling: two runs give the same bits.  It also does the bookkeeping of the
+// engine's capture plan: rows [row0, row0 + rows) of the batch (a CFG half), the token columns tok[0 .. ntok) (NULL: all Tk, in
+// order), and A += mean (accumulate) or A = mean.  A is fp32 [rows, T, ntok].
+__global__ __launch_bounds__(256) void attn_maps_reduce_kernel(const float* __restrict__ P, float* __restrict__ A, int H, int T, int Tk,
+                                                               int row0, const int* __restrict__ tok, int ntok, int accumulate, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int j = (int)(i % ntok);
+    const size_t bt = i / ntok;
+    const int t = (int)(bt % T), b = row0 + (int)(bt / T);
+    const int k = tok ? tok[j] : j;
+    float sum = 0.f;
+    for (int h = 0; h < H; ++h) sum += P[(((size_t)b * H + h) * T + t) * Tk + k];
+    const float v = sum / (float)H;
+    A[i] = accumulate ? A[i] + v : v;
+}
+size_t attention_capture_plane_floats(int B, int H, int T, int Tk) { return (size_t)B * H * T * Tk; }
+int attention_capture_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O, int ldo,
+                             int B, int H, int T, int Tk, int d, int q_prescaled, float* planes, hipStream_t s) {
+    if (!planes || Tk > ATT_CAP_MAX_KEYS) return FGDM_ERR_ARG;
+    return attention_dispatch(Q, ldq, K, ldk, Vt, ldvt, O, ldo, B, H, T, Tk, d, q_prescaled, planes, s);
+}
+int attention_maps_reduce(const float* planes, float* maps, int H, int T, int Tk, int row0, int rows, const int* tok, int ntok,
+                          int accumulate, hipStream_t s) {
+    if (!planes || !maps || H <= 0 || T <= 0 || Tk <= 0 || row0 < 0 || rows <= 0 || ntok <= 0 || (!tok && ntok != Tk)) return FGDM_ERR_ARG;
+    const size_t n = (size_t)rows * T * ntok;
+    FGDM_LAUNCH(attn_maps_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, planes, maps, H, T, Tk, row0, tok, ntok, accumulate, n);
+    return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
 }

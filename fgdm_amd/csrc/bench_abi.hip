@@ -114,7 +114,8 @@ int fgdm_bench_ff(int M, int Cw, int chunk, int iters, float* avg_ms) {
 }
 
 // Micro-benchmark of the fused attention kernel on random data: average device ms over `iters` launches.
-int fgdm_bench_attention(int B, int heads, int T, int Tk, int d, int iters, float* avg_ms) {
+// capture 0: attention_launch; 1: the capturing instantiation alone (per-head planes written); 2: ... and the head reduction
+static int bench_attention(int B, int heads, int T, int Tk, int d, int capture, int iters, float* avg_ms) {
     if (!avg_ms || iters <= 0 || B <= 0 || heads <= 0 || T <= 0 || Tk <= 0) return FGDM_ERR_ARG;
     const int C = heads * d, Tkp = (Tk + 63) / 64 * 64;
     unsigned st = 4242u;
@@ -129,7 +130,21 @@ int fgdm_bench_attention(int B, int heads, int T, int Tk, int d, int iters, floa
     if (!o) return FGDM_ERR_NOMEM;
     const half_t *dq = tmp.up(hq), *dk = tmp.up(hk), *dv = tmp.up(hv);
     if (!dq || !dk || !dv) return FGDM_ERR_NOMEM;
-    return time_launches(3, iters, avg_ms, [&]() { return attention_launch(dq, C, dk, C, dv, Tkp, o, C, B, heads, T, Tk, d, 0, nullptr); });
+    if (!capture) return time_launches(3, iters, avg_ms, [&]() { return attention_launch(dq, C, dk, C, dv, Tkp, o, C, B, heads, T, Tk, d, 0, nullptr); });
+    float* planes = tmp.alloc<float>(attention_capture_plane_floats(B, heads, T, Tk));
+    float* maps = tmp.alloc<float>((size_t)B * T * Tk);
+    if (!planes || !maps) return FGDM_ERR_NOMEM;
+    return time_launches(3, iters, avg_ms, [&]() {
+        int rc = attention_capture_launch(dq, C, dk, C, dv, Tkp, o, C, B, heads, T, Tk, d, 0, planes, nullptr);
+        if (rc == FGDM_OK && capture == 2) rc = attention_maps_reduce(planes, maps, heads, T, Tk, 0, B, nullptr, Tk, 0, nullptr);
+        return rc;
+    });
+}
+int fgdm_bench_attention(int B, int heads, int T, int Tk, int d, int iters, float* avg_ms) {
+    return bench_attention(B, heads, T, Tk, d, 0, iters, avg_ms);
+}
+int fgdm_bench_attention_maps(int B, int heads, int T, int Tk, int d, int with_reduce, int iters, float* avg_ms) {
+    return bench_attention(B, heads, T, Tk, d, with_reduce ? 2 : 1, iters, avg_ms);
 }
 
 // Micro-benchmark of one GroupNorm / LayerNorm shape on random data: average device ms over `iters` launches.

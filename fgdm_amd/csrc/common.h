@@ -159,6 +159,15 @@ int layernorm_launch(const half_t* x, int rows, int C, const float* gamma, const
 int attention_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt,
                      half_t* O, int ldo, int B, int H, int T, int Tk, int d, int q_prescaled, hipStream_t s);
 int attention_last_kernel();      // AttnKernelId (attention.hip) of the last successful attention_launch of this process
+// Cross-attention maps: attention_launch through the capturing instantiations, which also write planes [B, H, T, Tk] fp32
+// (attention_capture_plane_floats), the normalised probabilities per head; Tk <= 256 and a shape that the dispatch gives to a text
+// kernel or the general one, else FGDM_ERR_ARG.  attention_maps_reduce: maps [rows, T, ntok] (+)= the mean over heads, in head
+// order, of rows [row0, row0 + rows) and the token columns tok [ntok] (device; NULL: all Tk).
+size_t attention_capture_plane_floats(int B, int H, int T, int Tk);
+int attention_capture_launch(const half_t* Q, int ldq, const half_t* K, int ldk, const half_t* Vt, int ldvt, half_t* O, int ldo,
+                             int B, int H, int T, int Tk, int d, int q_prescaled, float* planes, hipStream_t s);
+int attention_maps_reduce(const float* planes, float* maps, int H, int T, int Tk, int row0, int rows, const int* tok, int ntok,
+                          int accumulate, hipStream_t s);
 
 // ---------------------------------------------------------------- elementwise
 int nchw_f32_to_nhwc_f16(const float* x, half_t* y, int B, int C, int HW, int Cpad, hipStream_t s);

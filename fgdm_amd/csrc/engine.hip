@@ -150,6 +150,73 @@ struct fgdm_engine : Model {
     std::unordered_map<const Layer*, CtxKV> ctx_cache;
     int ctx_B = 0, ctx_T = 0;
     int ctx_tokens = 77;                 // tokens behind every ctx / cond / uncond pointer (fgdm_set_context_tokens); 77 = one CLIP chunk
+    // Cross-attention maps (fgdm_attention_capture_*): the plan, one accumulator [rows, T, n_tok] per selected UNet block and the
+    // per-head planes the capturing kernels write (one scratch buffer: the launches that use it are ordered on the stream).  The
+    // ControlNets' layers are not in `planes`, so their cross-attentions are never captured.  capturing: inside an apply_model only.
+    struct CapPlane { int block = 0, heads = 0, h = 0, w = 0; float* acc = nullptr; };
+    struct Capture {
+        bool on = false, capturing = false;
+        int rows_sel = 0, mode = 0, Tk = 0;
+        int B = 0, H = 0, W = 0;         // the evaluations' batch and latent size (0: not fixed yet, nothing allocated)
+        int row0 = 0, rows = 0, n_evals = 0;
+        std::vector<int> tokens;
+        int* tok_dev = nullptr;
+        float* head_planes = nullptr;
+        std::vector<const Layer*> order;                       // the UNet's transformer blocks in walk order
+        std::unordered_map<const Layer*, CapPlane> planes;     // the selected ones
+    } cap;
+    void capture_free() {
+        for (auto& kv : cap.planes) { (void)hipFree(kv.second.acc); kv.second.acc = nullptr; }
+        (void)hipFree(cap.tok_dev); (void)hipFree(cap.head_planes);
+        cap.tok_dev = nullptr; cap.head_planes = nullptr;
+        cap.B = cap.H = cap.W = 0;
+    }
+    void capture_off() { capture_free(); cap = Capture{}; }
+    size_t capture_plane_floats(const CapPlane& p) const { return (size_t)cap.rows * p.h * p.w * cap.tokens.size(); }
+    // the accumulators for evaluations of B rows on an H x W latent: every selected block's h x w follows from its place in the walk
+    int capture_alloc(int B, int H, int W) {
+        capture_free();
+        const bool half = cap.rows_sel != FGDM_CAPTURE_ROWS_ALL;
+        if (half && (B & 1)) return fail(FGDM_ERR_STATE, "attention capture: the conditional / unconditional half of an odd batch");
+        cap.rows = half ? B / 2 : B;
+        cap.row0 = cap.rows_sel == FGDM_CAPTURE_ROWS_COND ? B / 2 : 0;      // cat([uncond, cond])
+        int h = H, w = W;
+        size_t scratch = 0;
+        auto walk = [&](const Block& blk) -> int {
+            for (const Layer& l : blk) {
+                if (l.type == L_DOWN) { h = (h + 1) / 2; w = (w + 1) / 2; }
+                if (l.type == L_UP) { h *= 2; w *= 2; }
+                auto it = l.type == L_ATTN ? cap.planes.find(&l) : cap.planes.end();
+                if (it == cap.planes.end()) continue;
+                CapPlane& p = it->second;
+                p.h = h; p.w = w; p.heads = l.heads;
+                scratch = std::max(scratch, attention_capture_plane_floats(B, l.heads, h * w, cap.Tk));
+            }
+            return FGDM_OK;
+        };
+        CHK0(for_each_block(unet, false, walk));
+        bool ok = hipMalloc(&cap.tok_dev, cap.tokens.size() * sizeof(int)) == hipSuccess &&
+                  hipMemcpy(cap.tok_dev, cap.tokens.data(), cap.tokens.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMalloc(&cap.head_planes, scratch * sizeof(float)) == hipSuccess;
+        for (auto& kv : cap.planes) {
+            const size_t bytes = capture_plane_floats(kv.second) * sizeof(float);
+            ok = ok && hipMalloc(&kv.second.acc, bytes) == hipSuccess && hipMemset(kv.second.acc, 0, bytes) == hipSuccess;
+        }
+        if (!ok) { capture_free(); return fail(FGDM_ERR_NOMEM, "hipMalloc (attention capture)"); }
+        cap.B = B; cap.H = H; cap.W = W;
+        cap.n_evals = 0;
+        return FGDM_OK;
+    }
+    // apply_model, before its first launch: is this an evaluation the plan captures?
+    int capture_begin(int B, int H, int W) {
+        if (cap.Tk != ctx_tokens) return fail(FGDM_ERR_STATE, "attention capture: the context token count changed after the plan was set");
+        if (!cap.B) CHK0(capture_alloc(B, H, W));
+        if (B != cap.B || H != cap.H || W != cap.W)
+            return fail(FGDM_ERR_STATE, "attention capture: this evaluation's batch or latent size is not the one the accumulators were made for");
+        cap.capturing = true;
+        ++cap.n_evals;
+        return FGDM_OK;
+    }
     // c_concat of a UNet fed cat([x] + c_concat, 1) (in_channels > 4; fgdm_set_concat): loop-invariant, kept as fp16 NHWC
     // [Bc, H W, in_channels - 4] (persistent hipMalloc, like a ControlNet's cached hint)
     Tensor ccat;
@@ -682,7 +749,18 @@ struct fgdm_engine : Model {
         if (!a.p) return fail(FGDM_ERR_NOMEM, "workspace");
         { char tag[56]; snprintf(tag, sizeof(tag), "attn B%d T%d Tk%d d%d", B, T, Tk, d);
           prof.begin(PC_ATTN, s, 4.0 * (double)B * T * (double)Tk * C, tag);
-          int rc = attention_launch(q2.p, C, k2.p, C, v2t.p, Tkp, a.p, C, B, l.heads, T, Tk, d, 1, s);
+          int rc;
+          auto cp = cap.capturing ? cap.planes.find(&l) : cap.planes.end();
+          if (cp != cap.planes.end()) {      // a selected UNet block: the capturing instantiation, then the head reduction into its accumulator
+              const CapPlane& p = cp->second;
+              if (B != cap.B || T != p.h * p.w || Tk != cap.Tk) return fail(FGDM_ERR_STATE, "attention capture: block shape differs from the plan's");
+              rc = attention_capture_launch(q2.p, C, k2.p, C, v2t.p, Tkp, a.p, C, B, l.heads, T, Tk, d, 1, cap.head_planes, s);
+              if (rc == FGDM_OK)
+                  rc = attention_maps_reduce(cap.head_planes, p.acc, l.heads, T, Tk, cap.row0, cap.rows, cap.tok_dev, (int)cap.tokens.size(),
+                                             cap.mode == FGDM_CAPTURE_SUM, s);
+          } else {
+              rc = attention_launch(q2.p, C, k2.p, C, v2t.p, Tkp, a.p, C, B, l.heads, T, Tk, d, 1, s);
+          }
           prof.end(s);
           if (rc != FGDM_OK) return fail(rc, "attention launch failed"); }
         tfree(q2);
@@ -1084,6 +1162,16 @@ struct fgdm_engine : Model {
 
     int apply_model(const float* x, const int64_t* t, const float* tf, const float* ctx, const float* pcond,
                     const float* scales, int B, int H, int W, int flags, float* eps_out) {
+        if (!cap.on) return apply_model_walk(x, t, tf, ctx, pcond, scales, B, H, W, flags, eps_out);
+        if (!finalized) return fail(FGDM_ERR_STATE, "weights not finalized");
+        if (B <= 0 || H <= 0 || W <= 0) return fail(FGDM_ERR_ARG, "bad shape");
+        CHK(capture_begin(B, H, W));
+        const int rc = apply_model_walk(x, t, tf, ctx, pcond, scales, B, H, W, flags, eps_out);
+        cap.capturing = false;
+        return rc;
+    }
+    int apply_model_walk(const float* x, const int64_t* t, const float* tf, const float* ctx, const float* pcond,
+                         const float* scales, int B, int H, int W, int flags, float* eps_out) {
         if (!finalized) return fail(FGDM_ERR_STATE, "weights not finalized");
         if (B <= 0 || H <= 0 || W <= 0) return fail(FGDM_ERR_ARG, "bad shape");
         Net& n = unet;
@@ -1652,6 +1740,7 @@ void fgdm_destroy(fgdm_engine* e) {
     e->drop_concat();
     e->drop_context();
     e->drop_adapter_conds();
+    e->capture_free();
     if (knob_text(KNOB_PAIR_DEBUG) && e->replay_stats.replayed)
         fprintf(stderr, "[fgdm] grouped twin launches: %ld of %ld replayed launches were fused (%ld problems)\n", e->replay_stats.fused, e->replay_stats.replayed, e->replay_stats.problems);
     if (e->s2) { (void)hipStreamSynchronize(e->s2); (void)hipStreamDestroy(e->s2); }
@@ -1837,6 +1926,94 @@ int fgdm_set_context_tokens(fgdm_engine* e, int tokens) {
 }
 
 int fgdm_get_context_tokens(const fgdm_engine* e) { return e ? e->ctx_tokens : FGDM_ERR_ARG; }
+
+// ------------------------------------------------------------------------------------------------ cross-attention maps
+int fgdm_attention_capture_set(fgdm_engine* e, const fgdm_attention_capture* plan) {
+    if (!e) return FGDM_ERR_ARG;
+    if (!plan) { e->capture_off(); return FGDM_OK; }
+    fgdm_attention_capture p;
+    if (!read_params(plan, FGDM_ATTENTION_CAPTURE_SIZE_V1, &p, sizeof(p)))
+        return e->fail(FGDM_ERR_ARG, "attention capture: struct_size is not the sizeof(fgdm_attention_capture) of a known header version");
+    if (p.reserved0) return e->fail(FGDM_ERR_ARG, "attention capture: reserved0 must be 0");
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
+    std::vector<const Layer*> order;
+    for_each_block(e->unet, false, [&](const Block& blk) {
+        for (const Layer& l : blk) if (l.type == L_ATTN) order.push_back(&l);
+        return FGDM_OK;
+    });
+    const int nb = (int)order.size(), Tk = e->ctx_tokens;
+    if (!p.block_mask || (nb < 32 && (p.block_mask >> nb)))
+        return e->fail(FGDM_ERR_ARG, "attention capture: block_mask must name at least one of the UNet's " + std::to_string(nb) + " transformer blocks and no other");
+    if (Tk > FGDM_ATTENTION_CAPTURE_MAX_KEYS)
+        return e->fail(FGDM_ERR_ARG, "attention capture: the context has " + std::to_string(Tk) + " tokens, more than FGDM_ATTENTION_CAPTURE_MAX_KEYS, the capturing kernels' key limit");
+    if (Tk >= 128 && Tk % 64 == 0)
+        return e->fail(FGDM_ERR_ARG, "attention capture: a context of 128, 192 or 256 tokens runs on the self-attention kernels, which have no capturing form");
+    if (p.n_tokens < 0 || p.n_tokens > Tk || (p.n_tokens > 0 && !p.tokens))
+        return e->fail(FGDM_ERR_ARG, "attention capture: n_tokens must lie in [0, context tokens], with tokens given when it is not 0");
+    std::vector<int> tokens;
+    for (int i = 0; i < (p.n_tokens ? p.n_tokens : Tk); ++i) {
+        const int k = p.n_tokens ? p.tokens[i] : i;
+        if (k < 0 || k >= Tk) return e->fail(FGDM_ERR_ARG, "attention capture: token index " + std::to_string(k) + " is outside the registered context of " + std::to_string(Tk) + " tokens");
+        tokens.push_back(k);
+    }
+    if (p.rows < FGDM_CAPTURE_ROWS_ALL || p.rows > FGDM_CAPTURE_ROWS_UNCOND) return e->fail(FGDM_ERR_ARG, "attention capture: rows must be FGDM_CAPTURE_ROWS_ALL, _COND or _UNCOND");
+    if (p.mode != FGDM_CAPTURE_SUM && p.mode != FGDM_CAPTURE_LAST) return e->fail(FGDM_ERR_ARG, "attention capture: mode must be FGDM_CAPTURE_SUM or FGDM_CAPTURE_LAST");
+    const bool sized = p.batch > 0 && p.latent_h > 0 && p.latent_w > 0;
+    if (!sized && (p.batch || p.latent_h || p.latent_w))
+        return e->fail(FGDM_ERR_ARG, "attention capture: batch, latent_h and latent_w must be all positive or all 0");
+    if (sized && p.rows != FGDM_CAPTURE_ROWS_ALL && (p.batch & 1))
+        return e->fail(FGDM_ERR_ARG, "attention capture: the conditional / unconditional half of an odd batch");
+    e->capture_off();
+    auto& c = e->cap;
+    c.rows_sel = p.rows; c.mode = p.mode; c.Tk = Tk;
+    c.tokens = tokens; c.order = order;
+    for (int i = 0; i < nb; ++i)
+        if ((p.block_mask >> i) & 1) { fgdm_engine::CapPlane pl; pl.block = i; c.planes[order[i]] = pl; }
+    if (sized) {
+        const int rc = e->capture_alloc(p.batch, p.latent_h, p.latent_w);
+        if (rc != FGDM_OK) { e->capture_off(); return rc; }
+    }
+    c.on = true;
+    return FGDM_OK;
+}
+static const fgdm_engine::CapPlane* capture_block(fgdm_engine* e, int block) {
+    if (!e->cap.on || block < 0 || block >= (int)e->cap.order.size()) return nullptr;
+    auto it = e->cap.planes.find(e->cap.order[block]);
+    return it == e->cap.planes.end() ? nullptr : &it->second;
+}
+int fgdm_attention_capture_reset(fgdm_engine* e, void* stream) {
+    if (!e) return FGDM_ERR_ARG;
+    if (!e->cap.on) return e->fail(FGDM_ERR_STATE, "attention capture is off");
+    e->cap.n_evals = 0;
+    for (auto& kv : e->cap.planes)
+        if (kv.second.acc && hipMemsetAsync(kv.second.acc, 0, e->capture_plane_floats(kv.second) * sizeof(float), as_stream(stream)) != hipSuccess)
+            return e->fail(FGDM_ERR_HIP, "hipMemsetAsync (attention capture)");
+    return FGDM_OK;
+}
+int fgdm_attention_capture_info(fgdm_engine* e, int block, int64_t shape[3], int32_t* n_evals) {
+    if (!e) return FGDM_ERR_ARG;
+    const auto* p = capture_block(e, block);
+    if (!p) return e->fail(FGDM_ERR_ARG, "attention capture: block " + std::to_string(block) + " is not selected");
+    if (shape) { shape[0] = e->cap.B ? e->cap.rows : 0; shape[1] = (int64_t)p->h * p->w; shape[2] = e->cap.B ? (int64_t)e->cap.tokens.size() : 0; }
+    if (n_evals) *n_evals = e->cap.n_evals;
+    return FGDM_OK;
+}
+int fgdm_attention_capture_block_size(fgdm_engine* e, int block, int32_t* h, int32_t* w) {
+    if (!e || !h || !w) return FGDM_ERR_ARG;
+    const auto* p = capture_block(e, block);
+    if (!p) return e->fail(FGDM_ERR_ARG, "attention capture: block " + std::to_string(block) + " is not selected");
+    *h = p->h; *w = p->w;
+    return FGDM_OK;
+}
+int fgdm_attention_capture_read(fgdm_engine* e, int block, float* dst_device, void* stream) {
+    if (!e || !dst_device) return FGDM_ERR_ARG;
+    const auto* p = capture_block(e, block);
+    if (!p) return e->fail(FGDM_ERR_ARG, "attention capture: block " + std::to_string(block) + " is not selected");
+    if (!p->acc) return e->fail(FGDM_ERR_STATE, "attention capture: no evaluation has been captured yet");
+    if (hipMemcpyAsync(dst_device, p->acc, e->capture_plane_floats(*p) * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess)
+        return e->fail(FGDM_ERR_HIP, "hipMemcpyAsync (attention capture)");
+    return FGDM_OK;
+}
 
 int fgdm_vae_decode(fgdm_engine* e, const float* z, int B, int H, int W, float scale, float* image, void* stream) {
     if (!e || !z || !image) return FGDM_ERR_ARG;

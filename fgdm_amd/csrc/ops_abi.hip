@@ -257,6 +257,23 @@ int fgdm_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const v
                             q_prescaled ? 1 : 0, as_stream(stream));
 }
 int fgdm_debug_last_attention_kernel(void) { return attention_last_kernel(); }
+// Diagnostic entry of tests/test_gpu_attention_maps.py: fgdm_op_attention_ex through the capturing instantiations, plus the head
+// reduction, as the engine's capture runs them; the per-head planes are scratch of this call (synchronises before it frees them).
+int fgdm_op_cross_attention_maps(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo, float* maps,
+                                 int B, int heads, int T, int Tk, int d, int q_prescaled, void* stream) {
+    if (!q || !k || !vt || !o || !maps) return FGDM_ERR_ARG;
+    if (B <= 0 || heads <= 0 || T <= 0 || Tk <= 0 || Tk > FGDM_ATTENTION_CAPTURE_MAX_KEYS) return FGDM_ERR_ARG;
+    if (d != 40 && d != 64 && d != 80 && d != 160) return FGDM_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    TmpDev tmp;
+    float* planes = tmp.alloc<float>(attention_capture_plane_floats(B, heads, T, Tk));
+    if (!planes) return FGDM_ERR_NOMEM;
+    int rc = attention_capture_launch((const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)vt, ldvt, (half_t*)o, ldo, B, heads, T, Tk,
+                                      d, q_prescaled ? 1 : 0, planes, s);
+    if (rc == FGDM_OK) rc = attention_maps_reduce(planes, maps, heads, T, Tk, 0, B, nullptr, Tk, 0, s);
+    if (hipStreamSynchronize(s) != hipSuccess && rc == FGDM_OK) rc = FGDM_ERR_HIP;
+    return rc;
+}
 int fgdm_op_small_attention(const void* qkv, int ld, int koff, int voff, void* out, int ldo, int B, int heads, int T, int d,
                             int causal, void* stream) {
     if (!qkv || !out) return FGDM_ERR_ARG;

@@ -138,6 +138,124 @@ class ContextCachePolicy:
         return verdict
 
 
+def attention_blocks(config):
+    """The UNet's transformer blocks in the order of the forward pass (csrc/model.h: input blocks, middle block, output blocks),
+    as (place, ds) pairs: place in 'down' / 'mid' / 'up', ds the block's downsampling factor against the latent.  Index i of this
+    list is bit i of fgdm_attention_capture.block_mask."""
+    ares = {config.attention_resolutions[i] for i in range(config.n_attention_resolutions)}
+    out, ds = [], 1
+    for level in range(config.n_levels):
+        out += [('down', ds)] * (config.num_res_blocks if ds in ares else 0)
+        if level != config.n_levels - 1:
+            ds *= 2
+    out.append(('mid', ds))
+    for level in reversed(range(config.n_levels)):
+        out += [('up', ds)] * (config.num_res_blocks + 1 if ds in ares else 0)
+        if level:
+            ds //= 2
+    return out
+
+
+def resolve_attention_blocks(config, blocks=None, latent=None):
+    """Block indices (sorted, unique) from what a caller names: None = every block; an index; 'down' / 'mid' / 'up'; ('down', 16)
+    -- a place and a side; or a side alone as a string of digits such as '16' -- the blocks whose maps are that many cells wide
+    for a latent `latent` cells wide (ptp_utils users select by place and resolution).  A bare int is an INDEX; pass the side as
+    a string or in a pair.  Raises ValueError for a name that selects nothing."""
+    table = attention_blocks(config)
+    if blocks is None:
+        return list(range(len(table)))
+    if isinstance(blocks, (str, int)) or (isinstance(blocks, tuple) and len(blocks) == 2 and isinstance(blocks[0], str)):
+        blocks = [blocks]
+
+    def side_of(ds):
+        if latent is None:
+            raise ValueError('selecting blocks by side needs the latent side (latent=...)')
+        return -(-int(latent) // ds)
+
+    picked = set()
+    for b in blocks:
+        if isinstance(b, int) and not isinstance(b, bool):
+            if not 0 <= b < len(table):
+                raise ValueError(f'block {b}: the UNet has transformer blocks 0..{len(table) - 1}')
+            hit = [b]
+        elif isinstance(b, str) and b.isdigit():
+            hit = [i for i, (_, ds) in enumerate(table) if side_of(ds) == int(b)]
+        elif isinstance(b, str):
+            hit = [i for i, (place, _) in enumerate(table) if place == b]
+        else:
+            place, side = b
+            hit = [i for i, (pl, ds) in enumerate(table) if pl == place and side_of(ds) == int(side)]
+        if not hit:
+            raise ValueError(f'{b!r} names no transformer block of this UNet (places: down, mid, up)')
+        picked.update(hit)
+    return sorted(picked)
+
+
+class AttentionCapture:
+    """What Engine.capture_attention yields: the head-averaged text cross-attention maps the engine accumulates while the plan is
+    set.  maps() -> {block: fp32 [rows, h, w, n_tokens] on the device}, the mean over the captured evaluations in 'sum' mode, the
+    last evaluation's in 'last' mode; reset() zeroes the accumulators and the evaluation count."""
+
+    def __init__(self, engine, blocks, tokens, rows, mode, batch=0, latent_hw=(0, 0)):
+        if rows not in _lib.CAPTURE_ROWS or mode not in _lib.CAPTURE_MODES:
+            raise ValueError("rows is 'cond', 'uncond' or 'all'; mode is 'sum' or 'last'")
+        self.engine, self.blocks, self.mode = engine, list(blocks), mode
+        self.tokens = None if tokens is None else [int(k) for k in tokens]
+        self.plan = _lib.FgdmAttentionCapture()
+        self.plan.struct_size = C.sizeof(self.plan)
+        if self.tokens is not None:
+            self._tok = (C.c_int32 * len(self.tokens))(*self.tokens)
+            self.plan.tokens = C.cast(self._tok, C.POINTER(C.c_int32))
+            self.plan.n_tokens = len(self.tokens)
+        for b in self.blocks:
+            self.plan.block_mask |= 1 << b
+        self.plan.rows, self.plan.mode = _lib.CAPTURE_ROWS[rows], _lib.CAPTURE_MODES[mode]
+        self.plan.batch, self.plan.latent_h, self.plan.latent_w = int(batch), int(latent_hw[0]), int(latent_hw[1])
+
+    def __enter__(self):
+        e = self.engine
+        e._check(e.lib.fgdm_attention_capture_set(e.h, C.byref(self.plan)), 'fgdm_attention_capture_set')
+        return self
+
+    def __exit__(self, *exc):
+        e = self.engine
+        e._check(e.lib.fgdm_attention_capture_set(e.h, None), 'fgdm_attention_capture_set')
+        return False
+
+    def info(self, block):
+        e = self.engine
+        shape, n = (C.c_int64 * 3)(), C.c_int32()
+        e._check(e.lib.fgdm_attention_capture_info(e.h, block, shape, C.byref(n)), 'fgdm_attention_capture_info')
+        return tuple(int(v) for v in shape), int(n.value)
+
+    @property
+    def n_evals(self):
+        return self.info(self.blocks[0])[1]
+
+    def reset(self):
+        e = self.engine
+        e._check(e.lib.fgdm_attention_capture_reset(e.h, _stream()), 'fgdm_attention_capture_reset')
+
+    def raw(self, block):
+        """the accumulated plane of `block` as the engine holds it, fp32 [rows, h * w, n_tokens], divided by nothing"""
+        e = self.engine
+        shape, _ = self.info(block)
+        out = torch.empty(shape, device=e.device, dtype=torch.float32)
+        e._check(e.lib.fgdm_attention_capture_read(e.h, block, _ptr(out), _stream()), 'fgdm_attention_capture_read')
+        return out
+
+    def maps(self):
+        e = self.engine
+        out = {}
+        for b in self.blocks:
+            (rows, _, ntok), n = self.info(b)
+            h, w = C.c_int32(), C.c_int32()
+            e._check(e.lib.fgdm_attention_capture_block_size(e.h, b, C.byref(h), C.byref(w)), 'fgdm_attention_capture_block_size')
+            m = self.raw(b).view(rows, h.value, w.value, ntok)
+            out[b] = m / n if self.mode == 'sum' and n > 1 else m
+        return out
+
+
 class Engine:
     """One engine per device: owns packed weights + activation workspace in HBM."""
 
@@ -185,6 +303,15 @@ class Engine:
         if rc != 0:
             msg = self.lib.fgdm_last_error(self.h)
             raise RuntimeError(f'{what} failed ({rc}): {msg.decode() if msg else ""}')
+
+    def capture_attention(self, blocks=None, tokens=None, rows='cond', mode='sum', latent=None, batch=0, latent_hw=(0, 0)):
+        """Context manager: while it is open, every evaluation of the UNet -- per-step samplers and device loops alike --
+        also accumulates the head-averaged text cross-attention maps of `blocks` (resolve_attention_blocks: indices, 'down' /
+        'mid' / 'up', ('up', 16), '16' with latent=) for the context positions `tokens` (None: all).  rows: 'cond' / 'uncond' =
+        that half of a CFG batch cat([uncond, cond]), 'all' = every row.  Yields an AttentionCapture.  eps is unchanged bit for
+        bit; the ControlNets' cross-attentions and all self-attentions are not captured.  batch / latent_hw: give the
+        evaluations' batch (2 B under CFG) and latent size to allocate now rather than at the first evaluation."""
+        return AttentionCapture(self, resolve_attention_blocks(self.config, blocks, latent), tokens, rows, mode, batch, latent_hw)
 
     # ------------------------------------------------------------------ weights
     def param_shapes(self):

@@ -412,6 +412,16 @@ class LatentDiffusion(_Buffers):
             raise ValueError(f'c_concat {tuple(cc.shape)} does not fit the latent batch {tuple(x_noisy.shape)}')
         return cc, (2 * cc.shape[0] == B or self._halves_equal(cc))
 
+    def capture_attention(self, blocks=None, tokens=None, rows='cond', mode='sum', latent=None, **kw):
+        """Engine.capture_attention with blocks named by place and resolution, as ptp_utils users select them: 'down', 'mid', 'up',
+        ('up', 16), or a side of the map alone -- here an int IS a side (16: the 16 x 16 blocks of a latent of image_size cells;
+        block indices go to Engine.capture_attention)."""
+        if blocks is not None:
+            blocks = [blocks] if isinstance(blocks, (str, int)) or (isinstance(blocks, tuple) and isinstance(blocks[0], str)) else list(blocks)
+            blocks = [str(b) if isinstance(b, int) and not isinstance(b, bool) else b for b in blocks]
+        return self.engine.capture_attention(blocks=blocks, tokens=tokens, rows=rows, mode=mode,
+                                             latent=self.image_size if latent is None else latent, **kw)
+
     def apply_model(self, x_noisy, t, cond, return_ids=False, **kwargs):
         sp = getattr(self, 'split_input_params', None)
         hybrid = self.model.conditioning_key == 'hybrid'

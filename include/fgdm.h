@@ -132,6 +132,64 @@ int fgdm_set_context(fgdm_engine* e, const float* ctx, int B, void* stream);
  * All samples of a batch share the count.  No launch, no synchronisation beyond freeing the dropped projections. */
 int fgdm_set_context_tokens(fgdm_engine* e, int tokens);
 int fgdm_get_context_tokens(const fgdm_engine* e);
+/* Cross-attention maps: what ldm/modules/attention.py:177-216 computes next to every text cross-attention and the reference's
+ * inspection and editing tools start from (utils/attention_utils.py get_token_maps, utils/ptp_utils.py AttentionStore): the
+ * probability every spatial query gives to every text token, averaged over heads, per transformer block, accumulated over the
+ * evaluations of a sampling.  Off by default; while it is off nothing here costs a launch, an allocation or another kernel.
+ *
+ * fgdm_attention_capture_set registers a plan (copied; NULL: capture off, planes freed).  From then on every fgdm_apply_model --
+ * and so every step of every device loop and of the per-step samplers -- runs the text cross-attention (attn2) of the selected UNet
+ * blocks through the capturing instantiations of its kernel (ids 7 - 9 of fgdm_debug_last_attention_kernel; eps keeps its bits),
+ * which write softmax(q k^T d^-1/2) per head in fp32; a second small kernel sums the heads IN HEAD ORDER (deterministic: no atomics),
+ * picks the rows and token columns of the plan and adds the mean into (sum) or overwrites (last) the block's accumulator, fp32
+ * [rows, T_block, n_tokens], T_block = the block's h * w queries in row-major order.
+ *   block_mask  bit i = transformer block i of the UNet in the order of the forward pass (input blocks, middle block, output
+ *               blocks: model.h, for_each_block; SD-v1 / SD-2: 0-5 down (two each at 1, 1/2, 1/4 of the latent), 6 middle, 7-15 up).
+ *   tokens      n_tokens indices into the concatenated context, [0, fgdm_get_context_tokens), host; NULL with n_tokens = 0: all.
+ *   rows        which rows of the batch to keep.  A CFG evaluation is ONE batch cat([uncond, cond]): FGDM_CAPTURE_ROWS_COND keeps its
+ *               second half, FGDM_CAPTURE_ROWS_UNCOND its first (the batch must be even), FGDM_CAPTURE_ROWS_ALL every row.
+ *   mode        FGDM_CAPTURE_SUM or FGDM_CAPTURE_LAST.
+ *   batch, latent_h, latent_w   the evaluations' batch (2 B under CFG) and latent size: all three > 0 allocates the accumulators now;
+ *               all three 0 leaves that to the first captured evaluation, which fixes them.  An evaluation of another shape, or
+ *               after fgdm_set_context_tokens changed the count, is FGDM_ERR_STATE before any launch.
+ * NOT captured: the ControlNets' cross-attentions (UNet blocks only: the tools read the UNet's), self-attention (4096^2 per head at
+ * level 0), and fgdm_run_block / fgdm_controlnet, which are no evaluations of the network (the patch routes ARE, one per pass of
+ * crops, and so must have the plan's shape).
+ * FGDM_ERR_ARG before any launch or allocation, with the reason in fgdm_last_error: a struct_size outside
+ * [FGDM_ATTENTION_CAPTURE_SIZE_V1, sizeof]; reserved0 != 0; a mask that is 0 or names a block the model does not have; n_tokens
+ * outside [0, context tokens], tokens NULL with n_tokens > 0, an index outside the context; an unknown rows / mode; batch / latent
+ * sizes that are negative, only partly given, or an odd batch with a half selected; and a context longer than
+ * FGDM_ATTENTION_CAPTURE_MAX_KEYS tokens -- the capturing kernels' key limit -- or of 128, 192 or 256 tokens, which the dispatch
+ * gives to the self-attention kernels, which have no capturing form.
+ * fgdm_attention_capture_reset zeroes the accumulators and the evaluation count (asynchronous on `stream`).
+ * fgdm_attention_capture_info: shape = {rows, T_block, n_tokens} of a selected block (zeros before the accumulators exist) and the
+ * number of captured evaluations since the last reset; either pointer may be NULL.  fgdm_attention_capture_block_size: the block's
+ * h, w (T_block = h * w).  fgdm_attention_capture_read copies the accumulated plane to dst_device (fp32, device, rows * T_block *
+ * n_tokens floats) DIVIDED BY NOTHING: under FGDM_CAPTURE_SUM the caller divides by n_evals.  A block that is not selected is
+ * FGDM_ERR_ARG; read before the accumulators exist is FGDM_ERR_STATE. */
+#define FGDM_ATTENTION_CAPTURE_MAX_KEYS 256
+#define FGDM_CAPTURE_ROWS_ALL 0
+#define FGDM_CAPTURE_ROWS_COND 1
+#define FGDM_CAPTURE_ROWS_UNCOND 2
+#define FGDM_CAPTURE_SUM 0
+#define FGDM_CAPTURE_LAST 1
+#define FGDM_ATTENTION_CAPTURE_SIZE_V1 48
+typedef struct fgdm_attention_capture {
+    int64_t struct_size;                /* sizeof(fgdm_attention_capture) of the caller's header */
+    const int32_t* tokens;              /* host, n_tokens entries, or NULL */
+    uint32_t block_mask;
+    int32_t n_tokens;
+    int32_t rows;                       /* FGDM_CAPTURE_ROWS_* */
+    int32_t mode;                       /* FGDM_CAPTURE_SUM / FGDM_CAPTURE_LAST */
+    int32_t batch, latent_h, latent_w;  /* all > 0, or all 0 */
+    int32_t reserved0;                  /* 0 */
+} fgdm_attention_capture;
+int fgdm_attention_capture_set(fgdm_engine* e, const fgdm_attention_capture* plan);
+int fgdm_attention_capture_reset(fgdm_engine* e, void* stream);
+int fgdm_attention_capture_info(fgdm_engine* e, int block, int64_t shape[3], int32_t* n_evals);
+int fgdm_attention_capture_block_size(fgdm_engine* e, int block, int32_t* h, int32_t* w);
+int fgdm_attention_capture_read(fgdm_engine* e, int block, float* dst_device, void* stream);
+
 /* UNets fed x | c_concat: DiffusionWrapper.forward in its 'hybrid' mode, xc = torch.cat([x] + c_concat, dim=1) handed to the
  * UNet together with the text context (ldm/models/diffusion/ddpm.py:1838-1841) -- the SD-v1 inpainting checkpoints (in_channels 9:
  * latent, mask, masked-image latent) and the InstructPix2Pix family (8).  An engine created with 4 < in_channels <= 32 is such a
@@ -649,6 +707,9 @@ int fgdm_bench_igemm(int B, int H, int W, int C0, int C1, int Cout, int ksize, i
  * chunks sharing one intermediate buffer; average device milliseconds for all M rows. */
 int fgdm_bench_ff(int M, int C, int chunk_rows, int iters, float* avg_ms);
 int fgdm_bench_attention(int B, int heads, int T, int Tk, int d, int iters, float* avg_ms);
+/* ... the same shape through the capturing instantiation (cross-attention maps: the per-head planes written), with_reduce: followed
+ * by the head reduction into maps [B, T, Tk]; FGDM_ERR_ARG where fgdm_op_cross_attention_maps is. */
+int fgdm_bench_attention_maps(int B, int heads, int T, int Tk, int d, int with_reduce, int iters, float* avg_ms);
 /* ... and one GroupNorm32(+SiLU) (kind 0, optional virtual concat C1) or LayerNorm (kind 1) shape. */
 int fgdm_bench_norm(int kind, int B, int HW, int C0, int C1, int silu, int iters, float* avg_ms);
 int fgdm_op_groupnorm(const void* x0, int C0, const void* x1, int C1, int B, int HW, const float* gamma,
@@ -675,6 +736,17 @@ int fgdm_op_attention(const void* q, int ldq, const void* k, int ldk, const void
 int fgdm_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo,
                          int B, int heads, int T, int Tk, int d, int q_prescaled, void* stream);
 int fgdm_debug_last_attention_kernel(void);
+/* Diagnostic entry (tests/test_gpu_attention_maps.py): fgdm_op_attention_ex through the CAPTURING instantiations of the two kernels
+ * that take text contexts, which besides O write the probabilities; maps fp32 [B, T, Tk] (device) is
+ *   maps[b, t, k] = mean over heads of softmax_k(q k^T d^-1/2)[b, h, t, k],
+ * from the fp32 exponentials before they are rounded to fp16 for the P V product, normalised by their own fp32 sum; heads are summed
+ * in head order by a second kernel, so two calls give the same bits.  O has the bits fgdm_op_attention_ex gives.  The dispatch is
+ * that of fgdm_op_attention_ex; fgdm_debug_last_attention_kernel then reports 7 general capturing (attn_kernel), 8 text-token
+ * capturing (attn_cross_kernel<D, 3>), 9 long-text capturing (attn_cross_kernel<D, 4 ... 8>).  FGDM_ERR_ARG before any launch: a NULL
+ * pointer; B, heads, T or Tk <= 0; Tk > FGDM_ATTENTION_CAPTURE_MAX_KEYS; another d; a shape the dispatch gives to a self-attention kernel
+ * (ids 4 - 6: these have no capturing form).  Allocates B heads T Tk floats of scratch and synchronises the stream. */
+int fgdm_op_cross_attention_maps(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo, float* maps,
+                                 int B, int heads, int T, int Tk, int d, int q_prescaled, void* stream);
 int fgdm_op_small_attention(const void* qkv, int ld, int koff, int voff, void* out, int ldo, int B, int heads, int T, int d,
                             int causal, void* stream);
 

@@ -4,7 +4,9 @@ ALGORITHMIC (4 B T Tk C).  Usage (GPU box): python tools/bench_attention.py [--i
 --long: the text-attention shapes at two and three 77-token parts (154 / 231 keys) with the 77-key shape as the control; run it
 once per setting of FGDM_ATTN_CROSS_LONG (0 = the general kernel, the dispatch of before) for a same-box A/B.
 --d64: head width 64 (SD-2.x networks: 5 / 10 heads) next to the d = 40 / 80 shapes of the same T; run it once more under
-FGDM_ATTN_DQ80=0 for two-strand against ping-pong (profiles/attention_d64.txt)."""
+FGDM_ATTN_DQ80=0 for two-strand against ping-pong (profiles/attention_d64.txt).
+--capture: the text shapes (Tk = 77) three ways: the product kernel, its capturing instantiation (cross-attention maps: per-head
+planes written), and that plus the head reduction (profiles/attention_capture_cost.txt)."""
 import argparse
 import ctypes as C
 import os
@@ -32,8 +34,20 @@ def main():
     ap.add_argument('--only', type=int, default=-1, help='index into SHAPES (profiling runs)')
     ap.add_argument('--long', action='store_true', help='the long-context text-attention shapes (LONG_SHAPES)')
     ap.add_argument('--d64', action='store_true', help='head width 64 against d = 40 / 80 (D64_SHAPES)')
+    ap.add_argument('--capture', action='store_true', help='Tk = 77 shapes: product kernel / capturing instantiation / + head reduction')
     a = ap.parse_args()
     lib = _lib.load()
+    if a.capture:
+        for B, H, T, Tk, d in [s for s in SHAPES if s[3] == 77]:
+            row = []
+            for call in (lambda ms: lib.fgdm_bench_attention(B, H, T, Tk, d, a.iters, ms),
+                         lambda ms: lib.fgdm_bench_attention_maps(B, H, T, Tk, d, 0, a.iters, ms),
+                         lambda ms: lib.fgdm_bench_attention_maps(B, H, T, Tk, d, 1, a.iters, ms)):
+                ms = C.c_float()
+                rc = call(C.byref(ms))
+                row.append(f'{ms.value * 1e3:9.1f} us' if rc == 0 else f'rc={rc}')
+            print(f'attn B{B} T{T} Tk{Tk} d{d:<4d} product {row[0]}   capturing {row[1]}   capturing + head reduction {row[2]}', flush=True)
+        return
     shapes = D64_SHAPES if a.d64 else LONG_SHAPES if a.long else SHAPES
     for B, H, T, Tk, d in (shapes if a.only < 0 else [shapes[a.only]]):
         ms = C.c_float()
