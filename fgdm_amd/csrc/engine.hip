@@ -9,6 +9,7 @@
 //   Adapter                         ldm/modules/encoders/adapter.py:280-346
 //   ControlNet / ControlledUnet     controlnet/cldm/cldm.py:27-50, 545-813, 836-849
 #include "model.h"
+#include "arena.h"
 #include "knobs.h"
 #include "replay.h"
 
@@ -25,67 +26,6 @@
 #include <vector>
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------ arena
-// First-fit free-list allocator over hipMalloc'ed slabs.  The allocation sequence of a forward pass is
-// deterministic, so buffers land at the same addresses every call (graph-capture friendly) and recently
-// freed (cache-hot) blocks are reused first.
-struct Arena {
-    struct Blk { char* p; size_t sz; bool free; };
-    std::vector<std::vector<Blk>> slabs;
-    std::vector<char*> bases;
-    size_t slab_bytes = (size_t)4 << 30;
-    size_t in_use = 0, peak = 0;
-    // Scope of one C-ABI call: every block handed out while a scope is open is remembered, and whatever is still
-    // allocated when the call fails (an early return somewhere below) is given back by end_scope(true).
-    bool scoped = false;
-    std::vector<void*> live;
-    void begin_scope() { scoped = true; live.clear(); }
-    void end_scope(bool failed) {
-        if (failed) { std::vector<void*> l; l.swap(live); scoped = false; for (void* p : l) release(p); }
-        scoped = false;
-        live.clear();
-    }
-
-    ~Arena() { for (char* b : bases) (void)hipFree(b); }
-    void* alloc(size_t bytes) {
-        bytes = (bytes + 255) & ~(size_t)255;
-        if (bytes == 0) bytes = 256;
-        for (auto& s : slabs)
-            for (size_t i = 0; i < s.size(); ++i)
-                if (s[i].free && s[i].sz >= bytes) {
-                    if (s[i].sz > bytes) {
-                        Blk rest{s[i].p + bytes, s[i].sz - bytes, true};
-                        s[i].sz = bytes;
-                        s.insert(s.begin() + i + 1, rest);
-                    }
-                    s[i].free = false;
-                    in_use += bytes;
-                    peak = std::max(peak, in_use);
-                    if (scoped) live.push_back(s[i].p);
-                    return s[i].p;
-                }
-        const size_t sz = std::max(slab_bytes, bytes);
-        char* base = nullptr;
-        if (hipMalloc(&base, sz) != hipSuccess) return nullptr;
-        bases.push_back(base);
-        slabs.push_back({Blk{base, sz, true}});
-        return alloc(bytes);
-    }
-    void release(void* p) {
-        if (!p) return;
-        if (scoped) { auto it = std::find(live.begin(), live.end(), p); if (it != live.end()) { *it = live.back(); live.pop_back(); } }
-        for (auto& s : slabs)
-            for (size_t i = 0; i < s.size(); ++i)
-                if (s[i].p == p && !s[i].free) {
-                    s[i].free = true;
-                    in_use -= s[i].sz;
-                    if (i + 1 < s.size() && s[i + 1].free) { s[i].sz += s[i + 1].sz; s.erase(s.begin() + i + 1); }
-                    if (i > 0 && s[i - 1].free) { s[i - 1].sz += s[i].sz; s.erase(s.begin() + i); }
-                    return;
-                }
-    }
-};
 
 // Built-in kernel timer: when enabled, every launch is bracketed by HIP events recorded on the launch stream
 // (the same stream the kernels run on), so per-kernel-class device time, launch counts and the ALGORITHMIC
@@ -104,7 +44,8 @@ struct Prof final : LaunchTimer {
         return pool[used++];
     }
     // Only every `stride`-th launch is bracketed: two event packets per launch cost ~3 % of a 41k-launch sampling
-    // step; a stride coprime with the launch pattern (830 launches per evaluation) samples every shape uniformly.
+    // step; a stride coprime with the number of bracketed launches per evaluation (it varies with the ControlNet count and the
+    // grouping knobs) samples every shape uniformly.
     int stride = 1;
     long counter = 0;
     bool armed = false;
@@ -234,8 +175,12 @@ struct fgdm_engine : Model {
     // RECORD time, so two walks recorded from one arena share blocks; replayed INTERLEAVED (grouped launches) they would overwrite
     // each other (three ControlNets at full size gave non-finite latents in round 3, fixed then by a hand-derived two-arena rule).
     // With an arena of its own every walk may be replayed next to any other.  cn_arena[0] also serves the second stream.
+    // OWNERSHIP (arena.h): every block is held by one Act / Buf / LnStats handle, which gives it back to the arena it came from --
+    // not to `ar`, which RecordScope moves -- when it is destroyed, reset() or assigned over.  A function that consumes its input
+    // takes the handle by value, one that only reads takes const Tensor&; an early `return fail(...)` unwinds what the call holds.
+    // The one thing unwinding cannot order by itself is the second stream: see SecondStreamGuard in apply_model_walk.
     std::vector<std::unique_ptr<Arena>> cn_arena;
-    Arena* ar = &arena;           // arena of the stream being enqueued
+    Arena* ar = &arena;           // arena of the stream being enqueued: where talloc / balloc take NEW blocks from
     hipStream_t s2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool twin_streams = false;
@@ -245,7 +190,9 @@ struct fgdm_engine : Model {
     int group_max = FGDM_MAX_GROUP;      // FGDM_GROUP_MAX (read at fgdm_create): 2 = round 3's pairwise replay; the A/B knob
     bool gn_group = true;                // FGDM_GN_GROUP (read at fgdm_create): the twins' single-pass GroupNorm launches group too
     ReplayStats replay_stats;            // behind fgdm_launch_stats
-    struct Deferred { const GemmW* w; Tensor src; int idx; float scale; Arena* owner; };
+    using Act = Owned<Tensor>;           // an fp16 activation of the workspace and the arena that served it
+    static Act borrow(const Tensor& t) { return Act(t, nullptr); }      // a view in a handle's clothes: owns nothing
+    struct Deferred { const GemmW* w; Act src; int idx; float scale; };  // a zero-conv the caller applies later; holds its input
     Prof prof;
 
     // ------------------------------------------------------------------------------------ weight packing
@@ -452,15 +399,21 @@ struct fgdm_engine : Model {
         fgdm_record(run);
         return FGDM_OK;
     }
-    Tensor talloc(int B, int H, int W, int C) {
-        Tensor t; t.B = B; t.H = H; t.W = W; t.C = C;
-        t.p = (half_t*)ar->alloc(t.numel() * sizeof(half_t));
-        return t;
+    // A new block of `ar` into *t (empty before: assigning over a live handle would release it AFTER the new block was taken)
+    int talloc(Act* t, int B, int H, int W, int C, const char* what = "workspace") {
+        Tensor v; v.B = B; v.H = H; v.W = W; v.C = C;
+        v.p = (half_t*)ar->alloc(v.numel() * sizeof(half_t));
+        *t = Act(v, ar);
+        return v.p ? FGDM_OK : fail(FGDM_ERR_NOMEM, what);
     }
-    void tfree(Tensor& t) { ar->release(t.p); t.p = nullptr; }
+    int balloc(Buf* b, size_t bytes) {
+        *b = Buf(Raw{ar->alloc(bytes)}, ar);
+        return b->p ? FGDM_OK : fail(FGDM_ERR_NOMEM, "workspace");
+    }
 
     // LayerNorm partial sums of a token matrix (IgemmArgs::stats_out / ln_stats): [rows][slots][2] floats in the arena
-    struct LnStats { float* p = nullptr; int slots = 0; };
+    struct LnView { float* p = nullptr; int slots = 0; };
+    using LnStats = Owned<LnView>;
     struct Epi {
         const LnStats* ln = nullptr;   // the A operand is to be LayerNorm-ed: the weights have it folded in (GemmW::ln_u)
         LnStats* stats = nullptr;      // also produce the partial sums of the OUTPUT rows (for the next folded LayerNorm)
@@ -504,9 +457,11 @@ struct fgdm_engine : Model {
         if (prof.on) snprintf(tag, sizeof(tag), "igemm M%d N%d K%d mode%d act%d out%d l%ds%dr%dv%d", a.M, a.N, a.K, a.mode, a.act, a.out_kind,
                               e.ln ? 1 : 0, e.stats ? 1 : 0, e.resid ? 1 : 0, e.rowvec ? 1 : 0);
         a.splitk = igemm_splitk_factor(a);
+        Buf ws;
         if (a.splitk > 1) {
-            a.ws = (float*)ar->alloc((size_t)a.splitk * a.M * a.N * sizeof(float));
-            if (!a.ws) return fail(FGDM_ERR_NOMEM, "workspace (split-K partials)");
+            ws = Buf(Raw{ar->alloc((size_t)a.splitk * a.M * a.N * sizeof(float))}, ar);
+            if (!ws.p) return fail(FGDM_ERR_NOMEM, "workspace (split-K partials)");
+            a.ws = ws.as<float>();
         }
         if (e.ln) {
             if (!w.ln_u || !e.ln->p || a.splitk > 1) return fail(FGDM_ERR_STATE, "gemm: LayerNorm fold without folded weights / statistics");
@@ -515,8 +470,8 @@ struct fgdm_engine : Model {
             return fail(FGDM_ERR_STATE, "gemm: these weights have a LayerNorm folded in; statistics are required");
         }
         if (e.stats) {     // partial sums of the output rows: from the GEMM's own epilogue when its kernel can, else one more pass
-            e.stats->slots = igemm_stats_slots(a);
-            e.stats->p = (float*)ar->alloc((size_t)a.M * std::max(e.stats->slots, row_stats_slots(nout)) * 2 * sizeof(float));
+            const int slots = igemm_stats_slots(a);
+            *e.stats = LnStats(LnView{(float*)ar->alloc((size_t)a.M * std::max(slots, row_stats_slots(nout)) * 2 * sizeof(float)), slots}, ar);
             if (!e.stats->p) return fail(FGDM_ERR_NOMEM, "workspace (LayerNorm statistics)");
             if (e.stats->slots) a.stats_out = e.stats->p;
         }
@@ -529,7 +484,7 @@ struct fgdm_engine : Model {
         prof.begin(PC_IGEMM, s, 2.0 * (double)x0.B * Ho * Wo * (double)w.N * (double)w.k_real, tag, nbytes);    // (algorithmic flops)
         int rc = igemm_launch(a, s);
         prof.end(s);
-        if (a.ws) ar->release(a.ws);
+        ws.reset();
         if (rc == FGDM_OK && e.stats && e.stats->slots == 0) {
             if (a.out_kind != OUT_F16 || a.ld_out != nout) return fail(FGDM_ERR_ARG, "gemm: row statistics need a dense fp16 output");
             e.stats->slots = row_stats_slots(nout);
@@ -540,17 +495,16 @@ struct fgdm_engine : Model {
         return rc == FGDM_OK ? rc : fail(rc, "igemm launch failed");
     }
     // conv3x3 (stride 1/2, FGDM_STRIDE2_PAD_BR, or on the nearest-2x upsampled input) -> new tensor
-    int conv3(const GemmW& w, const Tensor& x, const Tensor* x1, int stride, bool up, Epi e, Tensor* out) {
+    int conv3(const GemmW& w, const Tensor& x, const Tensor* x1, int stride, bool up, Epi e, Act* out) {
         int Ho = x.H, Wo = x.W, mode = IG_CONV3;
         if (up) { Ho *= 2; Wo *= 2; mode = IG_CONV3_UP2; }
         else if (stride == 2) { Ho = (x.H - 1) / 2 + 1; Wo = (x.W - 1) / 2 + 1; mode = IG_CONV3_S2; }
         else if (stride == FGDM_STRIDE2_PAD_BR) { Ho = (x.H - 2) / 2 + 1; Wo = (x.W - 2) / 2 + 1; mode = IG_CONV3_S2_BR; }
-        const bool own_out = (e.out == nullptr);
-        if (own_out) { *out = talloc(x.B, Ho, Wo, w.N); if (!out->p) return fail(FGDM_ERR_NOMEM, "workspace"); }
+        if (!e.out) CHK(talloc(out, x.B, Ho, Wo, w.N));
         if (!w.im2col) return gemm(w, mode, x, x1, Ho, Wo, e, out);
         if (up || x1 || x.C != w.cin_pad || stride == FGDM_STRIDE2_PAD_BR) return fail(FGDM_ERR_ARG, "im2col conv path: unsupported combination");
-        Tensor A = talloc(1, 1, x.B * Ho * Wo, w.K);
-        if (!A.p) return fail(FGDM_ERR_NOMEM, "workspace (im2col)");
+        Act A;
+        CHK(talloc(&A, 1, 1, x.B * Ho * Wo, w.K, "workspace (im2col)"));
         prof.begin(PC_ELEM, s, 2.0 * (double)A.numel() + 2.0 * (double)x.numel());
         bool in_gemm = false;
         const int rc = im2col_conv(x.p, A.p, x.B, x.H, x.W, x.C, stride, w.K, s, [&]() { prof.end(s); },
@@ -560,31 +514,27 @@ struct fgdm_engine : Model {
                 if (!e.rps) e.rps = rps;
                 return gemm(w, IG_LINEAR, Av, nullptr, Hv, Wv, e, out);
             });
-        if (rc != FGDM_OK && !in_gemm) return fail(rc, "im2col failed");
-        tfree(A);
-        return rc;
+        return rc != FGDM_OK && !in_gemm ? fail(rc, "im2col failed") : rc;
     }
-    int linear(const GemmW& w, const Tensor& x, Epi e, Tensor* out, const Tensor* x1 = nullptr) {
-        if (!e.out) { *out = talloc(x.B, x.H, x.W, e.act == ACT_GEGLU ? w.N / 2 : w.N); if (!out->p) return fail(FGDM_ERR_NOMEM, "workspace"); }
+    int linear(const GemmW& w, const Tensor& x, Epi e, Act* out, const Tensor* x1 = nullptr) {
+        if (!e.out) CHK(talloc(out, x.B, x.H, x.W, e.act == ACT_GEGLU ? w.N / 2 : w.N));
         return gemm(w, IG_LINEAR, x, x1, x.H, x.W, e, out);
     }
-    int gnorm(const NormW& n, const Tensor& x, const Tensor* x1, float eps, bool silu, Tensor* out) {
+    int gnorm(const NormW& n, const Tensor& x, const Tensor* x1, float eps, bool silu, Act* out) {
         const int C = x.C + (x1 ? x1->C : 0);
-        *out = talloc(x.B, x.H, x.W, C);
-        float* ws = (float*)ar->alloc(groupnorm_ws_floats(x.B, x.H * x.W) * sizeof(float));
-        if (!out->p || !ws) return fail(FGDM_ERR_NOMEM, "workspace");
+        Buf ws;
+        CHK(talloc(out, x.B, x.H, x.W, C));
+        CHK(balloc(&ws, groupnorm_ws_floats(x.B, x.H * x.W) * sizeof(float)));
         char tag[56] = "";
         if (prof.on) snprintf(tag, sizeof(tag), "groupnorm B%d HW%d C%d", x.B, x.H * x.W, C);
         prof.begin(PC_NORM, s, 4.0 * (double)out->numel(), tag);   // algorithmic: read once + write once, fp16
         const int rc = groupnorm_launch(x.p, x.C, x1 ? x1->p : nullptr, x1 ? x1->C : 0, x.B, x.H * x.W, n.g, n.b, eps,
-                                        silu ? 1 : 0, out->p, ws, s);
+                                        silu ? 1 : 0, out->p, ws.as<float>(), s);
         prof.end(s);
-        ar->release(ws);
         return rc == FGDM_OK ? rc : fail(rc, "groupnorm launch failed");
     }
-    int lnorm(const NormW& n, const Tensor& x, Tensor* out) {
-        *out = talloc(x.B, x.H, x.W, x.C);
-        if (!out->p) return fail(FGDM_ERR_NOMEM, "workspace");
+    int lnorm(const NormW& n, const Tensor& x, Act* out) {
+        CHK(talloc(out, x.B, x.H, x.W, x.C));
         char tag[56] = "";
         if (prof.on) snprintf(tag, sizeof(tag), "layernorm rows%d C%d", x.rows(), x.C);
         prof.begin(PC_NORM, s, 4.0 * (double)out->numel(), tag);
@@ -598,27 +548,26 @@ struct fgdm_engine : Model {
 
     // ResBlock._forward (openaimodel.py:275-301); x1 = skip tensor of the decoder's channel concat.  Also the first stage's
     // ResnetBlock.forward with temb = None (model.py:121-141): no timestep row, GroupNorm eps 1e-6
-    int res_fwd(const Layer& l, const Tensor& x, const Tensor* x1, const EmbCtx& ec, Tensor* out) {
-        Tensor g1, h, g2, sk, xp;
+    int res_fwd(const Layer& l, const Tensor& x, const Tensor* x1, const EmbCtx& ec, Act* out) {
+        Act g1, h, g2, sk, xp;
         CHK(gnorm(l.gn1, x, x1, l.eps, true, &g1));
         const Tensor* xs = &x;       // the tensor the skip path reads
         if (l.down) {                // ResBlock(down=True, use_conv=False): AvgPool2d(2) on h and on x (openaimodel.py:276-282)
             if (x1) return fail(FGDM_ERR_ARG, "down ResBlock with a concatenated input");
-            Tensor gp = talloc(x.B, x.H / 2, x.W / 2, x.C);
-            xp = talloc(x.B, x.H / 2, x.W / 2, x.C);
-            if (!gp.p || !xp.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            Act gp;
+            CHK(talloc(&gp, x.B, x.H / 2, x.W / 2, x.C));
+            CHK(talloc(&xp, x.B, x.H / 2, x.W / 2, x.C));
             if (avgpool2(g1.p, gp.p, x.B, x.H, x.W, x.C, s) != FGDM_OK || avgpool2(x.p, xp.p, x.B, x.H, x.W, x.C, s) != FGDM_OK)
                 return fail(FGDM_ERR_ARG, "avgpool2: latent size must be divisible by 8 for the adapter");
-            tfree(g1);
-            g1 = gp;
+            g1 = std::move(gp);
             xs = &xp;
         }
         Epi e1;
         if (l.emb_off >= 0) { e1.rowvec = ec.emb_all + l.emb_off; e1.rv_stride = ec.stride; }
         CHK(conv3(l.c1, g1, nullptr, 1, false, e1, &h));
-        tfree(g1);
+        g1.reset();
         CHK(gnorm(l.gn2, h, nullptr, l.eps, true, &g2));
-        tfree(h);
+        h.reset();
         Epi e2;
         if (l.cin != l.cout) {
             CHK(linear(l.skip, *xs, Epi{}, &sk, x1));
@@ -626,16 +575,12 @@ struct fgdm_engine : Model {
         } else {
             e2.resid = xs->p; e2.ld_res = xs->C;
         }
-        CHK(conv3(l.c2, g2, nullptr, 1, false, e2, out));
-        tfree(g2);
-        if (sk.p) tfree(sk);
-        if (xp.p) tfree(xp);
-        return FGDM_OK;
+        return conv3(l.c2, g2, nullptr, 1, false, e2, out);      // g2, sk and xp go back behind it
     }
 
     // attn2's k = to_k(context), v = to_v(context) (attention.py:183-186); V is produced transposed for the kernel.
-    // persistent = true: buffers come from hipMalloc and live in ctx_cache until the next set_context
-    int cross_kv(const Layer& l, const Tensor& ctx16, bool persistent, Tensor* k2, Tensor* v2t) {
+    // persistent = true: buffers come from hipMalloc and live in ctx_cache until the next set_context (the handles own nothing)
+    int cross_kv(const Layer& l, const Tensor& ctx16, bool persistent, Act* k2, Act* v2t) {
         const int B = ctx16.B, C = l.cin, Tk = ctx16.H * ctx16.W, Tkp = roundup(Tk, 64);
         if (persistent) {
             k2->B = B; k2->H = ctx16.H; k2->W = ctx16.W; k2->C = C;
@@ -645,8 +590,7 @@ struct fgdm_engine : Model {
             { Epi e; e.out = k2->p; e.ld_out = C; CHK(linear(l.k2, ctx16, e, nullptr)); }
         } else {
             CHK(linear(l.k2, ctx16, Epi{}, k2));
-            *v2t = talloc(B, 1, C, Tkp);
-            if (!v2t->p) return fail(FGDM_ERR_NOMEM, "workspace");
+            CHK(talloc(v2t, B, 1, C, Tkp));
         }
         if (Tkp != Tk) CHK(dzero(v2t->p, v2t->numel() * sizeof(half_t)));
         { Epi e; e.out_kind = OUT_F16_T; e.out = v2t->p; e.ld_out = Tkp; e.rps = Tk; CHK(linear(l.v2, ctx16, e, nullptr)); }
@@ -663,17 +607,16 @@ struct fgdm_engine : Model {
         if (!finalized) return fail(FGDM_ERR_STATE, "weights not finalized");
         if (B <= 0) return fail(FGDM_ERR_ARG, "bad shape");
         drop_context();
-        Tensor ctx16 = talloc(B, 1, ctx_tokens, cfg.context_dim);
-        if (!ctx16.p) return fail(FGDM_ERR_NOMEM, "workspace");
+        Act ctx16;
+        CHK(talloc(&ctx16, B, 1, ctx_tokens, cfg.context_dim));
         if (f32_to_f16(ctx, ctx16.p, ctx16.numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "convert kernel");
         auto walk = [&](const Block& blk) -> int {
             for (const Layer& l : blk)
-                if (l.type == L_ATTN) { CtxKV kv; CHK(cross_kv(l, ctx16, true, &kv.k, &kv.vt)); ctx_cache[&l] = kv; }
+                if (l.type == L_ATTN) { Act k, vt; CHK(cross_kv(l, ctx16, true, &k, &vt)); ctx_cache[&l] = CtxKV{k, vt}; }
             return FGDM_OK;
         };
         CHK(for_each_block(unet, false, walk));
         for (auto& n : cns) CHK(for_each_block(n, false, walk));
-        tfree(ctx16);
         ctx_B = B; ctx_T = ctx_tokens;
         return FGDM_OK;
     }
@@ -681,72 +624,67 @@ struct fgdm_engine : Model {
     // SpatialTransformer.forward with one BasicTransformerBlock (attention.py:234-292)
     // dup: x holds the SHARED half of a CFG batch (rows b and b + B/2 identical so far); the self-attention part runs on
     // it once, the result is duplicated where the (per-half) context enters, and `out` has 2 * x.B rows
-    int attn_fwd(const Layer& l, const Tensor& x_in, const Tensor& ctx16, Tensor* out, bool dup = false) {
-        Tensor x = x_in, x_full;
+    int attn_fwd(const Layer& l, const Tensor& x_in, const Tensor& ctx16, Act* out, bool dup = false) {
+        Tensor x = x_in;
         int B = x.B;
         const int T = x.H * x.W, C = x.C, d = C / l.heads;
-        Tensor g, h, qk, vt, a, h2, q2, k2, v2t, f;
+        Act g, h, qk, vt, a, h2, q2, k2, v2t, f, x_full;
         LnStats s1, s2, s3;      // row sums of h / h2 / h3 for norm1 / norm2 / norm3, which live inside the next GEMMs
         CHK(gnorm(l.gn, x, nullptr, 1e-6f, false, &g));
-        Tensor nrm;                 // FGDM_LN_FOLD=0 only: the normalised tokens as a tensor of their own
+        Act nrm;                    // FGDM_LN_FOLD=0 only: the normalised tokens as a tensor of their own
         { Epi e; if (ln_fold) e.stats = &s1; CHK(linear(l.pin, g, e, &h)); }
-        tfree(g);
+        g.reset();
         // --- attn1 (self): q | k and v^T straight from h, norm1 folded into both projections
         if (!ln_fold) CHK(lnorm(l.ln1, h, &nrm));
         const Tensor& a1 = ln_fold ? h : nrm;
         // ONE GEMM for to_q | to_k | to_v: q | k row-major [M, 2C], v transposed [B, C, Tp] (the attention kernel's PV operand)
         const int Tp = roundup(T, 64);
-        qk = talloc(B, x.H, x.W, 2 * C);
-        vt = talloc(B, 1, C, Tp);
-        if (!qk.p || !vt.p) return fail(FGDM_ERR_NOMEM, "workspace");
+        CHK(talloc(&qk, B, x.H, x.W, 2 * C));
+        CHK(talloc(&vt, B, 1, C, Tp));
         if (Tp != T) CHK(dzero(vt.p, vt.numel() * sizeof(half_t)));
         { Epi e; if (ln_fold) e.ln = &s1; e.out = qk.p; e.ld_out = 2 * C; e.rps = T;
           e.out2 = vt.p; e.out_kind2 = OUT_F16_T; e.ld_out2 = Tp; e.split_n = 2 * C;
           CHK(linear(l.qkv1, a1, e, nullptr)); }
-        if (s1.p) ar->release(s1.p);
-        if (nrm.p) tfree(nrm);
-        a = talloc(B, x.H, x.W, C);
-        if (!a.p) return fail(FGDM_ERR_NOMEM, "workspace");
+        s1.reset(); nrm.reset();
+        CHK(talloc(&a, B, x.H, x.W, C));
         { char tag[56]; snprintf(tag, sizeof(tag), "attn B%d T%d Tk%d d%d", B, T, T, d);
           prof.begin(PC_ATTN, s, 4.0 * (double)B * T * (double)T * C, tag);
           int rc = attention_launch(qk.p, 2 * C, qk.p + C, 2 * C, vt.p, Tp, a.p, C, B, l.heads, T, T, d, 1, s);
           prof.end(s);
           if (rc != FGDM_OK) return fail(rc, "attention launch failed (unsupported head dim?)"); }
-        tfree(qk); tfree(vt);
+        qk.reset(); vt.reset();
         { Epi e; e.resid = h.p; e.ld_res = C; if (ln_fold) e.stats = &s2; CHK(linear(l.o1, a, e, &h2)); }
-        tfree(a); tfree(h);
+        a.reset(); h.reset();
         if (dup) {     // from here on the two halves differ (their contexts do)
-            Tensor f2;
-            CHK(dup_rows(h2, &f2)); tfree(h2); h2 = f2;
+            Act f2;
+            CHK(dup_rows(h2, &f2)); h2 = std::move(f2);
             CHK(dup_rows(x, &x_full)); x = x_full;
             B *= 2;
         }
         if (dup && ln_fold) {
             const size_t sb = (size_t)(B / 2) * T * s2.slots * 2 * sizeof(float);
-            float* s2f = (float*)ar->alloc(2 * sb);
-            if (!s2f) return fail(FGDM_ERR_NOMEM, "workspace");
-            CHK(dcopy(s2f, s2.p, sb));
-            CHK(dcopy((char*)s2f + sb, s2.p, sb));
-            ar->release(s2.p); s2.p = s2f;
+            LnStats s2f(LnView{(float*)ar->alloc(2 * sb), s2.slots}, ar);
+            if (!s2f.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            CHK(dcopy(s2f.p, s2.p, sb));
+            CHK(dcopy((char*)s2f.p + sb, s2.p, sb));
+            s2 = std::move(s2f);
         }
         // --- attn2 (cross, ctx_tokens-token context), norm2 folded into to_q
         if (!ln_fold) CHK(lnorm(l.ln2, h2, &nrm));
         { Epi e; if (ln_fold) e.ln = &s2; CHK(linear(l.q2, ln_fold ? h2 : nrm, e, &q2)); }
-        if (s2.p) ar->release(s2.p);
-        if (nrm.p) tfree(nrm);
+        s2.reset(); nrm.reset();
         int Tk, Tkp;
         const bool cached = (ctx16.p == nullptr);
         if (cached) {      // K / V^T were projected once by set_context
             auto it = ctx_cache.find(&l);
             if (it == ctx_cache.end() || ctx_B != B) return fail(FGDM_ERR_STATE, "no cached context for this batch (fgdm_set_context)");
-            k2 = it->second.k; v2t = it->second.vt;
+            k2 = borrow(it->second.k); v2t = borrow(it->second.vt);
             Tk = ctx_T; Tkp = roundup(Tk, 64);
         } else {
             Tk = ctx16.H * ctx16.W; Tkp = roundup(Tk, 64);
             CHK(cross_kv(l, ctx16, false, &k2, &v2t));
         }
-        a = talloc(B, x.H, x.W, C);
-        if (!a.p) return fail(FGDM_ERR_NOMEM, "workspace");
+        CHK(talloc(&a, B, x.H, x.W, C));
         { char tag[56]; snprintf(tag, sizeof(tag), "attn B%d T%d Tk%d d%d", B, T, Tk, d);
           prof.begin(PC_ATTN, s, 4.0 * (double)B * T * (double)Tk * C, tag);
           int rc;
@@ -763,123 +701,93 @@ struct fgdm_engine : Model {
           }
           prof.end(s);
           if (rc != FGDM_OK) return fail(rc, "attention launch failed"); }
-        tfree(q2);
-        if (!cached) { tfree(k2); tfree(v2t); }
+        q2.reset(); k2.reset(); v2t.reset();      // (a cached K / V^T was only borrowed)
         { Epi e; e.resid = h2.p; e.ld_res = C; if (ln_fold) e.stats = &s3; CHK(linear(l.o2, a, e, &h)); }
-        tfree(a); tfree(h2);
+        a.reset(); h2.reset();
         // --- GEGLU feed-forward, norm3 folded into the projection
         if (!ln_fold) CHK(lnorm(l.ln3, h, &nrm));
         { Epi e; if (ln_fold) e.ln = &s3; e.act = ACT_GEGLU; CHK(linear(l.ffp, ln_fold ? h : nrm, e, &f)); }
-        if (s3.p) ar->release(s3.p);
-        if (nrm.p) tfree(nrm);
+        s3.reset(); nrm.reset();
         { Epi e; e.resid = h.p; e.ld_res = C; CHK(linear(l.ffo, f, e, &h2)); }
-        tfree(f); tfree(h);
-        { Epi e; e.resid = x.p; e.ld_res = C; CHK(linear(l.pout, h2, e, out)); }
-        tfree(h2);
-        if (x_full.p) tfree(x_full);
-        return FGDM_OK;
+        f.reset(); h.reset();
+        Epi e; e.resid = x.p; e.ld_res = C;
+        return linear(l.pout, h2, e, out);      // h2 and x_full go back behind it
     }
 
     // [x] -> [x; x]: the two halves of a classifier-free-guidance batch share everything up to the first cross-attention
-    int dup_rows(const Tensor& h, Tensor* full) {
-        *full = talloc(2 * h.B, h.H, h.W, h.C);
-        if (!full->p) return fail(FGDM_ERR_NOMEM, "workspace");
+    int dup_rows(const Tensor& h, Act* full) {
+        CHK(talloc(full, 2 * h.B, h.H, h.W, h.C));
         const size_t bytes = h.numel() * sizeof(half_t);
         CHK(dcopy(full->p, h.p, bytes));
         CHK(dcopy((char*)full->p + bytes, h.p, bytes));
         return FGDM_OK;
     }
-    // block_fwd for a block whose input is the SHARED half batch (FGDM_FLAG_CFG_PAIRS): layers run on B/2 rows until the
-    // context enters (attn2 of the first SpatialTransformer); the output has the full 2 * (B/2) rows.
-    int block_fwd_shared(const Block& blk, Tensor xh, bool own_x, const EmbCtx& ec, const Tensor& ctx16, Tensor* out) {
-        Tensor cur = xh;
-        bool own = own_x, full = false;
-        for (size_t j = 0; j < blk.size(); ++j) {
-            const Layer& l = blk[j];
-            Tensor nxt;
-            switch (l.type) {
-                case L_CONV: CHK(conv3(l.conv, cur, nullptr, 1, false, Epi{}, &nxt)); break;
-                case L_RES: CHK(res_fwd(l, cur, nullptr, ec, &nxt)); break;
-                case L_ATTN: CHK(attn_fwd(l, cur, ctx16, &nxt, !full)); full = true; break;
-                case L_DOWN: CHK(conv3(l.conv, cur, nullptr, 2, false, Epi{}, &nxt)); break;
-                case L_UP: CHK(conv3(l.conv, cur, nullptr, 1, true, Epi{}, &nxt)); break;
-            }
-            if (own) tfree(cur);
-            cur = nxt;
-            own = true;
-        }
-        if (!full) { Tensor f; CHK(dup_rows(cur, &f)); if (own) tfree(cur); cur = f; }
-        *out = cur;
-        return FGDM_OK;
-    }
 
-    // TimestepEmbedSequential over one block; x1 = decoder skip (consumed by the block's first ResBlock)
-    int block_fwd(const Block& blk, Tensor x, bool own_x, const Tensor* x1, const EmbCtx& ec, const Tensor& ctx16,
-                  const half_t* conv_resid, Tensor* out) {
-        Tensor cur = x;
-        bool own = own_x;
+    // TimestepEmbedSequential over one block; x1 = decoder skip (consumed by the block's first ResBlock).  x is consumed: it goes
+    // back to its arena as soon as the first layer has read it -- unless the caller only lent it (borrow()).
+    // shared: x holds the SHARED half of a CFG batch (FGDM_FLAG_CFG_PAIRS): the layers run on B/2 rows until the context enters
+    // (attn2 of the first SpatialTransformer); the output has the full 2 * (B/2) rows.
+    int block_fwd(const Block& blk, Act x, const Tensor* x1, const EmbCtx& ec, const Tensor& ctx16, const half_t* conv_resid, Act* out,
+                  bool shared = false) {
+        Act cur = std::move(x);
+        bool full = !shared;
         for (size_t j = 0; j < blk.size(); ++j) {
             const Layer& l = blk[j];
-            Tensor nxt;
+            Act nxt;
             switch (l.type) {
                 case L_CONV: { Epi e; if (conv_resid) { e.resid = conv_resid; e.ld_res = l.cout; }
                                CHK(conv3(l.conv, cur, nullptr, 1, false, e, &nxt)); break; }
                 case L_RES: CHK(res_fwd(l, cur, j == 0 ? x1 : nullptr, ec, &nxt)); break;
-                case L_ATTN: CHK(attn_fwd(l, cur, ctx16, &nxt)); break;
+                case L_ATTN: CHK(attn_fwd(l, cur, ctx16, &nxt, !full)); full = true; break;
                 case L_DOWN: CHK(conv3(l.conv, cur, nullptr, 2, false, Epi{}, &nxt)); break;
                 case L_UP: CHK(conv3(l.conv, cur, nullptr, 1, true, Epi{}, &nxt)); break;
             }
-            if (own) tfree(cur);
-            cur = nxt;
-            own = true;
+            cur = std::move(nxt);
         }
-        *out = cur;
+        if (!full) { Act f; CHK(dup_rows(cur, &f)); cur = std::move(f); }
+        *out = std::move(cur);
         return FGDM_OK;
     }
 
     // timestep_embedding -> time_embed -> SiLU -> all emb_layers (util.py:160-180; openaimodel.py:537-542,827-828,290)
-    int embed(Net& n, const int64_t* t, const float* tf, int B, float** emb_all) {
+    int embed(Net& n, const int64_t* t, const float* tf, int B, Buf* emb_all) {
         const int mc = cfg.model_channels;
-        Tensor te = talloc(1, 1, B, mc), e1, e2;
-        if (!te.p) return fail(FGDM_ERR_NOMEM, "workspace");
+        Act te, e1, e2;
+        CHK(talloc(&te, 1, 1, B, mc));
         if (timestep_embed(t, tf, te.p, B, mc, B, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "timestep_embed");
         { Epi e; e.act = ACT_SILU; e.rps = 1; CHK(linear(n.time0, te, e, &e1)); }
         { Epi e; e.act = ACT_SILU; e.rps = 1; CHK(linear(n.time2, e1, e, &e2)); }   // = SiLU(emb): the only use of emb
-        *emb_all = (float*)ar->alloc((size_t)B * n.emb_total * sizeof(float));
-        if (!*emb_all) return fail(FGDM_ERR_NOMEM, "workspace");
-        { Epi e; e.out_kind = OUT_F32; e.out = *emb_all; e.ld_out = n.emb_total; e.rps = 1; CHK(linear(n.emb_all, e2, e, nullptr)); }
-        tfree(te); tfree(e1); tfree(e2);
-        return FGDM_OK;
+        CHK(balloc(emb_all, (size_t)B * n.emb_total * sizeof(float)));
+        Epi e; e.out_kind = OUT_F32; e.out = emb_all->p; e.ld_out = n.emb_total; e.rps = 1;
+        return linear(n.emb_all, e2, e, nullptr);
     }
 
     // Adapter.forward (adapter.py:334-346): four feature maps from the (noisy) latent itself.
     // ResnetBlock (adapter.py:301-313, ksize=1, sk=True): [AvgPool2d(2)] -> [conv1x1] -> conv3x3 -> ReLU -> conv1x1 -> +x
-    int adapter_fwd(Net& n, const Tensor& x4, Tensor feats[4]) { return adapter_run(n.ad_conv_in, n.ad_body, x4, feats); }
-    int adapter_run(const GemmW& conv_in, const std::vector<AdapterBlk>& body, const Tensor& x4, Tensor feats[4]) {
-        Tensor cur;
-        CHK(conv3(conv_in, x4, nullptr, 1, false, Epi{}, &cur));
-        auto drop = [&](Tensor& t) {   // free a temporary unless it is one of the returned features
-            for (int f = 0; f < 4; ++f) if (feats[f].p == t.p) return;
-            tfree(t);
-        };
+    // The running activation is `cur` while it is a temporary; every second block's output is moved into feats[k], which owns it
+    // from then on, and `x` -- what the next layer reads -- goes on viewing it there.
+    int adapter_fwd(Net& n, const Tensor& x4, Act feats[4]) { return adapter_run(n.ad_conv_in, n.ad_body, x4, feats); }
+    int adapter_run(const GemmW& conv_in, const std::vector<AdapterBlk>& body, const Tensor& x4, Act feats[4]) {
+        Act cur;
+        Tensor x;
+        auto next = [&](Act& y) { cur = std::move(y); x = cur; };
+        { Act y; CHK(conv3(conv_in, x4, nullptr, 1, false, Epi{}, &y)); next(y); }
         for (size_t k = 0; k < body.size(); ++k) {
             const AdapterBlk& b = body[k];
             if (b.down) {
-                Tensor p = talloc(cur.B, cur.H / 2, cur.W / 2, cur.C);
-                if (!p.p) return fail(FGDM_ERR_NOMEM, "workspace");
-                if (avgpool2(cur.p, p.p, cur.B, cur.H, cur.W, cur.C, s) != FGDM_OK)
+                Act p;
+                CHK(talloc(&p, x.B, x.H / 2, x.W / 2, x.C));
+                if (avgpool2(x.p, p.p, x.B, x.H, x.W, x.C, s) != FGDM_OK)
                     return fail(FGDM_ERR_ARG, "avgpool2: latent size must be divisible by 8 for the adapter");
-                drop(cur);
-                cur = p;
+                next(p);
             }
-            if (b.ic != b.oc) { Tensor y; CHK(linear(b.in_conv, cur, Epi{}, &y)); drop(cur); cur = y; }
-            Tensor h, y;
-            { Epi e; e.act = ACT_RELU; CHK(conv3(b.b1, cur, nullptr, 1, false, e, &h)); }
-            { Epi e; e.resid = cur.p; e.ld_res = cur.C; CHK(linear(b.b2, h, e, &y)); }
-            tfree(h);
-            drop(cur);
-            cur = y;
-            if (k % 2 == 1) feats[k / 2] = cur;   // nums_rb = 2: a feature after every second block
+            if (b.ic != b.oc) { Act y; CHK(linear(b.in_conv, x, Epi{}, &y)); next(y); }
+            Act h, y;
+            { Epi e; e.act = ACT_RELU; CHK(conv3(b.b1, x, nullptr, 1, false, e, &h)); }
+            { Epi e; e.resid = x.p; e.ld_res = x.C; CHK(linear(b.b2, h, e, &y)); }
+            h.reset();
+            next(y);
+            if (k % 2 == 1) feats[k / 2] = std::move(cur);   // nums_rb = 2: a feature after every second block
         }
         return FGDM_OK;
     }
@@ -897,11 +805,10 @@ struct fgdm_engine : Model {
         if (nc < 0 || nc > (int)n.xad_body.size() || !conds) return fail(FGDM_ERR_ARG, "more conds than extra adapters (n_extra_adapters)");
         if (B <= 0 || (H & 7) || (W & 7)) return fail(FGDM_ERR_ARG, "latent size must be divisible by 8 for the adapter");
         for (int kk = 0; kk < nc; ++kk) {
-            Tensor c4 = talloc(B, H, W, 4), f[4];
-            if (!c4.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            Act c4, f[4];
+            CHK(talloc(&c4, B, H, W, 4));
             if (nchw_f32_to_nhwc_f16(conds[kk], c4.p, B, 4, H * W, 4, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
             CHK(adapter_run(n.xad_conv_in[kk], n.xad_body[kk], c4, f));
-            tfree(c4);
             for (int i = 0; i < 4; ++i) {
                 Tensor& acc = n.xad_sum[i];
                 if (kk == 0) {
@@ -911,7 +818,6 @@ struct fgdm_engine : Model {
                 } else if (add_f16(acc.p, f[i].p, acc.p, acc.numel(), s) != FGDM_OK) {
                     return fail(FGDM_ERR_HIP, "add kernel");
                 }
-                tfree(f[i]);
             }
         }
         n.xad_valid = true;
@@ -919,17 +825,17 @@ struct fgdm_engine : Model {
     }
 
     // TimeAdapter.forward (adapter.py:405-417): conv_in, then 8 time-conditioned ResBlocks, a feature every second one
-    int time_adapter_fwd(Net& n, const Tensor& x4, const EmbCtx& ec, Tensor feats[4]) {
-        Tensor cur;
+    int time_adapter_fwd(Net& n, const Tensor& x4, const EmbCtx& ec, Act feats[4]) {
+        Act cur;                 // as in adapter_run
+        Tensor x;
         CHK(conv3(n.ad_conv_in, x4, nullptr, 1, false, Epi{}, &cur));
+        x = cur;
         for (size_t k = 0; k < n.tad_body.size(); ++k) {
-            Tensor y;
-            CHK(res_fwd(n.tad_body[k], cur, nullptr, ec, &y));
-            bool keep = false;
-            for (int f = 0; f < 4; ++f) if (feats[f].p == cur.p) keep = true;
-            if (!keep) tfree(cur);
-            cur = y;
-            if (k % 2 == 1) feats[k / 2] = cur;
+            Act y;
+            CHK(res_fwd(n.tad_body[k], x, nullptr, ec, &y));
+            cur = std::move(y);
+            x = cur;
+            if (k % 2 == 1) feats[k / 2] = std::move(cur);
         }
         return FGDM_OK;
     }
@@ -974,22 +880,20 @@ struct fgdm_engine : Model {
             return FGDM_OK;
         };
         int64_t off = 0;
-        Tensor xin = talloc(B, H, W, C);
-        if (!xin.p) return fail(FGDM_ERR_NOMEM, "workspace");
+        Act xin;
+        CHK(talloc(&xin, B, H, W, C));
         if (nchw_f32_to_nhwc_f16(x, xin.p, B, C, HW, C, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
         if (adapter) {
             if (C != 4) return fail(FGDM_ERR_ARG, "adapter input has 4 channels");
-            Tensor fa[4];
+            Act fa[4];
             CHK(adapter_fwd(unet, xin, fa));
-            for (int i = 0; i < 4; ++i) { CHK(emit(fa[i], off)); tfree(fa[i]); }
-            tfree(xin);
+            for (int i = 0; i < 4; ++i) CHK(emit(fa[i], off));
             if (out_numel) *out_numel = off;
             return FGDM_OK;
         }
-        Tensor xsk, ctx16;
+        Act xsk, ctx16;
         if (x_skip) {
-            xsk = talloc(B, H, W, Cs);
-            if (!xsk.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            CHK(talloc(&xsk, B, H, W, Cs));
             if (nchw_f32_to_nhwc_f16(x_skip, xsk.p, B, Cs, HW, Cs, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
         }
         if ((*blk)[0].cin != C + (x_skip ? Cs : 0) || (C & 63) || (x_skip && (Cs & 63)))
@@ -998,28 +902,22 @@ struct fgdm_engine : Model {
         for (const Layer& l : *blk) { needs_ctx |= l.type == L_ATTN; needs_emb |= l.type == L_RES; }
         if ((needs_ctx && !ctx) || (needs_emb && !emb)) return fail(FGDM_ERR_ARG, "fgdm_run_block: this block needs ctx / emb");
         if (needs_ctx) {
-            ctx16 = talloc(B, 1, ctx_tokens, cfg.context_dim);
-            if (!ctx16.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            CHK(talloc(&ctx16, B, 1, ctx_tokens, cfg.context_dim));
             if (f32_to_f16(ctx, ctx16.p, ctx16.numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "convert kernel");
         }
-        float* emb_all = nullptr;
+        Buf emb_all;
         if (needs_emb) {   // emb_layers = SiLU -> Linear on the given `emb` (openaimodel.py:238-244), all ResBlocks in one GEMM
-            const int temb = 4 * cfg.model_channels;
-            Tensor e2 = talloc(1, 1, B, temb);
-            emb_all = (float*)ar->alloc((size_t)B * net->emb_total * sizeof(float));
-            if (!e2.p || !emb_all) return fail(FGDM_ERR_NOMEM, "workspace");
+            Act e2;
+            CHK(talloc(&e2, 1, 1, B, 4 * cfg.model_channels));
+            CHK(balloc(&emb_all, (size_t)B * net->emb_total * sizeof(float)));
             if (silu_f32_to_f16(emb, e2.p, e2.numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "silu kernel");
-            { Epi e; e.out_kind = OUT_F32; e.out = emb_all; e.ld_out = net->emb_total; e.rps = 1; CHK(linear(net->emb_all, e2, e, nullptr)); }
-            tfree(e2);
+            Epi e; e.out_kind = OUT_F32; e.out = emb_all.p; e.ld_out = net->emb_total; e.rps = 1;
+            CHK(linear(net->emb_all, e2, e, nullptr));
         }
-        EmbCtx ec{emb_all, net->emb_total};
-        Tensor y;
-        CHK(block_fwd(*blk, xin, false, x_skip ? &xsk : nullptr, ec, ctx16, nullptr, &y));
+        EmbCtx ec{emb_all.as<float>(), net->emb_total};
+        Act y;
+        CHK(block_fwd(*blk, borrow(xin), x_skip ? &xsk : nullptr, ec, ctx16, nullptr, &y));
         CHK(emit(y, off));
-        tfree(y); tfree(xin);
-        if (xsk.p) tfree(xsk);
-        if (ctx16.p) tfree(ctx16);
-        if (emb_all) ar->release(emb_all);
         if (out_numel) *out_numel = off;
         return FGDM_OK;
     }
@@ -1083,7 +981,7 @@ struct fgdm_engine : Model {
     // the UNet's skip tensor hs[i] / h_mid (cldm.py:40,46 + :846), so control residuals never hit HBM separately.
     // fused = false: raw residuals are written as fp32 NCHW into out32 (test entry).
     int controlnet_fwd(Net& n, const Tensor& x4, const int64_t* t, const float* tf, const Tensor& ctx16, const float* scales,
-                       std::vector<Tensor>* hs, Tensor* h_mid, bool only_mid, float* out32, int64_t out_cap, bool pairs = false,
+                       std::vector<Act>* hs, Act* h_mid, bool only_mid, float* out32, int64_t out_cap, bool pairs = false,
                        std::vector<Deferred>* defer = nullptr) {
         const int B = x4.B;
         LayerHints twins(*this, true);
@@ -1093,12 +991,16 @@ struct fgdm_engine : Model {
         if (!n.guided.p) return fail(FGDM_ERR_STATE, "fgdm_set_hint has not been called for this ControlNet");
         if (!(n.guided.B == B || 2 * n.guided.B == B) || n.guided.H != x4.H || n.guided.W != x4.W)
             return fail(FGDM_ERR_ARG, "cached hint does not match the batch / latent size");
-        float* emb = nullptr;
+        Buf emb;
         CHK(embed(n, t, tf, B, &emb));
-        EmbCtx ec{emb, n.emb_total};
-        Tensor h;
+        EmbCtx ec{emb.as<float>(), n.emb_total};
+        // the running activation: `h` owns it until a deferred zero-conv takes it over (it needs the block output later, on the
+        // main stream); the next block then only borrows it through `hv`
+        Act h;
+        Tensor hv;
+        auto input = [&]() -> Act { return h.p ? std::move(h) : borrow(hv); };
         int64_t off = 0;
-        auto zero_conv = [&](const GemmW& zw, const Tensor& src, int idx) -> int {
+        auto zero_conv = [&](const GemmW& zw, Act& src, int idx) -> int {
             Epi e;
             if (out32) {
                 const int64_t cnt = (int64_t)src.numel();
@@ -1109,22 +1011,21 @@ struct fgdm_engine : Model {
             }
             if (idx >= 0 && only_mid) return FGDM_OK;
             e.scale = scales ? scales[idx < 0 ? (int)n.input.size() : idx] : 1.f;
-            if (defer) { defer->push_back({&zw, src, idx, e.scale, ar}); return FGDM_OK; }     // applied by the caller on the main stream
+            if (defer) { defer->push_back({&zw, std::move(src), idx, e.scale}); return FGDM_OK; }     // applied by the caller on the main stream
             return zero_conv_into(zw, src, idx < 0 ? *h_mid : (*hs)[idx], e.scale);
         };
         for (size_t i = 0; i < n.input.size(); ++i) {
-            Tensor nxt;
+            Act nxt;
             if (i == 0) {
                 // h = conv_in(x) + guided_hint (cldm.py:803-805); a B-sized hint serves both halves of a 2B CFG batch
                 const Layer& l = n.input[0][0];
                 if (shared) {
                     Tensor xh = x4; xh.B = B / 2;
-                    CHK(block_fwd(n.input[0], xh, false, nullptr, ec, ctx16, n.guided.p, &nxt));
+                    CHK(block_fwd(n.input[0], borrow(xh), nullptr, ec, ctx16, n.guided.p, &nxt));
                 } else if (n.guided.B == B) {
-                    CHK(block_fwd(n.input[0], x4, false, nullptr, ec, ctx16, n.guided.p, &nxt));
+                    CHK(block_fwd(n.input[0], borrow(x4), nullptr, ec, ctx16, n.guided.p, &nxt));
                 } else {
-                    nxt = talloc(B, x4.H, x4.W, l.cout);
-                    if (!nxt.p) return fail(FGDM_ERR_NOMEM, "workspace");
+                    CHK(talloc(&nxt, B, x4.H, x4.W, l.cout));
                     for (int half = 0; half < 2; ++half) {
                         Tensor xs = x4; xs.B = B / 2; xs.p = x4.p + (size_t)half * xs.numel();
                         Epi e; e.resid = n.guided.p; e.ld_res = l.cout;
@@ -1132,27 +1033,23 @@ struct fgdm_engine : Model {
                         CHK(conv3(l.conv, xs, nullptr, 1, false, e, nullptr));
                     }
                 }
-            } else if (shared && i == 1) {
-                CHK(block_fwd_shared(n.input[1], h, !defer, ec, ctx16, &nxt));    // B/2 rows in, B rows out
             } else {
-                CHK(block_fwd(n.input[i], h, !defer, nullptr, ec, ctx16, nullptr, &nxt));
+                CHK(block_fwd(n.input[i], input(), nullptr, ec, ctx16, nullptr, &nxt, shared && i == 1));    // shared: B/2 rows in, B rows out
             }
-            h = nxt;
+            h = std::move(nxt);
+            hv = h;
             CHK(zero_conv(n.zero_convs[i], h, (int)i));
         }
-        Tensor m;
-        CHK(block_fwd(n.middle, h, !defer, nullptr, ec, ctx16, nullptr, &m));
-        CHK(zero_conv(n.mid_out, m, -1));
-        if (!defer) tfree(m);
-        ar->release(emb);
-        return FGDM_OK;
+        Act m;
+        CHK(block_fwd(n.middle, input(), nullptr, ec, ctx16, nullptr, &m));
+        return zero_conv(n.mid_out, m, -1);
     }
 
     // controlnet_fwd for every ControlNet of the engine (residuals into hs / h_mid, or deferred), each inside the scope that
     // `per_net(c)` returns: the list that records it and the arena that serves it
     template <class PerNet>
-    int controlnets_fwd(const Tensor& x4, const int64_t* t, const float* tf, const Tensor& ctx16, const float* scales, std::vector<Tensor>* hs,
-                        Tensor* h_mid, bool only_mid, bool pairs, std::vector<Deferred>* defer, PerNet per_net) {
+    int controlnets_fwd(const Tensor& x4, const int64_t* t, const float* tf, const Tensor& ctx16, const float* scales, std::vector<Act>* hs,
+                        Act* h_mid, bool only_mid, bool pairs, std::vector<Deferred>* defer, PerNet per_net) {
         for (size_t c = 0; c < cns.size(); ++c) {
             RecordScope scope = per_net(c);
             CHK(controlnet_fwd(cns[c], x4, t, tf, ctx16, scales ? scales + 13 * c : nullptr, hs, h_mid, only_mid, nullptr, 0, pairs, defer));
@@ -1183,10 +1080,18 @@ struct fgdm_engine : Model {
                 return fail(FGDM_ERR_STATE, "the registered c_concat has " + std::to_string(ccat.B) + " rows: the batch must have as many, or twice as many");
             if (ccat.H != H || ccat.W != W) return fail(FGDM_ERR_STATE, "the registered c_concat has another latent size than x");
         }
-        Tensor x4 = talloc(B, H, W, Cc > 0 ? n.input[0][0].conv.cin_pad : 4), ctx16;
-        if (ctx) ctx16 = talloc(B, 1, ctx_tokens, cfg.context_dim);
+        Act x4, ctx16;
+        Buf emb;
+        // FGDM_TWIN_STREAMS=1: between the fork and the join wait the second stream reads x4 / ctx16 / emb and writes the deferred
+        // block outputs, and the main stream does not wait for it.  Whatever path leaves in between, the second stream is drained
+        // BEFORE any of those blocks goes back to an arena (declared after them: destroyed before them, and before `deferred`).
+        struct SecondStreamGuard {
+            hipStream_t busy = nullptr;
+            ~SecondStreamGuard() { if (busy) (void)hipStreamSynchronize(busy); }
+        };
+        CHK(talloc(&x4, B, H, W, Cc > 0 ? n.input[0][0].conv.cin_pad : 4));
+        if (ctx) CHK(talloc(&ctx16, B, 1, ctx_tokens, cfg.context_dim));
         else if (ctx_B != B) return fail(FGDM_ERR_STATE, "ctx is NULL but no context of this batch size was registered (fgdm_set_context)");
-        if (!x4.p || (ctx && !ctx16.p)) return fail(FGDM_ERR_NOMEM, "workspace");
         const bool pairs = (flags & FGDM_FLAG_CFG_PAIRS) && (B % 2 == 0) && n.input.size() > 1;      // (see below)
         if (Cc > 0) {      // only the rows the first layer reads: with CFG pairs the shared half, rows [0, B/2) of x and of the stored
                            // c_concat, whether that holds B/2 rows or B (the caller's word that rows b and b + B/2 are equal)
@@ -1194,9 +1099,8 @@ struct fgdm_engine : Model {
             if (pack_xcat(x, ccat.p, x4.p, rows, std::min(ccat.B, rows), Cc, HW, x4.C, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "pack kernel");
         } else if (nchw_f32_to_nhwc_f16(x, x4.p, B, 4, HW, 4, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
         if (ctx && f32_to_f16(ctx, ctx16.p, ctx16.numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "convert kernel");
-        float* emb = nullptr;
         CHK(embed(n, t, tf, B, &emb));
-        EmbCtx ec{emb, n.emb_total};
+        EmbCtx ec{emb.as<float>(), n.emb_total};
 
         const bool use_adapter = n.has_adapter && !(flags & FGDM_FLAG_USE_ORIGINAL);
         // FGDM_FLAG_CFG_PAIRS: the batch is cat([x] * 2) of a classifier-free-guidance step (ddim.py:222-226): rows b and
@@ -1205,14 +1109,13 @@ struct fgdm_engine : Model {
         // B/2 rows and duplicated where the context enters.  Per-sample results are unchanged bit for bit.
         const int Bs = pairs ? B / 2 : B;              // rows of the shared prefix
         Tensor x4s = x4; x4s.B = Bs;
-        Tensor fa[4];
+        Act fa[4];
         if (use_adapter) {
             if (pcond) {
-                Tensor p4 = talloc(Bs, H, W, 4);
-                if (!p4.p) return fail(FGDM_ERR_NOMEM, "workspace");
+                Act p4;
+                CHK(talloc(&p4, Bs, H, W, 4));
                 if (nchw_f32_to_nhwc_f16(pcond, p4.p, Bs, 4, HW, 4, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
                 CHK(n.time_adapter ? time_adapter_fwd(n, p4, ec, fa) : adapter_fwd(n, p4, fa));
-                tfree(p4);
             } else {
                 CHK(n.time_adapter ? time_adapter_fwd(n, x4s, ec, fa) : adapter_fwd(n, x4s, fa));
             }
@@ -1224,21 +1127,22 @@ struct fgdm_engine : Model {
         // ---- grouped twin launches: record the ControlNet walks, then the UNet encoder + middle block, and replay them together
         const bool paired = pair_launch && with_cn && !twin && !(flags & FGDM_FLAG_ONLY_MID_CONTROL);
         // ---- encoder (openaimodel.py:849-858); the adapter feature is added BEFORE the skip is recorded
-        std::vector<Tensor> hs;
-        Tensor h, hm;
+        std::vector<Act> hs;      // every input block's output: the skip tensors, each also read (not consumed) by the next block
+        Act hm;
+        SecondStreamGuard second;
         auto encoder = [&]() -> int {
             LayerHints twins(*this, with_cn);                // encoder + middle block: the ControlNets' twins
             int k = 0;
-            Tensor h0s;        // input block 0 on the shared rows (CFG pairs)
+            Act h0s;           // input block 0 on the shared rows (CFG pairs)
             for (size_t i = 0; i < n.input.size(); ++i) {
-                Tensor nxt;
+                Act nxt;
                 if (pairs && i == 0) {
-                    CHK(block_fwd(n.input[0], x4s, false, nullptr, ec, ctx16, nullptr, &h0s));
+                    CHK(block_fwd(n.input[0], borrow(x4s), nullptr, ec, ctx16, nullptr, &h0s));
                     CHK(dup_rows(h0s, &nxt));                                        // the skip tensor hs[0] needs all B rows
                 } else if (pairs && i == 1) {
-                    CHK(block_fwd_shared(n.input[1], h0s, true, ec, ctx16, &nxt));   // B/2 rows in, B rows out
+                    CHK(block_fwd(n.input[1], std::move(h0s), nullptr, ec, ctx16, nullptr, &nxt, true));   // B/2 rows in, B rows out
                 } else {
-                    CHK(block_fwd(n.input[i], i == 0 ? x4 : h, false, nullptr, ec, ctx16, nullptr, &nxt));
+                    CHK(block_fwd(n.input[i], borrow(i == 0 ? x4 : hs.back()), nullptr, ec, ctx16, nullptr, &nxt));
                 }
                 if (use_adapter && (i + 1) % 3 == 0) {
                     // the adapter features cover Bs rows; with CFG pairs each is added to both halves
@@ -1252,14 +1156,12 @@ struct fgdm_engine : Model {
                         }
                         if (add_f16(dst, fa[k].p, dst, fa[k].numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "add kernel");
                     }
-                    tfree(fa[k]);
+                    fa[k].reset();
                     ++k;
                 }
-                h = nxt;
-                hs.push_back(h);
+                hs.push_back(std::move(nxt));
             }
-            CHK(block_fwd(n.middle, h, false, nullptr, ec, ctx16, nullptr, &hm));
-            return FGDM_OK;
+            return block_fwd(n.middle, borrow(hs.back()), nullptr, ec, ctx16, nullptr, &hm);
         };
         if (paired) {
             std::vector<RecWalk> walks(1 + cns.size());      // the UNet's, then one per ControlNet
@@ -1279,6 +1181,7 @@ struct fgdm_engine : Model {
         } else {
             if (twin) {      // the ControlNets start now, on the second stream, next to the UNet encoder
                 if (hipEventRecord(ev_fork, s) != hipSuccess || hipStreamWaitEvent(s2, ev_fork, 0) != hipSuccess) return fail(FGDM_ERR_HIP, "stream fork");
+                second.busy = s2;
                 hipStream_t main_s = s;
                 s = s2;
                 const int rc = controlnets_fwd(x4, t, tf, ctx16, scales, nullptr, nullptr, false, pairs, &deferred,
@@ -1292,34 +1195,29 @@ struct fgdm_engine : Model {
         // ---- ControlNets: residuals accumulate in place into hs / hm (cldm.py:40,46,846)
         if (twin || paired) {
             if (twin && hipStreamWaitEvent(s, ev_join, 0) != hipSuccess) return fail(FGDM_ERR_HIP, "stream join");
+            second.busy = nullptr;      // from here on the main stream is ordered behind the second
             for (const Deferred& d : deferred) CHK(zero_conv_into(*d.w, d.src, d.idx < 0 ? hm : hs[d.idx], d.scale));
             // the ControlNets' block outputs go back to their own arena: its next user is the next call's second stream, which
             // waits for that call's fork event, recorded behind these zero-convs
-            for (Deferred& d : deferred) { d.owner->release(d.src.p); d.src.p = nullptr; }
+            deferred.clear();
         } else if (with_cn) {
             CHK(controlnets_fwd(x4, t, tf, ctx16, scales, &hs, &hm, (flags & FGDM_FLAG_ONLY_MID_CONTROL) != 0, pairs, nullptr,
                                 [&](size_t) { return RecordScope(*this, nullptr, &arena); }));
         }
         // ---- decoder (openaimodel.py:868-870): virtual concat [h, skip]
-        h = hm;
+        Act h = std::move(hm);
         for (size_t i = 0; i < n.output.size(); ++i) {
-            Tensor skip = hs.back();
+            Act skip = std::move(hs.back()), nxt;      // the skip goes back when the block is done
             hs.pop_back();
-            Tensor nxt;
-            CHK(block_fwd(n.output[i], h, true, &skip, ec, ctx16, nullptr, &nxt));
-            tfree(skip);
-            h = nxt;
+            CHK(block_fwd(n.output[i], std::move(h), &skip, ec, ctx16, nullptr, &nxt));
+            h = std::move(nxt);
         }
         // ---- out: GN -> SiLU -> conv3x3 (openaimodel.py:724-728) straight to fp32 NCHW
-        Tensor g;
+        Act g;
         CHK(gnorm(n.out_gn, h, nullptr, 1e-5f, true, &g));
-        tfree(h);
-        { Epi e; e.out_kind = OUT_F32_NCHW; e.out = eps_out; e.ld_out = HW; CHK(conv3(n.out_conv, g, nullptr, 1, false, e, nullptr)); }
-        tfree(g);
-        tfree(x4);
-        if (ctx16.p) tfree(ctx16);
-        ar->release(emb);
-        return FGDM_OK;
+        h.reset();
+        Epi e; e.out_kind = OUT_F32_NCHW; e.out = eps_out; e.ld_out = HW;
+        return conv3(n.out_conv, g, nullptr, 1, false, e, nullptr);      // g, x4, ctx16 and emb go back behind it
     }
 
     // ------------------------------------------------------------------------------------ text encoder
@@ -1336,42 +1234,39 @@ struct fgdm_engine : Model {
         const int W = cfg.clip_width, rows = B * T;
         // the hidden states are an fp32 residual stream, as under the reference's autocast: fp32 embeddings, every branch
         // (attention / MLP output, a fp16 GEMM result) is promoted when added to it, LayerNorm reads fp32
-        Tensor n, qkv, a, f;
-        float* h = (float*)ar->alloc((size_t)rows * W * sizeof(float));
-        float* h2 = (float*)ar->alloc((size_t)rows * W * sizeof(float));
-        if (!h || !h2) return fail(FGDM_ERR_NOMEM, "workspace");
+        Act n, qkv, a, f;
+        Buf hb, h2b;
+        CHK(balloc(&hb, (size_t)rows * W * sizeof(float)));
+        CHK(balloc(&h2b, (size_t)rows * W * sizeof(float)));
+        float *const h = hb.as<float>(), *const h2 = h2b.as<float>();
         if (embed_tokens(ids, clip.tok, clip.pos, h, rows, T, W, cfg.clip_vocab, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "embedding kernel");
-        auto ln32 = [&](const NormW& nw, const float* src, Tensor* dst) -> int {
-            *dst = talloc(1, 1, rows, W);
-            if (!dst->p) return fail(FGDM_ERR_NOMEM, "workspace");
+        auto ln32 = [&](const NormW& nw, const float* src, Act* dst) -> int {
+            CHK(talloc(dst, 1, 1, rows, W));
             return layernorm32_launch(src, rows, W, nw.g, nw.b, 1e-5f, dst->p, nullptr, s) == FGDM_OK ? FGDM_OK : fail(FGDM_ERR_HIP, "layernorm");
         };
         for (const ClipLayer& l : clip.layers) {
             if (li++ >= n_run) break;
             CHK(ln32(l.ln1, h, &n));
             CHK(linear(l.qkv, n, Epi{}, &qkv));
-            tfree(n);
-            a = talloc(1, 1, rows, W);
-            if (!a.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            n.reset();
+            CHK(talloc(&a, 1, 1, rows, W));
             if (small_attention_launch(qkv.p, 3 * W, W, 2 * W, a.p, W, B, cfg.clip_heads, T, W / cfg.clip_heads, 1, s) != FGDM_OK)
                 return fail(FGDM_ERR_HIP, "text attention kernel");
-            tfree(qkv);
-            Tensor br;
+            qkv.reset();
+            Act br;
             CHK(linear(l.o, a, Epi{}, &br));                 // branch output fp16, as autocast leaves it
-            tfree(a);
+            a.reset();
             if (add_f16_to_f32(h, br.p, h2, br.numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "add kernel");
-            tfree(br);
+            br.reset();
             CHK(ln32(l.ln2, h2, &n));
             { Epi e; e.act = ACT_QGELU; CHK(linear(l.fc1, n, e, &f)); }
-            tfree(n);
+            n.reset();
             CHK(linear(l.fc2, f, Epi{}, &br));
-            tfree(f);
+            f.reset();
             if (add_f16_to_f32(h2, br.p, h, br.numel(), s) != FGDM_OK) return fail(FGDM_ERR_HIP, "add kernel");
-            tfree(br);
         }
         // final_layer_norm: fp32 in, fp32 out -- straight into the caller's buffer
         if (layernorm32_launch(h, rows, W, clip.final_ln.g, clip.final_ln.b, 1e-5f, nullptr, out, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layernorm");
-        ar->release(h); ar->release(h2);
         return FGDM_OK;
     }
 
@@ -1379,24 +1274,24 @@ struct fgdm_engine : Model {
     // AttnBlock.forward (model.py:176-203): ONE head over all C channels.  d = C = 512 does not fit the flash kernel's
     // register budget, so per image: S = C^-1/2 Q K^T (fp32, GEMM with K as the "weight"), row softmax, O = P V
     // (GEMM with V^T, written transposed by the v projection's epilogue, as the weight).
-    int vattn_fwd(const VAttn& at, const Tensor& x, Tensor* out) {
+    int vattn_fwd(const VAttn& at, const Tensor& x, Act* out) {
         const int B = x.B, T = x.H * x.W, C = x.C;
         if (T & 63) return fail(FGDM_ERR_ARG, "first-stage attention: H*W must be a multiple of 64");
-        Tensor g, q, k, vt, a, P;
+        Act g, q, k, vt, a, P;
+        Buf S;
         CHK(gnorm(at.norm, x, nullptr, 1e-6f, false, &g));
         CHK(linear(at.q, g, Epi{}, &q));
-        k = talloc(1, 1, B * T + 128, C);        // + 128 rows: the GEMM reads whole 128-row weight tiles
-        vt = talloc(B, 1, C, T);
-        a = talloc(B, x.H, x.W, C);
-        P = talloc(1, 1, T, T);
-        float* S = (float*)ar->alloc((size_t)T * T * sizeof(float));
-        if (!k.p || !vt.p || !a.p || !P.p || !S) return fail(FGDM_ERR_NOMEM, "workspace");
+        CHK(talloc(&k, 1, 1, B * T + 128, C));        // + 128 rows: the GEMM reads whole 128-row weight tiles
+        CHK(talloc(&vt, B, 1, C, T));
+        CHK(talloc(&a, B, x.H, x.W, C));
+        CHK(talloc(&P, 1, 1, T, T));
+        CHK(balloc(&S, (size_t)T * T * sizeof(float)));
         HIP_TRY(hipMemsetAsync(k.p + (size_t)B * T * C, 0, (size_t)128 * C * sizeof(half_t), s));
         { Epi e; e.out = k.p; e.ld_out = C; e.rps = T; CHK(linear(at.k, g, e, nullptr)); }
         { Epi e; e.out_kind = OUT_F16_T; e.out = vt.p; e.ld_out = T; e.rps = T; CHK(linear(at.v, g, e, nullptr)); }
-        tfree(g);
+        g.reset();
         bool softmax_failed = false;
-        const int rc = vattn_core(q.p, k.p, vt.p, a.p, S, P.p, B, T, C, s, &softmax_failed,
+        const int rc = vattn_core(q.p, k.p, vt.p, a.p, S.as<float>(), P.p, B, T, C, s, &softmax_failed,
             [&](const half_t* Wt, int N, int K, const half_t* A, int M, int out_kind, void* o, int ld_out, float scale) {
                 GemmW w; w.w = const_cast<half_t*>(Wt); w.N = N; w.K = K; w.k_real = K;
                 Tensor xa; xa.p = const_cast<half_t*>(A); xa.B = 1; xa.H = 1; xa.W = M; xa.C = K;
@@ -1404,11 +1299,9 @@ struct fgdm_engine : Model {
                 return gemm(w, IG_LINEAR, xa, nullptr, 1, M, e, nullptr);
             });
         if (rc != FGDM_OK) return softmax_failed ? fail(rc, "softmax kernel") : rc;
-        ar->release(S);
-        tfree(P); tfree(q); tfree(k); tfree(vt);
-        { Epi e; e.resid = x.p; e.ld_res = C; CHK(linear(at.o, a, e, out)); }
-        tfree(a);
-        return FGDM_OK;
+        S.reset(); P.reset(); q.reset(); k.reset(); vt.reset();
+        Epi e; e.resid = x.p; e.ld_res = C;
+        return linear(at.o, a, e, out);
     }
     // LatentDiffusion.decode_first_stage (ddpm.py:839,889) -> AutoencoderKL.decode (autoencoder.py:330-333) ->
     // Decoder.forward (model.py:532-560).  z fp32 NCHW [B,4,H,W] -> image fp32 NCHW [B,out_ch,f*H,f*W]
@@ -1425,24 +1318,22 @@ struct fgdm_engine : Model {
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, ((size_t)3 << 30) / std::max<size_t>(big, 1)));
         for (int b0 = 0; b0 < B; b0 += chunk) {
             const int nb = std::min(chunk, B - b0);
-            Tensor z4 = talloc(nb, H, W, 4), h, t;
-            if (!z4.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            Act z4, h, t, g;
+            CHK(talloc(&z4, nb, H, W, 4));
             if (vae_prequant(z + (size_t)b0 * 4 * HW, v.pq, scale, z4.p, nb, HW, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "prequant kernel");
             CHK(conv3(v.conv_in, z4, nullptr, 1, false, Epi{}, &h));
-            tfree(z4);
-            CHK(res_fwd(v.mid1, h, nullptr, no_emb, &t)); tfree(h); h = t;
-            CHK(vattn_fwd(v.attn, h, &t)); tfree(h); h = t;
-            CHK(res_fwd(v.mid2, h, nullptr, no_emb, &t)); tfree(h); h = t;
+            z4.reset();
+            CHK(res_fwd(v.mid1, h, nullptr, no_emb, &t)); h = std::move(t);
+            CHK(vattn_fwd(v.attn, h, &t)); h = std::move(t);
+            CHK(res_fwd(v.mid2, h, nullptr, no_emb, &t)); h = std::move(t);
             for (const VLevel& lv : v.levels) {
-                for (const Layer& r : lv.blocks) { CHK(res_fwd(r, h, nullptr, no_emb, &t)); tfree(h); h = t; }
-                if (lv.up) { CHK(conv3(lv.upconv, h, nullptr, 1, true, Epi{}, &t)); tfree(h); h = t; }
+                for (const Layer& r : lv.blocks) { CHK(res_fwd(r, h, nullptr, no_emb, &t)); h = std::move(t); }
+                if (lv.up) { CHK(conv3(lv.upconv, h, nullptr, 1, true, Epi{}, &t)); h = std::move(t); }
             }
-            Tensor g;
             CHK(gnorm(v.norm_out, h, nullptr, 1e-6f, true, &g));
-            tfree(h);
+            h.reset();
             { Epi e; e.out_kind = OUT_F32_NCHW; e.out = out + (size_t)b0 * out_per_img; e.ld_out = g.H * g.W;
               CHK(conv3(v.conv_out, g, nullptr, 1, false, e, nullptr)); }
-            tfree(g);
         }
         return FGDM_OK;
     }
@@ -1464,27 +1355,25 @@ struct fgdm_engine : Model {
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, ((size_t)3 << 30) / std::max<size_t>(big, 1)));
         for (int b0 = 0; b0 < B; b0 += chunk) {
             const int nb = std::min(chunk, B - b0);
-            Tensor x4 = talloc(nb, H, W, en.conv_in.cin_pad), h, t;      // 3 -> 4 channels
-            if (!x4.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            Act x4, h, t, g;
+            Buf h32;                                                     // conv_out, fp32 [pixel][2 z_channels]
+            CHK(talloc(&x4, nb, H, W, en.conv_in.cin_pad));              // 3 -> 4 channels
             if (nchw_f32_to_nhwc_f16(image + (size_t)b0 * 3 * H * W, x4.p, nb, 3, H * W, x4.C, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "layout kernel");
             CHK(conv3(en.conv_in, x4, nullptr, 1, false, Epi{}, &h));
-            tfree(x4);
+            x4.reset();
             for (const VDown& lv : en.levels) {
-                for (const Layer& r : lv.blocks) { CHK(res_fwd(r, h, nullptr, no_emb, &t)); tfree(h); h = t; }
-                if (lv.down) { CHK(conv3(lv.downconv, h, nullptr, FGDM_STRIDE2_PAD_BR, false, Epi{}, &t)); tfree(h); h = t; }
+                for (const Layer& r : lv.blocks) { CHK(res_fwd(r, h, nullptr, no_emb, &t)); h = std::move(t); }
+                if (lv.down) { CHK(conv3(lv.downconv, h, nullptr, FGDM_STRIDE2_PAD_BR, false, Epi{}, &t)); h = std::move(t); }
             }
-            CHK(res_fwd(en.mid1, h, nullptr, no_emb, &t)); tfree(h); h = t;
-            CHK(vattn_fwd(en.attn, h, &t)); tfree(h); h = t;
-            CHK(res_fwd(en.mid2, h, nullptr, no_emb, &t)); tfree(h); h = t;
-            Tensor g;
+            CHK(res_fwd(en.mid1, h, nullptr, no_emb, &t)); h = std::move(t);
+            CHK(vattn_fwd(en.attn, h, &t)); h = std::move(t);
+            CHK(res_fwd(en.mid2, h, nullptr, no_emb, &t)); h = std::move(t);
             CHK(gnorm(en.norm_out, h, nullptr, 1e-6f, true, &g));
-            tfree(h);
-            float* h32 = (float*)ar->alloc((size_t)nb * hw * zc2 * sizeof(float));      // conv_out, fp32 [pixel][2 z_channels]
-            if (!h32) return fail(FGDM_ERR_NOMEM, "workspace");
-            { Epi e; e.out_kind = OUT_F32; e.out = h32; e.ld_out = zc2; CHK(conv3(en.conv_out, g, nullptr, 1, false, e, nullptr)); }
-            tfree(g);
-            if (vae_moments(h32, en.qc, moments + (size_t)b0 * zc2 * hw, nb, hw, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "moments kernel");
-            ar->release(h32);
+            h.reset();
+            CHK(balloc(&h32, (size_t)nb * hw * zc2 * sizeof(float)));
+            { Epi e; e.out_kind = OUT_F32; e.out = h32.p; e.ld_out = zc2; CHK(conv3(en.conv_out, g, nullptr, 1, false, e, nullptr)); }
+            g.reset();
+            if (vae_moments(h32.as<float>(), en.qc, moments + (size_t)b0 * zc2 * hw, nb, hw, s) != FGDM_OK) return fail(FGDM_ERR_HIP, "moments kernel");
         }
         return FGDM_OK;
     }
@@ -1505,19 +1394,18 @@ struct fgdm_engine : Model {
         const int chunk = std::max(1, std::min(B, (int)(((size_t)512 << 20) / ((size_t)Hh * Wh * 192 * 2 + 1))));
         for (int b0 = 0; b0 < B; b0 += chunk) {
             const int nb = std::min(chunk, B - b0);
-            Tensor cur = talloc(nb, Hh, Wh, hc);
-            if (!cur.p) return fail(FGDM_ERR_NOMEM, "workspace");
+            Act cur;
+            CHK(talloc(&cur, nb, Hh, Wh, hc));
             if (nchw_f32_to_nhwc_f16(hint + (size_t)b0 * cfg.hint_channels * Hh * Wh, cur.p, nb, cfg.hint_channels, Hh * Wh, hc, s) != FGDM_OK)
                 return fail(FGDM_ERR_HIP, "layout kernel");
             for (int k = 0; k < 8; ++k) {
                 const int stride = (k == 2 || k == 4 || k == 6) ? 2 : 1;
                 Epi e;
                 e.act = k < 7 ? ACT_SILU : ACT_NONE;
-                Tensor nxt;
+                Act nxt;
                 if (k == 7) { e.out = n.guided.p + (size_t)b0 * Hl * Wl * mc; e.ld_out = mc; }
                 CHK(conv3(n.hint_convs[k], cur, nullptr, stride, false, e, k == 7 ? nullptr : &nxt));
-                tfree(cur);
-                cur = nxt;
+                cur = std::move(nxt);
             }
         }
         return FGDM_OK;
@@ -1559,19 +1447,12 @@ static int make_desc(const fgdm_config* cfg, fgdm_engine** out) {
     return FGDM_OK;
 }
 
-// One C-ABI call that uses the activation workspace: on a non-OK return everything it still holds goes back to the arena
-template <typename F> static int scoped_call(fgdm_engine* e, void* stream, F f) {
+// One C-ABI call that uses the activation workspace, on the caller's stream and the main arena.  Whatever it returns, the handles
+// it held have given their blocks back by then (arena.h).
+template <typename F> static int stream_call(fgdm_engine* e, void* stream, F f) {
     e->s = as_stream(stream);
     e->ar = &e->arena;
-    e->arena.begin_scope();
-    for (auto& a : e->cn_arena) a->begin_scope();
-    const int rc = f();
-    e->s = as_stream(stream);
-    e->ar = &e->arena;
-    if (rc != FGDM_OK && e->s2) (void)hipStreamSynchronize(e->s2);      // nothing of the second stream may outlive its blocks
-    e->arena.end_scope(rc != FGDM_OK);
-    for (auto& a : e->cn_arena) a->end_scope(rc != FGDM_OK);
-    return rc;
+    return f();
 }
 
 // ------------------------------------------------------------------------------------------------ device sampler loops: the driver
@@ -1599,7 +1480,7 @@ template <typename T> static int upload_repeated(const T* host, int count, int B
 static bool loop_cfg_on(const float* uncond, float cfg_scale) { return uncond && cfg_scale != 1.0f; }
 static int loop_flags(int flags, bool cfg_on) { return cfg_on ? flags | FGDM_FLAG_CFG_PAIRS : flags & ~FGDM_FLAG_CFG_PAIRS; }
 
-// The driver of the six device loops (inside the entry's scoped_call).  It owns what every loop holds while it runs -- the
+// The driver of the six device loops (inside the entry's stream_call).  It owns what every loop holds while it runs -- the
 // network's input x2 (Bm rows: cat([x] * 2), or x with CFG off), its output eps, the loop-invariant context cat([uncond, cond])
 // (ddim.py:226), registered (projected) once so that every evaluation passes ctx = NULL, the history planes an entry asks for and
 // the device time table (int64 timesteps or fractional times, whichever the entry has) -- and does every allocation, copy and
@@ -1613,6 +1494,7 @@ struct Loop {
     bool cfg_on;
     const int32_t* log_steps;
     int n_log;
+    Buf x2_buf, eps_buf, c2_buf, hist_buf, t_buf;      // ... which go back to the arena with the Loop
     float *x2 = nullptr, *eps = nullptr, *c2 = nullptr, *hist = nullptr;
     int64_t* t_int = nullptr;
     float* t_float = nullptr;
@@ -1628,10 +1510,10 @@ struct Loop {
         Bm = cfg_on ? 2 * B : B;
         n = (size_t)B * 4 * H * W;
         const size_t nctx = (size_t)B * e->ctx_tokens * e->cfg.context_dim;
-        x2 = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
-        eps = (float*)e->arena.alloc(Bm * 4 * (size_t)H * W * sizeof(float));
-        c2 = (float*)e->arena.alloc(Bm * (size_t)e->ctx_tokens * e->cfg.context_dim * sizeof(float));
-        if (!x2 || !eps || !c2) return e->fail(FGDM_ERR_NOMEM, "workspace");
+        CHK(e->balloc(&x2_buf, Bm * 4 * (size_t)H * W * sizeof(float)));
+        CHK(e->balloc(&eps_buf, Bm * 4 * (size_t)H * W * sizeof(float)));
+        CHK(e->balloc(&c2_buf, Bm * (size_t)e->ctx_tokens * e->cfg.context_dim * sizeof(float)));
+        x2 = x2_buf.as<float>(); eps = eps_buf.as<float>(); c2 = c2_buf.as<float>();
         if (cfg_on) {
             HIP_TRY(hipMemcpyAsync(c2, uncond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
             HIP_TRY(hipMemcpyAsync(c2 + nctx, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1639,11 +1521,11 @@ struct Loop {
             HIP_TRY(hipMemcpyAsync(c2, cond, nctx * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
         CHK(e->set_context(c2, Bm));
-        if (hist_planes) hist = (float*)e->arena.alloc(hist_planes * n * sizeof(float));
-        void* tdev = e->arena.alloc((size_t)K * Bm * (times_int ? sizeof(int64_t) : sizeof(float)));
-        if (!tdev || (hist_planes && !hist)) return e->fail(FGDM_ERR_NOMEM, "workspace");
-        if (times_int) return upload_repeated(times_int, K, Bm, t_int = (int64_t*)tdev, s);
-        return upload_repeated(times_float, K, Bm, t_float = (float*)tdev, s);
+        if (hist_planes) CHK(e->balloc(&hist_buf, hist_planes * n * sizeof(float)));
+        CHK(e->balloc(&t_buf, (size_t)K * Bm * (times_int ? sizeof(int64_t) : sizeof(float))));
+        hist = hist_buf.as<float>();
+        if (times_int) return upload_repeated(times_int, K, Bm, t_int = t_buf.as<int64_t>(), s);
+        return upload_repeated(times_float, K, Bm, t_float = t_buf.as<float>(), s);
     }
     float* plane(int j) const { return hist + (size_t)j * n; }
     // x into the network's input, once, for the loops whose first launch is not a blend
@@ -1668,15 +1550,10 @@ struct Loop {
     // step i's slot in the log tensors, or -1: not logged
     int log_slot(int i) { return logged < n_log && log_steps[logged] == i ? logged++ : -1; }
     float* log_plane(float* out, int slot) const { return out && slot >= 0 ? out + (size_t)slot * n : nullptr; }
-    int end(int rc) {
-        e->arena.release(x2); e->arena.release(eps); e->arena.release(c2); e->arena.release(hist);
-        e->arena.release(t_int); e->arena.release(t_float);
-        return rc;
-    }
 };
 
 // What the six entries do in front of their loop, in this order: NULL engine or struct; the struct's size; the entry's own checks
-// (`check`: nullptr / empty = consistent); hybrid networks; unfinalized weights; then `body(e, known, stream)` in a scoped_call.
+// (`check`: nullptr / empty = consistent); hybrid networks; unfinalized weights; then `body(e, known, stream)` in a stream_call.
 static std::string why_text(const char* why) { return why ? why : ""; }
 static std::string why_text(const std::string& why) { return why; }
 template <typename P, typename Check, typename Body>
@@ -1691,7 +1568,7 @@ static int loop_entry(fgdm_engine* e, const P* caller, void* stream, int64_t siz
     if (!why.empty()) return e->fail(FGDM_ERR_ARG, name + ": " + why);
     if (refuse_hybrid && e->cfg.in_channels > 4) return e->fail(FGDM_ERR_ARG, name + ": in_channels > 4 (hybrid c_concat) is not taken by the device loops");
     if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
-    return scoped_call(e, stream, [&] { return body(e, known, as_stream(stream)); });
+    return stream_call(e, stream, [&] { return body(e, known, as_stream(stream)); });
 }
 
 extern "C" {
@@ -1862,12 +1739,8 @@ int fgdm_profile_end(fgdm_engine* e, double* out) {
 int fgdm_workspace_stats(fgdm_engine* e, int64_t* peak_bytes, int64_t* reserved_bytes) {
     if (!e || !peak_bytes || !reserved_bytes) return FGDM_ERR_ARG;
     // all arenas: the main one and the ControlNets' (with grouped launches every ControlNet activation lives in those)
-    size_t pk = e->arena.peak, r = 0;
-    for (auto& sl : e->arena.slabs) for (auto& b : sl) r += b.sz;
-    for (auto& a : e->cn_arena) {
-        pk += a->peak;
-        for (auto& sl : a->slabs) for (auto& b : sl) r += b.sz;
-    }
+    size_t pk = e->arena.peak, r = e->arena.reserved();
+    for (auto& a : e->cn_arena) { pk += a->peak; r += a->reserved(); }
     *peak_bytes = (int64_t)pk;
     *reserved_bytes = (int64_t)r;
     return FGDM_OK;
@@ -1883,39 +1756,39 @@ int fgdm_launch_stats(fgdm_engine* e, int64_t* replayed_launches, int64_t* fused
 
 int fgdm_set_hint(fgdm_engine* e, int cn, const float* hint, int B, int Hh, int Wh, void* stream) {
     if (!e || !hint) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->set_hint(cn, hint, B, Hh, Wh); });
+    return stream_call(e, stream, [&] { return e->set_hint(cn, hint, B, Hh, Wh); });
 }
 
 int fgdm_set_concat(fgdm_engine* e, const float* c_concat, int B, int Cc, int H, int W, void* stream) {
     if (!e) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->set_concat(c_concat, B, Cc, H, W); });
+    return stream_call(e, stream, [&] { return e->set_concat(c_concat, B, Cc, H, W); });
 }
 
 int fgdm_apply_model(fgdm_engine* e, const float* x, const int64_t* t, const float* t_float, const float* ctx,
                      const float* pcond, const float* control_scales, int B, int H, int W, int flags, float* eps_out,
                      void* stream) {
     if (!e || !x || (!t && !t_float) || !eps_out) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->apply_model(x, t, t_float, ctx, pcond, control_scales, B, H, W, flags, eps_out); });
+    return stream_call(e, stream, [&] { return e->apply_model(x, t, t_float, ctx, pcond, control_scales, B, H, W, flags, eps_out); });
 }
 
 int fgdm_set_adapter_conds(fgdm_engine* e, const float* const* conds, int n_conds, int B, int H, int W, void* stream) {
     if (!e) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->set_adapter_conds(conds, n_conds, B, H, W); });
+    return stream_call(e, stream, [&] { return e->set_adapter_conds(conds, n_conds, B, H, W); });
 }
 
 int fgdm_set_context(fgdm_engine* e, const float* ctx, int B, void* stream) {
     if (!e || !ctx) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->set_context(ctx, B); });
+    return stream_call(e, stream, [&] { return e->set_context(ctx, B); });
 }
 
 int fgdm_clip_encode(fgdm_engine* e, const int64_t* ids, int B, int T, float* out, void* stream) {
     if (!e || !ids || !out) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->clip_encode(ids, B, T, out); });
+    return stream_call(e, stream, [&] { return e->clip_encode(ids, B, T, out); });
 }
 
 int fgdm_clip_encode_skip(fgdm_engine* e, const int64_t* ids, int B, int T, int clip_skip, float* out, void* stream) {
     if (!e || !ids || !out) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->clip_encode(ids, B, T, out, clip_skip); });
+    return stream_call(e, stream, [&] { return e->clip_encode(ids, B, T, out, clip_skip); });
 }
 
 int fgdm_set_context_tokens(fgdm_engine* e, int tokens) {
@@ -2017,12 +1890,12 @@ int fgdm_attention_capture_read(fgdm_engine* e, int block, float* dst_device, vo
 
 int fgdm_vae_decode(fgdm_engine* e, const float* z, int B, int H, int W, float scale, float* image, void* stream) {
     if (!e || !z || !image) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->vae_decode(z, B, H, W, scale, image); });
+    return stream_call(e, stream, [&] { return e->vae_decode(z, B, H, W, scale, image); });
 }
 
 int fgdm_vae_encode(fgdm_engine* e, const float* image, int B, int H, int W, float* moments, void* stream) {
     if (!e || !image || !moments) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->vae_encode(image, B, H, W, moments); });
+    return stream_call(e, stream, [&] { return e->vae_encode(image, B, H, W, moments); });
 }
 int fgdm_posterior_sample(const float* moments, const float* noise, float scale, float* z, int B, int zc, int HW, void* stream) {
     if (!moments || !z || B <= 0 || zc <= 0 || HW <= 0) return FGDM_ERR_ARG;
@@ -2049,11 +1922,12 @@ int fgdm_vae_decode_patches(fgdm_engine* e, const float* z, int B, int H, int W,
         const size_t imgs = std::max<size_t>(1, std::min<size_t>((size_t)L * B, ((size_t)3 << 30) / std::max<size_t>(big, 1)));
         step = (int)std::max<size_t>(1, std::min<size_t>((size_t)L, imgs / (size_t)B));
     }
-    return scoped_call(e, stream, [&]() -> int {
+    return stream_call(e, stream, [&]() -> int {
         const size_t zc_n = (size_t)B * 4 * kh * kw, oc_n = (size_t)B * oc * gi.kh * gi.kw;
-        float* zc = (float*)e->arena.alloc((size_t)step * zc_n * sizeof(float));
-        float* ocr = (float*)e->arena.alloc((size_t)step * oc_n * sizeof(float));
-        if (!zc || !ocr) return e->fail(FGDM_ERR_NOMEM, "workspace");
+        Buf zc_buf, ocr_buf;
+        CHK(e->balloc(&zc_buf, (size_t)step * zc_n * sizeof(float)));
+        CHK(e->balloc(&ocr_buf, (size_t)step * oc_n * sizeof(float)));
+        float *const zc = zc_buf.as<float>(), *const ocr = ocr_buf.as<float>();
         for (int l0 = 0; l0 < L; l0 += step) {
             const int n = std::min(step, L - l0);
             if (unfold_crops(z, zc, gz, l0, n, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "unfold kernel");
@@ -2061,7 +1935,6 @@ int fgdm_vae_decode_patches(fgdm_engine* e, const float* z, int B, int H, int W,
             if (fold_accumulate(ocr, w_pix, w_tie, image, gi, l0, n, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "fold kernel");
         }
         if (fold_finish(image, w_pix, w_tie, image, gi, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "fold kernel");
-        e->arena.release(zc); e->arena.release(ocr);
         return FGDM_OK;
     });
 }
@@ -2083,13 +1956,15 @@ int fgdm_apply_model_patches(fgdm_engine* e, const float* x, const int64_t* t, c
         return e->fail(FGDM_ERR_ARG, "patch apply_model: the crops do not cover the latent grid ((size - ks) % stride != 0, stride > ks or ks > size)");
     const int L = g.Ly * g.Lx, step = max_crops_per_pass > 0 ? std::min(max_crops_per_pass, L) : L;
     const int fl = (flags & FGDM_FLAG_USE_ORIGINAL) | FGDM_FLAG_NO_CONTROL;      // CFG_PAIRS cleared: rows are (l, b)
-    return scoped_call(e, stream, [&]() -> int {
+    return stream_call(e, stream, [&]() -> int {
         const size_t xc_n = (size_t)B * 4 * kh * kw, ctx_n = (size_t)B * e->ctx_tokens * e->cfg.context_dim;
-        float* xc = (float*)e->arena.alloc((size_t)step * xc_n * sizeof(float));
-        float* ec = (float*)e->arena.alloc((size_t)step * xc_n * sizeof(float));
-        float* cr = (float*)e->arena.alloc((size_t)step * ctx_n * sizeof(float));
-        void* tr = e->arena.alloc((size_t)step * B * sizeof(int64_t));
-        if (!xc || !ec || !cr || !tr) return e->fail(FGDM_ERR_NOMEM, "workspace");
+        Buf xc_buf, ec_buf, cr_buf, tr_buf;
+        CHK(e->balloc(&xc_buf, (size_t)step * xc_n * sizeof(float)));
+        CHK(e->balloc(&ec_buf, (size_t)step * xc_n * sizeof(float)));
+        CHK(e->balloc(&cr_buf, (size_t)step * ctx_n * sizeof(float)));
+        CHK(e->balloc(&tr_buf, (size_t)step * B * sizeof(int64_t)));
+        float *const xc = xc_buf.as<float>(), *const ec = ec_buf.as<float>(), *const cr = cr_buf.as<float>();
+        void* const tr = tr_buf.p;
         // t and the context of every crop (ddpm.py:1116,1119); a shorter last pass reads a prefix of the same buffers
         if (repeat_words(ctx, cr, ctx_n, step, e->s) != FGDM_OK ||
             repeat_words(t_float ? (const void*)t_float : (const void*)t, tr, t_float ? (size_t)B : (size_t)2 * B, step, e->s) != FGDM_OK)
@@ -2102,7 +1977,6 @@ int fgdm_apply_model_patches(fgdm_engine* e, const float* x, const int64_t* t, c
             if (fold_accumulate(ec, w_pix, w_tie, eps_out, g, l0, n, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "fold kernel");
         }
         if (fold_finish(eps_out, w_pix, w_tie, eps_out, g, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "fold kernel");
-        e->arena.release(xc); e->arena.release(ec); e->arena.release(cr); e->arena.release(tr);
         return FGDM_OK;
     });
 }
@@ -2112,14 +1986,13 @@ int fgdm_controlnet(fgdm_engine* e, int cn, const float* x, const int64_t* t, co
     if (!e || !x || !t || !ctx || !out) return FGDM_ERR_ARG;
     if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized");
     if (cn < 0 || cn >= (int)e->cns.size()) return e->fail(FGDM_ERR_ARG, "no such ControlNet");
-    return scoped_call(e, stream, [&]() -> int {
-        Tensor x4 = e->talloc(B, H, W, 4), ctx16 = e->talloc(B, 1, e->ctx_tokens, e->cfg.context_dim);
-        if (!x4.p || !ctx16.p) return e->fail(FGDM_ERR_NOMEM, "workspace");
+    return stream_call(e, stream, [&]() -> int {
+        fgdm_engine::Act x4, ctx16;
+        CHK(e->talloc(&x4, B, H, W, 4));
+        CHK(e->talloc(&ctx16, B, 1, e->ctx_tokens, e->cfg.context_dim));
         if (nchw_f32_to_nhwc_f16(x, x4.p, B, 4, H * W, 4, e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "layout kernel");
         if (f32_to_f16(ctx, ctx16.p, ctx16.numel(), e->s) != FGDM_OK) return e->fail(FGDM_ERR_HIP, "convert kernel");
-        const int rc = e->controlnet_fwd(e->cns[cn], x4, t, nullptr, ctx16, nullptr, nullptr, nullptr, false, out, out_capacity_floats);
-        e->tfree(x4); e->tfree(ctx16);
-        return rc;
+        return e->controlnet_fwd(e->cns[cn], x4, t, nullptr, ctx16, nullptr, nullptr, nullptr, false, out, out_capacity_floats);
     });
 }
 
@@ -2127,7 +2000,7 @@ int fgdm_run_block(fgdm_engine* e, const char* prefix, const float* x, int C, co
                    const float* ctx, int B, int H, int W, float* out, int64_t out_capacity_floats, int64_t* out_numel,
                    void* stream) {
     if (!e || !prefix || !x || !out) return FGDM_ERR_ARG;
-    return scoped_call(e, stream, [&] { return e->run_block(prefix, x, C, x_skip, Cs, emb, ctx, B, H, W, out, out_capacity_floats, out_numel); });
+    return stream_call(e, stream, [&] { return e->run_block(prefix, x, C, x_skip, Cs, emb, ctx, B, H, W, out, out_capacity_floats, out_numel); });
 }
 
 int fgdm_ddim_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float a_t, float a_prev,
@@ -2219,7 +2092,7 @@ static const char* walk_error(const Walk& p) {
     return log_steps_error(p.log_steps, p.n_log, p.S);
 }
 
-// The walk itself (inside the entry's scoped_call): per step one evaluation of the network on cat([x] * 2) (or x, CFG off), then
+// The walk itself (inside the entry's stream_call): per step one evaluation of the network on cat([x] * 2) (or x, CFG off), then
 // one launch of k_loop_step, which also does the NEXT step's blend and writes x into the network's input.  PLMS (plms.py:178-236)
 // differs in the three history planes, the probe and the second evaluation of the first step, and the mode / order of the launch.
 static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
@@ -2272,7 +2145,7 @@ static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
         a.io.log_x = L.log_plane(p.x_inter_out, slot); a.log_p0 = L.log_plane(p.pred_x0_out, slot);
         rc = loop_step(a, s);
     }
-    return L.end(rc);
+    return rc;
 }
 
 static Walk ddim_walk(const fgdm_ddim_params& known) {
@@ -2347,7 +2220,7 @@ static int run_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params& p, hipStream_t s) 
         a.m1 = k > 0 ? L.plane((k - 1) % 2) : nullptr;
         rc = dpmpp_loop_step(a, s);
     }
-    return L.end(rc);
+    return rc;
 }
 int fgdm_sample_dpmpp(fgdm_engine* e, const fgdm_dpmpp_params* caller, void* stream) {
     return loop_entry(e, caller, stream, FGDM_DPMPP_PARAMS_SIZE_V1, "fgdm_sample_dpmpp", "fgdm_dpmpp_params", true,
@@ -2402,7 +2275,7 @@ static int run_dpm_program(fgdm_engine* e, const fgdm_dpm_solver_params& p, hipS
         a.conv_x = p.conv_x[k]; a.conv_e = p.conv_e[k];
         rc = dpm_program_step(a, s);
     }
-    return L.end(rc);
+    return rc;
 }
 int fgdm_sample_dpm_solver(fgdm_engine* e, const fgdm_dpm_solver_params* caller, void* stream) {
     return loop_entry(e, caller, stream, FGDM_DPM_SOLVER_PARAMS_SIZE_V1, "fgdm_sample_dpm_solver", "fgdm_dpm_solver_params", true,
@@ -2447,7 +2320,7 @@ static int run_ancestral(fgdm_engine* e, const fgdm_ancestral_params& p, hipStre
         a.io.log_x = L.log_plane(p.x_inter_out, L.log_slot(i));
         rc = ancestral_loop_step(a, s);
     }
-    return L.end(rc);
+    return rc;
 }
 int fgdm_sample_ancestral(fgdm_engine* e, const fgdm_ancestral_params* caller, void* stream) {
     return loop_entry(e, caller, stream, FGDM_ANCESTRAL_PARAMS_SIZE_V1, "fgdm_sample_ancestral", "fgdm_ancestral_params", true,
@@ -2479,7 +2352,7 @@ static int run_ddim_encode(fgdm_engine* e, const fgdm_ddim_encode_params& p, hip
         a.io.log_x = L.log_plane(p.x_inter_out, L.log_slot(i));
         rc = invert_loop_step(a, s);
     }
-    return L.end(rc);
+    return rc;
 }
 int fgdm_ddim_encode(fgdm_engine* e, const fgdm_ddim_encode_params* caller, void* stream) {
     return loop_entry(e, caller, stream, FGDM_DDIM_ENCODE_PARAMS_SIZE_V1, "fgdm_ddim_encode", "fgdm_ddim_encode_params", true,
