@@ -991,197 +991,94 @@ __global__ __launch_bounds__(512) void attn_pp_kernel(const half_t* __restrict__
 // vector-ALU time (vector instructions of ANOTHER wave hardly enter a wave's MFMA shadows; instructions of the
 // SAME wave do), and 1.4x the algorithmic MFMAs.  Here one wave owns 64 queries as two independent 32-query STRANDS A and B, and its
 // instruction stream is written so that every MFMA of one strand is followed by softmax work of the other:
-//   * S^T = K Q^T stays on v_mfma_f32_32x32x16_f16 (keys on the rows, d = 40 -> 48 with the scale / running-max fold in slot 40),
-//     but O^T += V^T P^T runs on v_mfma_f32_16x16x32_f16: three 16-row tiles cover d = 40 (+ the ones row) instead of two 32-row
-//     tiles, 192 instead of 256 matrix cycles per 32 x 64 block.  The fp16 probabilities reach the B-operand layout of the 16-wide
-//     shape by FOUR v_permlane16_swap per 32 keys: lane n keeps the key groups of query n, lane n + 16 hands over its own in
-//     exchange -- and the K rows of a tile sit in LDS in the order that makes every lane group's eight keys CONTIGUOUS in V^T, so a
-//     V^T fragment is one ds_read_b128;
-//   * K / V^T tiles arrive by LDS-DMA (global_load_lds_dwordx4) into a ring of 64-key slots, two tiles ahead, one raw s_barrier
-//     per tile: no staging registers, no ds_write, no second barrier.  Both images are ROW-major like their sources (a wave
-//     instruction fetches whole rows), conflict-free for the fragment reads: K rows of 80 bytes (20 banks: sixteen consecutive rows
-//     tile the 64 banks), V^T rows of 128 bytes with their 16-byte pieces XOR-swizzled on the SOURCE side by (row >> 1) & 7;
-//     the constant pieces (K[:, 40] = 1, the ones row of V^T, zero padding) live in 48 bytes of LDS that the pad lanes read instead;
-//   * NW = 4 waves per workgroup (256 queries), two workgroups per CU: the two waves of a SIMD belong to different workgroups and
-//     drift apart instead of meeting at the same barrier; NW = 8: one workgroup of 512 queries per CU, half the L2 -> LDS bytes.
-// Needs T % (64 NW) == 0 and Tk % 64 == 0 (the self-attention shapes).
+//   * S^T = K Q^T runs on v_mfma_f32_32x32x16_f16 (keys on the rows; the contraction carries one slot more than d, d = 40 -> 48,
+//     for the scale / running-max fold: K[:, d] = 1, Q[:, d] = -max);
+//   * K / V^T tiles arrive by LDS-DMA (global_load_lds_dwordx4) into a ring of three 64-key slots, two tiles ahead, one raw
+//     s_barrier per tile: no staging registers, no ds_write, no second barrier.  Both images are ROW-major like their sources (a
+//     wave instruction fetches whole rows), conflict-free for the fragment reads: V^T rows of 128 bytes with their 16-byte pieces
+//     XOR-swizzled on the SOURCE side by (row >> 1) & 7, K rows of 16 d / 8 bytes (see KXOR / ROT in the kernel); the K pieces of the
+//     fold slot ([1 0 0 0 0 0 0 0], zeros) live in constant LDS pieces behind the ring that the pad lanes read instead;
+//   * the K rows of a tile sit in LDS in the order that makes the eight keys of a lane's slice of the B operand P^T CONTIGUOUS in
+//     V^T, so a V^T fragment is one ds_read_b128;
+//   * four waves per workgroup (ATT_TS_Q = 256 queries), two workgroups per CU at d = 40: the two waves of a SIMD belong to
+//     different workgroups and drift apart instead of meeting at the same barrier (eight waves, one workgroup of 512 queries per
+//     CU, would halve the L2 -> LDS bytes and lose that).
+// Needs T % ATT_TS_Q == 0 and Tk % 64 == 0 (the self-attention shapes).
+//
+// O^T += V^T P^T comes in two forms, the policy types Pv16 / Pv32 below; everything else stands once, in attn_two_strand_kernel.
+//   Pv16  v_mfma_f32_16x16x32_f16: three 16-row tiles cover d = 40 (+ the ones row) instead of two 32-row tiles, 192 instead of 256
+//         matrix cycles per 32 x 64 block.  The fp16 probabilities reach the B-operand layout of the 16-wide shape by FOUR
+//         v_permlane16_swap per 32 keys: lane n keeps the key groups of query n, lane n + 16 hands over its own in exchange.  The
+//         ones row of V^T and its zero padding are constant LDS pieces as well.  Reached under FGDM_ATTN_DQ=1 (d = 40 only).
+//   Pv32  v_mfma_f32_32x32x16_f16 again (after the ablations of the 16-wide form: the kernel's time is the SUM of its vector-ALU
+//         issue cycles and 8 issue cycles per MFMA -- the matrix pipe's own time hides in the shadows -- so what counts is the
+//         NUMBER of MFMAs and of vector instructions, not the matrix cycles): 8 MFMAs per 32 x 64 block instead of 12, no permlane
+//         swaps (the S^T accumulators, converted, ARE the B operand), O^T as two 32-row tiles (d = 40 -> 64, rows 41.. zero).  The
+//         constant rows of V^T (ones row, zero rows) are part of the LDS image (written once per slot; the DMA fills rows
+//         0 .. D - 1 only).  The default at d = 40, 64 and 80; d > 40 runs at one wave per SIMD (two strands need ~280 registers).
 __device__ __forceinline__ void att_dma16(unsigned voff, const void* sbase, unsigned lds_wave_addr) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_wave_addr) : "memory", "m0");
 }
 template <int N> __device__ __forceinline__ void att_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+constexpr int ATT_TS_Q = 256;      // queries per workgroup = its threads: four waves of 64 queries (two 32-query strands) each
 
-// ABL: ablation switches for tools/bench_attention.py (FGDM_ATTN_ABL; results are then meaningless): 1 = no exponentials,
-// 2 = no maximum / offset decision, 4 = no LDS-DMA after the first two tiles, 16 = no V^T P^T MFMAs, 32 = no K Q^T MFMAs
-template <int D, int NW, int ABL = 0>
-__global__ __launch_bounds__(NW * 64, 2) void attn_dq_kernel(const half_t* __restrict__ Q, int ldq,
-                                                         const half_t* __restrict__ K, int ldk,
-                                                         const half_t* __restrict__ Vt, int ldvt,
-                                                         half_t* __restrict__ O, int ldo,
-                                                         int H, int T, int Tk, float sl2e) {
-    constexpr int DP = (D + 16) / 16 * 16, NKS = DP / 16;    // contraction length of K Q^T incl. the fold slot; k-steps of 16
-    constexpr int DT = DP / 16;                              // 16-row tiles of O^T; row D carries the softmax denominator
-    constexpr int DC = D / 8;                                // 16-byte pieces per K row
-    constexpr int PS = D / 16, PH = (D % 16) / 8;            // fragment / lane half of contraction slot D
-    constexpr int KROW = DC * 16, KBYTES = 64 * KROW, VBYTES = D * 128, SLOT = KBYTES + VBYTES;
-    constexpr int NSLOT = 3;
-    constexpr int NDMA = SLOT / 1024, NI = (NDMA + NW - 1) / NW;   // 1 KiB LDS-DMA wave-instructions per tile; per wave
-    static_assert(KBYTES % 1024 == 0 && VBYTES % 1024 == 0 && NDMA >= NW, "whole wave-instructions per image");
-    static_assert((KROW / 4) % 8 == 4, "K row stride: 4 mod 8 dwords so that sixteen consecutive rows tile the banks");
-    __shared__ __attribute__((aligned(1024))) char smem[NSLOT * SLOT + 64];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n32 = lane & 31, h = lane >> 5;                // S^T layout: query on lane & 31, key half on lane >> 5
-    const int n16 = lane & 15, g = lane >> 4;                // O^T layout: query on lane & 15, row quad on lane >> 4
-    const int nqb = T / (NW * 64);
-    const int logical = att_logical_block();
-    const int qblk = logical % nqb, bh = logical / nqb;
-    const int b = bh / H, head = bh - b * H;
-    const int q0w = qblk * (NW * 64) + wave * 64;                  // first query of this wave; strand X: q0w + 32 X + [0, 32)
-    const int nt = Tk >> 6;
-
+// A V^T P^T form carries: DT (O^T tiles), VBYTES (V^T bytes per slot), MIN_BLOCKS (workgroups per CU for __launch_bounds__), C_ZERO
+// (offset of the zero piece among the constants), key_of_row (the K row order inside a 32-key sub-tile), init_lds (the constant parts
+// of the LDS image), its fragments (V^T, packed probabilities, O^T) with rd_v / pack / mma / rescale / store, and the schedule facts
+// of a tile: the NRD V^T fragment reads in the order they are issued, the first RD_B of them between the MFMAs of stage (b) and the
+// rest from the second sub-tile of stage (c) on, and the V^T P^T steps of stage (d) (NPV per 32-key sub-tile and strand) at which
+// strand B's two max_part calls and its att_max_cross run.
+template <int D>
+struct Pv16 {
+    static constexpr int DT = (D + 16) / 16;                 // 16-row tiles of O^T; row D carries the softmax denominator
+    static constexpr int VBYTES = D * 128, MIN_BLOCKS = 2, C_ZERO = 32;
+    static constexpr int NPV = DT * 2, NRD = DT * 2, RD_B = NRD;
+    static constexpr int MAXB0 = 1, MAXB1 = 3, MAXBX = 4;
+    static_assert(((D / 8 * 16) / 4) % 8 == 4, "K rows unswizzled (nothing instantiates the 16-wide form beyond d = 40)");
+    // LDS row rho = 8 a + 4 b + c holds key 16 b + 4 a + c, so that the keys whose probabilities end up in lane group g of the
+    // 16-wide B operand (after the permlane16 swaps) are keys 8 g .. 8 g + 7
+    static __device__ __forceinline__ int key_of_row(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
     // constant pieces: [1 0 0 0 0 0 0 0] (K[:, D] of the fold), eight ones (row D of V^T), zeros
-    char* const cst = smem + NSLOT * SLOT;
-    if (tid < 3) {
-        h8 v = (h8)(half_t)0;
-        if (tid == 0) v[0] = (half_t)1;
-        if (tid == 1) v = (h8)(half_t)1;
-        *(h8*)(cst + tid * 16) = v;
-    }
-
-    // ---- LDS-DMA plan of this wave: wave-instruction j = wave + 4 u of a tile (a surplus one repeats the wave's previous piece:
-    // same bytes to the same address).  K piece L = 64 j + lane: LDS row L / DC (row order below), 16-byte piece L % DC;
-    // V^T piece L: row L / 8, LDS position L % 8 holds source piece (L % 8) ^ ((row >> 1) & 7).
-    // K row order inside a 32-key sub-tile: LDS row rho = 8 a + 4 b + c holds key 16 b + 4 a + c, so that the keys whose
-    // probabilities end up in lane group g of the 16-wide B operand (after the permlane16 swaps) are keys 8 g .. 8 g + 7.
-    const half_t* Kb = K + (size_t)b * Tk * ldk + head * D;
-    const half_t* Vb = Vt + ((size_t)b * H + head) * D * ldvt;
-    unsigned voff[NI], ldst[NI];
-    bool isk[NI];
-#pragma unroll
-    for (int u = 0; u < NI; ++u) {
-        int j = wave + NW * u;
-        if (j >= NDMA) j -= NW;
-        isk[u] = j < DC * 64 * 16 / 1024;
-        ldst[u] = (unsigned)j * 1024u;
-        if (isk[u]) {
-            const int L = 64 * j + lane, rp = L / DC, c = L - rp * DC;
-            const int rho = rp & 31, key = (rp & 32) + 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3);
-            voff[u] = (unsigned)(key * ldk + c * 8) * 2u;
-        } else {
-            const int L = 64 * (j - KBYTES / 1024) + lane, d = L >> 3, x = L & 7;
-            voff[u] = (unsigned)(d * ldvt + ((x ^ ((d >> 1) & 7)) * 8)) * 2u;
+    static __device__ __forceinline__ void init_lds(char* smem, char* cst, int slots, int slot_bytes, int kbytes, int tid) {
+        if (tid < 3) {
+            h8 v = (h8)(half_t)0;
+            if (tid == 0) v[0] = (half_t)1;
+            if (tid == 1) v = (h8)(half_t)1;
+            *(h8*)(cst + tid * 16) = v;
         }
     }
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)smem;
-    auto issue = [&](int t, auto slotc) {                    // tile t -> slot t % NSLOT
-        const char* kb = (const char*)(Kb + (size_t)t * 64 * ldk);
-        const char* vb = (const char*)(Vb + t * 64);
-        const unsigned base = lds0 + (unsigned)decltype(slotc)::value * SLOT;
-#pragma unroll
-        for (int u = 0; u < NI; ++u) att_dma16(voff[u], isk[u] ? kb : vb, base + ldst[u]);
-    };
-    issue(0, std::integral_constant<int, 0>{});
-    if (nt > 1) issue(1, std::integral_constant<int, 1>{});
 
-    // ---- Q^T fragments (B operand of K Q^T), pre-scaled; slot D will carry -max
-    h8 qf[2][NKS];
-#pragma unroll
-    for (int X = 0; X < 2; ++X)
-#pragma unroll
-        for (int s = 0; s < NKS; ++s) {
-            const int c = 16 * s + 8 * h;
-            qf[X][s] = (h8)(half_t)0;
-            if (c < D) qf[X][s] = *(const h8*)(Q + ((size_t)b * T + q0w + 32 * X + n32) * ldq + head * D + c);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qf[X][s][e] = (half_t)((float)qf[X][s][e] * sl2e);
-        }
+    int n16, g;                                              // O^T layout: query on lane & 15, row quad on lane >> 4
+    int v_lane[2];                                           // V^T: row 16 t + n16, source piece 4 sub + g at position (4 sub + g) ^ ((n16 >> 1) & 7)
+    const char* c_ones, *c_zero;
+    h8 vf[DT][2], pb[2][2][2];
     f32x4 oacc[2][DT][2];
+    __device__ __forceinline__ Pv16(int lane, int kbytes, const char* cst) : n16(lane & 15), g(lane >> 4), c_ones(cst + 16), c_zero(cst + C_ZERO) {
 #pragma unroll
-    for (int X = 0; X < 2; ++X)
+        for (int X = 0; X < 2; ++X)
 #pragma unroll
-        for (int t = 0; t < DT; ++t)
+            for (int t = 0; t < DT; ++t)
 #pragma unroll
-            for (int qg = 0; qg < 2; ++qg) oacc[X][t][qg] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run[2] = {0.f, 0.f};
-
-    // ---- fragment addresses inside a slot.  K: row (32 sub + n32), piece 2 s + h -> immediate offsets 2560 sub + 32 s;
-    // pieces >= DC are the constants.  V^T: row 16 t + n16, source piece 4 sub + g at position (4 sub + g) ^ ((n16 >> 1) & 7).
-    const int k_lane = n32 * KROW + h * 16;
-    const int v_lane0 = KBYTES + n16 * 128 + ((g ^ ((n16 >> 1) & 7)) * 16);
-    const int v_lane1 = KBYTES + n16 * 128 + (((4 + g) ^ ((n16 >> 1) & 7)) * 16);
-    const char* const c_one = cst, *const c_ones = cst + 16, *const c_zero = cst + 32;
-
-    f32x16 sacc[2][2];
-    h8 kf[2][NKS], vf[DT][2], pb[2][2][2];
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    auto rd_k = [&](const char* sl, int sub, int s) {
-        const int ci0 = 2 * s;                               // piece index of lane half 0; half 1 reads ci0 + 1
-        const char* p = sl + k_lane + sub * 32 * KROW + s * 32;
-        if (ci0 + 1 >= DC) {                                 // some lanes read a constant piece
-            const char* cp0 = ci0 < DC ? p : (ci0 == DC ? c_one : c_zero);
-            const char* cp1 = ci0 + 1 == DC ? c_one : c_zero;
-            p = h ? cp1 : cp0;
-        }
-        kf[sub][s] = *(const h8*)p;
-    };
-    auto rd_v = [&](const char* sl, int t, int sub) {
-        const char* p = sl + (sub ? v_lane1 : v_lane0) + t * 16 * 128;
+                for (int qg = 0; qg < 2; ++qg) oacc[X][t][qg] = f32x4{0.f, 0.f, 0.f, 0.f};
+        v_lane[0] = kbytes + n16 * 128 + ((g ^ ((n16 >> 1) & 7)) * 16);
+        v_lane[1] = kbytes + n16 * 128 + (((4 + g) ^ ((n16 >> 1) & 7)) * 16);
+    }
+    __device__ __forceinline__ void rd_v(const char* sl, int n) {
+        const int t = n % DT, sub = n / DT;
+        const char* p = sl + v_lane[sub] + t * 16 * 128;
         if (16 * t + 15 >= D) {                              // rows >= D of the last tile: the ones row, then zeros
             const int d = 16 * t + n16;
             p = d < D ? p : (d == D ? c_ones : c_zero);
         }
         vf[t][sub] = *(const h8*)p;
-    };
-    auto qk = [&](int X, int sub, int s) {
-        if constexpr ((ABL & 32) != 0) { if (s == 0) asm volatile("" : "=v"(sacc[X][sub])); return; }
-        sacc[X][sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[sub][s], qf[X][s], s == 0 ? zero16 : sacc[X][sub], 0, 0, 0);
-    };
-    auto pv = [&](int X, int sub, int t, int qg) {
-        if constexpr ((ABL & 16) != 0) { asm volatile("" : "+v"(oacc[X][t][qg]) : "v"(vf[t][sub]), "v"(pb[X][sub][qg])); return; }
-        oacc[X][t][qg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[t][sub], pb[X][sub][qg], oacc[X][t][qg], 0, 0, 0);
-    };
-    auto max_part = [&](int X, int sub, float mx) {          // 8 v_max3 over one sub-tile's 16 scores of this lane
-        if constexpr ((ABL & 2) != 0) return mx;
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) mx = fmaxf(fmaxf(mx, sacc[X][sub][r]), sacc[X][sub][r + 1]);
-        return mx;
-    };
-    // the offset moves only when some query of the strand outgrew it by more than 2^ATT_THR (or on the first tile)
-    auto decide = [&](int X, float mx, bool first) {
-        if constexpr ((ABL & 2) != 0) return;
-        if (first || !__all(mx <= ATT_THR)) {
-            const float m_new = first ? mx : m_run[X] + fmaxf(mx, 0.f);
-            const float m_hat = (float)(half_t)m_new;        // exactly what Q[q][D] can hold
-            const float delta = m_run[X] - m_hat;
-            m_run[X] = m_hat;
-            if (!first) {
-                const float alpha = __builtin_amdgcn_exp2f(delta);
-#pragma unroll
-                for (int qg = 0; qg < 2; ++qg) {             // O^T keeps query 16 qg + n16 on this lane: fetch ITS factor
-                    const float aq = __shfl(alpha, 16 * qg + n16);
-#pragma unroll
-                    for (int t = 0; t < DT; ++t) oacc[X][t][qg] *= aq;
-                }
-            }
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc[X][sub][r] += delta;   // this tile was taken against the old offset
-            if (h == PH) qf[X][PS][0] = (half_t)(-m_hat);
-        }
-    };
-    auto expo = [&](int X, int sub, int r0, int r1) {
-#pragma unroll
-        for (int r = r0; r < r1; ++r) sacc[X][sub][r] = (ABL & 1) ? sacc[X][sub][r] : __builtin_amdgcn_exp2f(sacc[X][sub][r]);
-    };
+    }
     // fp16 probabilities of one 32-key sub-tile -> the two B operands (queries 0-15 / 16-31 of the strand) of the 16-wide MFMA
-    auto pack = [&](int X, int sub) {
+    __device__ __forceinline__ void pack(int X, int sub, const f32x16& s) {
         unsigned pk[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const h2 t2 = {(half_t)sacc[X][sub][2 * i], (half_t)sacc[X][sub][2 * i + 1]};
+            const h2 t2 = {(half_t)s[2 * i], (half_t)s[2 * i + 1]};
             pk[i] = __builtin_bit_cast(unsigned, t2);
         }
         u32x4 lo, hi;
@@ -1192,148 +1089,150 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_dq_kernel(const half_t* __res
         }
         pb[X][sub][0] = __builtin_bit_cast(h8, lo);
         pb[X][sub][1] = __builtin_bit_cast(h8, hi);
-    };
-
-    // one tile; the ring slot is a compile-time constant (the loop below is unrolled over the slots), so every fragment address is
-    // a loop-invariant register plus an immediate
-    auto tile = [&](int kt, auto slotc) {
-        constexpr int slot = decltype(slotc)::value;
-        // my pieces of tile kt landed (tile kt + 1 may fly), then everybody's: one barrier per tile; behind it nobody reads the
-        // slot that tile kt + 2 goes to (the one of tile kt - 1) any more
-        if (!(ABL & 4) && kt + 1 < nt) att_wait_vmcnt<NI>(); else att_wait_vmcnt<0>();
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_s_barrier();
-        if (!(ABL & 4) && kt + 2 < nt) issue(kt + 2, std::integral_constant<int, (slot + 2) % NSLOT>{});
-        const char* sl = smem + slot * SLOT;
-        const bool first = kt == 0;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int s = 0; s < NKS; ++s) rd_k(sl, sub, s);
-        ATT_SB();
-        // (b) K Q^T of strand A; the V^T fragments of the tile are requested between its MFMAs
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int s = 0; s < NKS; ++s) {
-                qk(0, sub, s);
-                if (sub * NKS + s < DT * 2) rd_v(sl, (sub * NKS + s) % DT, (sub * NKS + s) / DT);
-                ATT_SB();
-            }
-        // (c) K Q^T of strand B  |  strand A: maximum, decision, exp and pack of its first 32 keys
-        float mx = sacc[0][0][0];                   // (sub-tile 0 first: its MFMAs retired three MFMAs ago)
-        qk(1, 0, 0); mx = max_part(0, 0, mx); ATT_SB();
-        qk(1, 0, 1); mx = max_part(0, 1, mx); ATT_SB();
-        qk(1, 0, 2 % NKS); mx = att_max_cross(mx); ATT_SB();
-#pragma unroll
-        for (int s = 3; s < NKS; ++s) { qk(1, 0, s); ATT_SB(); }
-        decide(0, mx, first);
-        ATT_SB();
-#pragma unroll
-        for (int s = 0; s < NKS; ++s) {
-            qk(1, 1, s);
-            expo(0, 0, 16 * s / NKS, 16 * (s + 1) / NKS);
-            ATT_SB();
-        }
-        pack(0, 0);
-        ATT_SB();
-        // (d) V^T P^T of strand A, first 32 keys  |  strand A: exp of its second 32 keys; strand B: maximum
-        float mxb = sacc[1][0][0];
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int qg = 0; qg < 2; ++qg) {
-                const int i = t * 2 + qg, n = DT * 2;
-                pv(0, 0, t, qg);
-                expo(0, 1, 16 * i / n, 16 * (i + 1) / n);
-                if (i == 1) mxb = max_part(1, 0, mxb);
-                if (i == 3) mxb = max_part(1, 1, mxb);
-                if (i == 4) mxb = att_max_cross(mxb);
-                ATT_SB();
-            }
-        pack(0, 1);
-        ATT_SB();
-        decide(1, mxb, first);
-        ATT_SB();
-        // (e) V^T P^T of strand A, second 32 keys  |  strand B: exp and pack of its first 32 keys
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int qg = 0; qg < 2; ++qg) {
-                const int i = t * 2 + qg, n = DT * 2;
-                pv(0, 1, t, qg);
-                expo(1, 0, 16 * i / n, 16 * (i + 1) / n);
-                ATT_SB();
-            }
-        pack(1, 0);
-        ATT_SB();
-        // (f) V^T P^T of strand B, first 32 keys  |  strand B: exp and pack of its second 32 keys
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int qg = 0; qg < 2; ++qg) {
-                const int i = t * 2 + qg, n = DT * 2;
-                pv(1, 0, t, qg);
-                expo(1, 1, 16 * i / n, 16 * (i + 1) / n);
-                ATT_SB();
-            }
-        pack(1, 1);
-        ATT_SB();
-        // (g) V^T P^T of strand B, second 32 keys
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int qg = 0; qg < 2; ++qg) pv(1, 1, t, qg);
-        ATT_SB();
-    };
-    for (int kt = 0; kt < nt; kt += NSLOT) {
-        tile(kt, std::integral_constant<int, 0>{});
-        if (kt + 1 < nt) tile(kt + 1, std::integral_constant<int, 1>{});
-        if (kt + 2 < nt) tile(kt + 2, std::integral_constant<int, 2>{});
     }
-
-    // ---- O = O^T / l: row D of O^T (tile D / 16, row D % 16: lane group (D % 16) / 4, register D % 4) is the denominator
-    constexpr int LT = D / 16, LG = (D % 16) / 4, LR = D % 4;
+    template <bool OFF>                                      // OFF: the ablation without V^T P^T MFMAs
+    __device__ __forceinline__ void mma(int X, int sub, int i) {
+        const int t = i / 2, qg = i & 1;
+        if constexpr (OFF) { asm volatile("" : "+v"(oacc[X][t][qg]) : "v"(vf[t][sub]), "v"(pb[X][sub][qg])); return; }
+        oacc[X][t][qg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[t][sub], pb[X][sub][qg], oacc[X][t][qg], 0, 0, 0);
+    }
+    __device__ __forceinline__ void rescale(int X, float alpha) {
 #pragma unroll
-    for (int X = 0; X < 2; ++X)
+        for (int qg = 0; qg < 2; ++qg) {                     // O^T keeps query 16 qg + n16 on this lane: fetch ITS factor
+            const float aq = __shfl(alpha, 16 * qg + n16);
 #pragma unroll
-        for (int qg = 0; qg < 2; ++qg) {
-            const float l = __shfl(oacc[X][LT][qg][LR], 16 * LG + n16);
-            const float inv = 1.0f / l;
-            half_t* op = O + ((size_t)b * T + q0w + 32 * X + 16 * qg + n16) * ldo + head * D;
+            for (int t = 0; t < DT; ++t) oacc[X][t][qg] *= aq;
+        }
+    }
+    // O = O^T / l: row D of O^T (tile D / 16, row D % 16: lane group (D % 16) / 4, register D % 4) is the denominator
+    __device__ __forceinline__ void store(half_t* __restrict__ O, int ldo, size_t row0, int col0) {
+        constexpr int LT = D / 16, LG = (D % 16) / 4, LR = D % 4;
 #pragma unroll
-            for (int t = 0; t < DT; ++t) {
-                const int dd = 16 * t + 4 * g;
-                if (dd < D) {
-                    const h4 o4 = {(half_t)(oacc[X][t][qg][0] * inv), (half_t)(oacc[X][t][qg][1] * inv),
-                                   (half_t)(oacc[X][t][qg][2] * inv), (half_t)(oacc[X][t][qg][3] * inv)};
-                    *(h4*)(op + dd) = o4;
+        for (int X = 0; X < 2; ++X)
+#pragma unroll
+            for (int qg = 0; qg < 2; ++qg) {
+                const float l = __shfl(oacc[X][LT][qg][LR], 16 * LG + n16);
+                const float inv = 1.0f / l;
+                half_t* op = O + (row0 + 32 * X + 16 * qg + n16) * ldo + col0;
+#pragma unroll
+                for (int t = 0; t < DT; ++t) {
+                    const int dd = 16 * t + 4 * g;
+                    if (dd < D) {
+                        const h4 o4 = {(half_t)(oacc[X][t][qg][0] * inv), (half_t)(oacc[X][t][qg][1] * inv),
+                                       (half_t)(oacc[X][t][qg][2] * inv), (half_t)(oacc[X][t][qg][3] * inv)};
+                        *(h4*)(op + dd) = o4;
+                    }
                 }
             }
-        }
-}
+    }
+};
 
-// The same two-strand structure with V^T P^T back on v_mfma_f32_32x32x16_f16 (round 4, after the ablations of the kernel above:
-// its time is the SUM of its vector-ALU issue cycles and 8 issue cycles per MFMA -- the matrix pipe's own time hides in the
-// shadows -- so what counts is the NUMBER of MFMAs and of vector instructions, not the matrix cycles): 8 MFMAs per 32 x 64 block
-// instead of 12, no permlane swaps (the S^T accumulators, converted, ARE the B operand), O^T as two 32-row tiles (d = 40 -> 64,
-// rows 41.. zero).  K rows sit in LDS in the order that makes the eight keys of a lane's B-operand slice contiguous in V^T, so a
-// V^T fragment is again one ds_read_b128.  The constant rows of V^T (ones row, zero rows) are part of the LDS image (written once
-// per slot; the DMA fills rows 0 .. D - 1 only), so only the K fragment of the fold slot needs a per-lane address.
-template <int D, int NW, int ABL = 0>
-__global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(const half_t* __restrict__ Q, int ldq,
-                                                           const half_t* __restrict__ K, int ldk,
-                                                           const half_t* __restrict__ Vt, int ldvt,
-                                                           half_t* __restrict__ O, int ldo,
-                                                           int H, int T, int Tk, float sl2e) {
+template <int D>
+struct Pv32 {
+    static constexpr int DT = (D + 32) / 32;                 // 32-row tiles of O^T; row D carries the softmax denominator
+    static constexpr int VBYTES = DT * 32 * 128, MIN_BLOCKS = D <= 40 ? 2 : 1, C_ZERO = 16;
+    static constexpr int NPV = DT * 2, NRD = 2 * NPV, RD_B = NPV;      // the fragments of the first 32 keys in stage (b), the others in (c)
+    static constexpr int MAXB0 = NPV - 3, MAXB1 = NPV - 2, MAXBX = NPV - 1;
+    // LDS row rho = 8 a + 4 b + c holds key 16 (a >> 1) + 8 b + 4 (a & 1) + c: lane half b of the B operand of k-step s2 = a >> 1
+    // holds the probabilities of LDS rows {8 (2 s2) + 4 b + c, 8 (2 s2 + 1) + 4 b + c}, i.e. of keys 16 s2 + 8 b + [0, 8)
+    static __device__ __forceinline__ int key_of_row(int rho) {
+        const int a = rho >> 3;
+        return 16 * (a >> 1) + 8 * ((rho >> 2) & 1) + 4 * (a & 1) + (rho & 3);
+    }
+    // constant parts of the LDS image: rows D .. 32 DT - 1 of every slot's V^T (row D = ones), and [1 0 0 0 0 0 0 0] / zeros for
+    // the fold slot of K
+    static __device__ __forceinline__ void init_lds(char* smem, char* cst, int slots, int slot_bytes, int kbytes, int tid) {
+        if (tid < 2) {
+            h8 v = (h8)(half_t)0;
+            if (tid == 0) v[0] = (half_t)1;
+            *(h8*)(cst + tid * 16) = v;
+        }
+        for (int i = tid; i < slots * (DT * 32 - D) * 8; i += ATT_TS_Q) {
+            const int sl_i = i / ((DT * 32 - D) * 8), rem = i - sl_i * ((DT * 32 - D) * 8), row = D + rem / 8, pc = rem & 7;
+            *(h8*)(smem + sl_i * slot_bytes + kbytes + row * 128 + pc * 16) = row == D ? (h8)(half_t)1 : (h8)(half_t)0;
+        }
+    }
+
+    int n32, h;                                              // query (O^T) / row (fragments) on lane & 31, half on lane >> 5
+    int v_lane[2][2];                                        // V^T: row 32 t + n32, source piece 4 sub + 2 s2 + h at position (that) ^ ((n32 >> 1) & 7)
+    h8 vf[DT][2][2], pf[2][2][2];
+    f32x16 oacc[2][DT];
+    __device__ __forceinline__ Pv32(int lane, int kbytes, const char* cst) : n32(lane & 31), h(lane >> 5) {
+#pragma unroll
+        for (int X = 0; X < 2; ++X)
+#pragma unroll
+            for (int t = 0; t < DT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) oacc[X][t][r] = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) v_lane[sub][s2] = kbytes + n32 * 128 + (((4 * sub + 2 * s2 + h) ^ ((n32 >> 1) & 7)) * 16);
+    }
+    __device__ __forceinline__ void rd_v(const char* sl, int n) {
+        const int sub = n / NPV, t = (n % NPV) / 2, s2 = n & 1;
+        vf[t][sub][s2] = *(const h8*)(sl + v_lane[sub][s2] + t * 32 * 128);
+    }
+    __device__ __forceinline__ void pack(int X, int sub, const f32x16& s) {      // registers 8 s2 .. 8 s2 + 7 are k-step s2's B operand
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) pf[X][sub][s2][e] = (half_t)s[8 * s2 + e];
+    }
+    template <bool OFF>
+    __device__ __forceinline__ void mma(int X, int sub, int i) {
+        const int t = i / 2, s2 = i & 1;
+        if constexpr (OFF) { asm volatile("" : "+v"(oacc[X][t]) : "v"(vf[t][sub][s2]), "v"(pf[X][sub][s2])); return; }
+        oacc[X][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[t][sub][s2], pf[X][sub][s2], oacc[X][t], 0, 0, 0);
+    }
+    __device__ __forceinline__ void rescale(int X, float alpha) {
+#pragma unroll
+        for (int t = 0; t < DT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) oacc[X][t][r] *= alpha;
+    }
+    // O = O^T / l: row D of O^T lives in tile D / 32, register ((D % 32) & 3) + 4 ((D % 32) >> 3) of the half with 4 h == (D % 32) & 4
+    __device__ __forceinline__ void store(half_t* __restrict__ O, int ldo, size_t row0, int col0) {
+        constexpr int rr = D % 32, reg = (rr & 3) + 4 * (rr >> 3), owner_half = (rr >> 2) & 1;
+#pragma unroll
+        for (int X = 0; X < 2; ++X) {
+            const float mine = oacc[X][D / 32][reg];
+            const float other = __shfl_xor(mine, 32);
+            const float inv = 1.0f / (h == owner_half ? mine : other);
+            half_t* op = O + (row0 + 32 * X + n32) * ldo + col0;
+#pragma unroll
+            for (int t = 0; t < DT; ++t)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const int dd = t * 32 + 8 * g4 + 4 * h;
+                    if (dd < D) {
+                        const h4 o4 = {(half_t)(oacc[X][t][4 * g4] * inv), (half_t)(oacc[X][t][4 * g4 + 1] * inv),
+                                       (half_t)(oacc[X][t][4 * g4 + 2] * inv), (half_t)(oacc[X][t][4 * g4 + 3] * inv)};
+                        *(h4*)(op + dd) = o4;
+                    }
+                }
+        }
+    }
+};
+
+// ABL: ablation switches for tools/bench_attention.py (FGDM_ATTN_ABL; results are then meaningless): 1 = no exponentials,
+// 2 = no maximum / offset decision, 4 = no LDS-DMA after the first two tiles, 16 = no V^T P^T MFMAs, 32 = no K Q^T MFMAs
+template <int D, class PV, int ABL = 0>
+__global__ __launch_bounds__(ATT_TS_Q, PV::MIN_BLOCKS) void attn_two_strand_kernel(const half_t* __restrict__ Q, int ldq,
+                                                                                 const half_t* __restrict__ K, int ldk,
+                                                                                 const half_t* __restrict__ Vt, int ldvt,
+                                                                                 half_t* __restrict__ O, int ldo,
+                                                                                 int H, int T, int Tk, float sl2e) {
+    constexpr int NW = ATT_TS_Q / 64;                        // waves
     constexpr int DP = (D + 16) / 16 * 16, NKS = DP / 16;    // contraction length of K Q^T incl. the fold slot; k-steps of 16
-    constexpr int DT = (D + 32) / 32;                        // 32-row tiles of O^T; row D carries the softmax denominator
     constexpr int DC = D / 8;                                // 16-byte pieces per K row
     constexpr int PS = D / 16, PH = (D % 16) / 8;            // fragment / lane half of contraction slot D
-    constexpr int KROW = DC * 16, KBYTES = 64 * KROW, VDATA = D * 128, VBYTES = DT * 32 * 128, SLOT = KBYTES + VBYTES;
+    constexpr int KROW = DC * 16, KBYTES = 64 * KROW, VDATA = D * 128, SLOT = KBYTES + PV::VBYTES;
     constexpr int NSLOT = 3;
     constexpr int NDMA = (KBYTES + VDATA) / 1024, NI = (NDMA + NW - 1) / NW;   // 1 KiB LDS-DMA wave-instructions per tile; per wave
+    constexpr int NPV = PV::NPV;                             // V^T P^T MFMAs per 32-key sub-tile and strand
     static_assert(KBYTES % 1024 == 0 && VDATA % 1024 == 0 && NDMA >= NW, "whole wave-instructions per image");
+    static_assert(PV::RD_B <= 2 * NKS && PV::MAXBX < NPV, "the schedule facts fit the stages they ride in");
     // K row stride: 4 mod 8 dwords makes sixteen consecutive rows tile the banks (d = 40: 80-byte rows).  d = 80 (160-byte rows: rows
     // r and r + 8 would meet in the same banks): the 16-byte pieces of rows with (r >> 3) & 1 are ROTATED by ROT = 5 positions,
     // half a row, on the source side -- sixteen consecutive rows then tile the banks again
@@ -1346,30 +1245,21 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n32 = lane & 31, h = lane >> 5;                // query (S^T, O^T) / row (fragments) on lane & 31, half on lane >> 5
-    const int nqb = T / (NW * 64);
+    const int n32 = lane & 31, h = lane >> 5;                // S^T layout: query on lane & 31, key half on lane >> 5
+    const int nqb = T / ATT_TS_Q;
     const int logical = att_logical_block();
     const int qblk = logical % nqb, bh = logical / nqb;
     const int b = bh / H, head = bh - b * H;
-    const int q0w = qblk * (NW * 64) + wave * 64;            // first query of this wave; strand X: q0w + 32 X + [0, 32)
+    const int q0w = qblk * ATT_TS_Q + wave * 64;             // first query of this wave; strand X: q0w + 32 X + [0, 32)
     const int nt = Tk >> 6;
 
-    // constant parts of the LDS image: rows D .. 32 DT - 1 of every slot's V^T (row D = ones), and [1 0 0 0 0 0 0 0] / zeros for
-    // the fold slot of K
     char* const cst = smem + NSLOT * SLOT;
-    if (tid < 2) {
-        h8 v = (h8)(half_t)0;
-        if (tid == 0) v[0] = (half_t)1;
-        *(h8*)(cst + tid * 16) = v;
-    }
-    for (int i = tid; i < NSLOT * (DT * 32 - D) * 8; i += NW * 64) {
-        const int sl_i = i / ((DT * 32 - D) * 8), rem = i - sl_i * ((DT * 32 - D) * 8), row = D + rem / 8, pc = rem & 7;
-        *(h8*)(smem + sl_i * SLOT + KBYTES + row * 128 + pc * 16) = row == D ? (h8)(half_t)1 : (h8)(half_t)0;
-    }
+    PV::init_lds(smem, cst, NSLOT, SLOT, KBYTES, tid);
 
-    // ---- LDS-DMA plan of this wave (see the kernel above).  K row order inside a 32-key sub-tile: LDS row rho = 8 a + 4 b + c
-    // holds key 16 (a >> 1) + 8 b + 4 (a & 1) + c: lane half b of the B operand of k-step s2 = a >> 1 holds the probabilities of
-    // LDS rows {8 (2 s2) + 4 b + c, 8 (2 s2 + 1) + 4 b + c}, i.e. of keys 16 s2 + 8 b + [0, 8)
+    // ---- LDS-DMA plan of this wave: wave-instruction j = wave + 4 u of a tile (a surplus one repeats the wave's previous piece:
+    // same bytes to the same address).  K piece L = 64 j + lane: LDS row L / DC (row order inside a 32-key sub-tile:
+    // PV::key_of_row), position L % DC (which source piece it holds: KXOR / ROT); V^T piece L: row L / 8, LDS position L % 8 holds
+    // source piece (L % 8) ^ ((row >> 1) & 7).
     const half_t* Kb = K + (size_t)b * Tk * ldk + head * D;
     const half_t* Vb = Vt + ((size_t)b * H + head) * D * ldvt;
     unsigned voff[NI], ldst[NI];
@@ -1382,9 +1272,8 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
         ldst[u] = (unsigned)j * 1024u;
         if (isk[u]) {
             const int L = 64 * j + lane, rp = L / DC, c = L - rp * DC;
-            const int rho = rp & 31, a = rho >> 3;
-            const int key = (rp & 32) + 16 * (a >> 1) + 8 * ((rho >> 2) & 1) + 4 * (a & 1) + (rho & 3);
-            const int cs = KXOR ? (c ^ ((rho >> 1) & 7)) : (c + DC - ROT * ((rho >> 3) & 1)) % DC;      // LDS position c of this row holds source piece cs
+            const int rho = rp & 31, key = (rp & 32) + PV::key_of_row(rho);
+            const int cs = KXOR ? (c ^ ((rho >> 1) & 7)) : ROT ? (c + DC - ROT * ((rho >> 3) & 1)) % DC : c;      // LDS position c of this row holds source piece cs
             voff[u] = (unsigned)(key * ldk + cs * 8) * 2u;
         } else {
             const int L = 64 * (j - KBYTES / 1024) + lane, d = L >> 3, x = L & 7;
@@ -1414,30 +1303,21 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
 #pragma unroll
             for (int e = 0; e < 8; ++e) qf[X][s][e] = (half_t)((float)qf[X][s][e] * sl2e);
         }
-    f32x16 oacc[2][DT];
-#pragma unroll
-    for (int X = 0; X < 2; ++X)
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[X][t][r] = 0.f;
+    PV pv(lane, KBYTES, cst);                                // O^T = 0; V^T fragment addresses inside a slot (the V^T image follows the K image)
     float m_run[2] = {0.f, 0.f};
 
-    // ---- fragment addresses inside a slot.  K: row (32 sub + n32), piece 2 s + h -> immediate offsets 32 KROW sub + 32 s;
-    // pieces >= DC are the constants.  V^T: row 32 t + n32, source piece 4 sub + 2 s2 + h at position (that) ^ ((n32 >> 1) & 7).
-    int k_lane[NKS];                                         // byte offset of piece 2 s + h in this lane's row (rotated rows: see ROT)
+    // ---- K fragment addresses inside a slot: row (32 sub + n32), piece 2 s + h (swizzled: KXOR / ROT) -> immediate offsets
+    // 32 KROW sub; pieces >= DC are the constants (the fold slot's k_lane is never used)
+    int k_lane[NKS];
 #pragma unroll
-    for (int s2 = 0; s2 < NKS; ++s2)      // (the fold slot's pieces, 2 s2 + h >= DC, are the constants: its k_lane is never used)
-        k_lane[s2] = n32 * KROW + (KXOR ? ((2 * s2 + h) & 7) ^ ((n32 >> 1) & 7) : (2 * s2 + h + ROT * ((n32 >> 3) & 1)) % DC) * 16;
-    int v_lane[2][2];
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) v_lane[sub][s2] = KBYTES + n32 * 128 + (((4 * sub + 2 * s2 + h) ^ ((n32 >> 1) & 7)) * 16);
-    const char* const c_one = cst, *const c_zero = cst + 16;
+    for (int s2 = 0; s2 < NKS; ++s2)
+        k_lane[s2] = KXOR  ? n32 * KROW + (((2 * s2 + h) & 7) ^ ((n32 >> 1) & 7)) * 16
+                     : ROT ? n32 * KROW + ((2 * s2 + h + ROT * ((n32 >> 3) & 1)) % DC) * 16
+                           : n32 * KROW + h * 16 + s2 * 32;      // unswizzled: one register, the k-step is an immediate
+    const char* const c_one = cst, *const c_zero = cst + PV::C_ZERO;
 
     f32x16 sacc[2][2];
-    h8 kf[2][NKS], vf[DT][2][2], pf[2][2][2];
+    h8 kf[2][NKS];
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     auto rd_k = [&](const char* sl, int sub, int s) {
         const int ci0 = 2 * s;                               // piece index of lane half 0; half 1 reads ci0 + 1
@@ -1449,21 +1329,18 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
         }
         kf[sub][s] = *(const h8*)p;
     };
-    auto rd_v = [&](const char* sl, int t, int sub, int s2) { vf[t][sub][s2] = *(const h8*)(sl + v_lane[sub][s2] + t * 32 * 128); };
     auto qk = [&](int X, int sub, int s) {
         if constexpr ((ABL & 32) != 0) { if (s == 0) asm volatile("" : "=v"(sacc[X][sub])); return; }
         sacc[X][sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[sub][s], qf[X][s], s == 0 ? zero16 : sacc[X][sub], 0, 0, 0);
     };
-    auto pv = [&](int X, int sub, int t, int s2) {
-        if constexpr ((ABL & 16) != 0) { asm volatile("" : "+v"(oacc[X][t]) : "v"(vf[t][sub][s2]), "v"(pf[X][sub][s2])); return; }
-        oacc[X][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[t][sub][s2], pf[X][sub][s2], oacc[X][t], 0, 0, 0);
-    };
+    auto pvm = [&](int X, int sub, int i) { pv.template mma<(ABL & 16) != 0>(X, sub, i); };      // V^T P^T step i of a sub-tile
     auto max_part = [&](int X, int sub, float mx) {          // 8 v_max3 over one sub-tile's 16 scores of this lane
         if constexpr ((ABL & 2) != 0) return mx;
 #pragma unroll
         for (int r = 0; r < 16; r += 2) mx = fmaxf(fmaxf(mx, sacc[X][sub][r]), sacc[X][sub][r + 1]);
         return mx;
     };
+    // the offset moves only when some query of the strand outgrew it by more than 2^ATT_THR (or on the first tile)
     auto decide = [&](int X, float mx, bool first) {
         if constexpr ((ABL & 2) != 0) return;
         if (first || !__all(mx <= ATT_THR)) {
@@ -1471,13 +1348,7 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
             const float m_hat = (float)(half_t)m_new;        // exactly what Q[q][D] can hold
             const float delta = m_run[X] - m_hat;
             m_run[X] = m_hat;
-            if (!first) {
-                const float alpha = __builtin_amdgcn_exp2f(delta);
-#pragma unroll
-                for (int t = 0; t < DT; ++t)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) oacc[X][t][r] *= alpha;
-            }
+            if (!first) pv.rescale(X, __builtin_amdgcn_exp2f(delta));
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
@@ -1489,15 +1360,13 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
 #pragma unroll
         for (int r = r0; r < r1; ++r) sacc[X][sub][r] = (ABL & 1) ? sacc[X][sub][r] : __builtin_amdgcn_exp2f(sacc[X][sub][r]);
     };
-    auto pack = [&](int X, int sub) {                        // fp16 probabilities: registers 8 s2 .. 8 s2 + 7 are k-step s2's B operand
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pf[X][sub][s2][e] = (half_t)sacc[X][sub][8 * s2 + e];
-    };
-    constexpr int NPV = DT * 2;                              // V^T P^T MFMAs per 32-key sub-tile and strand
+
+    // one tile; the ring slot is a compile-time constant (the loop below is unrolled over the slots), so every fragment address is
+    // a loop-invariant register plus an immediate
     auto tile = [&](int kt, auto slotc) {
         constexpr int slot = decltype(slotc)::value;
+        // my pieces of tile kt landed (tile kt + 1 may fly), then everybody's: one barrier per tile; behind it nobody reads the
+        // slot that tile kt + 2 goes to (the one of tile kt - 1) any more
         if (!(ABL & 4) && kt + 1 < nt) att_wait_vmcnt<NI>(); else att_wait_vmcnt<0>();
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_s_barrier();
@@ -1509,14 +1378,14 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
 #pragma unroll
             for (int s = 0; s < NKS; ++s) rd_k(sl, sub, s);
         ATT_SB();
-        // (b) K Q^T of strand A; the V^T fragments of the first 32 keys are requested between its MFMAs
+        // (b) K Q^T of strand A; the first RD_B V^T fragments of the tile are requested between its MFMAs
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
             for (int s = 0; s < NKS; ++s) {
                 const int i = sub * NKS + s;
                 qk(0, sub, s);
-                if (i < NPV) rd_v(sl, i / 2, 0, i & 1);
+                if (i < PV::RD_B) pv.rd_v(sl, i);
                 ATT_SB();
             }
         // (c) K Q^T of strand B  |  strand A: maximum, decision, exp and pack of its first 32 keys
@@ -1532,49 +1401,49 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
         for (int s = 0; s < NKS; ++s) {
             qk(1, 1, s);
             expo(0, 0, 16 * s / NKS, 16 * (s + 1) / NKS);
-            if (s < NPV) rd_v(sl, s / 2, 1, s & 1);          // ... and the V^T fragments of the second 32 keys
+            if (PV::RD_B + s < PV::NRD) pv.rd_v(sl, PV::RD_B + s);      // ... and the remaining V^T fragments
             ATT_SB();
         }
 #pragma unroll
-        for (int i = NKS; i < NPV; ++i) rd_v(sl, i / 2, 1, i & 1);
-        pack(0, 0);
+        for (int n = PV::RD_B + NKS; n < PV::NRD; ++n) pv.rd_v(sl, n);
+        pv.pack(0, 0, sacc[0][0]);
         ATT_SB();
         // (d) V^T P^T of strand A, first 32 keys  |  strand A: exp of its second 32 keys; strand B: maximum
         float mxb = sacc[1][0][0];
 #pragma unroll
         for (int i = 0; i < NPV; ++i) {
-            pv(0, 0, i / 2, i & 1);
+            pvm(0, 0, i);
             expo(0, 1, 16 * i / NPV, 16 * (i + 1) / NPV);
-            if (i == NPV - 3) mxb = max_part(1, 0, mxb);
-            if (i == NPV - 2) mxb = max_part(1, 1, mxb);
-            if (i == NPV - 1) mxb = att_max_cross(mxb);
+            if (i == PV::MAXB0) mxb = max_part(1, 0, mxb);
+            if (i == PV::MAXB1) mxb = max_part(1, 1, mxb);
+            if (i == PV::MAXBX) mxb = att_max_cross(mxb);
             ATT_SB();
         }
-        pack(0, 1);
+        pv.pack(0, 1, sacc[0][1]);
         ATT_SB();
         decide(1, mxb, first);
         ATT_SB();
         // (e) V^T P^T of strand A, second 32 keys  |  strand B: exp and pack of its first 32 keys
 #pragma unroll
         for (int i = 0; i < NPV; ++i) {
-            pv(0, 1, i / 2, i & 1);
+            pvm(0, 1, i);
             expo(1, 0, 16 * i / NPV, 16 * (i + 1) / NPV);
             ATT_SB();
         }
-        pack(1, 0);
+        pv.pack(1, 0, sacc[1][0]);
         ATT_SB();
         // (f) V^T P^T of strand B, first 32 keys  |  strand B: exp and pack of its second 32 keys
 #pragma unroll
         for (int i = 0; i < NPV; ++i) {
-            pv(1, 0, i / 2, i & 1);
+            pvm(1, 0, i);
             expo(1, 1, 16 * i / NPV, 16 * (i + 1) / NPV);
             ATT_SB();
         }
-        pack(1, 1);
+        pv.pack(1, 1, sacc[1][1]);
         ATT_SB();
         // (g) V^T P^T of strand B, second 32 keys
 #pragma unroll
-        for (int i = 0; i < NPV; ++i) pv(1, 1, i / 2, i & 1);
+        for (int i = 0; i < NPV; ++i) pvm(1, 1, i);
         ATT_SB();
     };
     for (int kt = 0; kt < nt; kt += NSLOT) {
@@ -1583,26 +1452,7 @@ __global__ __launch_bounds__(NW * 64, D <= 40 ? 2 : 1) void attn_dq32_kernel(con
         if (kt + 2 < nt) tile(kt + 2, std::integral_constant<int, 2>{});
     }
 
-    // ---- O = O^T / l: row D of O^T lives in tile D / 32, register ((D % 32) & 3) + 4 ((D % 32) >> 3) of the half with 4 h == (D % 32) & 4
-    constexpr int rr = D % 32, reg = (rr & 3) + 4 * (rr >> 3), owner_half = (rr >> 2) & 1;
-#pragma unroll
-    for (int X = 0; X < 2; ++X) {
-        const float mine = oacc[X][D / 32][reg];
-        const float other = __shfl_xor(mine, 32);
-        const float inv = 1.0f / (h == owner_half ? mine : other);
-        half_t* op = O + ((size_t)b * T + q0w + 32 * X + n32) * ldo + head * D;
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int dd = t * 32 + 8 * g4 + 4 * h;
-                if (dd < D) {
-                    const h4 o4 = {(half_t)(oacc[X][t][4 * g4] * inv), (half_t)(oacc[X][t][4 * g4 + 1] * inv),
-                                   (half_t)(oacc[X][t][4 * g4 + 2] * inv), (half_t)(oacc[X][t][4 * g4 + 3] * inv)};
-                    *(h4*)(op + dd) = o4;
-                }
-            }
-    }
+    pv.store(O, ldo, (size_t)b * T + q0w, head * D);
 }
 
 // Which kernel attention_launch chose on its last successful call in this process (fgdm_debug_last_attention_kernel: the parity
@@ -1659,19 +1509,19 @@ static int launch_pp(const AttnCall& c) {
     return att_launch<attn_pp_kernel<D>>(c, dim3(((c.T + 255) / 256) * c.H * c.B), 512, 0, ATT_KID_PP);
 }
 
-// The two-strand kernels: whole 256-query blocks, whole 64-key tiles and at least two of them, and a tile's K / V^T byte offsets
+// The two-strand kernel: whole ATT_TS_Q-query blocks, whole 64-key tiles and at least two of them, and a tile's K / V^T byte offsets
 // (the 32-bit voffset of the LDS-DMA) below 2^31
 static bool two_strand_ok(const AttnCall& c, int d) {
-    return c.T % 256 == 0 && c.Tk % 64 == 0 && c.Tk >= 128 && (size_t)64 * c.ldk * 2 < (1u << 31) && (size_t)d * c.ldvt * 2 < (1u << 31);
+    return c.T % ATT_TS_Q == 0 && c.Tk % 64 == 0 && c.Tk >= 128 && (size_t)64 * c.ldk * 2 < (1u << 31) && (size_t)d * c.ldvt * 2 < (1u << 31);
 }
 template <auto Kernel>
 static int launch_two_strand(const AttnCall& c, int kid) {
-    return att_launch<Kernel>(c, dim3((c.T / 256) * c.H * c.B), 256, 0, kid);
+    return att_launch<Kernel>(c, dim3((c.T / ATT_TS_Q) * c.H * c.B), ATT_TS_Q, 0, kid);
 }
 // FGDM_ATTN_ABL (tools/bench_attention.py only; see ABL above): the d = 40 kernels with parts of their work removed
 template <int ABL>
 static int launch_ablation(const AttnCall& c, bool wide) {
-    return wide ? launch_two_strand<attn_dq32_kernel<40, 4, ABL>>(c, ATT_KID_DQ32) : launch_two_strand<attn_dq_kernel<40, 4, ABL>>(c, ATT_KID_DQ16);
+    return wide ? launch_two_strand<attn_two_strand_kernel<40, Pv32<40>, ABL>>(c, ATT_KID_DQ32) : launch_two_strand<attn_two_strand_kernel<40, Pv16<40>, ABL>>(c, ATT_KID_DQ16);
 }
 static int launch_ablation_bits(const AttnCall& c, int abl, bool wide) {
     switch (abl) {
@@ -1742,16 +1592,16 @@ static int attention_dispatch(const half_t* Q, int ldq, const half_t* K, int ldk
     if (dq > 0 && d == 40 && two_strand_ok(c, d)) {
         if (cap) return FGDM_ERR_ARG;
         if (const int abl = knob_once(KNOB_ATTN_ABL)) return launch_ablation_bits(c, abl, dq == 3);
-        return dq == 1 ? launch_two_strand<attn_dq_kernel<40, 4>>(c, ATT_KID_DQ16) : launch_two_strand<attn_dq32_kernel<40, 4>>(c, ATT_KID_DQ32);
+        return dq == 1 ? launch_two_strand<attn_two_strand_kernel<40, Pv16<40>>>(c, ATT_KID_DQ16) : launch_two_strand<attn_two_strand_kernel<40, Pv32<40>>>(c, ATT_KID_DQ32);
     }
     // d = 80: the 32-wide kernel at one wave per SIMD (its two strands need ~280 registers); FGDM_ATTN_DQ80=0 switches it off (A/B)
     const int dq80 = knob_once(KNOB_ATTN_DQ80);
     if (cap && ((dq80 > 0 && (d == 80 || d == 64) && two_strand_ok(c, d)) || (pp_on && T >= 256 && Tk >= 256 && (d == 40 || d == 64 || d == 80))))
         return FGDM_ERR_ARG;
-    if (dq80 > 0 && d == 80 && two_strand_ok(c, d)) return launch_two_strand<attn_dq32_kernel<80, 4>>(c, ATT_KID_DQ32);
+    if (dq80 > 0 && d == 80 && two_strand_ok(c, d)) return launch_two_strand<attn_two_strand_kernel<80, Pv32<80>>>(c, ATT_KID_DQ32);
     // d = 64 (SD-2.x: a fixed head width): the 32-wide kernel as well, one wave per SIMD like d = 80 and behind the same switch --
     // FGDM_ATTN_DQ80=0 sends both to the ping-pong kernel (A/B; the measurement behind the default: profiles/attention_d64.txt)
-    if (dq80 > 0 && d == 64 && two_strand_ok(c, d)) return launch_two_strand<attn_dq32_kernel<64, 4>>(c, ATT_KID_DQ32);
+    if (dq80 > 0 && d == 64 && two_strand_ok(c, d)) return launch_two_strand<attn_two_strand_kernel<64, Pv32<64>>>(c, ATT_KID_DQ32);
     // every other long shape at d = 40 / 64 / 80: the eight-wave ping-pong kernel (256 queries per workgroup); FGDM_ATTN_PP=0 switches it off (A/B)
     if (pp_on && T >= 256 && Tk >= 256 && (d == 40 || d == 64 || d == 80)) return d == 40 ? launch_pp<40>(c) : d == 64 ? launch_pp<64>(c) : launch_pp<80>(c);
     // one text part (64 < Tk <= 96, NS = 3): the key-resident kernel.  FGDM_ATTN_CROSS: query chunks per wave, 0 = off (A/B)

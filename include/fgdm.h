@@ -729,7 +729,7 @@ int fgdm_op_attention(const void* q, int ldq, const void* k, int ldk, const void
  * log2(e) d^-1/2 (the engine folds it into the to_q weights), so O = softmax(ln 2 * Q K^T) V and the kernels scale by exactly 1.
  * fgdm_debug_last_attention_kernel: which kernel the dispatch chose on the last successful attention call of this process:
  * 0 none yet, 1 general (attn_kernel), 2 text-token (attn_cross_kernel<D, 3>), 3 long-text (attn_cross_kernel<D, 4 ... 8>), 4 ping-pong
- * (attn_pp_kernel), 5 two-strand 16-wide (attn_dq_kernel), 6 two-strand 32-wide (attn_dq32_kernel).
+ * (attn_pp_kernel), 5 two-strand 16-wide (attn_two_strand_kernel<D, Pv16<D>>), 6 two-strand 32-wide (attn_two_strand_kernel<D, Pv32<D>>).
  * fgdm_op_small_attention: the text encoder's attention, softmax(q k^T d^-1/2 (j <= i when causal)) v with q | k | v as column
  * blocks of one fp16 [B T, ld] matrix (q at column 0, k at koff, v at voff; head h at columns [64 h, 64 h + 64) of its block),
  * out fp16 [B T, ldo]; d = 64 and 1 <= T <= 128, anything else is FGDM_ERR_ARG before any launch. */
