@@ -99,6 +99,13 @@ class FgdmAttentionCapture(C.Structure):
         (name, C.c_int32) for name in ('n_tokens', 'rows', 'mode', 'batch', 'latent_h', 'latent_w', 'reserved0')]
 
 
+class FgdmNoisePlan(C.Structure):
+    """fgdm_noise_plan of include/fgdm.h (fgdm_loop_noise_set); struct_size must be ctypes.sizeof of this class."""
+    _fields_ = [('struct_size', C.c_int64), ('seed', C.c_uint64), ('first_sample', C.c_int32), ('first_step', C.c_int32),
+                ('temperature', C.c_float), ('repeat_noise', C.c_int32), ('reserved0', C.c_int32), ('reserved1', C.c_int32)]
+
+
+NOISE_STREAM_STEP, NOISE_STREAM_Q = 0, 1      # the generator's stream ids: the sampler's step noise, q_sample's noise
 ATTENTION_CAPTURE_MAX_KEYS = 256                                        # FGDM_ATTENTION_CAPTURE_MAX_KEYS
 CAPTURE_ROWS = {'all': 0, 'cond': 1, 'uncond': 2}                       # FGDM_CAPTURE_ROWS_*
 CAPTURE_MODES = {'sum': 0, 'last': 1}                                   # FGDM_CAPTURE_SUM / FGDM_CAPTURE_LAST
@@ -164,6 +171,9 @@ SIGNATURES = {
     'fgdm_op_dpm_program_step': (_i, [_p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
     'fgdm_sample_ancestral': (_i, [_p, C.POINTER(FgdmAncestralParams), _p]),
     'fgdm_ddim_encode': (_i, [_p, C.POINTER(FgdmDdimEncodeParams), _p]),
+    'fgdm_loop_noise_set': (_i, [_p, C.POINTER(FgdmNoisePlan)]),
+    'fgdm_randn': (_i, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _p, C.c_int32, C.c_int32, _p]),
+    'fgdm_op_rand_bits': (_i, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _p, _i64, _p]),
     'fgdm_op_ancestral_loop_step': (_i, [_p, _p, _f, _f, _f, _f, _f, _p, _p, _p, _p, _f, _f, _p, _p, _p, _i64, _p]),
     'fgdm_op_invert_loop_step': (_i, [_p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _i64, _p]),
     'fgdm_profile_begin': (_i, [_p, _i]),

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "noise.h"
 
 typedef _Float16 half_t;
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -228,6 +229,7 @@ struct LoopStep {
     float *e_out, *log_p0;
     float a_t, a_prev, sigma, s1m, sa_next, s1m_next;
     int mode, order;
+    NoiseGen gen;      // gen.step_on: sigma * noise from the generator (noise is NULL); gen.q_on: qnoise likewise (noise.h)
 };
 int loop_step(const LoopStep& a, hipStream_t s);
 // One launch per network evaluation of the device DPM-Solver++ loop (k_dpmpp_loop_step): the data prediction
@@ -278,6 +280,7 @@ struct AncestralLoopStep {
     StepIO io;
     const float *noise, *mask, *x0, *qnoise;
     float cr, crm1, c1, c2, std, sa_t, s1m_t;
+    NoiseGen gen;      // as LoopStep's; both streams at the walk position of this step
 };
 int ancestral_loop_step(const AncestralLoopStep& a, hipStream_t s);
 // One launch per network evaluation of the device DDIM inversion (k_invert_loop_step): x_next = axpby(x, cx, CFG(ec, eu), ce),
@@ -287,6 +290,11 @@ struct InvertLoopStep {
     float cx, ce;
 };
 int invert_loop_step(const InvertLoopStep& a, hipStream_t s);
+// out [B, per_sample] = the normals the armed loops make at (seed, stream_id, step, first_sample + row) (noise.h; fgdm_randn)
+int randn_fill(uint64_t seed, uint32_t stream_id, uint32_t step, uint32_t first_sample, int repeat, float temperature, float* out,
+               int B, uint32_t per_sample, hipStream_t s);
+// out [n_blocks, 4] = Philox4x32-10 of the 128-bit counter (c[0] lowest) + block index, carries included (fgdm_op_rand_bits)
+int rand_bits(uint64_t seed, const uint32_t c[4], uint32_t* out, size_t n_blocks, hipStream_t s);
 
 // ---------------------------------------------------------------- patch-wise routes (patches.hip)
 // An NCHW fp32 tensor [B, C, H, W] cut into Ly x Lx crops of [kh, kw] cells every (sh, sw): crop l = ly * Lx + lx starts at

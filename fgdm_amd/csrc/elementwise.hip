@@ -292,8 +292,12 @@ static bool step_io_ok(const StepIO& io, bool need_ec = true, bool need_x = true
 // The next step's inpainting blend (k_axpby, then k_mask_blend; ddim.py:151-154), then the shared store: the tail of k_loop_step.
 __device__ __forceinline__ void loop_blend_store(const LoopStep& a, size_t i, float xp) {
     float xn = xp;
-    if (a.mask) xn = mask_blend_rn(axpby_rn(a.sa_next, a.x0[i], a.s1m_next, a.qnoise[i]), xp, a.mask[i]);
+    if (a.mask) xn = mask_blend_rn(axpby_rn(a.sa_next, a.x0[i], a.s1m_next, a.qnoise ? a.qnoise[i] : noise_q(a.gen, i)), xp, a.mask[i]);
     step_store(a.io, i, xn);
+}
+// ... and the host check of a step's generator (noise.h): off, or whole samples of a multiple of four elements
+static bool noise_gen_ok(const NoiseGen& g, size_t n) {
+    return (!g.step_on && !g.q_on) || (g.per_sample != 0 && g.per_sample % 4 == 0 && n % g.per_sample == 0);
 }
 
 // One launch per network evaluation of the device DDIM and PLMS loops (fgdm_sample_ddim_ex, fgdm_sample_plms), one pass over the n
@@ -318,6 +322,7 @@ __global__ void k_loop_step(const LoopStep a) {
             const float p0 = pred_x0_rn(xp, ep, a.s1m, sa);
             xp = x_prev_rn(p0, ep, sp, dir);
             if (a.noise) xp = add_noise_rn(xp, a.sigma, a.noise[i]);
+            else if (a.gen.step_on) xp = add_noise_rn(xp, a.sigma, noise_step(a.gen, i));
             if (a.mode == LOOP_PROBE) {
                 if (a.io.xin_a) a.io.xin_a[i] = xp;
                 if (a.io.xin_b) a.io.xin_b[i] = xp;
@@ -330,7 +335,7 @@ __global__ void k_loop_step(const LoopStep a) {
     }
 }
 int loop_step(const LoopStep& a, hipStream_t s) {
-    if (!step_io_ok(a.io, false) || (a.mask && (!a.x0 || !a.qnoise))) return FGDM_ERR_ARG;
+    if (!step_io_ok(a.io, false) || (a.mask && (!a.x0 || (!a.qnoise && !a.gen.q_on))) || !noise_gen_ok(a.gen, a.io.n)) return FGDM_ERR_ARG;
     if (a.io.ec) {
         if (a.mode != LOOP_PLAIN && a.mode != LOOP_PROBE && a.mode != LOOP_FINISH_FIRST && a.mode != LOOP_MULTISTEP) return FGDM_ERR_ARG;
         if (a.mode == LOOP_FINISH_FIRST && !a.e1) return FGDM_ERR_ARG;
@@ -471,17 +476,18 @@ int ancestral_step(const float* x, const float* eps, float sqrt_recip, float sqr
 __global__ void k_ancestral_loop_step(const AncestralLoopStep a) {
     EW_LOOP(i, a.io.n) {
         float xn = ancestral_rn(a.io.x[i], step_eps(a.io, i), a.cr, a.crm1, a.c1, a.c2, a.std, a.noise, i);
-        if (a.mask) xn = mask_blend_rn(axpby_rn(a.sa_t, a.x0[i], a.s1m_t, a.qnoise[i]), xn, a.mask[i]);
+        if (!a.noise && a.gen.step_on) xn = add_noise_rn(xn, a.std, noise_step(a.gen, i));
+        if (a.mask) xn = mask_blend_rn(axpby_rn(a.sa_t, a.x0[i], a.s1m_t, a.qnoise ? a.qnoise[i] : noise_q(a.gen, i)), xn, a.mask[i]);
         step_store(a.io, i, xn);
         if (a.io.log_x) a.io.log_x[i] = xn;
     }
 }
 int ancestral_loop_step(const AncestralLoopStep& a, hipStream_t s) {
-    if (!step_io_ok(a.io) || (a.mask && (!a.x0 || !a.qnoise))) return FGDM_ERR_ARG;
+    if (!step_io_ok(a.io) || (a.mask && (!a.x0 || (!a.qnoise && !a.gen.q_on))) || !noise_gen_ok(a.gen, a.io.n)) return FGDM_ERR_ARG;
     AncestralLoopStep b = a;
     // std == 0 is the t == 0 step: the per-step route hands k_ancestral no noise there.  (With temperature 0 std is 0 at t > 0 too,
     // where that route computes fma(0, noise, mean): a difference only in the sign of an exact zero, or on non-finite noise.)
-    if (b.std == 0.f) b.noise = nullptr;
+    if (b.std == 0.f) { b.noise = nullptr; b.gen.step_on = 0; }
     FGDM_LAUNCH(k_ancestral_loop_step, dim3(ew_grid(b.io.n)), dim3(EW_BLOCK), 0, s, b);
     return LAUNCH_OK();
 }
@@ -499,6 +505,36 @@ __global__ void k_invert_loop_step(const InvertLoopStep a) {
 int invert_loop_step(const InvertLoopStep& a, hipStream_t s) {
     if (!step_io_ok(a.io)) return FGDM_ERR_ARG;
     FGDM_LAUNCH(k_invert_loop_step, dim3(ew_grid(a.io.n)), dim3(EW_BLOCK), 0, s, a);
+    return LAUNCH_OK();
+}
+
+// The generator of the armed loops on its own (noise.h): fgdm_randn's plane, which an unarmed loop and the per-step route read, and
+// the raw words of fgdm_op_rand_bits.
+__global__ void k_randn_fill(uint32_t key0, uint32_t key1, uint32_t stream_id, uint32_t step, uint32_t first_sample, int repeat,
+                             float temperature, uint32_t per_sample, float* __restrict__ out, size_t n) {
+    EW_LOOP(i, n) out[i] = noise_normal(key0, key1, stream_id, step, first_sample, repeat, temperature, per_sample, i);
+}
+int randn_fill(uint64_t seed, uint32_t stream_id, uint32_t step, uint32_t first_sample, int repeat, float temperature, float* out,
+               int B, uint32_t per_sample, hipStream_t s) {
+    if (!out || B <= 0 || per_sample == 0 || per_sample % 4 != 0) return FGDM_ERR_ARG;
+    const size_t n = (size_t)B * per_sample;
+    FGDM_LAUNCH(k_randn_fill, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, s, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, step,
+                first_sample, repeat, temperature, per_sample, out, n);
+    return LAUNCH_OK();
+}
+__global__ void k_rand_bits(uint32_t key0, uint32_t key1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                            uint32_t* __restrict__ out, size_t n_blocks) {
+    EW_LOOP(k, n_blocks) {
+        const uint64_t lo = ((uint64_t)c1 << 32 | c0) + k, hi = ((uint64_t)c3 << 32 | c2) + (lo < k ? 1u : 0u);
+        const PhiloxWords w = philox4x32_10((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32), key0, key1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[4 * k + j] = w.r[j];
+    }
+}
+int rand_bits(uint64_t seed, const uint32_t c[4], uint32_t* out, size_t n_blocks, hipStream_t s) {
+    if (!c || !out || n_blocks == 0) return FGDM_ERR_ARG;
+    FGDM_LAUNCH(k_rand_bits, dim3(ew_grid(n_blocks)), dim3(EW_BLOCK), 0, s, (uint32_t)seed, (uint32_t)(seed >> 32), c[0], c[1], c[2],
+                c[3], out, n_blocks);
     return LAUNCH_OK();
 }
 

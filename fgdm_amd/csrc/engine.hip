@@ -106,6 +106,24 @@ struct fgdm_engine : Model {
         std::vector<const Layer*> order;                       // the UNet's transformer blocks in walk order
         std::unordered_map<const Layer*, CapPlane> planes;     // the selected ones
     } cap;
+    // Device noise (fgdm_loop_noise_set): while `on`, a loop call makes the noise it is not handed inside its step kernels (noise.h)
+    struct LoopNoise {
+        bool on = false;
+        uint64_t seed = 0;
+        int32_t first_sample = 0, first_step = 0, repeat = 0;
+        float temperature = 1.f;
+    } loop_noise;
+    // the generator of a launch at local walk position `i`: stream 0 there, stream 1 at local position `qi`
+    NoiseGen noise_gen(int H, int W, int i, int qi, bool step_on, bool q_on) const {
+        NoiseGen g{};
+        if (!loop_noise.on || (!step_on && !q_on)) return g;
+        g.key0 = (uint32_t)loop_noise.seed; g.key1 = (uint32_t)(loop_noise.seed >> 32);
+        g.first_sample = (uint32_t)loop_noise.first_sample; g.per_sample = 4u * (uint32_t)H * (uint32_t)W;
+        g.step = (uint32_t)loop_noise.first_step + (uint32_t)i; g.q_step = (uint32_t)loop_noise.first_step + (uint32_t)qi;
+        g.temperature = loop_noise.temperature; g.repeat = loop_noise.repeat;
+        g.step_on = step_on; g.q_on = q_on;
+        return g;
+    }
     void capture_free() {
         for (auto& kv : cap.planes) { (void)hipFree(kv.second.acc); kv.second.acc = nullptr; }
         (void)hipFree(cap.tok_dev); (void)hipFree(cap.head_planes);
@@ -1849,6 +1867,31 @@ int fgdm_attention_capture_set(fgdm_engine* e, const fgdm_attention_capture* pla
     c.on = true;
     return FGDM_OK;
 }
+// ------------------------------------------------------------------------------------------------ device noise
+int fgdm_loop_noise_set(fgdm_engine* e, const fgdm_noise_plan* plan) {
+    if (!e) return FGDM_ERR_ARG;
+    if (!plan) { e->loop_noise = fgdm_engine::LoopNoise{}; return FGDM_OK; }
+    fgdm_noise_plan p;
+    if (!read_params(plan, FGDM_NOISE_PLAN_SIZE_V1, &p, sizeof(p)))
+        return e->fail(FGDM_ERR_ARG, "loop noise: struct_size is not the sizeof(fgdm_noise_plan) of a known header version");
+    if (p.reserved0 || p.reserved1) return e->fail(FGDM_ERR_ARG, "loop noise: reserved0 and reserved1 must be 0");
+    if (p.first_sample < 0 || p.first_step < 0) return e->fail(FGDM_ERR_ARG, "loop noise: first_sample and first_step must not be negative");
+    uint32_t tbits;                     // by the exponent field: this file is compiled with -fno-honor-nans
+    memcpy(&tbits, &p.temperature, sizeof(tbits));
+    if ((tbits & 0x7F800000u) == 0x7F800000u) return e->fail(FGDM_ERR_ARG, "loop noise: temperature must be finite");
+    auto& n = e->loop_noise;
+    n.on = true; n.seed = p.seed; n.first_sample = p.first_sample; n.first_step = p.first_step;
+    n.temperature = p.temperature; n.repeat = p.repeat_noise != 0;
+    return FGDM_OK;
+}
+int fgdm_randn(uint64_t seed, int32_t stream_id, int32_t step, int32_t first_sample, int32_t repeat, float temperature, float* out,
+               int32_t B, int32_t per_sample, void* stream) {
+    if (stream_id < 0 || step < 0 || first_sample < 0 || per_sample <= 0 || B <= 0 || (int64_t)first_sample + B - 1 > INT32_MAX)
+        return FGDM_ERR_ARG;
+    return randn_fill(seed, (uint32_t)stream_id, (uint32_t)step, (uint32_t)first_sample, repeat != 0, temperature, out, B,
+                      (uint32_t)per_sample, as_stream(stream));
+}
+
 static const fgdm_engine::CapPlane* capture_block(fgdm_engine* e, int block) {
     if (!e->cap.on || block < 0 || block >= (int)e->cap.order.size()) return nullptr;
     auto it = e->cap.planes.find(e->cap.order[block]);
@@ -2080,15 +2123,25 @@ static const char* log_steps_error(const int32_t* log_steps, int n_log, int S) {
     return nullptr;
 }
 // Host-side checks of a walk, in front of any launch; nullptr: the parameters are consistent.
-static const char* walk_error(const Walk& p) {
+// The sample and step ranges of an armed call: global sample indices and walk positions are 32-bit counter words (noise.h).
+static const char* loop_noise_range_error(const fgdm_engine* e, int B, int S) {
+    const auto& n = e->loop_noise;
+    if ((int64_t)n.first_sample + B > INT32_MAX || (int64_t)n.first_step + S > INT32_MAX)
+        return "loop noise: first_sample + B and first_step + S must not exceed INT32_MAX";
+    return nullptr;
+}
+static const char* walk_error(const Walk& p, const fgdm_engine* e) {
+    const bool armed = e->loop_noise.on;
     if (p.reserved0 != 0) return "reserved0 must be 0";
     if (!p.x || !p.cond || !p.timesteps || !p.alphas || !p.alphas_prev || !p.sqrt_one_minus_alphas) return "x, cond or a schedule table is NULL";
     if (p.S <= 0 || p.B <= 0 || p.H <= 0 || p.W <= 0) return "S, B, H and W must be positive";
-    if (p.mask && (!p.x0 || !p.q_noise || !p.sqrt_alphas_cumprod_t || !p.sqrt_one_minus_alphas_cumprod_t))
+    if (p.mask && (!p.x0 || (!p.q_noise && !armed) || !p.sqrt_alphas_cumprod_t || !p.sqrt_one_minus_alphas_cumprod_t))
         return "mask needs x0, q_noise and q_sample's two coefficient tables";
-    if (p.sigmas && !p.step_noise)
+    if (p.sigmas && !p.step_noise && !armed)
         for (int k = 0; k < p.S; ++k)
             if (p.sigmas[k] != 0.f) return "a sigma is not 0 and step_noise is NULL";
+    if (armed)
+        if (const char* why = loop_noise_range_error(e, p.B, p.S)) return why;
     return log_steps_error(p.log_steps, p.n_log, p.S);
 }
 
@@ -2105,14 +2158,20 @@ static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
     auto blend = [&](LoopStep& a, int i) {
         if (!p.mask) return;
         const int k = S - 1 - i;
-        a.mask = p.mask; a.x0 = p.x0; a.qnoise = p.q_noise + (size_t)i * n;
+        a.mask = p.mask; a.x0 = p.x0; a.qnoise = p.q_noise ? p.q_noise + (size_t)i * n : nullptr;
         a.sa_next = p.sqrt_alphas_cumprod_t[k]; a.s1m_next = p.sqrt_one_minus_alphas_cumprod_t[k];
+    };
+    // what the launch behind step `i` makes itself while the engine is armed: its sigma * noise where no plane is given, and the
+    // q_sample noise of the blend in front of step `qi` (-1: no blend in this launch) likewise
+    auto gen = [&](const LoopStep& a, int i, int qi) {
+        return e->noise_gen(p.H, p.W, i, qi < 0 ? 0 : qi, i >= 0 && a.sigma != 0.f && !a.noise, qi >= 0 && a.mask && !a.qnoise);
     };
     int rc;
     {                                   // in front of the first step: its blend, and x into the network's input
         LoopStep a{};
         a.io.x = L.x; a.io.n = n; L.feed(a.io);
         blend(a, 0);
+        a.gen = gen(a, -1, 0);
         a.io.x_out = p.mask ? L.x : nullptr;
         rc = loop_step(a, s);
     }
@@ -2124,7 +2183,8 @@ static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
         a.io = L.step_io(i, p.cfg_scales ? p.cfg_scales[i] : p.cfg_scale);
         a.a_t = p.alphas[index]; a.a_prev = p.alphas_prev[index]; a.s1m = p.sqrt_one_minus_alphas[index];
         a.sigma = p.sigmas ? p.sigmas[index] : 0.f;
-        a.noise = a.sigma != 0.f ? p.step_noise + (size_t)i * n : nullptr;
+        a.noise = a.sigma != 0.f && p.step_noise ? p.step_noise + (size_t)i * n : nullptr;
+        a.gen = gen(a, i, -1);
         if (!p.plms) {
             a.mode = LOOP_PLAIN;
         } else if (i == 0) {            // pseudo improved Euler (plms.py:219-223): probe, second evaluation at t_next, finish
@@ -2140,7 +2200,7 @@ static int run_walk(fgdm_engine* e, const Walk& p, hipStream_t s) {
             if (i >= 2) a.e2 = plane(i - 2);
             if (i >= 3) a.e3 = plane(i - 3);      // the plane e_out replaces
         }
-        if (i + 1 < S) blend(a, i + 1);
+        if (i + 1 < S) { blend(a, i + 1); a.gen = gen(a, i, i + 1); }
         const int slot = L.log_slot(i);
         a.io.log_x = L.log_plane(p.x_inter_out, slot); a.log_p0 = L.log_plane(p.pred_x0_out, slot);
         rc = loop_step(a, s);
@@ -2156,7 +2216,7 @@ static Walk ddim_walk(const fgdm_ddim_params& known) {
 // This entry takes hybrid networks, and the flags go to the network as given; CFG is on when any step's scale is not 1
 int fgdm_sample_ddim_ex(fgdm_engine* e, const fgdm_ddim_params* caller, void* stream) {
     return loop_entry(e, caller, stream, FGDM_DDIM_PARAMS_SIZE_V1, "fgdm_sample_ddim_ex", "fgdm_ddim_params", false,
-                      [](const fgdm_ddim_params& known) { return walk_error(ddim_walk(known)); },
+                      [e](const fgdm_ddim_params& known) { return walk_error(ddim_walk(known), e); },
                       [](fgdm_engine* e, const fgdm_ddim_params& known, hipStream_t s) {
                           Walk p = ddim_walk(known);
                           if (p.uncond)
@@ -2180,7 +2240,7 @@ int fgdm_sample_ddim(fgdm_engine* e, float* x, const float* cond, const float* u
 
 int fgdm_sample_plms(fgdm_engine* e, const fgdm_plms_params* caller, void* stream) {
     return loop_entry(e, caller, stream, FGDM_PLMS_PARAMS_SIZE_V1, "fgdm_sample_plms", "fgdm_plms_params", true,
-                      [](const fgdm_plms_params& known) { return walk_error(walk_from(known)); },
+                      [e](const fgdm_plms_params& known) { return walk_error(walk_from(known), e); },
                       [](fgdm_engine* e, const fgdm_plms_params& known, hipStream_t s) {
                           Walk p = walk_from(known);
                           p.plms = true;
@@ -2282,17 +2342,20 @@ int fgdm_sample_dpm_solver(fgdm_engine* e, const fgdm_dpm_solver_params* caller,
                       [](const fgdm_dpm_solver_params& known) { return dpm_program_error(&known); }, run_dpm_program);
 }
 
-static const char* ancestral_params_error(const fgdm_ancestral_params* p) {
+static const char* ancestral_params_error(const fgdm_ancestral_params* p, const fgdm_engine* e) {
+    const bool armed = e->loop_noise.on;
     if (p->reserved0 != 0 || p->reserved1 != 0) return "reserved0 and reserved1 must be 0";
     if (!p->x || !p->cond || !p->timesteps || !p->sqrt_recip_alphas_cumprod || !p->sqrt_recipm1_alphas_cumprod ||
         !p->posterior_mean_coef1 || !p->posterior_mean_coef2 || !p->std)
         return "x, cond or a table is NULL";
     if (p->S <= 0 || p->B <= 0 || p->H <= 0 || p->W <= 0) return "S, B, H and W must be positive";
-    if (p->mask && (!p->x0 || !p->q_noise || !p->sqrt_alphas_cumprod_t || !p->sqrt_one_minus_alphas_cumprod_t))
+    if (p->mask && (!p->x0 || (!p->q_noise && !armed) || !p->sqrt_alphas_cumprod_t || !p->sqrt_one_minus_alphas_cumprod_t))
         return "mask needs x0, q_noise and q_sample's two coefficient tables";
-    if (!p->step_noise)
+    if (!p->step_noise && !armed)
         for (int i = 0; i < p->S; ++i)
             if (p->std[i] != 0.f) return "a std is not 0 and step_noise is NULL";
+    if (armed)
+        if (const char* why = loop_noise_range_error(e, p->B, p->S)) return why;
     return log_steps_error(p->log_steps, p->n_log, p->S);
 }
 
@@ -2312,11 +2375,12 @@ static int run_ancestral(fgdm_engine* e, const fgdm_ancestral_params& p, hipStre
         a.io = L.step_io(i, 0.f);
         a.cr = p.sqrt_recip_alphas_cumprod[i]; a.crm1 = p.sqrt_recipm1_alphas_cumprod[i];
         a.c1 = p.posterior_mean_coef1[i]; a.c2 = p.posterior_mean_coef2[i]; a.std = p.std[i];
-        a.noise = a.std != 0.f ? p.step_noise + (size_t)i * n : nullptr;
+        a.noise = a.std != 0.f && p.step_noise ? p.step_noise + (size_t)i * n : nullptr;
         if (p.mask) {
-            a.mask = p.mask; a.x0 = p.x0; a.qnoise = p.q_noise + (size_t)i * n;
+            a.mask = p.mask; a.x0 = p.x0; a.qnoise = p.q_noise ? p.q_noise + (size_t)i * n : nullptr;
             a.sa_t = p.sqrt_alphas_cumprod_t[i]; a.s1m_t = p.sqrt_one_minus_alphas_cumprod_t[i];
         }
+        a.gen = e->noise_gen(p.H, p.W, i, i, a.std != 0.f && !a.noise, a.mask && !a.qnoise);
         a.io.log_x = L.log_plane(p.x_inter_out, L.log_slot(i));
         rc = ancestral_loop_step(a, s);
     }
@@ -2324,7 +2388,7 @@ static int run_ancestral(fgdm_engine* e, const fgdm_ancestral_params& p, hipStre
 }
 int fgdm_sample_ancestral(fgdm_engine* e, const fgdm_ancestral_params* caller, void* stream) {
     return loop_entry(e, caller, stream, FGDM_ANCESTRAL_PARAMS_SIZE_V1, "fgdm_sample_ancestral", "fgdm_ancestral_params", true,
-                      [](const fgdm_ancestral_params& known) { return ancestral_params_error(&known); }, run_ancestral);
+                      [e](const fgdm_ancestral_params& known) { return ancestral_params_error(&known, e); }, run_ancestral);
 }
 
 static const char* ddim_encode_params_error(const fgdm_ddim_encode_params* p) {

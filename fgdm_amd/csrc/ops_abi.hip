@@ -413,6 +413,13 @@ int fgdm_op_invert_loop_step(const float* x, const float* e_cond, const float* e
     return invert_loop_step(a, as_stream(stream));
 }
 
+// Diagnostic entry of tests/test_gpu_device_noise.py: the raw words of the loops' generator (noise.h).
+int fgdm_op_rand_bits(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t* out, int64_t n_blocks, void* stream) {
+    if (n_blocks <= 0) return FGDM_ERR_ARG;
+    const uint32_t c[4] = {c0, c1, c2, c3};
+    return rand_bits(seed, c, out, (size_t)n_blocks, as_stream(stream));
+}
+
 // Host-only entry of tests/test_replay_plan.py: the planner of replay_plan.h on caller-made walks.  Never touches the device.
 int fgdm_replay_plan(int n_walks, const int32_t* lens, const uint64_t* key, const uint32_t* grid_x, const uint64_t* shape, int group_max,
                      int chunk, int32_t* out, int out_cap, int* limits) {

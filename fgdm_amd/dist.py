@@ -24,6 +24,15 @@ def shard(t, rank, world):
     return t[lo:hi]
 
 
+def shard_device_noise(obj, n_global, rank, world):
+    """Tell a sampler or model built with device_noise=seed which rows of the global batch this rank holds: its generator then
+    gives row b of the shard the noise of global sample lo + b (first_sample of fgdm_noise_plan), so the ranks together draw
+    what one process would draw for the whole batch.  Returns lo."""
+    lo, _ = shard_bounds(n_global, rank, world)
+    obj.noise_first_sample = lo
+    return lo
+
+
 # Weights the engine transforms in fp32 BEFORE it rounds them to fp16 (fgdm_finalize_weights): a tensor shipped as fp16 would be
 # rounded twice there.  to_q: log2(e) d^-1/2 is folded in; the consumers of a folded LayerNorm (norm1 -> attn1.to_q|to_k|to_v,
 # norm2 -> attn2.to_q, norm3 -> ff.net.0.proj) are packed as fp16(gamma_k W_nk) with bias / u sums taken over the fp32 W; the text

@@ -256,6 +256,45 @@ class AttentionCapture:
         return out
 
 
+class LoopNoise:
+    """What Engine.loop_noise yields: while it is open the engine is armed with a fgdm_noise_plan (include/fgdm.h), and a device
+    loop that is handed no step_noise / q_noise makes that noise in its step kernels.  Leaving it disarms the engine."""
+
+    def __init__(self, engine, seed, first_sample=0, first_step=0, temperature=1., repeat_noise=False):
+        self.engine = engine
+        self.plan = _lib.FgdmNoisePlan()
+        self.plan.struct_size = C.sizeof(self.plan)
+        self.plan.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.plan.first_sample, self.plan.first_step = int(first_sample), int(first_step)
+        self.plan.temperature, self.plan.repeat_noise = float(temperature), int(bool(repeat_noise))
+
+    def __enter__(self):
+        e = self.engine
+        e._check(e.lib.fgdm_loop_noise_set(e.h, C.byref(self.plan)), 'fgdm_loop_noise_set')
+        return self
+
+    def __exit__(self, *exc):
+        e = self.engine
+        e._check(e.lib.fgdm_loop_noise_set(e.h, None), 'fgdm_loop_noise_set')
+        return False
+
+
+def randn(seed, stream, step, shape, first_sample=0, repeat=False, temperature=1., device=None, out=None):
+    """fp32 `shape` = [B, ...] of the normals an armed device loop makes at walk position `step` on `stream` (0: the sampler's
+    step noise, 1: q_sample's) for the global rows first_sample .. first_sample + B - 1 (fgdm_randn, include/fgdm.h): what the
+    per-step route draws with device_noise, so both routes give the same bits.  repeat: every row is sample 0; the values are
+    multiplied by temperature (one rounding)."""
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(tuple(shape), device=device if device is not None else 'cuda', dtype=torch.float32)
+    B = out.shape[0]
+    rc = lib.fgdm_randn(int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(step), int(first_sample), int(bool(repeat)), float(temperature),
+                        _ptr(out), B, out[0].numel(), _stream())
+    if rc != 0:
+        raise RuntimeError(f'fgdm_randn failed: {rc}')
+    return out
+
+
 class Engine:
     """One engine per device: owns packed weights + activation workspace in HBM."""
 
@@ -312,6 +351,18 @@ class Engine:
         bit; the ControlNets' cross-attentions and all self-attentions are not captured.  batch / latent_hw: give the
         evaluations' batch (2 B under CFG) and latent size to allocate now rather than at the first evaluation."""
         return AttentionCapture(self, resolve_attention_blocks(self.config, blocks, latent), tokens, rows, mode, batch, latent_hw)
+
+    def loop_noise(self, seed, first_sample=0, first_step=0, temperature=1., repeat_noise=False):
+        """Context manager: while it is open, a device loop (sample_ddim_ex, sample_plms, sample_ancestral) called without
+        step_noise / q_noise makes that noise in its step kernels from a counter-based generator (fgdm_loop_noise_set): no
+        [S, B,4,H,W] planes, whatever the number of steps.  first_sample: the global index of row 0 (a rank's shard offset);
+        first_step: the walk position of the call's step 0; temperature / repeat_noise: of the step noise.  Tensors that are
+        passed are still read.  Engine.randn gives the same numbers as a tensor."""
+        return LoopNoise(self, seed, first_sample, first_step, temperature, repeat_noise)
+
+    def randn(self, seed, stream, step, shape, first_sample=0, repeat=False, temperature=1.):
+        """randn (this module) on the engine's device"""
+        return randn(seed, stream, step, shape, first_sample, repeat, temperature, device=self.device)
 
     # ------------------------------------------------------------------ weights
     def param_shapes(self):

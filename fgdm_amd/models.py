@@ -115,7 +115,7 @@ class LatentDiffusion(_Buffers):
                  beta_schedule='linear', linear_start=0.00085, linear_end=0.012, cosine_s=8e-3, given_betas=None,
                  v_posterior=0.0, parameterization='eps', conditioning_key='crossattn', scale_factor=0.18215,
                  channels=4, image_size=32, log_every_t=200, clip_denoised=False, device=0, first_stage_config=None,
-                 cond_stage_config=None, first_stage_encoder=False, device_loop=False, **ignored):
+                 cond_stage_config=None, first_stage_encoder=False, device_loop=False, device_noise=None, **ignored):
         if parameterization != 'eps':
             raise NotImplementedError(f'parameterization={parameterization!r}: only eps-parameterization is implemented (the shipped '
                                       f'configs, models/config.yaml; {_cfg.SD2_LIMIT}; v-prediction checkpoints are refused)')
@@ -150,6 +150,17 @@ class LatentDiffusion(_Buffers):
         self._finalized = False
         self.device_loop = bool(device_loop)                # p_sample_loop / sample as engine calls where nothing needs the host between steps
         self.max_loop_noise_bytes = 256 << 20               # pre-drawn noise per engine call of that route: a memory bound, not a tuned number
+        # None: p_sample / q_sample draw from torch's generator.  A seed: from the engine's counter-based generator (fgdm_loop_noise_set /
+        # fgdm_randn, include/fgdm.h) -- the device route then draws nothing on the host, holds no noise planes and runs the whole walk
+        # as ONE engine call; the per-step route takes the same numbers from Engine.randn, so both still agree bit for bit.  x_T stays
+        # a torch draw.  noise_first_sample: the global index of row 0 (a rank's shard offset, fgdm_amd.dist).
+        self.device_noise = device_noise
+        self.noise_first_sample = 0
+        self._noise_pos = 0                                 # walk position of the step the per-step route is in
+
+    def _generated(self, stream, shape, repeat=False):
+        """the per-step route's draw at the walk position it is in, from the engine's generator (device_noise is a seed)"""
+        return _k.randn(self.device_noise, stream, self._noise_pos, shape, self.noise_first_sample, repeat, device=self.device)
 
     @classmethod
     def engine_args(cls, unet_config=None, use_adapter=None, n_controlnets=0, num_prompts=1, first_stage_config=None,
@@ -492,7 +503,9 @@ class LatentDiffusion(_Buffers):
         assert bool((t == ti).all()), 'p_sample expects one timestep per call'
         eps = self.apply_model(x, t, c, **kwargs)
         h = self._host
-        if noise is None:
+        if noise is None and getattr(self, 'device_noise', None) is not None:
+            noise = self._generated(_lib.NOISE_STREAM_STEP, x.shape, repeat_noise)
+        elif noise is None:
             noise = _randn((1, *x.shape[1:]) if repeat_noise else x.shape, x.device)
             noise = noise.expand_as(x).contiguous()
         std = 0.0 if ti == 0 else float(np.exp(0.5 * h['posterior_log_variance_clipped'][ti])) * temperature
@@ -541,6 +554,13 @@ class LatentDiffusion(_Buffers):
             tables['sqrt_alphas_cumprod_t'] = tab('sqrt_alphas_cumprod')
             tables['sqrt_one_minus_alphas_cumprod_t'] = tab('sqrt_one_minus_alphas_cumprod')
         logs = [j for j, t in enumerate(ts) if log_every_t and (t % log_every_t == 0 or t == timesteps - 1)]
+        if getattr(self, 'device_noise', None) is not None:
+            # no planes, so no bound to respect and no cut: the armed engine makes both streams in its step kernel (std carries the
+            # temperature, as on the per-step route)
+            with self.engine.loop_noise(self.device_noise, self.noise_first_sample, 0, 1., repeat_noise):
+                img, x_inter = self.engine.sample_ancestral(img, ctx, ts, tables, mask=m, x0=None if mask is None else x0, log_steps=logs,
+                                                            control_scales=control_scales, flags=flags)
+            return img, [] if x_inter is None else list(x_inter)
         inter = []
         step_bytes = img.numel() * 4 * (1 if mask is None else 2)
         for a, b in plan_noise_segments(len(ts), step_bytes, getattr(self, 'max_loop_noise_bytes', 256 << 20)):
@@ -579,11 +599,13 @@ class LatentDiffusion(_Buffers):
         if plan is not None:
             img, logged = self._device_ancestral(plan, img, timesteps, mask, x0, log_every_t if return_intermediates else None, **kwargs)
             return (img, inter + logged) if return_intermediates else img
+        generated = getattr(self, 'device_noise', None) is not None
         for i in reversed(range(0, timesteps)):
             ts = torch.full((b,), i, device=self.device, dtype=torch.long)
+            self._noise_pos = timesteps - 1 - i
             img = self.p_sample(img, cond, ts, clip_denoised=self.clip_denoised, **kwargs)
             if mask is not None:
-                img_orig = self.q_sample(x0, ts)
+                img_orig = self.q_sample(x0, ts, self._generated(_lib.NOISE_STREAM_Q, x0.shape)) if generated else self.q_sample(x0, ts)
                 img = _k.mask_blend(img_orig.contiguous(), img.contiguous(),
                                     mask.to(img.dtype).expand_as(img).contiguous())
             if i % log_every_t == 0 or i == timesteps - 1:

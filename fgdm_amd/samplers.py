@@ -18,10 +18,17 @@ per-step loop below.  PLMSSampler and DPMSolverSampler take the same keyword and
 fgdm_sample_plms and fgdm_sample_dpmpp; the DPM-Solver++ coefficients of both routes come from dpmpp_tables.
 ControlDDIMSampler.encode goes to fgdm_ddim_encode under the same rule, with the coefficients of encode_tables on both routes; the
 ancestral loop's switch is the model's (fgdm_amd.models.LatentDiffusion(device_loop=True)).
+
+device_noise=seed (DDIMSampler, ControlDDIMSampler, PLMSSampler; default None: everything above, bit for bit): the step noise and
+q_sample's noise come from the engine's counter-based generator (fgdm_loop_noise_set / fgdm_randn, include/fgdm.h) instead of torch's.
+The device route then draws nothing on the host and holds no [S, B,4,H,W] planes: the step kernels make the noise; the per-step
+route takes the same numbers from Engine.randn at the same (stream, walk position, sample), so both routes still agree bit for bit.
+x_T stays a torch draw.  noise_first_sample (default 0) is the global index of row 0: a rank's shard offset (fgdm_amd.dist).
 """
 import numpy as np
 import torch
 
+from . import _lib
 from . import engine as _k
 from . import schedule
 
@@ -88,10 +95,17 @@ def _loop_plan(m, sampler, cond, uc, scales, mask, x0, img, host_hooks, kwargs, 
 
 
 class _SamplerBase:
-    def __init__(self, model, schedule="linear", **kwargs):
+    def __init__(self, model, schedule="linear", device_noise=None, **kwargs):
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
         self.schedule = schedule
+        self.device_noise = device_noise        # None: torch's generator; a seed: the engine's generator (module docstring)
+        self.noise_first_sample = 0
+        self._noise_pos = 0                     # walk position of the step the per-step route is in
+
+    def _generated(self, stream, shape, device, repeat=False, temperature=1.):
+        """the per-step route's draw at the walk position it is in, from the engine's generator (device_noise is a seed)"""
+        return _k.randn(self.device_noise, stream, getattr(self, '_noise_pos', 0), shape, getattr(self, 'noise_first_sample', 0), repeat, temperature, device=device)
 
     def register_buffer(self, name, attr):
         if isinstance(attr, torch.Tensor) and attr.device != torch.device(self.model.device):
@@ -194,9 +208,14 @@ class _SamplerBase:
         # the reference draws noise_like(x.shape) on EVERY step, also when sigma == 0 (ddim.py:265); drawing it
         # keeps the generator stream aligned with the reference (matters when q_sample also draws: mask blending)
         shape = (1, *x.shape[1:]) if repeat_noise else x.shape
-        noise = _randn(shape, x.device)
+        generated = getattr(self, 'device_noise', None) is not None
+        noise = None if generated else _randn(shape, x.device)
         if sigma == 0.0:
             noise = None
+        elif generated:                                           # repeat_noise and temperature are the generator's
+            noise = self._generated(_lib.NOISE_STREAM_STEP, x.shape, x.device, repeat_noise, temperature)
+            if noise_dropout > 0.:
+                noise = torch.nn.functional.dropout(noise, p=noise_dropout)
         else:
             if repeat_noise:
                 noise = noise.expand_as(x).contiguous()
@@ -208,7 +227,10 @@ class _SamplerBase:
                             sigma, float(s1m[index]), noise, want_pred_x0)
 
     def _blend_mask(self, img, mask, x0, ts):
-        img_orig = self.model.q_sample(x0, ts)
+        if getattr(self, 'device_noise', None) is None:
+            img_orig = self.model.q_sample(x0, ts)
+        else:
+            img_orig = self.model.q_sample(x0, ts, self._generated(_lib.NOISE_STREAM_Q, x0.shape, x0.device))
         m = mask.to(img.dtype).expand_as(img).contiguous()
         return _k.mask_blend(img_orig.contiguous(), img.contiguous(), m)
 
@@ -225,11 +247,12 @@ class _SamplerBase:
 
 
     def _mask_kw(self, mask, x0, qn, img, timesteps):
-        """the mask group of a device loop's arguments ({} without a mask); qn: q_sample's noise of every step, already drawn"""
+        """the mask group of a device loop's arguments ({} without a mask); qn: q_sample's noise of every step, already drawn
+        (None: the armed engine makes it)"""
         if mask is None:
             return {}
         h = self.model._host
-        return dict(mask=mask.to(img.dtype).expand_as(img).contiguous(), x0=x0, q_noise=torch.stack(qn),
+        return dict(mask=mask.to(img.dtype).expand_as(img).contiguous(), x0=x0, q_noise=None if qn is None else torch.stack(qn),
                     sqrt_alphas_cumprod_t=[h['sqrt_alphas_cumprod'][int(t)] for t in timesteps],
                     sqrt_one_minus_alphas_cumprod_t=[h['sqrt_one_minus_alphas_cumprod'][int(t)] for t in timesteps])
 
@@ -250,6 +273,13 @@ class DDIMSampler(_SamplerBase):
         ctx, uctx, flags, control_scales = plan
         S = len(timesteps)
         alphas, alphas_prev, s1m, sigmas = (np.asarray(t)[:S] for t in tabs)
+        cfg_on = uctx is not None
+        if getattr(self, 'device_noise', None) is not None:      # nothing is drawn: the armed engine makes both streams in its step kernels
+            with self.model.engine.loop_noise(self.device_noise, self.noise_first_sample, 0, temperature):
+                return self.model.engine.sample_ddim_ex(img, ctx, uctx, scales[0] if cfg_on else 1.0, [int(t) for t in timesteps], alphas,
+                                                        alphas_prev, s1m, sigmas=sigmas, cfg_scales=scales if cfg_on else None,
+                                                        log_steps=log_steps, control_scales=control_scales, flags=flags,
+                                                        **self._mask_kw(mask, x0, None, img, timesteps))
         qn, sn = [], []
         for i in range(S):
             if mask is not None:
@@ -260,7 +290,6 @@ class DDIMSampler(_SamplerBase):
             if sigmas.any():
                 sn.append(noise)
         kw = self._mask_kw(mask, x0, qn, img, timesteps)
-        cfg_on = uctx is not None
         return self.model.engine.sample_ddim_ex(img, ctx, uctx, scales[0] if cfg_on else 1.0, [int(t) for t in timesteps], alphas,
                                                 alphas_prev, s1m, sigmas=sigmas, cfg_scales=scales if cfg_on else None,
                                                 step_noise=torch.stack(sn) if sn else None, log_steps=log_steps,
@@ -319,6 +348,7 @@ class DDIMSampler(_SamplerBase):
             return img, intermediates
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
+            self._noise_pos = i
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             if mask is not None:
                 assert x0 is not None
@@ -389,6 +419,7 @@ class DDIMSampler(_SamplerBase):
                                      [unconditional_guidance_scale] * total_steps, None, None, 1., ())[0]
         for i, step in enumerate(np.flip(timesteps)):
             index = total_steps - i - 1
+            self._noise_pos = i
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
             x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
                                           unconditional_guidance_scale=unconditional_guidance_scale,
@@ -409,6 +440,11 @@ class PLMSSampler(_SamplerBase):
         ctx, uctx, flags, control_scales = plan
         S = len(timesteps)
         alphas, alphas_prev, s1m = (np.asarray(t)[:S] for t in tabs[:3])
+        if getattr(self, 'device_noise', None) is not None:      # nothing is drawn: the armed engine makes q_sample's noise in its step kernel
+            with self.model.engine.loop_noise(self.device_noise, self.noise_first_sample):
+                return self.model.engine.sample_plms(img, ctx, uctx, scale if uctx is not None else 1.0, [int(t) for t in timesteps],
+                                                     alphas, alphas_prev, s1m, log_steps=log_steps, control_scales=control_scales,
+                                                     flags=flags, **self._mask_kw(mask, x0, None, img, timesteps))
         qn = []
         for i in range(S):
             if mask is not None:
@@ -476,6 +512,7 @@ class PLMSSampler(_SamplerBase):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             ts_next = torch.full((b,), int(time_range[min(i + 1, len(time_range) - 1)]), device=device, dtype=torch.long)
+            self._noise_pos = i
             if mask is not None:
                 assert x0 is not None
                 img = self._blend_mask(img, mask, x0, ts)

@@ -654,6 +654,52 @@ typedef struct fgdm_ddim_encode_params {
 } fgdm_ddim_encode_params;
 int fgdm_ddim_encode(fgdm_engine* e, const fgdm_ddim_encode_params* p, void* stream);
 
+/* Device noise for the stochastic loops: a counter-based generator inside the step kernels instead of pre-drawn [S, B,4,H,W]
+ * planes.  It replaces, for a caller who opts in, the host draws of ddim.py:265-268 (noise_like per step), ddpm.py:1295-1323
+ * (p_sample's noise_like) and ddpm.py:342-345 (q_sample's randn_like for the inpainting blend), and util.py noise_like's
+ * repeat=True; it does not reproduce torch's generator stream, and x_T stays the caller's.
+ *
+ * The generator is Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) with
+ *   key     = seed, low word first
+ *   counter = (j >> 2, global sample index, walk position, stream id)
+ * j: the element's index inside its sample (4 H W elements); global sample index = first_sample + row (0 for every row on stream 0
+ * with repeat_noise); walk position = first_step + the step's position in this call (0 = the first step of the whole walk that
+ * runs); stream id 0 = the sampler's step noise, 1 = q_sample's noise.  The four output words give the normals of elements
+ * 4q .. 4q+3 (q = j >> 2) by Box-Muller: (r0, r1) -> (rho cos theta, rho sin theta), (r2, r3) likewise, u1 = ((r >> 8) + 1) 2^-24,
+ * u2 = (r >> 8) 2^-24, rho = sqrtf(-2 logf(u1)), theta = 2 pi u2 (accurate logf / sincospif, each product rounded once).  |z| <= 5.77
+ * by construction.  Stream 0's value is temperature * z, rounded once: the host's noise_like(...) * temperature; stream 1 is z.
+ * So the noise of a sample at a step does not depend on how a walk is cut into calls, how a batch is sharded, or the launch.
+ *
+ * fgdm_loop_noise_set arms the engine with a plan (NULL: disarms; a plan replaces the one before).  While armed
+ *   fgdm_sample_ddim_ex, fgdm_sample_ancestral: a NULL step_noise where a sigma / std is not 0 makes stream 0 in the step kernel;
+ *   fgdm_sample_ddim_ex, fgdm_sample_plms, fgdm_sample_ancestral: a NULL q_noise with a mask makes stream 1 in the step kernel.  The
+ *     DDIM-family kernels blend in front of the NEXT step and use that step's walk position, as q_noise[i + 1] is read today; the
+ *     ancestral kernel blends behind the step, at its own position;
+ *   a pointer that is given is read as before.  fgdm_sample_dpmpp, fgdm_sample_dpm_solver and fgdm_ddim_encode take no noise and no
+ *     mask: they are not touched by the plan.
+ * Unarmed, every loop behaves and fails as documented above.  FGDM_ERR_ARG from fgdm_loop_noise_set (the plan before stays): a
+ * struct_size outside [FGDM_NOISE_PLAN_SIZE_V1, the library's sizeof], reserved0 / reserved1 != 0, first_sample or first_step < 0, a
+ * temperature that is not finite.  FGDM_ERR_ARG from an armed loop call before any launch: first_sample + B or first_step + S above
+ * INT32_MAX (the counter words are 32 bits wide). */
+#define FGDM_NOISE_PLAN_SIZE_V1 40
+typedef struct fgdm_noise_plan {
+    int64_t struct_size;
+    uint64_t seed;
+    int32_t first_sample;               /* global index of row 0 of x: a rank's shard offset */
+    int32_t first_step;                 /* walk position of the call's step 0: a later segment of a walk cut into calls */
+    float temperature;                  /* stream 0 only; 1: plain normals */
+    int32_t repeat_noise;               /* stream 0 only; not 0: every row gets sample 0's noise */
+    int32_t reserved0;                  /* 0 */
+    int32_t reserved1;                  /* 0 */
+} fgdm_noise_plan;
+int fgdm_loop_noise_set(fgdm_engine* e, const fgdm_noise_plan* plan);
+/* out [B, per_sample] (device) = the numbers an armed loop makes at walk position `step` on stream `stream_id` for the rows
+ * first_sample .. first_sample + B - 1 (every row sample 0 with `repeat`), times temperature: what the per-step Python route and
+ * an unarmed loop are fed to give the armed loop's bits.  FGDM_ERR_ARG: a NULL out; B <= 0; per_sample <= 0 or no multiple of 4;
+ * a negative stream_id, step or first_sample; first_sample + B - 1 above INT32_MAX. */
+int fgdm_randn(uint64_t seed, int32_t stream_id, int32_t step, int32_t first_sample, int32_t repeat, float temperature, float* out,
+               int32_t B, int32_t per_sample, void* stream);
+
 /* Built-in kernel timer (no reference counterpart: the reference only prints wall-clock, scripts/txt2img.py:381-396).
  * Between begin and end every stride-th kernel launch is bracketed by HIP events on the launch stream
  * (work / bytes / time totals then refer to the bracketed launches only).
@@ -867,6 +913,11 @@ int fgdm_op_ancestral_loop_step(const float* x, const float* eps, float sqrt_rec
                                 void* stream);
 int fgdm_op_invert_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float cx, float ce,
                              float* x_out, float* xin_a, float* xin_b, float* log_x, int64_t n, void* stream);
+
+/* Diagnostic entry (tests/test_gpu_device_noise.py): the raw words of the loops' generator (fgdm_loop_noise_set).
+ * out [n_blocks, 4] uint32 (device): row k = Philox4x32-10, key = seed (low word first), of the 128-bit counter (c0 lowest word)
+ * + k, carries into the higher words included.  FGDM_ERR_ARG: out NULL, n_blocks <= 0. */
+int fgdm_op_rand_bits(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t* out, int64_t n_blocks, void* stream);
 
 /* Diagnostic entry (tests/test_gpu_qkv_projection.py); the product path does not call it.
  *
