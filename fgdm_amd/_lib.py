@@ -207,6 +207,14 @@ SIGNATURES = {
     'fgdm_op_timestep_embed': (_i, [_p, _p, _p, _i, _i, _i, _p]),
     'fgdm_op_add_f16': (_i, [_p, _p, _p, _i64, _p]),
     'fgdm_op_ln_qkv': (_i, [_p] * 6 + [_i] * 5 + [_p, _p, _p]),
+    'fgdm_weights_begin_update': (_i, [_p]),
+    'fgdm_weights_update_tensor': (_i, [_p, C.c_char_p, _p, C.POINTER(_i64), _i]),
+    'fgdm_weights_commit_update': (_i, [_p, _p]),
+    'fgdm_weights_snapshot': (_i, [_p, C.POINTER(C.c_char_p), _i]),
+    'fgdm_weights_restore': (_i, [_p, _p]),
+    'fgdm_weights_snapshot_bytes': (_i64, [_p]),
+    'fgdm_weights_update_plan': (_i, [C.POINTER(FgdmConfig), C.POINTER(C.c_char_p), _i, C.c_char_p, _i]),
+    'fgdm_op_lora_merge': (_i, [_p, _p, _p, _f, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

@@ -309,6 +309,8 @@ int fold_accumulate(const float* o, const float* w_pix, const float* w_tie, floa
                     hipStream_t s);
 int fold_finish(const float* acc, const float* w_pix, const float* w_tie, float* out, const PatchGeom& g, hipStream_t s);
 int repeat_words(const void* src, void* dst /* [reps][words] */, size_t words /* 32-bit */, int reps, hipStream_t s);
+// out = W + s up down over fp32 [O, I] / [O, r] / [r, I] (lora.hip: ascending-k fmaf chain, then one fmaf); 1 <= r <= 128; out may be W
+int lora_merge(const float* W, const float* up, const float* down, float s, int O, int I, int r, float* out, hipStream_t st);
 
 #define HIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return FGDM_ERR_HIP; } while (0)
 

@@ -182,6 +182,14 @@ struct fgdm_engine : Model {
     Arena arena;
     half_t* zero = nullptr;
     int cur_comp = -1;            // the component being packed: its Component::allocs takes the uploads
+    // Weight updates of a finalized engine (fgdm_weights_*): the tensors supplied since begin_update, staged on the host until the
+    // commit re-packs the units that own them IN PLACE; the size of every packed buffer; the snapshot (device copies of units'
+    // buffers, put back by fgdm_weights_restore)
+    bool upd_open = false, in_place = false;
+    std::unordered_map<std::string, std::vector<float>> upd;
+    std::unordered_map<void*, size_t> alloc_bytes;
+    struct Snap { void* dst; void* copy; size_t bytes; };
+    std::vector<Snap> snap;
     // LayerNorms of the transformer blocks folded into the GEMMs they feed (default) or run as kernels of their own
     // (FGDM_LN_FOLD=0 at fgdm_create: the A/B switch for tools/ab_bench.sh; numerics differ only in rounding points)
     bool ln_fold = true;
@@ -219,11 +227,20 @@ struct fgdm_engine : Model {
         if (it == params.end() || !it->second.loaded) { err = "parameter not loaded: " + name; return nullptr; }
         return &it->second;
     }
-    template <typename T> T* upload(const std::vector<T>& h) {
+    // `into`: the buffer the unit holds now.  A weight update (fgdm_weights_commit_update) writes the new bytes over it -- same
+    // shapes, so the same size -- and every pointer the engine handed out stays good; a first packing allocates.
+    template <typename T> T* upload(const std::vector<T>& h, T* into = nullptr) {
+        if (in_place) {
+            auto it = into ? alloc_bytes.find(into) : alloc_bytes.end();
+            if (it == alloc_bytes.end() || it->second < h.size() * sizeof(T)) return nullptr;
+            return hipMemcpy(into, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess ? into : nullptr;
+        }
         T* d = nullptr;
-        if (hipMalloc(&d, std::max<size_t>(h.size() * sizeof(T), 256)) != hipSuccess) return nullptr;
+        const size_t bytes = std::max<size_t>(h.size() * sizeof(T), 256);
+        if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
         if (hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
         comps[cur_comp].allocs.push_back(d);
+        alloc_bytes[d] = bytes;
         return d;
     }
     // rows: list of (source float*, n_rows) stacked along N; each source is [n][K_src] row-major;
@@ -270,9 +287,9 @@ struct fgdm_engine : Model {
             bias[pr] = bflat[sr] * rs;
         }
         g.N = N; g.K = K; g.k_real = K_src;
-        g.w = upload(w);
-        g.bias = upload(bias);
-        g.ln_u = ln_gamma ? upload(lnu) : nullptr;
+        g.w = upload(w, g.w);
+        g.bias = upload(bias, g.bias);
+        g.ln_u = ln_gamma ? upload(lnu, g.ln_u) : nullptr;
         if (ln_gamma && !kmap.empty()) return fail(FGDM_ERR_ARG, "LayerNorm fold: plain Linear weights only");
         return (g.w && g.bias && (!ln_gamma || g.ln_u)) ? FGDM_OK : fail(FGDM_ERR_NOMEM, "hipMalloc failed while packing weights");
     }
@@ -319,9 +336,10 @@ struct fgdm_engine : Model {
         const std::vector<int> kmap = conv3_kmap(Cin, &cp);      // source row layout is [Cin][3][3]
         g.im2col = (Cin % 64) != 0;
         g.cin_pad = cp;
+        half_t* const wph_now = g.wph;
         g.wph = nullptr;
         if (up && Cin % 64 == 0 && N % 320 == 0) {
-            g.wph = upload(up_phase_pack(w->host.data(), N, Cin, igemm_npad(N)));
+            g.wph = upload(up_phase_pack(w->host.data(), N, Cin, igemm_npad(N)), wph_now);
             if (!g.wph) return fail(FGDM_ERR_NOMEM, "hipMalloc failed while packing weights");
         }
         return pack_rows(g, {{w->host.data(), N}}, Cin * 9, (int)kmap.size(), kmap, {b->host.data()}, false);
@@ -331,8 +349,8 @@ struct fgdm_engine : Model {
         const ParamSlot* b = slot(pre + ".bias");
         if (!w || !b) return FGDM_ERR_STATE;
         n.C = (int)w->shape[0];
-        n.g = upload(w->host);
-        n.b = upload(b->host);
+        n.g = upload(w->host, n.g);
+        n.b = upload(b->host, n.b);
         return (n.g && n.b) ? FGDM_OK : fail(FGDM_ERR_NOMEM, "hipMalloc failed");
     }
     // fp32 [co][ci] weights of a 1x1 convolution followed by its biases, for the per-pixel kernels (vae_prequant, vae_moments)
@@ -342,14 +360,14 @@ struct fgdm_engine : Model {
         if (!w || !b) return FGDM_ERR_STATE;
         std::vector<float> wb(w->host);
         wb.insert(wb.end(), b->host.begin(), b->host.end());
-        *dst = upload(wb);
+        *dst = upload(wb, *dst);
         return *dst ? FGDM_OK : fail(FGDM_ERR_NOMEM, "hipMalloc failed");
     }
     // fp32 table as it is (CLIP's embeddings)
     int pack_table(float** dst, const std::string& name) {
         const ParamSlot* w = slot(name);
         if (!w) return FGDM_ERR_STATE;
-        *dst = upload(w->host);
+        *dst = upload(w->host, *dst);
         return *dst ? FGDM_OK : fail(FGDM_ERR_NOMEM, "hipMalloc failed");
     }
     // The packing visitor of model.h's traversals: every call lands in one of the pack_* above; after the first failure the rest
@@ -389,7 +407,8 @@ struct fgdm_engine : Model {
                 return fail(FGDM_ERR_STATE, "tensor " + name + " was released after packing: reload every tensor of " + comp.prefix +
                                             " before finalizing again");
         }
-        for (void* p : comp.allocs) (void)hipFree(p);
+        drop_snapshot();            // it holds copies of buffers that are freed here
+        for (void* p : comp.allocs) { (void)hipFree(p); alloc_bytes.erase(p); }
         comp.allocs.clear();
         cur_comp = c;
         Packer pk{*this};
@@ -400,6 +419,115 @@ struct fgdm_engine : Model {
         comp.packed = true;
         comp.dirty = false;
         return FGDM_OK;
+    }
+
+    // ------------------------------------------------------------------------------------ weight updates of a finalized engine
+    void drop_snapshot() {
+        for (auto& sn : snap) (void)hipFree(sn.copy);
+        snap.clear();
+    }
+    size_t snapshot_bytes() const { size_t n = 0; for (auto& sn : snap) n += sn.bytes; return n; }
+    // everything computed from weights and kept across calls: the registered context's K / V^T, the summed adapter features, the
+    // ControlNets' hint-block outputs.  Their owners set them again (a call that needs one and finds none is refused by name).
+    void drop_derived() {
+        drop_context();
+        drop_adapter_conds();
+        for (auto& n : cns) if (n.guided.p) { (void)hipFree(n.guided.p); n.guided = Tensor{}; }
+    }
+    // the visitor that lists the device buffers of the units it is shown
+    struct Collector {
+        std::vector<void*> ptrs;
+        void add(void* p) { if (p) ptrs.push_back(p); }
+        void gemm(GemmW& g) { add(g.w); add(g.bias); add(g.ln_u); add(g.wph); }
+        void norm(NormW& n, const std::string&, int) { add(n.g); add(n.b); }
+        void layernorm(NormW& n, const std::string& pre, int C) { norm(n, pre, C); }
+        void conv3(GemmW& g, const std::string&, int, int) { gemm(g); }
+        void conv3_up(GemmW& g, const std::string&, int, int) { gemm(g); }
+        void pointwise(float*& d, const std::string&, int, int) { add(d); }
+        void table(float*& d, const std::string&, int, int) { add(d); }
+        void linear(GemmW& g, const std::string&, int, int, bool, bool, const LinOpt& = LinOpt()) { gemm(g); }
+        void stack(GemmW& g, const std::vector<std::string>&, bool, const LinOpt& = LinOpt()) { gemm(g); }
+    };
+    static bool any_of_keys(const Keys& keys, const std::function<bool(const std::string&)>& has) {
+        for (auto& k : keys) if (has(k)) return true;
+        return false;
+    }
+    int weights_snapshot(const char* const* keys, int n) {
+        if (!finalized) return fail(FGDM_ERR_STATE, "weights not finalized");
+        std::unordered_map<std::string, int> want;
+        for (int i = 0; i < n; ++i) {
+            if (!keys[i] || !params.count(keys[i])) return fail(FGDM_ERR_ARG, std::string("unknown parameter key: ") + (keys[i] ? keys[i] : "(null)"));
+            want[keys[i]] = 1;
+        }
+        Collector col;
+        visit_units(ln_fold, [&](const Keys& unit, auto&& replay) {
+            if (any_of_keys(unit, [&](const std::string& k) { return want.count(k) != 0; })) replay(col);
+        });
+        (void)hipDeviceSynchronize();      // no packed buffer is being written: updates and restores are synchronous
+        const size_t had = snap.size();
+        for (void* p : col.ptrs) {
+            bool held = false;
+            for (auto& sn : snap) held = held || sn.dst == p;
+            if (held) continue;             // the bytes kept are the ones from before the FIRST update
+            Snap sn{p, nullptr, alloc_bytes.at(p)};
+            if (hipMalloc(&sn.copy, sn.bytes) != hipSuccess || hipMemcpy(sn.copy, p, sn.bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
+                (void)hipFree(sn.copy);
+                for (size_t i = had; i < snap.size(); ++i) (void)hipFree(snap[i].copy);
+                snap.resize(had);
+                return fail(FGDM_ERR_NOMEM, "hipMalloc (weight snapshot)");
+            }
+            snap.push_back(sn);
+        }
+        return FGDM_OK;
+    }
+    int weights_restore(hipStream_t st) {
+        if (!finalized) return fail(FGDM_ERR_STATE, "weights not finalized");
+        if (snap.empty()) return fail(FGDM_ERR_STATE, "no weight snapshot to restore (fgdm_weights_snapshot)");
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(FGDM_ERR_HIP, "hipStreamSynchronize");      // launches still reading the weights
+        for (auto& sn : snap)
+            if (hipMemcpy(sn.dst, sn.copy, sn.bytes, hipMemcpyDeviceToDevice) != hipSuccess) return fail(FGDM_ERR_HIP, "hipMemcpy (weight restore)");
+        (void)hipDeviceSynchronize();
+        drop_snapshot();
+        drop_derived();
+        return FGDM_OK;
+    }
+    int weights_update_tensor(const char* key, const float* dev, const int64_t* shape, int ndim) {
+        if (!finalized) return fail(FGDM_ERR_STATE, "weights not finalized: fgdm_weights_update_tensor changes a packed engine (load with fgdm_load_tensor)");
+        if (!upd_open) return fail(FGDM_ERR_STATE, "fgdm_weights_begin_update has not been called");
+        auto it = params.find(key);
+        if (it == params.end()) return fail(FGDM_ERR_ARG, std::string("unknown parameter key: ") + key);
+        const ParamSlot& ps = it->second;
+        if ((int)ps.shape.size() != ndim) return fail(FGDM_ERR_ARG, std::string("rank mismatch for ") + key);
+        for (int i = 0; i < ndim; ++i)
+            if (ps.shape[i] != shape[i]) return fail(FGDM_ERR_ARG, std::string("shape mismatch for ") + key);
+        std::vector<float> h(ps.numel());
+        if (hipMemcpy(h.data(), dev, h.size() * sizeof(float), hipMemcpyDefault) != hipSuccess) return fail(FGDM_ERR_HIP, "hipMemcpy failed");
+        upd[key] = std::move(h);
+        return FGDM_OK;
+    }
+    int weights_commit(hipStream_t st) {
+        if (!finalized) return fail(FGDM_ERR_STATE, "weights not finalized");
+        if (!upd_open) return fail(FGDM_ERR_STATE, "fgdm_weights_begin_update has not been called");
+        upd_open = false;                   // a commit ends the update, refused or not
+        std::unordered_map<std::string, std::vector<float>> staged;
+        staged.swap(upd);
+        auto has = [&](const std::string& k) { return staged.count(k) != 0; };
+        for (const Keys& unit : plan_units(ln_fold, has))
+            for (auto& k : unit)
+                if (!has(k)) return fail(FGDM_ERR_ARG, "partly supplied packed layer: " + k + " is packed together with " +
+                                                       *std::find_if(unit.begin(), unit.end(), has) + " and was not supplied");
+        if (staged.empty()) return FGDM_OK;
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(FGDM_ERR_HIP, "hipStreamSynchronize");      // launches still reading the weights
+        for (auto& kv : staged) params[kv.first].host.swap(kv.second);
+        Packer pk{*this};
+        in_place = true;
+        visit_units(ln_fold, [&](const Keys& unit, auto&& replay) { if (any_of_keys(unit, has)) replay(pk); });
+        in_place = false;
+        for (auto& kv : staged) std::vector<float>().swap(params[kv.first].host);
+        (void)hipDeviceSynchronize();
+        drop_derived();
+        if (pk.rc == FGDM_ERR_NOMEM) return fail(FGDM_ERR_HIP, "writing the re-packed weights failed");
+        return pk.rc;
     }
 
 #define CHK(x) do { int _rc = (x); if (_rc != FGDM_OK) return _rc; } while (0)
@@ -1630,6 +1758,7 @@ void fgdm_destroy(fgdm_engine* e) {
     if (!e) return;
     for (hipEvent_t ev : e->prof.pool) (void)hipEventDestroy(ev);
     for (auto& c : e->comps) for (void* p : c.allocs) (void)hipFree(p);
+    e->drop_snapshot();
     if (e->zero) (void)hipFree(e->zero);
     for (auto& n : e->cns) if (n.guided.p) (void)hipFree(n.guided.p);
     e->drop_concat();
@@ -1702,14 +1831,56 @@ int fgdm_finalize_weights(fgdm_engine* e) {
     if (!e) return FGDM_ERR_ARG;
     int rc = e->ensure_device();
     if (rc != FGDM_OK) return rc;
-    e->drop_context();          // everything derived from the previous weights is stale
-    e->drop_adapter_conds();
-    for (auto& n : e->cns) if (n.guided.p) { (void)hipFree(n.guided.p); n.guided = Tensor{}; }
+    e->drop_derived();          // everything derived from the previous weights is stale
+    e->upd_open = false;
+    e->upd.clear();
     // only components whose tensors changed since the last call are packed again (their previous HBM copy is freed
     // first): loading the base checkpoint and then a ControlNet checkpoint does not re-pack or leak the UNet
     for (int c = 0; c < (int)e->comps.size(); ++c) { rc = e->repack(c); if (rc != FGDM_OK) return rc; }
     e->finalized = true;
     return FGDM_OK;
+}
+
+int fgdm_weights_begin_update(fgdm_engine* e) {
+    if (!e) return FGDM_ERR_ARG;
+    if (!e->finalized) return e->fail(FGDM_ERR_STATE, "weights not finalized: an update changes a packed engine (load with fgdm_load_tensor)");
+    e->upd.clear();
+    e->upd_open = true;
+    return FGDM_OK;
+}
+int fgdm_weights_update_tensor(fgdm_engine* e, const char* key, const float* device_fp32, const int64_t* shape, int ndim) {
+    if (!e || !key || !device_fp32 || !shape) return FGDM_ERR_ARG;
+    return e->weights_update_tensor(key, device_fp32, shape, ndim);
+}
+int fgdm_weights_commit_update(fgdm_engine* e, void* stream) {
+    if (!e) return FGDM_ERR_ARG;
+    return e->weights_commit(as_stream(stream));
+}
+int fgdm_weights_snapshot(fgdm_engine* e, const char* const* keys, int n) {
+    if (!e || n < 0 || (n && !keys)) return FGDM_ERR_ARG;
+    return e->weights_snapshot(keys, n);
+}
+int fgdm_weights_restore(fgdm_engine* e, void* stream) {
+    if (!e) return FGDM_ERR_ARG;
+    return e->weights_restore(as_stream(stream));
+}
+int64_t fgdm_weights_snapshot_bytes(const fgdm_engine* e) { return e ? (int64_t)e->snapshot_bytes() : FGDM_ERR_ARG; }
+int fgdm_weights_update_plan(const fgdm_config* cfg, const char* const* keys, int n, char* out, int out_cap) {
+    if (!cfg || n < 0 || (n && !keys) || out_cap < 0 || (out_cap && !out)) return FGDM_ERR_ARG;
+    fgdm_engine* d = desc_for(cfg);
+    if (!d) return FGDM_ERR_ARG;
+    std::unordered_map<std::string, int> want;
+    for (int i = 0; i < n; ++i) {
+        if (!keys[i] || !d->params.count(keys[i])) { g_create_err = std::string("unknown parameter key: ") + (keys[i] ? keys[i] : "(null)"); return FGDM_ERR_ARG; }
+        want[keys[i]] = 1;
+    }
+    std::string text;
+    for (const auto& unit : d->plan_units(knob_on(KNOB_LN_FOLD), [&](const std::string& k) { return want.count(k) != 0; })) {
+        for (size_t i = 0; i < unit.size(); ++i) text += (i ? " " : "") + unit[i];
+        text += "\n";
+    }
+    if ((int)text.size() + 1 <= out_cap) memcpy(out, text.c_str(), text.size() + 1);
+    return (int)text.size() + 1;
 }
 
 int fgdm_profile_begin(fgdm_engine* e, int stride) {

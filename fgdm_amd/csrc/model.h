@@ -1,7 +1,8 @@
 // Model description of the FG-DM engine: the networks as structs of (still empty) packed weights, the topology builders with
 // their config checks, and ONE traversal per module kind that names every state-dict key, with its shape and the GemmW / NormW it
 // lands in, exactly once.  Two visitors run that traversal: the Registrar below fills the parameter table (build()), the engine's
-// Packer (engine.hip) uploads the kernel layouts (fgdm_finalize_weights).  A traversal takes its references when it runs, so
+// Packer (engine.hip) uploads the kernel layouts (fgdm_finalize_weights).  A third, Units, wraps either kind of visitor and shows
+// it only the packed layers a set of keys belongs to (fgdm_weights_*).  A traversal takes its references when it runs, so
 // nothing here points into a Block or a Net that construction is still copying around.
 //
 // Reference structure being reproduced (file:line in the reference checkout):
@@ -357,6 +358,49 @@ struct Model {
         }
         void stack(GemmW&, const std::vector<std::string>&, bool, const LinOpt& = LinOpt()) {}
     };
+
+    // The third use of the traversal: the PACKED UNITS.  Every visitor call that packs something -- one GemmW, NormW or table -- is
+    // one unit, built from the state-dict keys listed here: a Linear's weight and bias, the LayerNorm folded into it (ln_fold: the
+    // engine's FGDM_LN_FOLD), every source of a stacked GEMM.  f(keys, replay) is told each unit; replay(visitor) repeats the call on
+    // another visitor, so the engine re-packs (its Packer) or collects the buffers of exactly the units it picks.
+    typedef std::vector<std::string> Keys;
+    template <class F> struct Units {
+        bool ln_fold;
+        F f;
+        static Keys wb(Keys k, const std::string& pre, bool bias = true) {
+            k.push_back(pre + ".weight");
+            if (bias) k.push_back(pre + ".bias");
+            return k;
+        }
+        Keys folded(Keys k, const LinOpt& o) const { return ln_fold && !o.ln.empty() ? wb(std::move(k), o.ln) : k; }
+        void norm(NormW& n, const std::string& pre, int C) { f(wb({}, pre), [&](auto& v) { v.norm(n, pre, C); }); }
+        void layernorm(NormW& n, const std::string& pre, int C) { if (!ln_fold) f(wb({}, pre), [&](auto& v) { v.layernorm(n, pre, C); }); }
+        void conv3(GemmW& g, const std::string& pre, int co, int ci) { f(wb({}, pre), [&](auto& v) { v.conv3(g, pre, co, ci); }); }
+        void conv3_up(GemmW& g, const std::string& pre, int co, int ci) { f(wb({}, pre), [&](auto& v) { v.conv3_up(g, pre, co, ci); }); }
+        void pointwise(float*& d, const std::string& pre, int co, int ci) { f(wb({}, pre), [&](auto& v) { v.pointwise(d, pre, co, ci); }); }
+        void table(float*& d, const std::string& key, int rows, int W) { f(Keys{key}, [&](auto& v) { v.table(d, key, rows, W); }); }
+        void source(const std::string&, int, int, bool) {}
+        void linear(GemmW& g, const std::string& pre, int N, int K, bool c1, bool bias, const LinOpt& o = LinOpt()) {
+            f(folded(wb({}, pre, bias), o), [&](auto& v) { v.linear(g, pre, N, K, c1, bias, o); });
+        }
+        void stack(GemmW& g, const std::vector<std::string>& pres, bool bias, const LinOpt& o = LinOpt()) {
+            Keys k;
+            for (auto& pre : pres) k = wb(std::move(k), pre, bias);
+            f(folded(std::move(k), o), [&](auto& v) { v.stack(g, pres, bias, o); });
+        }
+    };
+    template <class F> void visit_units(bool ln_fold, F f) {
+        Units<F> u{ln_fold, f};
+        for (int c = 0; c < (int)comps.size(); ++c) visit_component(c, u);
+    }
+    // the key sets of the units that own any of `touched` (pure: no device), in traversal order
+    template <class Has> std::vector<Keys> plan_units(bool ln_fold, Has touched) {
+        std::vector<Keys> out;
+        visit_units(ln_fold, [&](const Keys& keys, auto&&) {
+            for (auto& k : keys) if (touched(k)) { out.push_back(keys); break; }
+        });
+        return out;
+    }
 
     // ------------------------------------------------------------------------------------ topology: which layers, what channels
     static Layer mk(LType t, int cin, int cout, int heads = 0) {

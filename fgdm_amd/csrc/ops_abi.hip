@@ -420,6 +420,12 @@ int fgdm_op_rand_bits(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint
     return rand_bits(seed, c, out, (size_t)n_blocks, as_stream(stream));
 }
 
+// The LoRA merge kernel on caller-owned device buffers (tests/test_gpu_lora.py; fgdm_amd/lora.py merges each touched tensor with it)
+int fgdm_op_lora_merge(const float* W, const float* up, const float* down, float s, int O, int I, int r, float* out, void* stream) {
+    if (!W || !up || !down || !out || O <= 0 || I <= 0 || r < 1 || r > 128 || O > 65535 * 16) return FGDM_ERR_ARG;
+    return lora_merge(W, up, down, s, O, I, r, out, as_stream(stream));
+}
+
 // Host-only entry of tests/test_replay_plan.py: the planner of replay_plan.h on caller-made walks.  Never touches the device.
 int fgdm_replay_plan(int n_walks, const int32_t* lens, const uint64_t* key, const uint32_t* grid_x, const uint64_t* shape, int group_max,
                      int chunk, int32_t* out, int out_cap, int* limits) {

@@ -409,6 +409,42 @@ class Engine:
         self._hint_keys = [None] * self.n_controlnets
         self._conds_key, self._conds_keep = None, None
 
+    # ------------------------------------------------------------------ weight updates of a finalized engine (include/fgdm.h)
+    def _forget_derived(self):
+        """the engine dropped what it had computed from weights (registered context, hint features, adapter conds): the next
+        call hands each over again instead of taking a cache hit"""
+        self._ctx_policy = ContextCachePolicy()
+        self._hint_keys = [None] * self.n_controlnets
+        self._conds_key, self._conds_keep = None, None
+
+    def weights_snapshot(self, keys):
+        keys = [k.encode() for k in keys]
+        arr = (C.c_char_p * len(keys))(*keys)
+        self._check(self.lib.fgdm_weights_snapshot(self.h, arr, len(keys)), 'fgdm_weights_snapshot')
+
+    def weights_snapshot_bytes(self):
+        return int(self.lib.fgdm_weights_snapshot_bytes(self.h))
+
+    def weights_restore(self):
+        self._check(self.lib.fgdm_weights_restore(self.h, _stream()), 'fgdm_weights_restore')
+        self._forget_derived()
+
+    def weights_begin_update(self):
+        self._check(self.lib.fgdm_weights_begin_update(self.h), 'fgdm_weights_begin_update')
+
+    def weights_update_tensor(self, key, value):
+        """one parameter of the update: an fp32 tensor on the engine's device (the producing stream is synchronised here)"""
+        v = value.detach().to(self.device, torch.float32).contiguous()
+        torch.cuda.current_stream().synchronize()
+        sh = (C.c_int64 * v.dim())(*v.shape)
+        self._check(self.lib.fgdm_weights_update_tensor(self.h, key.encode(), _ptr(v), sh, v.dim()), f'fgdm_weights_update_tensor({key})')
+
+    def weights_commit_update(self):
+        try:
+            self._check(self.lib.fgdm_weights_commit_update(self.h, _stream()), 'fgdm_weights_commit_update')
+        finally:
+            self._forget_derived()
+
     # ------------------------------------------------------------------ forward
     def set_hint(self, cn, hint):
         """hint fp32 NCHW [B,3,8H,8W] in [0,1]; cached until a different tensor is given.  The source object is kept

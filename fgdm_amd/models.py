@@ -249,6 +249,20 @@ class LatentDiffusion(_Buffers):
             self._finalized = True
         return missing, unexpected
 
+    def load_lora(self, lora_state_dict, base_state_dict, scale=1.0):
+        """Merge a LoRA adapter (fgdm_amd/lora.py: ldm or kohya key names) into the finalized engine in place: the UNet, the
+        ControlNets (`control_model.` keys) and the text tower when the engine has one.  base_state_dict: the checkpoint the engine
+        was loaded from (the packed engine keeps no fp32 weights).  A further call merges on top: the sum is rebuilt from the base
+        with the deltas in call order.  The effective scale of a module is scale * alpha / rank."""
+        from . import lora
+        self._loras = lora.load(self.engine, getattr(self, '_loras', []), lora_state_dict, base_state_dict, scale)
+
+    def unload_lora(self):
+        """Put back, byte for byte, the packed weights from before the first load_lora."""
+        if getattr(self, '_loras', None):
+            self.engine.weights_restore()
+            self._loras = []
+
     def _tokenize(self, text):
         """FrozenCLIPEmbedder.forward's tokenizer call (modules.py:153-155)."""
         if self.tokenizer is None:

@@ -941,6 +941,50 @@ int fgdm_op_rand_bits(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint
 int fgdm_op_ln_qkv(const void* h, const float* gamma, const float* beta, const float* wq, const float* wk, const float* wv,
                    int B, int T, int C, int Tp, int fold, void* qk, void* vt, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Weight updates of a FINALIZED engine (LoRA adapters and the like): selected parameters are supplied again as fp32 in device
+ * memory and the packed layers that own them are re-packed in place, through the packer fgdm_finalize_weights runs -- so every
+ * fold (stacked q | k | v with norm1 and the query scale, the GEGLU pair with norm3, conv layouts, the stacked emb_layers and text
+ * projections) applies as it did at the first packing.  No packed buffer moves; what the engine had computed from weights and kept
+ * (the registered context's K / V^T, the summed adapter features, the ControlNets' hint-block outputs) is dropped by a commit and
+ * by a restore: call fgdm_set_context / fgdm_set_adapter_conds / fgdm_set_hint again (a call that needs one is refused by name
+ * until then, never served stale).
+ *
+ * A packed layer is built from several parameters -- a weight and its bias, the LayerNorm folded into a Linear, q, k and v of one
+ * attention, every emb_layers Linear of a network.  A commit needs ALL parameters of every layer it touches;
+ * fgdm_weights_update_plan lists them without a device.
+ *
+ *   fgdm_weights_begin_update    opens an update, forgetting tensors of an unfinished one.
+ *   fgdm_weights_update_tensor   one parameter, fp32 in device (or host) memory, complete when the call is made (synchronise the
+ *                                stream that produced it); copied to host staging, the caller's buffer is free on return.
+ *   fgdm_weights_commit_update   waits for `stream`, re-packs, ends the update.  Synchronous.
+ *   fgdm_weights_snapshot        keeps a device copy of the packed bytes of the layers that own `keys`; layers already held keep
+ *                                their FIRST copy, so the snapshot stays the state before any update.
+ *   fgdm_weights_restore         waits for `stream`, puts the snapshot back byte for byte and releases it.
+ *   fgdm_weights_snapshot_bytes  device memory the snapshot holds now.
+ *
+ * Refusals leave the packed weights as they were: FGDM_ERR_STATE for an engine that is not finalized, an update_tensor or commit
+ * without begin_update, a restore without a snapshot; FGDM_ERR_ARG for an unknown key, a rank or shape that differs from the
+ * registered one, and a commit with a partly supplied packed layer (the message names the missing key; the update is over and its
+ * tensors are forgotten).  fgdm_finalize_weights after new fgdm_load_tensor calls drops the snapshot.
+ *
+ * fgdm_weights_update_plan: the packed layers owning any of `keys`, as text in `out`: one layer per line, its keys separated by one
+ * blank.  Returns the bytes needed including the final NUL (nothing is written when out_cap is smaller), FGDM_ERR_ARG for an
+ * unknown key (named by fgdm_last_error of NULL). */
+int fgdm_weights_begin_update(fgdm_engine* e);
+int fgdm_weights_update_tensor(fgdm_engine* e, const char* key, const float* device_fp32, const int64_t* shape, int ndim);
+int fgdm_weights_commit_update(fgdm_engine* e, void* stream);
+int fgdm_weights_snapshot(fgdm_engine* e, const char* const* keys, int n);
+int fgdm_weights_restore(fgdm_engine* e, void* stream);
+int64_t fgdm_weights_snapshot_bytes(const fgdm_engine* e);
+int fgdm_weights_update_plan(const fgdm_config* cfg, const char* const* keys, int n, char* out, int out_cap);
+
+/* fgdm_op_lora_merge: out[o, i] = W[o, i] + s sum_{k < r} up[o, k] down[k, i] over fp32 device buffers W, out [O, I], up [O, r],
+ * down [r, I]; a conv weight is taken as [Cout, Cin kh kw].  Per element: acc = 0, then acc = fmaf(up[o, k], down[k, i], acc) for
+ * k = 0 .. r - 1 in that order, then fmaf(s, acc, W[o, i]) -- the same bits whatever the launch.  out may be W.
+ * FGDM_ERR_ARG before any launch: a NULL pointer, O or I <= 0, r outside 1..128. */
+int fgdm_op_lora_merge(const float* W, const float* up, const float* down, float s, int O, int I, int r, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
