@@ -206,6 +206,13 @@ SIGNATURES = {
     'fgdm_op_transpose_pad': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgdm_op_timestep_embed': (_i, [_p, _p, _p, _i, _i, _i, _p]),
     'fgdm_op_add_f16': (_i, [_p, _p, _p, _i64, _p]),
+    'fgdm_op_embed_tokens': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    'fgdm_op_layernorm32': (_i, [_p, _i, _i, _p, _p, _f, _p, _p, _p]),
+    'fgdm_op_add_f16_to_f32': (_i, [_p, _p, _p, _i64, _p]),
+    'fgdm_op_f32_to_f16': (_i, [_p, _p, _i64, _p]),
+    'fgdm_op_silu_f32_to_f16': (_i, [_p, _p, _i64, _p]),
+    'fgdm_op_vae_prequant': (_i, [_p, _p, _f, _p, _i, _i, _p]),
+    'fgdm_op_vae_moments': (_i, [_p, _p, _p, _i, _i, _p]),
     'fgdm_op_ln_qkv': (_i, [_p] * 6 + [_i] * 5 + [_p, _p, _p]),
     'fgdm_weights_begin_update': (_i, [_p]),
     'fgdm_weights_update_tensor': (_i, [_p, C.c_char_p, _p, C.POINTER(_i64), _i]),

@@ -194,7 +194,6 @@ int embed_tokens(const int64_t* ids, const float* tok, const float* pos, float* 
 // LayerNorm of an fp32 matrix -> fp16 (out16) or fp32 (out32), exactly one of them non-null
 int layernorm32_launch(const float* x, int rows, int C, const float* gamma, const float* beta, float eps, half_t* out16,
                        float* out32, hipStream_t s);
-int f16_to_f32(const half_t* x, float* y, size_t n, hipStream_t s);
 // causal / full attention over short sequences (T <= 128, d = 64) with q|k|v as column blocks of one matrix
 int small_attention_launch(const half_t* qkv, int ld, int koff, int voff, half_t* out, int ldo, int B, int heads, int T,
                            int d, int causal, hipStream_t s);

@@ -334,6 +334,40 @@ int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stre
     return add_f16((const half_t*)a, (const half_t*)b, (half_t*)y, (size_t)n, as_stream(stream));
 }
 
+// Diagnostic entries of tests/test_gpu_fp32_ops.py; the product path does not call them.
+// Pass-throughs to the fp32-side launchers of the text encoder (text.hip, norm.hip, elementwise.hip) and of the first stage
+// (elementwise.hip), pointer / shape checks in front.
+int fgdm_op_embed_tokens(const int64_t* ids, const float* tok, const float* pos, float* out, int rows, int T, int W, int vocab,
+                         void* stream) {
+    if (!ids || !tok || !pos || !out || rows <= 0 || T <= 0 || W <= 0 || (W & 7) || vocab <= 0) return FGDM_ERR_ARG;
+    return embed_tokens(ids, tok, pos, out, rows, T, W, vocab, as_stream(stream));
+}
+int fgdm_op_layernorm32(const float* x, int rows, int C, const float* gamma, const float* beta, float eps, void* out16, float* out32,
+                        void* stream) {
+    if (!x || !gamma || !beta || rows <= 0 || C <= 0 || (C & 3) || (!out16 == !out32)) return FGDM_ERR_ARG;
+    return layernorm32_launch(x, rows, C, gamma, beta, eps, (half_t*)out16, out32, as_stream(stream));
+}
+int fgdm_op_add_f16_to_f32(const float* a, const void* b16, float* y, int64_t n, void* stream) {
+    if (!a || !b16 || !y || n <= 0) return FGDM_ERR_ARG;
+    return add_f16_to_f32(a, (const half_t*)b16, y, (size_t)n, as_stream(stream));
+}
+int fgdm_op_f32_to_f16(const float* x, void* y, int64_t n, void* stream) {
+    if (!x || !y || n <= 0) return FGDM_ERR_ARG;
+    return f32_to_f16(x, (half_t*)y, (size_t)n, as_stream(stream));
+}
+int fgdm_op_silu_f32_to_f16(const float* x, void* y, int64_t n, void* stream) {
+    if (!x || !y || n <= 0) return FGDM_ERR_ARG;
+    return silu_f32_to_f16(x, (half_t*)y, (size_t)n, as_stream(stream));
+}
+int fgdm_op_vae_prequant(const float* z, const float* wb, float scale, void* y, int B, int HW, void* stream) {
+    if (!z || !wb || !y || B <= 0 || HW <= 0) return FGDM_ERR_ARG;
+    return vae_prequant(z, wb, scale, (half_t*)y, B, HW, as_stream(stream));
+}
+int fgdm_op_vae_moments(const float* h, const float* wb, float* moments, int B, int HW, void* stream) {
+    if (!h || !wb || !moments || B <= 0 || HW <= 0) return FGDM_ERR_ARG;
+    return vae_moments(h, wb, moments, B, HW, as_stream(stream));
+}
+
 // Diagnostic entry of tests/test_gpu_ddim_loop.py: one launch of the device DDIM loop's step kernel on caller-owned buffers.
 int fgdm_op_ddim_loop_step(const float* x, const float* e_cond, const float* e_uncond, float cfg_scale, float a_t, float a_prev,
                            float sigma_t, float sqrt_one_minus_at, const float* noise, const float* mask, const float* x0,

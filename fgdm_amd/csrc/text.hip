@@ -29,15 +29,6 @@ int embed_tokens(const int64_t* ids, const float* tok, const float* pos, float* 
     return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
 }
 
-__global__ void k_f16_to_f32(const half_t* __restrict__ x, float* __restrict__ y, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) y[i] = (float)x[i];
-}
-int f16_to_f32(const half_t* x, float* y, size_t n, hipStream_t s) {
-    size_t g = (n + 255) / 256;
-    FGDM_LAUNCH(k_f16_to_f32, dim3((unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g))), dim3(256), 0, s, x, y, n);
-    return hipGetLastError() == hipSuccess ? FGDM_OK : FGDM_ERR_HIP;
-}
-
 // O[b, i, h*D + :] = softmax_j( scale * q_i . k_j  (j <= i when causal) ) v_j ; q/k/v are column blocks of one
 // [B*T, ld] matrix (the stacked q|k|v projection).  One 256-thread workgroup per (head, prompt); T <= 128.
 template <int D>

@@ -840,6 +840,30 @@ int fgdm_op_transpose_pad(const void* v, void* vt, int B, int Tk, int C, int Tkp
 int fgdm_op_timestep_embed(const int64_t* t, const float* t_float, void* y, int B, int dim, int rows_pad, void* stream);
 int fgdm_op_add_f16(const void* a, const void* b, void* y, int64_t n, void* stream);
 
+/* Diagnostic entries (tests/test_gpu_fp32_ops.py); the product path does not call them.  One entry per fp32-side kernel of the text
+ * encoder and of the first stage, on caller-owned device buffers; asynchronous on `stream`.  Every argument error -- a NULL
+ * pointer, a count <= 0, what each entry names below -- is FGDM_ERR_ARG before any launch.
+ *  fgdm_op_embed_tokens: out fp32 [rows, W], row r = tok[clamp(ids[r], 0, vocab - 1)] + pos[r % T]: CLIPTextEmbeddings on int64 ids
+ *      [rows = B T], fp32 tables tok [vocab, W] and pos [>= T, W], one fp32 add per element.  W a multiple of 8.
+ *  fgdm_op_layernorm32: LayerNorm over the C columns of each of `rows` fp32 rows (two-pass fp32 statistics, biased variance),
+ *      gamma / beta fp32 [C], stored as fp16 to out16 or as fp32 to out32: exactly one of the two non-NULL.  C a multiple of 4.
+ *  fgdm_op_add_f16_to_f32: y = a + float(b16) on n elements (a, y fp32; b16 fp16): the residual add of a CLIP layer.
+ *  fgdm_op_f32_to_f16: y = fp16(x) on n elements, round to nearest even (the context upload).
+ *  fgdm_op_silu_f32_to_f16: y = fp16(x sigmoid(x)) on n elements, evaluated in fp32 (`emb` handed in from outside).
+ *  fgdm_op_vae_prequant: post_quant_conv (1x1, 4 -> 4; ldm/models/autoencoder.py:331) on scale z with the layout change:
+ *      z fp32 [B, 4, HW] -> y fp16 [B, HW, 4], y[b, p, co] = fp16(wb[16 + co] + sum_ci wb[4 co + ci] (scale z[b, ci, p])); wb fp32 [20].
+ *  fgdm_op_vae_moments: quant_conv (1x1, 8 -> 8; autoencoder.py:326) with the layout change: h fp32 [B, HW, 8] (16-byte aligned)
+ *      -> moments fp32 [B, 8, HW], moments[b, co, p] = wb[64 + co] + sum_ci wb[8 co + ci] h[b, p, ci]; wb fp32 [72]. */
+int fgdm_op_embed_tokens(const int64_t* ids, const float* tok, const float* pos, float* out, int rows, int T, int W, int vocab,
+                         void* stream);
+int fgdm_op_layernorm32(const float* x, int rows, int C, const float* gamma, const float* beta, float eps, void* out16, float* out32,
+                        void* stream);
+int fgdm_op_add_f16_to_f32(const float* a, const void* b16, float* y, int64_t n, void* stream);
+int fgdm_op_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
+int fgdm_op_silu_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
+int fgdm_op_vae_prequant(const float* z, const float* wb, float scale, void* y, int B, int HW, void* stream);
+int fgdm_op_vae_moments(const float* h, const float* wb, float* moments, int B, int HW, void* stream);
+
 /* Diagnostic entry (tests/test_gpu_ddim_loop.py); only fgdm_sample_ddim_ex's loop launches this kernel in the product path.
  *
  * fgdm_op_ddim_loop_step: one launch of k_loop_step in its plain mode, the per-step kernel of fgdm_sample_ddim_ex, on n fp32 elements:

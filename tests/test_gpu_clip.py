@@ -5,7 +5,7 @@ import pytest
 import torch
 
 import golden_inputs as gi
-from common import check_net, gold, net_tol, params, relerr, report
+from common import CAP_EVAL, NET_K, check_net, check_net_vs_oracle, gold, net_tol, params, relerr, report
 from fgdm_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -56,3 +56,38 @@ def test_get_learned_conditioning_mirror(engine):
     c = m.get_learned_conditioning(['a photo of a cat', 'a bedroom'])
     assert torch.equal(c, engine.clip_encode(ids))
     assert torch.equal(m.get_learned_conditioning(ids), c)
+
+
+MASSIVE_CHANNELS = (133, 587)
+MASSIVE_OFFSET_STDS = 100
+
+
+def test_clip_encode_with_massive_channels():
+    """The residual stream of a real CLIP checkpoint carries a few channels with a large constant offset through every layer; the
+    synthetic weights give O(1) hidden states only.  Here token_embedding.weight and position_embedding.weight get a constant
+    added in two fixed channels (+off in channel 133, -off in channel 587, in both tables: the hidden state starts at +-2 off
+    there, against a spread of 0.05 elsewhere), and the engine is judged like every network: against oracle.clip.text_encode on
+    the same parameters, within net_tol(floor) of its fp32 mode, the floor measured on these inputs and capped at CAP_EVAL.
+    off = 100 standard deviations of token_embedding.weight (0.03609: off = 3.609), the largest of 10, 30 and 100 for which the
+    oracle's own floor stays below CAP_EVAL / NET_K = 3.67e-3: the floors are 7.44e-4, 7.21e-4 and 7.10e-4 (no offset: 8.98e-4)."""
+    from fgdm_amd.engine import Engine
+    from oracle import clip as oclip
+    e = Engine(gi.SMALL_CFG, clip=True)
+    try:
+        p = params(oclip.param_shapes())
+        tok, pos = (oclip.PREFIX + f'embeddings.{n}_embedding.weight' for n in ('token', 'position'))
+        off = MASSIVE_OFFSET_STDS * float(p[tok].std())
+        for k in (tok, pos):
+            p[k] = p[k].clone()
+            p[k][:, MASSIVE_CHANNELS[0]] += off
+            p[k][:, MASSIVE_CHANNELS[1]] -= off
+        for k, shape in e.param_shapes().items():
+            e.load_tensor(k, p[k] if k in p else synth.make_tensor(k, shape))
+        e.finalize()
+        ids = gi.clip_ids()
+        z = e.clip_encode(ids).cpu()
+    finally:
+        e.close()
+    assert tuple(z.shape) == (2, 77, 768)
+    _, floor = check_net_vs_oracle(f'clip text encoder, massive channels (offset {off:.3f})', z, lambda: oclip.text_encode(p, ids))
+    assert floor < CAP_EVAL / NET_K, floor

@@ -140,6 +140,41 @@ def test_narrow_op_entries_refuse_bad_arguments(lib):
     assert lib.fgdm_op_add_f16(p, p, p, 0, null) < 0
 
 
+def test_fp32_op_entries_refuse_bad_arguments(lib):
+    """The diagnostic entries of tests/test_gpu_fp32_ops.py return FGDM_ERR_ARG before any launch (so without a GPU too): the
+    pointers below are never dereferenced."""
+    import ctypes as C
+    p, null = C.c_void_p(1 << 20), None
+    ERR_ARG = -1
+
+    def refuses(fn, good, bad):
+        """every argument set that differs from `good` in the named positions is refused"""
+        for change in bad:
+            args = list(good)
+            for i, v in change.items():
+                args[i] = v
+            assert fn(*args) == ERR_ARG, (fn.__name__, change)
+
+    nulls = lambda *idx: [{i: null} for i in idx]
+    nonpos = lambda *idx: [{i: v} for i in idx for v in (0, -1)]
+    # ids, tok, pos, out, rows, T, W, vocab, stream
+    refuses(lib.fgdm_op_embed_tokens, (p, p, p, p, 154, 77, 768, 1000, null),
+            nulls(0, 1, 2, 3) + nonpos(4, 5, 6, 7) + [{6: 4}, {6: 12}, {6: 769}, {6: 772}])           # W % 8 != 0
+    # x, rows, C, gamma, beta, eps, out16, out32, stream: exactly one output
+    for good in ((p, 5, 768, p, p, 1e-5, p, null, null), (p, 5, 768, p, p, 1e-5, null, p, null)):
+        refuses(lib.fgdm_op_layernorm32, good, nulls(0, 3, 4) + nonpos(1, 2) + [{2: 1}, {2: 2}, {2: 767}, {2: 770}]  # C % 4 != 0
+                + [{6: p, 7: p}, {6: null, 7: null}])
+    # a, b16, y, n, stream
+    refuses(lib.fgdm_op_add_f16_to_f32, (p, p, p, 12345, null), nulls(0, 1, 2) + nonpos(3))
+    # x, y, n, stream
+    refuses(lib.fgdm_op_f32_to_f16, (p, p, 12345, null), nulls(0, 1) + nonpos(2))
+    refuses(lib.fgdm_op_silu_f32_to_f16, (p, p, 12345, null), nulls(0, 1) + nonpos(2))
+    # z, wb, scale, y, B, HW, stream
+    refuses(lib.fgdm_op_vae_prequant, (p, p, 1.0, p, 3, 1000, null), nulls(0, 1, 3) + nonpos(4, 5))
+    # h, wb, moments, B, HW, stream
+    refuses(lib.fgdm_op_vae_moments, (p, p, p, 3, 1000, null), nulls(0, 1, 2) + nonpos(3, 4))
+
+
 def test_ln_qkv_entry_refuses_bad_arguments(lib):
     """fgdm_op_ln_qkv (tests/test_gpu_qkv_projection.py) returns FGDM_ERR_ARG before any launch or copy for every refusal
     include/fgdm.h lists (so without a GPU too): the pointers below are never dereferenced."""
